@@ -5,15 +5,21 @@ One step = one DSGD epoch (numBlocks supersteps, DSGDforMF.scala:341-344) over t
 split, fast f32 mode, factors and rating blocks resident in HBM before timing starts.
 
     python bench.py [--gpus N --steps K --warmup W] [--config NFLX|ML20M|...] [--mode fast|det]
+                    [--dump-outputs DIR] [--full]
 
 N > 1 is launched by torch.distributed.run (one process per GPU).  Each rank owns
 numBlocks/N user blocks; item blocks rotate between ranks over RCCL inside libmfhip
 (mf_create_rank).  torch.distributed (gloo) carries only the control plane: the RCCL
 unique id, the barriers around the timed region and the max/sum reductions.
 
-Prints ONE JSON line on rank 0 with the contract fields plus "roofline" (dominant kernel,
-HIP-event timed over the timed region) and "cpu_baseline" (oracle/ C restatement of the
-reference, rank 0 at N=1 only, on a bounded sample of the same workload).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the
+contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step, config); every other
+block of the line is null.  --dump-outputs DIR writes the factors the last timed step left
+(dump_outputs).  --full adds the legs that take runs of their own: the 10-epoch RMSE against the
+oracle's, "roofline" (dominant kernel, HIP-event timed over a profiled replay), "online",
+"deterministic", "ml20m" and "cpu_baseline" (oracle/ C restatement of the reference, rank 0 at
+N=1 only, on a bounded sample of the same workload); the options that size or drop a single leg
+act only under --full.
 """
 from __future__ import annotations
 
@@ -36,6 +42,12 @@ def parse():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", default="NFLX")
     ap.add_argument("--mode", default="fast", choices=["fast", "det"])
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: 10-epoch RMSE, profiled replay (roofline), online, "
+                         "deterministic f64, ML20M and the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the factors they left as DIR/<name>.npy (a fixed seeded "
+                         "sample of the rows of a side too large to write whole)")
     ap.add_argument("--scale", type=float, default=1.0, help="shrink the synthetic (tests only)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-supersteps", type=int, default=-1, help="oracle sample size (default: 1 epoch)")
@@ -526,9 +538,44 @@ def online_leg(ctx, stream, a, batch=ONLINE_BATCH):
                       f"one {kernel} launch, sync; median over the timed batches after one warmup batch"}
 
 
+DUMP_SIDE_BYTES = 24 * 2**20  # per factor side; both sides with their id lists stay under 64 MB
+DUMP_SEED = 20240607
+
+
+def dump_ids(col, max_rows, rng):
+    """The ids of one side of the training split, ascending; more than max_rows of them are cut to
+    a sample drawn from rng (sorted)."""
+    import numpy as np
+    ids = np.flatnonzero(np.bincount(col)).astype(np.int32)
+    if len(ids) > max_rows:
+        ids = np.sort(rng.choice(ids, size=max_rows, replace=False))
+    return ids
+
+
+def dump_outputs(ctx, a, k, tu, ti):
+    """What a caller of the timed path receives after its last step: the user and item factor rows
+    (mf_lookup), float32 in fast mode and float64 in the deterministic one, as <side>_factors.npy
+    beside the ids of those rows, <side>_ids.npy (float64).  A side of more than DUMP_SIDE_BYTES is
+    cut to a seeded sample of its ids (sorted), the same from run to run."""
+    import numpy as np
+    dtype = np.float32 if a.mode == "fast" else np.float64
+    max_rows = DUMP_SIDE_BYTES // (k * np.dtype(dtype).itemsize)
+    os.makedirs(a.dump_outputs, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    for side, name, col in ((0, "user", tu), (1, "item", ti)):
+        ids = dump_ids(col, max_rows, rng)
+        vecs, found = ctx.lookup(side, ids)
+        if not found.all():
+            raise RuntimeError(f"{name} side: {int((~found).sum())} trained ids have no factor row")
+        np.save(os.path.join(a.dump_outputs, f"{name}_factors.npy"), vecs.astype(dtype))
+        np.save(os.path.join(a.dump_outputs, f"{name}_ids.npy"), ids.astype(np.float64))
+
+
 def main():
     a = parse()
     D = Dist()
+    if a.dump_outputs and D.world > 1:
+        raise SystemExit("--dump-outputs reads the factors of one context: use --gpus 1")
     import numpy as np
     import mfhip
     from mfhip import _lib as L
@@ -581,14 +628,17 @@ def main():
     elapsed = D.reduce(t1 - t0, "max")
     updates = D.reduce(float(st["updates"]), "sum")
 
-    # Roofline: replay min(steps, 2) epochs of the same workload with a start/stop event pair on
+    if a.dump_outputs:  # before anything below runs the model further
+        dump_outputs(ctx, a, k, tu, ti)
+
+    # Roofline (--full): replay min(steps, 2) epochs of the same workload with a start/stop event pair on
     # every sweep launch (on the library's stream; for the pair kernel recorded by the dispatch
     # packet itself).  achieved = the bytes the sweep kernel requests per launch (its row loads
     # and stores with in-range offsets plus its schedule records: mf_stats.moved_bytes, counted
     # from the device plan) / its average launch time.  The SURVEY 8d per-update model
     # (16k+20 B) is reported beside it as algorithmic_frac: it charges an item row per update,
     # which this kernel keeps in registers through a run, so it overstates the bytes.
-    prof_epochs = 0 if a.no_profile else min(a.steps, 2)
+    prof_epochs = 0 if a.no_profile or not a.full else min(a.steps, 2)
     st_p = {"kernel_ms": 0.0, "kernel_launches": 0, "algorithmic_bytes": 0.0, "moved_bytes": 0.0, "updates": 0}
     if prof_epochs:
         ctx.reset_stats()
@@ -599,37 +649,39 @@ def main():
         ctx.set_profiling(False)
         st_p = ctx.stats()
 
-    # RMSE after exactly 10 epochs (the metric's second half): the same prepared fit restarted
+    # RMSE after exactly 10 epochs (--full; the metric's second half): the same prepared fit restarted
     # from its initial factors, 10 epochs, held-out RMSE; beside it the oracle's RMSE on the same
     # data (f64, reference order) when the committed fixture matches.
-    t0 = time.time()
-    ctx.restart()
-    ctx.run(10 * nb)
-    rmse, matched = ctx.rmse(eu, ei, er)
-    t_eval = time.time() - t0
-    ref = rmse_reference(a, (tu, ti, tr, eu, ei, er)) if D.rank == 0 else None
+    rmse = matched = t_eval = ref = None
+    if a.full:
+        t0 = time.time()
+        ctx.restart()
+        ctx.run(10 * nb)
+        rmse, matched = ctx.rmse(eu, ei, er)
+        t_eval = time.time() - t0
+        ref = rmse_reference(a, (tu, ti, tr, eu, ei, er)) if D.rank == 0 else None
 
     value = updates / elapsed
     roof = fast_roofline(a, k, st["groups"], st_p, prof_epochs, D.world, int(nu * a.scale))
 
     online = None
-    stream = online_stream(a, synth, nu, ni) if D.world == 1 and a.online_batches > 0 else None
+    stream = online_stream(a, synth, nu, ni) if a.full and D.world == 1 and a.online_batches > 0 else None
     if stream is not None:
         online = {"f32": online_leg(ctx, stream, a)}
     det = None
-    if D.world == 1 and a.mode == "fast" and a.det_epochs > 0:
+    if a.full and D.world == 1 and a.mode == "fast" and a.det_epochs > 0:
         ctx.close()  # its HBM is not needed any more
         det = det_leg(a, k, nb, (tu, ti, tr), (eu, ei, er), ref, stream)
         if online is not None and det.get("online"):
             online["f64"] = det.pop("online")
 
     ml20m = None
-    if D.world == 1 and a.config == "NFLX" and a.mode == "fast" and a.ml20m_epochs > 0:
+    if a.full and D.world == 1 and a.config == "NFLX" and a.mode == "fast" and a.ml20m_epochs > 0:
         ctx.close()  # (closed already when the det leg ran)
         ml20m = ml20m_leg(a)
 
     cpu = None
-    if D.rank == 0 and D.world == 1 and not a.no_cpu_baseline:
+    if a.full and D.rank == 0 and D.world == 1 and not a.no_cpu_baseline:
         cpu = cpu_baseline(tu, ti, tr, k, nb, a.cpu_supersteps if a.cpu_supersteps > 0 else nb)
 
     if D.rank == 0:
@@ -644,13 +696,14 @@ def main():
                        "train_ratings": int(len(tr)), "rank": k, "num_blocks": nb, "lambda": 1.0, "lr": 0.001,
                        "lr_method": "Default", "blocking": a.blocking, "item_split": a.item_split, "groups": st["groups"], "pad_records": st["pads"],
                        "parallelism": f"dsgd-ring{D.world}"},
-            "rmse": round(rmse, 6), "rmse_epochs": 10, "rmse_matched": matched,
-            "rmse_ref": round(ref["oracle_rmse"], 6) if ref else None,
+            "full": a.full, "rmse": round(rmse, 6) if a.full else None, "rmse_epochs": 10 if a.full else None,
+            "rmse_matched": matched, "rmse_ref": round(ref["oracle_rmse"], 6) if ref else None,
             "rmse_rel": round((rmse - ref["oracle_rmse"]) / ref["oracle_rmse"], 5) if ref else None,
             "rmse_ref_source": "tests/golden/rmse_ref.json (tools/rmse_parity.py, oracle f64, same data sha256)"
                                if ref else None,
             "roofline": roof, "cpu_baseline": cpu, "online": online, "deterministic": det, "ml20m": ml20m,
-            "setup_s": {"generate": round(t_gen, 2), "prepare": round(t_prep, 2), "rmse_eval": round(t_eval, 3)},
+            "setup_s": {"generate": round(t_gen, 2), "prepare": round(t_prep, 2),
+                        "rmse_eval": round(t_eval, 3) if a.full else None},
         }
         print(json.dumps(out), flush=True)
     ctx.close()

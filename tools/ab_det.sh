@@ -14,7 +14,7 @@ done
 for rep in 1 2; do
   for lib in base new; do
     if [ $lib = base ]; then export MFHIP_LIB=$B; else unset MFHIP_LIB; fi
-    timeout -k 10 400 python bench.py --steps 1 --no-cpu-baseline --ml20m-epochs 0 --block-update-reps 1 --no-profile > $O/b_${lib}_$rep.json 2> $O/b_${lib}_$rep.err || { echo bench failed; tail -5 $O/b_${lib}_$rep.err; exit 1; }
+    timeout -k 10 400 python bench.py --full --steps 1 --no-cpu-baseline --ml20m-epochs 0 --block-update-reps 1 --no-profile > $O/b_${lib}_$rep.json 2> $O/b_${lib}_$rep.err || { echo bench failed; tail -5 $O/b_${lib}_$rep.err; exit 1; }
     python3 -c "
 import json
 d=json.loads(open('$O/b_${lib}_$rep.json').read().strip().splitlines()[-1])

@@ -9,7 +9,7 @@ tail -1 $O/pytest.log
 for rep in 1 2; do
   for mode in host device; do
     if [ $mode = host ]; then unset MFHIP_TEST; else export MFHIP_TEST=det_build=device; fi
-    MFHIP_TIMING=1 timeout -k 10 400 python bench.py --steps 1 --no-cpu-baseline --ml20m-epochs 0 --block-update-reps 0 --online-batches 0 --no-profile > $O/b_${mode}_$rep.json 2> $O/b_${mode}_$rep.err || { echo bench failed; tail -5 $O/b_${mode}_$rep.err; exit 1; }
+    MFHIP_TIMING=1 timeout -k 10 400 python bench.py --full --steps 1 --no-cpu-baseline --ml20m-epochs 0 --block-update-reps 0 --online-batches 0 --no-profile > $O/b_${mode}_$rep.json 2> $O/b_${mode}_$rep.err || { echo bench failed; tail -5 $O/b_${mode}_$rep.err; exit 1; }
     python3 -c "
 import json
 d=json.loads(open('$O/b_${mode}_$rep.json').read().strip().splitlines()[-1]); de=d['deterministic']

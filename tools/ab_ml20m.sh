@@ -8,7 +8,7 @@ for rep in 1 2; do
   for spec in "$@"; do
     name=${spec%%=*}; L=${spec#*=}; K=
     case $L in *@*) K=${L#*@}; L=${L%%@*};; esac
-    MFHIP_TEST=$K MFHIP_LIB=$L timeout -k 10 300 python bench.py --config ${CONFIG:-ML20M} --steps 5 --no-cpu-baseline --online-batches 0 --det-epochs 0 --block-update-reps 0 --no-profile > $O/b_${name}_$rep.json 2> $O/b_${name}_$rep.err || { echo bench failed $name; tail -5 $O/b_${name}_$rep.err; exit 1; }
+    MFHIP_TEST=$K MFHIP_LIB=$L timeout -k 10 300 python bench.py --full --config ${CONFIG:-ML20M} --steps 5 --no-cpu-baseline --online-batches 0 --det-epochs 0 --block-update-reps 0 --no-profile > $O/b_${name}_$rep.json 2> $O/b_${name}_$rep.err || { echo bench failed $name; tail -5 $O/b_${name}_$rep.err; exit 1; }
     python3 -c "
 import json
 d=json.loads(open('$O/b_${name}_$rep.json').read().strip().splitlines()[-1])

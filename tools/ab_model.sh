@@ -7,7 +7,7 @@ mkdir -p $O
 for rep in 1 2; do
   for spec in "$@"; do
     name=${spec%%=*}; M=${spec#*=}
-    MFHIP_SYS_MODEL=$M MFHIP_LIB=$L timeout -k 10 300 python bench.py --config ${CONFIG:-ML20M} --steps 5 --no-cpu-baseline --online-batches 0 --det-epochs 0 --block-update-reps 0 --no-profile > $O/b_${name}_$rep.json 2> $O/b_${name}_$rep.err || { echo bench failed $name; tail -5 $O/b_${name}_$rep.err; exit 1; }
+    MFHIP_SYS_MODEL=$M MFHIP_LIB=$L timeout -k 10 300 python bench.py --full --config ${CONFIG:-ML20M} --steps 5 --no-cpu-baseline --online-batches 0 --det-epochs 0 --block-update-reps 0 --no-profile > $O/b_${name}_$rep.json 2> $O/b_${name}_$rep.err || { echo bench failed $name; tail -5 $O/b_${name}_$rep.err; exit 1; }
     python3 -c "
 import json
 d=json.loads(open('$O/b_${name}_$rep.json').read().strip().splitlines()[-1])

@@ -6,7 +6,7 @@ tail -2 $O/pytest.log
 for rep in 1 2; do
   for lib in base new; do
     if [ $lib = base ]; then L=large-scale-recommendation_amd/lib_base/libmfhip.so; else L=large-scale-recommendation_amd/lib/libmfhip.so; fi
-    MFHIP_LIB=$L timeout -k 10 300 python bench.py --steps 5 --no-cpu-baseline --online-batches 0 --det-epochs 0 --block-update-reps 0 --no-profile > $O/b_${lib}_$rep.json 2> $O/b_${lib}_$rep.err || { echo bench failed; tail -5 $O/b_${lib}_$rep.err; exit 1; }
+    MFHIP_LIB=$L timeout -k 10 300 python bench.py --full --steps 5 --no-cpu-baseline --online-batches 0 --det-epochs 0 --block-update-reps 0 --no-profile > $O/b_${lib}_$rep.json 2> $O/b_${lib}_$rep.err || { echo bench failed; tail -5 $O/b_${lib}_$rep.err; exit 1; }
     python3 -c "
 import json,sys
 d=json.loads(open('$O/b_${lib}_$rep.json').read().strip().splitlines()[-1])

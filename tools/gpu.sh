@@ -9,6 +9,8 @@
 #                                          shell-parsed: quote a -k expression)
 #   smoke                                  __graft_entry__.smoke()
 #   bench:<tag>:<bench.py args>            one bench line -> <tag>.json, summary printed
+#                                          (everywhere below: give bench.py --full for the rmse, roofline,
+#                                          det, online and ML20M legs; a plain run times the headline only)
 #   ab:<tag>:<reps>:<envA>|<envB>[|...]:<bench.py args>
 #                                          alternating A/B of environment settings on the bench line
 #   prof:<tag>:<kernel>:<cfg>:<mode>:<rank>:<bench.py args>   (<kernel> may be k1=sfx1;k2=sfx2;...:
