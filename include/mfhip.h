@@ -183,6 +183,25 @@ int mf_rmse(mf_ctx* ctx, const int32_t* users, const int32_t* items, const doubl
 int mf_empirical_risk(mf_ctx* ctx, const int32_t* users, const int32_t* items,
                       const double* ratings, int64_t n, double lambda, double* risk);
 
+/* MatrixFactorizationModel.recommendProducts / recommendUsers / recommendProductsForUsers (the
+   model sp/OnlineSpark.scala:12, 126 builds): scored and selected on the device.
+   query_side = MF_SIDE_USER: for each queries[j] (a user id) the top_n item ids by p.q.
+   query_side = MF_SIDE_ITEM: for each item id the top_n user ids.
+   ids_out / scores_out (may be NULL): n_queries x top_n, row-major; counts_out[j] = valid entries
+   of row j = min(top_n, candidates left after exclusion), 0 for an unknown query id.  Ids may be
+   negative, so counts_out is the only validity signal; slots past it hold id 0 and score 0.0.
+   (excl_query[e], excl_cand[e]) pairs are never returned for that query; pairs naming an unknown id
+   or a query not in queries[] are ignored, duplicates allowed, n_excl == 0 takes NULL pointers.
+   A row is sorted by score descending, ties by candidate id ascending, NaN below every number
+   (-inf included).  Scores: MF_MODE_DETERMINISTIC_F64 bitwise mf_predict's value of the pair;
+   MF_MODE_FAST_F32 the f32 fmaf chain over f = 0..k-1 from 0, widened.
+   Single-process contexts only (a rank-mode context returns MF_ERR_STATE). */
+#define MF_RECOMMEND_MAX_TOP 128
+int mf_recommend(mf_ctx* ctx, int query_side, const int32_t* queries, int64_t n_queries,
+                 int32_t top_n,
+                 const int32_t* excl_query, const int32_t* excl_cand, int64_t n_excl,
+                 int32_t* ids_out, double* scores_out, int32_t* counts_out);
+
 /* Exact updateLocalFactors replacement (DSGDforMF.scala:378-418) on caller buffers:
    users[nu x k], items[ni x k] are updated in place; omegas are per row.  Reentrant
    on disjoint buffers with distinct contexts, as Flink calls it per task slot. */

@@ -40,7 +40,12 @@ public final class MfHip {
   public static native void predict(long ctx, int[] users, int[] items, double[] out, byte[] found);
   public static native double rmse(long ctx, int[] users, int[] items, double[] r);
   public static native double empiricalRisk(long ctx, int[] users, int[] items, double[] r, double lambda);
-  // updateLocalFactors (DSGDforMF.scala:378-418) on the caller's flattened factor blocks
+  // MatrixFactorizationModel.recommendProducts / recommendUsers / recommendProductsForUsers:
+  // idsOut / scoresOut (may be null) hold queries.length * topN entries, countsOut queries.length;
+  // exclQuery / exclCand (both null, or equal lengths) are pairs never returned
+  public static native void recommend(long ctx, int querySide, int[] queries, int topN,
+                                      int[] exclQuery, int[] exclCand,
+                                      int[] idsOut, double[] scoresOut, int[] countsOut);
   public static native void blockUpdate(long ctx, double[] r, int[] uidx, int[] iidx,
                                         double[] users, int[] uomega, double[] items, int[] iomega,
                                         int k, int iteration, int ratingBlockId, long seed,

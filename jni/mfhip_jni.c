@@ -240,6 +240,40 @@ JNIEXPORT void JNICALL JFN(predict)(JNIEnv* env, jclass c, jlong h, jintArray u,
   check(env, st);
 }
 
+JNIEXPORT void JNICALL JFN(recommend)(JNIEnv* env, jclass c, jlong h, jint side, jintArray q, jint top, jintArray xq,
+                                      jintArray xc, jintArray ids, jdoubleArray scores, jintArray counts) {
+  if (require(env, q && ids && counts, "queries, idsOut and countsOut must not be null")) return;
+  if (require(env, top >= 1 && top <= MF_RECOMMEND_MAX_TOP, "topN out of range")) return;
+  const jsize n = len(env, q);
+  if (require(env, (jlong)len(env, ids) >= (jlong)n * top && (!scores || (jlong)len(env, scores) >= (jlong)n * top) &&
+                       len(env, counts) >= n,
+              "idsOut / scoresOut must hold queries.length * topN entries and countsOut queries.length"))
+    return;
+  if (require(env, (!xq && !xc) || (xq && xc && len(env, xq) == len(env, xc)),
+              "exclQuery and exclCand must both be null or match in length"))
+    return;
+  const jsize ne = xq ? len(env, xq) : 0;
+  Elems eq = {0}, exq = {0}, exc = {0}, ei = {0}, es = {0}, ec = {0};
+  if (acquire(env, &eq, q, kInt) || acquire(env, &exq, xq, kInt) || acquire(env, &exc, xc, kInt) ||
+      acquire(env, &ei, ids, kInt) || acquire(env, &es, scores, kDouble) || acquire(env, &ec, counts, kInt)) {
+    release(env, &es, JNI_ABORT);
+    release(env, &ei, JNI_ABORT);
+    release(env, &exc, JNI_ABORT);
+    release(env, &exq, JNI_ABORT);
+    release(env, &eq, JNI_ABORT);
+    return;
+  }
+  int st = mf_recommend(CTX(h), side, (const int32_t*)eq.p, n, top, ne ? (const int32_t*)exq.p : NULL,
+                        ne ? (const int32_t*)exc.p : NULL, ne, (int32_t*)ei.p, (double*)es.p, (int32_t*)ec.p);
+  release(env, &ec, st == MF_OK ? 0 : JNI_ABORT);
+  release(env, &es, st == MF_OK ? 0 : JNI_ABORT);
+  release(env, &ei, st == MF_OK ? 0 : JNI_ABORT);
+  release(env, &exc, JNI_ABORT);
+  release(env, &exq, JNI_ABORT);
+  release(env, &eq, JNI_ABORT);
+  check(env, st);
+}
+
 typedef int (*eval_fn)(JNIEnv*, jlong, const int32_t*, const int32_t*, const double*, jsize, jdouble, double*);
 
 static int call_rmse(JNIEnv* env, jlong h, const int32_t* u, const int32_t* i, const double* r, jsize n, jdouble unused,

@@ -179,6 +179,19 @@ void launch_predict(hipStream_t st, const int32_t* urow, const int32_t* irow, in
                     const void* U, const void* I, int k, bool f64, double* out, const double* r,
                     const int32_t* mult, double lambda, double* partials);
 
+// Top-N recommendation (kernels_recommend.hip): for each of the nq query rows qrows[] of slab Q (all
+// valid rows) the top_n best of candidate rows [0, C) of slab Cf by p.q, as ids / scores / counts
+// ([nq][top_n], [nq]; device).  f64: the sequential pq = pq + a*b chain (k_predict's value); f32:
+// the fmaf chain over f = 0..k-1 on the f32-input MFMA.  cand_id: row -> id of the candidate side.
+// excl_off (nq + 1) / excl_rows: per query the sorted candidate rows never returned.  The candidate
+// rows are walked in S <= 64 splits; part: nq * S * top_n keys of recommend_key_bytes(f64) scratch.
+// recommend_query_tile: the queries one workgroup owns (the host sizes S by it).
+size_t recommend_key_bytes(bool f64);
+int recommend_query_tile(int top_n, bool f64);
+void launch_recommend(hipStream_t st, const void* Q, const void* Cf, const int32_t* qrows, int nq, int32_t C, int S,
+                      int k, int top_n, bool f64, const int32_t* cand_id, const int64_t* excl_off,
+                      const int32_t* excl_rows, void* part, int32_t* ids, double* scores, int32_t* counts);
+
 // DSGD blocking on the device (kernels_block.hip): both SideLayouts (initFactorBlockAndIndices,
 // DSGDforMF.scala:513-588, the reference's seeded blocking) and the rating blocks of user blocks
 // [ub_lo, ub_hi) (:301-327; sort_ui: (user, item) order inside a block), bitwise what

@@ -1,0 +1,447 @@
+// kernels_recommend.hip -- top-N recommendation (mf_recommend): score every candidate row against
+// a batch of query rows and keep each query's N best, without materialising the score matrix.
+//
+//  k_rec_f32    fast contexts.  The dense product runs on the matrix cores (v_mfma_f32_32x32x2_f32):
+//               candidates are the A operand, queries the B operand, so a lane's 16 accumulator
+//               registers hold 16 candidates' scores of ONE query (column = lane & 31) and the
+//               selection needs no cross-lane traffic.  A block of NW waves owns NW * 32 queries
+//               (32 per wave) and walks its split of the candidate rows in tiles of 128: four
+//               independent 32 x 32 accumulator tiles per wave, each taking the whole k loop in
+//               ascending f (the f32-input MFMA is bit for bit the fmaf chain over f, so a score
+//               depends on no tiling, split or batch size).  Both operands are staged through LDS in
+//               k chunks of 16, double-buffered, stored k-major so that the fragment reads of a wave
+//               fall on 64 distinct banks.
+//  k_rec_f64    deterministic contexts.  Plain VALU: a lane owns one candidate's chain
+//               pq = pq + a * b over f = 0..k-1 (this file is compiled with -ffp-contract=off), the
+//               value k_predict gives for the pair, against QW query rows of its wave.
+//  k_rec_merge  the S partial lists of a query (one per candidate split) -> its final top N.
+//
+// Selection (shared): a query's list is N keys in LDS, sorted descending; a key orders by score
+// descending, then candidate id ascending, NaN below every number -- one unsigned compare.  A score
+// is tested against the exclusion rows of its query (CSR, sorted candidate rows, binary search) only
+// when it beats the list's N-th key, so insertions become rare after the first tiles.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <string>
+
+#include "common.hpp"
+#include "kernels.hpp"
+#include "mfhip.h"
+
+namespace mfhip {
+namespace {
+
+// ---- keys ---------------------------------------------------------------------------------
+// Candidate id part: a smaller id gives a larger value.
+__device__ __forceinline__ uint32_t id_bits(int32_t id) { return ~(static_cast<uint32_t>(id) ^ 0x80000000u); }
+__device__ __forceinline__ int32_t id_from_bits(uint32_t b) { return static_cast<int32_t>((~b) ^ 0x80000000u); }
+
+// f32: (order-preserving u32 of the score) << 32 | id part.  The score part is >= 1 for every real
+// key (1 = NaN, which no number maps to), so 0 is the empty slot.  -0 orders as +0.
+struct Key32 {
+  uint64_t v;
+};
+__device__ __forceinline__ bool key_gt(Key32 a, Key32 b) { return a.v > b.v; }
+__device__ __forceinline__ bool key_empty(Key32 a) { return a.v == 0; }
+__device__ __forceinline__ uint32_t ord32(float s) {
+  if (s != s) return 1u;
+  if (s == 0.0f) return 0x80000000u;
+  const uint32_t b = __float_as_uint(s);
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ Key32 make_key(float s, int32_t id) {
+  return Key32{(static_cast<uint64_t>(ord32(s)) << 32) | id_bits(id)};
+}
+__device__ __forceinline__ double key_score(Key32 k) {
+  const uint32_t o = static_cast<uint32_t>(k.v >> 32);
+  if (o == 1u) return __longlong_as_double(0x7ff8000000000000LL);
+  const uint32_t b = (o & 0x80000000u) ? (o ^ 0x80000000u) : ~o;
+  return static_cast<double>(__uint_as_float(b));
+}
+__device__ __forceinline__ int32_t key_id(Key32 k) { return id_from_bits(static_cast<uint32_t>(k.v)); }
+__device__ __forceinline__ Key32 key_shfl_xor(Key32 k, int m) {
+  const uint32_t lo = __shfl_xor(static_cast<uint32_t>(k.v), m), hi = __shfl_xor(static_cast<uint32_t>(k.v >> 32), m);
+  return Key32{(static_cast<uint64_t>(hi) << 32) | lo};
+}
+
+// f64: the same with a 64-bit score part (hi) and the id part in lo.
+struct Key64 {
+  uint64_t hi, lo;
+};
+__device__ __forceinline__ bool key_gt(Key64 a, Key64 b) { return a.hi > b.hi || (a.hi == b.hi && a.lo > b.lo); }
+__device__ __forceinline__ bool key_empty(Key64 a) { return a.hi == 0; }
+__device__ __forceinline__ Key64 make_key(double s, int32_t id) {
+  uint64_t o;
+  if (s != s) o = 1u;
+  else if (s == 0.0) o = 0x8000000000000000ULL;
+  else {
+    const uint64_t b = static_cast<uint64_t>(__double_as_longlong(s));
+    o = (b >> 63) ? ~b : (b | 0x8000000000000000ULL);
+  }
+  return Key64{o, id_bits(id)};
+}
+__device__ __forceinline__ double key_score(Key64 k) {
+  if (k.hi == 1u) return __longlong_as_double(0x7ff8000000000000LL);
+  const uint64_t b = (k.hi >> 63) ? (k.hi ^ 0x8000000000000000ULL) : ~k.hi;
+  return __longlong_as_double(static_cast<long long>(b));
+}
+__device__ __forceinline__ int32_t key_id(Key64 k) { return id_from_bits(static_cast<uint32_t>(k.lo)); }
+__device__ __forceinline__ Key64 key_shfl_xor(Key64 k, int m) {
+  const Key32 a = key_shfl_xor(Key32{k.hi}, m), b = key_shfl_xor(Key32{k.lo}, m);
+  return Key64{a.v, b.v};
+}
+
+// list[0..N) sorted descending, key beats list[N-1]: insert it, dropping the last.
+template <typename K>
+__device__ __forceinline__ void list_insert(K* list, int N, K key) {
+  int p = N - 1;
+  while (p > 0 && key_gt(key, list[p - 1])) {
+    list[p] = list[p - 1];
+    --p;
+  }
+  list[p] = key;
+}
+
+// Is candidate row `crow` in the query's sorted exclusion rows [b, e)?
+__device__ __forceinline__ bool excluded(const int32_t* __restrict__ rows, int64_t b, int64_t e, int32_t crow) {
+  while (b < e) {
+    const int64_t m = (b + e) >> 1;
+    const int32_t v = rows[m];
+    if (v == crow) return true;
+    if (v < crow) b = m + 1;
+    else e = m;
+  }
+  return false;
+}
+
+// ---- f32: MFMA score + select -----------------------------------------------------------------
+using f32x16 = __attribute__((ext_vector_type(16))) float;
+
+constexpr int kCT = 128;   // candidate rows per tile (4 accumulator tiles of 32)
+constexpr int kKC = 16;    // k chunk staged per step
+constexpr int kPend = 8;   // parked candidates per lane between two drains of the selection
+constexpr int kAStr = 160; // LDS row stride of the candidate stage (k-major): 160 = 32 mod 64 banks
+
+__host__ __device__ constexpr int rec_bstr(int nw) { return nw * 32 + ((nw * 32) % 64 == 0 ? 32 : 0); }
+__host__ __device__ constexpr int rec_stage_floats(int nw) { return kKC * (kAStr + rec_bstr(nw)); }
+
+// Grid: (query tiles, S).  qrows: the batch's query rows (all valid), nq of them.  Candidates:
+// rows [0, C) of slab Cf, split s takes [s * per, min(C, (s + 1) * per)).  part: [nq][S][N] keys.
+// VEC: k % 4 == 0, rows are loaded as float4.
+template <int NW, bool VEC>
+__global__ __launch_bounds__(NW * 64) void k_rec_f32(const float* __restrict__ Qf, const float* __restrict__ Cf,
+                                                     const int32_t* __restrict__ qrows, int nq, int32_t C, int32_t per,
+                                                     int k, int N, const int32_t* __restrict__ cand_id,
+                                                     const int64_t* __restrict__ excl_off,
+                                                     const int32_t* __restrict__ excl_rows, Key32* __restrict__ part) {
+  constexpr int NT = NW * 64, QT = NW * 32, BSTR = rec_bstr(NW);
+  constexpr int A_PER = kCT * 4 / NT;  // float4 slots of the candidate stage per thread
+  constexpr int B_PER = QT * 4 / NT;   // ... of the query stage (= 2)
+  extern __shared__ __align__(16) unsigned char rec_smem[];
+  Key32* lists = reinterpret_cast<Key32*>(rec_smem);                         // [QT][N]
+  uint64_t* pend = reinterpret_cast<uint64_t*>(rec_smem + sizeof(Key32) * QT * N);  // [kPend][NT]
+  float* stage = reinterpret_cast<float*>(pend + kPend * NT);                      // [2][kKC][kAStr + BSTR]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int q0 = blockIdx.x * QT, S = gridDim.y, s = blockIdx.y;
+  const int32_t cbeg = static_cast<int32_t>(min(static_cast<int64_t>(C), static_cast<int64_t>(s) * per));
+  const int32_t cend = static_cast<int32_t>(min(static_cast<int64_t>(C), static_cast<int64_t>(cbeg) + per));
+
+  for (int x = tid; x < QT * N; x += NT) lists[x] = Key32{0};
+
+  // this thread's share of the query stage: row x / 4 of the tile, floats 4 * (x % 4) .. + 3 of a chunk
+  const float* bsrc[B_PER];
+#pragma unroll
+  for (int i = 0; i < B_PER; ++i) {
+    const int q = q0 + (tid + i * NT) / 4;
+    bsrc[i] = q < nq ? Qf + static_cast<int64_t>(qrows[q]) * k : nullptr;
+  }
+  float4 ra[A_PER], rb[B_PER];
+  auto load4 = [&](const float* row, int f) -> float4 {
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (row == nullptr) return v;
+    if (VEC) {
+      if (f < k) v = *reinterpret_cast<const float4*>(row + f);
+    } else {
+      if (f < k) v.x = row[f];
+      if (f + 1 < k) v.y = row[f + 1];
+      if (f + 2 < k) v.z = row[f + 2];
+      if (f + 3 < k) v.w = row[f + 3];
+    }
+    return v;
+  };
+  auto fetch = [&](int32_t c0, int f0) {
+#pragma unroll
+    for (int i = 0; i < A_PER; ++i) {
+      const int x = tid + i * NT;
+      const int32_t crow = c0 + x / 4;
+      ra[i] = load4(crow < cend ? Cf + static_cast<int64_t>(crow) * k : nullptr, f0 + 4 * (x & 3));
+    }
+#pragma unroll
+    for (int i = 0; i < B_PER; ++i) rb[i] = load4(bsrc[i], f0 + 4 * ((tid + i * NT) & 3));
+  };
+  auto put = [&](float* buf) {
+#pragma unroll
+    for (int i = 0; i < A_PER; ++i) {
+      const int x = tid + i * NT, row = x / 4, kf = 4 * (x & 3);
+      buf[(kf + 0) * kAStr + row] = ra[i].x;
+      buf[(kf + 1) * kAStr + row] = ra[i].y;
+      buf[(kf + 2) * kAStr + row] = ra[i].z;
+      buf[(kf + 3) * kAStr + row] = ra[i].w;
+    }
+    float* bb = buf + kKC * kAStr;
+#pragma unroll
+    for (int i = 0; i < B_PER; ++i) {
+      const int x = tid + i * NT, row = x / 4, kf = 4 * (x & 3);
+      bb[(kf + 0) * BSTR + row] = rb[i].x;
+      bb[(kf + 1) * BSTR + row] = rb[i].y;
+      bb[(kf + 2) * BSTR + row] = rb[i].z;
+      bb[(kf + 3) * BSTR + row] = rb[i].w;
+    }
+  };
+
+  const int nkc = (k + kKC - 1) / kKC;
+  const int ntile = (cend - cbeg + kCT - 1) / kCT;
+  const int total = ntile * nkc;
+  // the lane's query: column lane & 31 of its wave's 32; half h takes candidate rows 4h + ...
+  const int jq = wave * 32 + (lane & 31), h = lane >> 5;
+  const int qme = q0 + jq;
+  const bool qok = qme < nq;
+  Key32* mylist = lists + jq * N;
+  int64_t eb = 0, ee = 0;
+  if (qok) { eb = excl_off[qme]; ee = excl_off[qme + 1]; }
+
+  f32x16 acc[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+
+  if (total > 0) {
+    fetch(cbeg, 0);
+    put(stage);
+  }
+  __syncthreads();
+  int tile = 0, kc = 0;
+  for (int it = 0; it < total; ++it) {
+    const float* cur = stage + (it & 1) * rec_stage_floats(NW);
+    int ntile_i = tile, nkc_i = kc + 1;
+    if (nkc_i == nkc) { nkc_i = 0; ++ntile_i; }
+    if (it + 1 < total) fetch(cbeg + ntile_i * kCT, nkc_i * kKC);
+    const float* ca = cur + h * kAStr + (lane & 31);
+    const float* cb = cur + kKC * kAStr + h * BSTR + jq;
+#pragma unroll
+    for (int kk = 0; kk < kKC / 2; ++kk) {
+      const float b = cb[2 * kk * BSTR];
+#pragma unroll
+      for (int t = 0; t < 4; ++t)
+        acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(ca[2 * kk * kAStr + 32 * t], b, acc[t], 0, 0, 0);
+    }
+    if (kc == nkc - 1) {
+      // select: register r of accumulator tile t is candidate row c0 + 32 t + (r & 3) + 8 (r >> 2) + 4 h.
+      // A score that reaches the list's N-th (as of the last drain) is parked in the lane's pending
+      // slots; a drain then lets every lane insert its own parked candidates side by side, so the
+      // wave pays one insertion round per parked candidate of its busiest lane, not one per score.
+      const int32_t c0 = cbeg + tile * kCT;
+      uint32_t thr_hi = static_cast<uint32_t>(mylist[N - 1].v >> 32);
+      int cnt = 0;
+      auto drain = [&]() {
+        for (int i = 0; __any(i < cnt); ++i) {
+          bool have = i < cnt;
+          Key32 key{0};
+          if (have) {
+            const uint64_t pv = pend[i * NT + tid];
+            const int32_t crow = c0 + static_cast<int32_t>(pv & 0xFFFFFFFFu);
+            key = Key32{(pv & 0xFFFFFFFF00000000ULL) | id_bits(cand_id[crow])};
+            have = key_gt(key, mylist[N - 1]) && !excluded(excl_rows, eb, ee, crow);
+          }
+          // the two halves of the wave share a query's list: one half at a time
+#pragma unroll
+          for (int hh = 0; hh < 2; ++hh) {
+            if (have && h == hh && key_gt(key, mylist[N - 1])) list_insert(mylist, N, key);
+            __builtin_amdgcn_wave_barrier();
+          }
+        }
+        cnt = 0;
+        thr_hi = static_cast<uint32_t>(mylist[N - 1].v >> 32);
+      };
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int32_t local = 32 * t + (r & 3) + 8 * (r >> 2) + 4 * h;
+          const uint32_t o = ord32(acc[t][r]);
+          if (qok && c0 + local < cend && o >= thr_hi) {
+            pend[cnt * NT + tid] = (static_cast<uint64_t>(o) << 32) | static_cast<uint32_t>(local);
+            ++cnt;
+          }
+          if (__any(cnt == kPend)) drain();
+          acc[t][r] = 0.f;
+        }
+      }
+      drain();
+    }
+    if (it + 1 < total) put(stage + ((it + 1) & 1) * rec_stage_floats(NW));
+    __syncthreads();
+    tile = ntile_i;
+    kc = nkc_i;
+  }
+  // the wave's lists -> part[q][s][0..N)
+  for (int x = lane; x < 32 * N; x += 64) {
+    const int j = x / N, q = q0 + wave * 32 + j;
+    if (q < nq) part[(static_cast<int64_t>(q) * S + s) * N + (x - j * N)] = lists[wave * 32 * N + x];
+  }
+}
+
+// ---- f64: VALU score + select -----------------------------------------------------------------
+constexpr int kQW = 4;  // queries per wave
+
+// Grid: (ceil(nq / (4 * kQW)), S), 4 waves per block.  Lane = candidate; the wave's kQW query rows
+// are wave-uniform reads.
+__global__ __launch_bounds__(256) void k_rec_f64(const double* __restrict__ Qf, const double* __restrict__ Cf,
+                                                 const int32_t* __restrict__ qrows, int nq, int32_t C, int32_t per,
+                                                 int k, int N, const int32_t* __restrict__ cand_id,
+                                                 const int64_t* __restrict__ excl_off,
+                                                 const int32_t* __restrict__ excl_rows, Key64* __restrict__ part) {
+  __shared__ Key64 lists[4][kQW * MF_RECOMMEND_MAX_TOP];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int S = gridDim.y, s = blockIdx.y;
+  const int q0 = (blockIdx.x * 4 + wave) * kQW;
+  const int32_t cbeg = static_cast<int32_t>(min(static_cast<int64_t>(C), static_cast<int64_t>(s) * per));
+  const int32_t cend = static_cast<int32_t>(min(static_cast<int64_t>(C), static_cast<int64_t>(cbeg) + per));
+  Key64* wl = lists[wave];
+  for (int x = lane; x < kQW * N; x += 64) wl[x] = Key64{0, 0};
+  const double* qp[kQW];
+#pragma unroll
+  for (int i = 0; i < kQW; ++i) {
+    const int q = min(q0 + i, nq - 1);
+    qp[i] = Qf + static_cast<int64_t>(qrows[max(q, 0)]) * k;
+  }
+  for (int32_t c0 = cbeg; c0 < cend; c0 += 64) {
+    const int32_t crow = c0 + lane;
+    const bool cok = crow < cend;
+    const double* cp = Cf + static_cast<int64_t>(cok ? crow : cbeg) * k;
+    double pq[kQW];
+#pragma unroll
+    for (int i = 0; i < kQW; ++i) pq[i] = 0.0;
+    for (int f = 0; f < k; ++f) {
+      const double c = cp[f];
+#pragma unroll
+      for (int i = 0; i < kQW; ++i) pq[i] = pq[i] + qp[i][f] * c;
+    }
+    const int32_t cid = cok ? cand_id[crow] : 0;
+#pragma unroll
+    for (int i = 0; i < kQW; ++i) {
+      const int q = q0 + i;
+      if (q >= nq) break;  // wave-uniform
+      Key64* list = wl + i * N;
+      const Key64 key = make_key(pq[i], cid);
+      bool want = cok && key_gt(key, list[N - 1]);
+      if (want) want = !excluded(excl_rows, excl_off[q], excl_off[q + 1], crow);
+      // one lane at a time inserts into the query's list
+      for (;;) {
+        want = want && key_gt(key, list[N - 1]);
+        const uint64_t m = __ballot(want);
+        if (m == 0) break;
+        if (lane == __ffsll(static_cast<long long>(m)) - 1) {
+          list_insert(list, N, key);
+          want = false;
+        }
+        __builtin_amdgcn_wave_barrier();
+      }
+    }
+  }
+  for (int x = lane; x < kQW * N; x += 64) {
+    const int i = x / N, q = q0 + i;
+    if (q < nq) part[(static_cast<int64_t>(q) * S + s) * N + (x - i * N)] = wl[x];
+  }
+}
+
+// ---- merge ------------------------------------------------------------------------------------
+// One wave per query: lane l < S holds the head of partial list l (each sorted descending); N
+// rounds of a wave-wide maximum.  Slots past the count hold id 0 / score 0.0.
+template <typename K>
+__global__ __launch_bounds__(256) void k_rec_merge(const K* __restrict__ part, int nq, int S, int N,
+                                                   int32_t* __restrict__ ids, double* __restrict__ scores,
+                                                   int32_t* __restrict__ counts) {
+  const int lane = threadIdx.x & 63;
+  const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (q >= nq) return;
+  const K* mine = part + (static_cast<int64_t>(q) * S + lane) * N;
+  int pos = 0;
+  int cnt = 0;
+  for (int o = 0; o < N; ++o) {
+    K head{};
+    if (lane < S && pos < N) head = mine[pos];
+    K best = head;
+    for (int m = 1; m < 64; m <<= 1) {
+      const K other = key_shfl_xor(best, m);
+      if (key_gt(other, best)) best = other;
+    }
+    const bool live = !key_empty(best);
+    // keys are unique (one per candidate), so exactly one lane holds the maximum
+    if (live && lane < S && pos < N && !key_gt(best, head) && !key_gt(head, best)) ++pos;
+    if (lane == 0) {
+      ids[static_cast<int64_t>(q) * N + o] = live ? key_id(best) : 0;
+      scores[static_cast<int64_t>(q) * N + o] = live ? key_score(best) : 0.0;
+    }
+    cnt += live ? 1 : 0;
+  }
+  if (lane == 0) counts[q] = cnt;
+}
+
+template <int NW>
+void rec_f32_dispatch(hipStream_t st, const float* Q, const float* Cf, const int32_t* qrows, int nq, int32_t C, int S,
+                      int32_t per, int k, int N, const int32_t* cand_id, const int64_t* eo, const int32_t* er,
+                      void* part) {
+  const dim3 grid(static_cast<unsigned>((nq + NW * 32 - 1) / (NW * 32)), static_cast<unsigned>(S)), block(NW * 64);
+  const size_t smem = sizeof(Key32) * NW * 32 * N + 8 * kPend * NW * 64 + sizeof(float) * 2 * rec_stage_floats(NW);
+  // up to 72 KB (NW = 4, top 16): above the 64 KB a kernel gets without asking
+  const void* fn = k % 4 == 0 ? reinterpret_cast<const void*>(&k_rec_f32<NW, true>)
+                              : reinterpret_cast<const void*>(&k_rec_f32<NW, false>);
+  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(smem)) != hipSuccess)
+    fail(MF_ERR_HIP, "k_rec_f32: " + std::to_string(smem) + " bytes of LDS refused");
+  if (k % 4 == 0)
+    hipLaunchKernelGGL((k_rec_f32<NW, true>), grid, block, smem, st, Q, Cf, qrows, nq, C, per, k, N, cand_id, eo, er,
+                       static_cast<Key32*>(part));
+  else
+    hipLaunchKernelGGL((k_rec_f32<NW, false>), grid, block, smem, st, Q, Cf, qrows, nq, C, per, k, N, cand_id, eo, er,
+                       static_cast<Key32*>(part));
+}
+
+}  // namespace
+
+size_t recommend_key_bytes(bool f64) { return f64 ? sizeof(Key64) : sizeof(Key32); }
+
+int recommend_query_tile(int top_n, bool f64) {
+  if (f64) return 4 * kQW;
+  return top_n <= 16 ? 128 : top_n <= 48 ? 64 : 32;
+}
+
+void launch_recommend(hipStream_t st, const void* Q, const void* Cf, const int32_t* qrows, int nq, int32_t C, int S,
+                      int k, int top_n, bool f64, const int32_t* cand_id, const int64_t* excl_off,
+                      const int32_t* excl_rows, void* part, int32_t* ids, double* scores, int32_t* counts) {
+  if (nq <= 0) return;
+  const int32_t per = (C + S - 1) / S;
+  if (f64) {
+    const dim3 grid(static_cast<unsigned>((nq + 4 * kQW - 1) / (4 * kQW)), static_cast<unsigned>(S)), block(256);
+    hipLaunchKernelGGL(k_rec_f64, grid, block, 0, st, static_cast<const double*>(Q), static_cast<const double*>(Cf),
+                       qrows, nq, C, per, k, top_n, cand_id, excl_off, excl_rows, static_cast<Key64*>(part));
+  } else {
+    const float* q = static_cast<const float*>(Q);
+    const float* c = static_cast<const float*>(Cf);
+    // the lists of a block stay within 32 KB of LDS: 128 queries per block up to top 16, 64 up to 48, else 32
+    if (top_n <= 16) rec_f32_dispatch<4>(st, q, c, qrows, nq, C, S, per, k, top_n, cand_id, excl_off, excl_rows, part);
+    else if (top_n <= 48) rec_f32_dispatch<2>(st, q, c, qrows, nq, C, S, per, k, top_n, cand_id, excl_off, excl_rows, part);
+    else rec_f32_dispatch<1>(st, q, c, qrows, nq, C, S, per, k, top_n, cand_id, excl_off, excl_rows, part);
+  }
+  const dim3 mgrid(static_cast<unsigned>((nq + 3) / 4)), mblock(256);
+  if (f64)
+    hipLaunchKernelGGL((k_rec_merge<Key64>), mgrid, mblock, 0, st, static_cast<const Key64*>(part), nq, S, top_n, ids,
+                       scores, counts);
+  else
+    hipLaunchKernelGGL((k_rec_merge<Key32>), mgrid, mblock, 0, st, static_cast<const Key32*>(part), nq, S, top_n, ids,
+                       scores, counts);
+}
+
+}  // namespace mfhip

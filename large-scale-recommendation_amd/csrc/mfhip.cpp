@@ -137,6 +137,12 @@ struct Shard {
   uint32_t det_wave_bound = 1;
   // evaluation scratch
   DevBuf ev_u, ev_i, ev_r, ev_mult, ev_out, ev_part;
+  // recommendation (mf_recommend): the row -> id table of each side (valid while rec_id_gen matches
+  // the context's layout_gen), the query rows and exclusion CSR of a call, and a batch's partial
+  // lists and results
+  DevBuf rec_id[2];
+  uint64_t rec_id_gen[2] = {0, 0};
+  DevBuf rec_q, rec_eoff, rec_erows, rec_part, rec_ids, rec_scores, rec_counts;
   // profiling
   std::vector<hipEvent_t> ev;
   size_t ev_used = 0;
@@ -189,6 +195,7 @@ struct mf_ctx {
   bool profiling = false;
   std::vector<int32_t> rows_by_id_u, rows_by_id_i;  // ascending-id row permutations
   bool order_dirty = true;
+  uint64_t layout_gen = 1;  // bumped wherever a side's rows change (with order_dirty): device row -> id tables
   int64_t init_seed = 0;      // seed of the initial factors (P.seed, or a random one when unseeded)
   std::string failed;         // non-empty: a device-side bound tripped; the fit must be prepared again
   // deterministic sweep: the next run's first supersteps, built on worker threads when a run ends
@@ -592,6 +599,7 @@ void build_model(mf_ctx* ctx, const int32_t* u, const int32_t* i, int64_t n, boo
   init_factors(ctx);
   ctx->have_model = true;
   ctx->order_dirty = true;
+  ++ctx->layout_gen;
 }
 
 void ensure_order(mf_ctx* ctx) {
@@ -2046,6 +2054,130 @@ EvalOut evaluate(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* 
 }
 
 // ---------------------------------------------------------------------------------------
+// Top-N recommendation (mf_recommend): ids resolved on the host, score + select on the device
+// (kernels_recommend.hip), on shard 0 like evaluate.  Distinct known query rows are scored once, in
+// batches that bound the device scratch at batch x S x top_n keys (S = candidate splits, chosen so
+// that a small batch against a large catalogue still fills the device); every position of
+// queries[] then takes its row's result.  MFHIP_TEST rec_batch=B / rec_split=S override both.
+void recommend(mf_ctx* ctx, int qside, const int32_t* queries, int64_t nq, int32_t top_n, const int32_t* eq,
+               const int32_t* ec, int64_t ne, int32_t* ids_out, double* scores_out, int32_t* counts_out) {
+  Shard& s = ctx->shards[0];
+  consolidate(ctx, s);
+  sync_all(ctx);  // a run may still be sweeping (mf_dsgd_run returns early)
+  const int cside = 1 - qside;
+  const SideLayout& QS = side_of(ctx, qside);
+  const SideLayout& CS = side_of(ctx, cside);
+  const int64_t C = CS.rows();
+  const int k = ctx->P.num_factors;
+  const size_t N = static_cast<size_t>(top_n);
+  constexpr uint32_t kMiss = 0xFFFFFFFFu;
+
+  // distinct known query rows, ascending; pos[j] = queries[j]'s index among them (-1: unknown id)
+  std::vector<uint32_t> qr;
+  lookup_rows(QS, queries, nq, qr);
+  std::vector<int32_t> uniq;
+  uniq.reserve(qr.size());
+  for (uint32_t r : qr)
+    if (r != kMiss) uniq.push_back(static_cast<int32_t>(r));
+  std::sort(uniq.begin(), uniq.end());
+  uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
+  const int64_t nu = static_cast<int64_t>(uniq.size());
+  auto upos = [&](uint32_t row) -> int64_t {
+    if (row == kMiss) return -1;
+    auto it = std::lower_bound(uniq.begin(), uniq.end(), static_cast<int32_t>(row));
+    return it != uniq.end() && *it == static_cast<int32_t>(row) ? it - uniq.begin() : -1;
+  };
+
+  // exclusion CSR: one row per distinct query, sorted candidate rows inside it
+  std::vector<int64_t> eoff(static_cast<size_t>(nu) + 1, 0);
+  std::vector<int32_t> erows;
+  if (ne > 0 && nu > 0 && C > 0) {
+    std::vector<uint32_t> er_q, er_c;
+    lookup_rows(QS, eq, ne, er_q);
+    lookup_rows(CS, ec, ne, er_c);
+    std::vector<uint64_t> pairs;
+    pairs.reserve(static_cast<size_t>(ne));
+    for (int64_t e = 0; e < ne; ++e) {
+      const int64_t u = upos(er_q[e]);
+      if (u < 0 || er_c[e] == kMiss) continue;
+      pairs.push_back((static_cast<uint64_t>(u) << 32) | er_c[e]);
+    }
+    std::sort(pairs.begin(), pairs.end());
+    pairs.erase(std::unique(pairs.begin(), pairs.end()), pairs.end());
+    erows.resize(pairs.size());
+    for (size_t x = 0; x < pairs.size(); ++x) {
+      ++eoff[(pairs[x] >> 32) + 1];
+      erows[x] = static_cast<int32_t>(pairs[x] & 0xFFFFFFFFu);
+    }
+    for (int64_t u = 0; u < nu; ++u) eoff[u + 1] += eoff[u];
+  }
+
+  std::vector<int32_t> uid(static_cast<size_t>(nu) * N, 0), ucnt(static_cast<size_t>(nu), 0);
+  std::vector<double> usc(scores_out ? static_cast<size_t>(nu) * N : 0, 0.0);
+  if (nu > 0 && C > 0) {
+    DeviceGuard g(s.device);
+    if (s.rec_id_gen[cside] != ctx->layout_gen || s.rec_id[cside].bytes() < static_cast<size_t>(C) * 4) {
+      s.rec_id[cside].alloc(static_cast<size_t>(C) * 4);
+      MF_HIP(hipMemcpy(s.rec_id[cside].get(), CS.row_id.data(), static_cast<size_t>(C) * 4, hipMemcpyHostToDevice));
+      s.rec_id_gen[cside] = ctx->layout_gen;
+    }
+    s.rec_q.alloc(static_cast<size_t>(nu) * 4);
+    s.rec_eoff.alloc(eoff.size() * 8);
+    s.rec_erows.alloc(std::max<size_t>(erows.size(), 1) * 4);
+    MF_HIP(hipMemcpy(s.rec_q.get(), uniq.data(), static_cast<size_t>(nu) * 4, hipMemcpyHostToDevice));
+    MF_HIP(hipMemcpy(s.rec_eoff.get(), eoff.data(), eoff.size() * 8, hipMemcpyHostToDevice));
+    if (!erows.empty()) MF_HIP(hipMemcpy(s.rec_erows.get(), erows.data(), erows.size() * 4, hipMemcpyHostToDevice));
+
+    int64_t batch = 8192;
+    if (const std::string v = test_knob("rec_batch"); !v.empty()) batch = std::max<int64_t>(1, std::atoll(v.c_str()));
+    batch = std::min(batch, nu);
+    // S: enough workgroups for two per CU, each split at least one candidate tile of 128 rows
+    const int qt = recommend_query_tile(top_n, ctx->f64);
+    const int64_t qtiles = (batch + qt - 1) / qt;
+    int64_t S = std::min<int64_t>((512 + qtiles - 1) / qtiles, (C + 127) / 128);
+    if (const std::string v = test_knob("rec_split"); !v.empty()) S = std::atoll(v.c_str());
+    S = std::max<int64_t>(1, std::min<int64_t>({S, 64, C}));
+
+    s.rec_part.alloc(static_cast<size_t>(batch) * S * N * recommend_key_bytes(ctx->f64));
+    s.rec_ids.alloc(static_cast<size_t>(batch) * N * 4);
+    s.rec_scores.alloc(static_cast<size_t>(batch) * N * 8);
+    s.rec_counts.alloc(static_cast<size_t>(batch) * 4);
+    const void* Q = qside == kSideU ? s.uf.get() : s.itf.get();
+    const void* Cf = cside == kSideU ? s.uf.get() : s.itf.get();
+    for (int64_t b0 = 0; b0 < nu; b0 += batch) {
+      const int64_t nb = std::min(batch, nu - b0);
+      launch_recommend(s.stream, Q, Cf, s.rec_q.as<int32_t>() + b0, static_cast<int>(nb), static_cast<int32_t>(C),
+                       static_cast<int>(S), k, top_n, ctx->f64, s.rec_id[cside].as<int32_t>(),
+                       s.rec_eoff.as<int64_t>() + b0, s.rec_erows.as<int32_t>(), s.rec_part.get(),
+                       s.rec_ids.as<int32_t>(), s.rec_scores.as<double>(), s.rec_counts.as<int32_t>());
+      MF_HIP(hipGetLastError());
+      MF_HIP(hipStreamSynchronize(s.stream));
+      MF_HIP(hipMemcpy(uid.data() + static_cast<size_t>(b0) * N, s.rec_ids.get(), static_cast<size_t>(nb) * N * 4,
+                       hipMemcpyDeviceToHost));
+      if (scores_out)
+        MF_HIP(hipMemcpy(usc.data() + static_cast<size_t>(b0) * N, s.rec_scores.get(), static_cast<size_t>(nb) * N * 8,
+                         hipMemcpyDeviceToHost));
+      MF_HIP(hipMemcpy(ucnt.data() + b0, s.rec_counts.get(), static_cast<size_t>(nb) * 4, hipMemcpyDeviceToHost));
+    }
+  }
+  parallel_for(nq, [&](int64_t b, int64_t e, int) {
+    for (int64_t j = b; j < e; ++j) {
+      const int64_t u = upos(qr[j]);
+      int32_t* io = ids_out + static_cast<size_t>(j) * N;
+      if (u < 0) {
+        counts_out[j] = 0;
+        std::fill(io, io + N, 0);
+        if (scores_out) std::fill(scores_out + static_cast<size_t>(j) * N, scores_out + static_cast<size_t>(j + 1) * N, 0.0);
+        continue;
+      }
+      counts_out[j] = ucnt[u];
+      std::memcpy(io, uid.data() + static_cast<size_t>(u) * N, N * 4);
+      if (scores_out) std::memcpy(scores_out + static_cast<size_t>(j) * N, usc.data() + static_cast<size_t>(u) * N, N * 8);
+    }
+  });
+}
+
+// ---------------------------------------------------------------------------------------
 // Online micro-batches (single shard).
 int32_t online_row(mf_ctx* ctx, SideLayout& S, int32_t id, std::vector<int32_t>& fresh) {
   const int32_t row = S.index.find(id);
@@ -2057,6 +2189,7 @@ int32_t online_row(mf_ctx* ctx, SideLayout& S, int32_t id, std::vector<int32_t>&
   S.row_block.push_back(-1);
   fresh.push_back(id);
   ctx->order_dirty = true;
+  ++ctx->layout_gen;
   return nr;
 }
 
@@ -2107,6 +2240,7 @@ void online_update(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double
     ctx->U = SideLayout();
     ctx->I = SideLayout();
     ctx->have_model = true;
+    ++ctx->layout_gen;
   }
   const int k = ctx->P.num_factors;
   PhaseClock clk;
@@ -2773,7 +2907,7 @@ int mf_set_factors(mf_ctx* ctx, int side, const int32_t* ids, const double* vecs
     MF_REQUIRE(ctx && (n == 0 || (ids && vecs)), "null argument");
     MF_REQUIRE(side == MF_SIDE_USER || side == MF_SIDE_ITEM, "bad side");
     det_spec_wait(ctx, true);  // rows may be added: the layouts change
-    if (!ctx->have_model) { ctx->U = SideLayout(); ctx->I = SideLayout(); ctx->have_model = true; }
+    if (!ctx->have_model) { ctx->U = SideLayout(); ctx->I = SideLayout(); ctx->have_model = true; ++ctx->layout_gen; }
     SideLayout& S = side_of(ctx, side);
     std::vector<int32_t> fresh;
     std::vector<int32_t> rows(n);
@@ -2840,6 +2974,30 @@ int mf_empirical_risk(mf_ctx* ctx, const int32_t* u, const int32_t* i, const dou
     }
     EvalOut e = evaluate(ctx, u, i, r, n, mult.data(), lambda, nullptr, nullptr);
     *risk = e.risk;
+  });
+}
+
+int mf_recommend(mf_ctx* ctx, int query_side, const int32_t* queries, int64_t n_queries, int32_t top_n,
+                 const int32_t* excl_query, const int32_t* excl_cand, int64_t n_excl, int32_t* ids_out,
+                 double* scores_out, int32_t* counts_out) {
+  return guarded([&] {
+    MF_REQUIRE(ctx, "null context");
+    MF_REQUIRE(query_side == MF_SIDE_USER || query_side == MF_SIDE_ITEM, "bad side");
+    MF_REQUIRE(top_n >= 1 && top_n <= MF_RECOMMEND_MAX_TOP,
+               "top_n must be in [1, " + std::to_string(MF_RECOMMEND_MAX_TOP) + "]");
+    MF_REQUIRE(n_queries >= 0 && n_excl >= 0, "negative count");
+    MF_REQUIRE(n_excl == 0 || (excl_query && excl_cand), "null exclusion list");
+    if (ctx->rank_mode)
+      fail(MF_ERR_STATE, "mf_recommend runs on a single-process context; a rank-mode context (mf_create_rank) "
+                         "holds only its own users' rows");
+    if (!ctx->have_model)
+      fail(MF_ERR_NOT_FITTED, "The MatrixFactorization model has not been fitted to data. "
+                              "Prior to predicting values, it has to be trained on data.");
+    require_healthy(ctx);
+    if (n_queries == 0) return;
+    MF_REQUIRE(queries && ids_out && counts_out, "null argument");
+    recommend(ctx, query_side, queries, n_queries, top_n, excl_query, excl_cand, n_excl, ids_out, scores_out,
+              counts_out);
   });
 }
 

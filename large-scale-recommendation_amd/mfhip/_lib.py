@@ -36,6 +36,7 @@ ONLINE_SPARK_SWEEP = 2
 INIT_PSEUDO_RANDOM = 0
 INIT_SEEDED = 1
 UID_BYTES = 128
+RECOMMEND_MAX_TOP = 128
 
 
 class MFError(RuntimeError):
@@ -94,7 +95,7 @@ EXPORTS = [
     "mf_block_update", "mf_online_update", "mf_lookup", "mf_set_profiling", "mf_get_stats",
     "mf_reset_stats", "mf_jvm_shuffle", "mf_jvm_block_of", "mf_jvm_random_factors",
     "mf_learning_rate", "mf_get_params", "mf_read_ratings", "mf_save_model", "mf_load_model",
-    "mf_dsgd_restart", "mf_online_update_out",
+    "mf_dsgd_restart", "mf_online_update_out", "mf_recommend",
 ]
 # The test hooks include/mfhip_testing.h declares (not product surface; same library).
 TESTING_EXPORTS = [
@@ -169,6 +170,8 @@ def lib() -> C.CDLL:
         "mf_dsgd_restart": (C.c_int, [_ctxp]),
         "mf_online_update_out": (C.c_int, [_ctxp, _i32p, _i32p, _f64p, C.c_int64, C.c_int, C.c_int, _i64p, _i64p,
                                            _f64p, _f64p]),
+        "mf_recommend": (C.c_int, [_ctxp, C.c_int, _i32p, C.c_int64, C.c_int32, _i32p, _i32p, C.c_int64, _i32p, _f64p,
+                                   _i32p]),
         "mf_debug_ring_schedule": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, _i32p, _i32p, _i32p, _i32p]),
         "mf_debug_plan_digest": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
         "mf_debug_build_flags": (C.c_int32, []),

@@ -142,6 +142,29 @@ class Context:
                                         float(lam), C.byref(v)))
         return v.value
 
+    def recommend(self, queries, top_n: int, side: int = L.SIDE_USER, exclude=None, scores: bool = True):
+        """mf_recommend: for every query id (users for side=SIDE_USER, items for SIDE_ITEM) the top_n ids
+        of the other side by p.q, scored and selected on the device.  exclude: (query ids, candidate
+        ids) pairs never returned.  Returns (ids [n, top_n], scores [n, top_n] or None, counts [n]):
+        row j holds counts[j] valid entries, score descending, ties by id ascending; the rest is 0."""
+        q = as_i32(queries)
+        n, top_n = len(q), int(top_n)
+        rows = max(n, 1) * max(top_n, 1)
+        ids = np.zeros(rows, np.int32)
+        sc = np.zeros(rows, np.float64) if scores else None
+        counts = np.zeros(max(n, 1), np.int32)
+        eq = ec = None
+        ne = 0
+        if exclude is not None:
+            eq, ec = as_i32(exclude[0]), as_i32(exclude[1])
+            ne = same_length(eq, ec)
+        check(L.lib().mf_recommend(self._h, int(side), ptr(q, C.c_int32), n, top_n,
+                                   ptr(eq, C.c_int32) if ne else None, ptr(ec, C.c_int32) if ne else None, ne,
+                                   ptr(ids, C.c_int32), ptr(sc, C.c_double) if scores else None,
+                                   ptr(counts, C.c_int32)))
+        shape = (n, max(top_n, 1))
+        return (ids[:n * shape[1]].reshape(shape), sc[:n * shape[1]].reshape(shape) if scores else None, counts[:n])
+
     # -- online ----------------------------------------------------------------
     def online_update(self, u, i, r, flavour: int = L.ONLINE_NEXT_FACTORS, num_partitions: int = 0):
         u, i, r = as_i32(u), as_i32(i), as_f64(r)

@@ -192,6 +192,28 @@ class DSGDforMF:
         self._require_fit()
         return self._ctx.predict(u, i)
 
+    # MatrixFactorizationModel.recommendProducts / recommendUsers / recommendProductsForUsers (the
+    # model OnlineSpark.scala:12, 126 builds); Rating(user, product, rating) as (user, item, score)
+    def recommendProducts(self, user: int, num: int) -> List[Tuple[int, int, float]]:
+        self._require_fit()
+        ids, sc, cnt = self._ctx.recommend([int(user)], num, side=L.SIDE_USER)
+        return [(int(user), int(ids[0, x]), float(sc[0, x])) for x in range(int(cnt[0]))]
+
+    def recommendUsers(self, item: int, num: int) -> List[Tuple[int, int, float]]:
+        self._require_fit()
+        ids, sc, cnt = self._ctx.recommend([int(item)], num, side=L.SIDE_ITEM)
+        return [(int(ids[0, x]), int(item), float(sc[0, x])) for x in range(int(cnt[0]))]
+
+    def recommendProductsForUsers(self, num: int, users=None, exclude=None) -> dict:
+        """users=None: every user of the model.  exclude: (user ids, item ids) pairs never recommended."""
+        self._require_fit()
+        if users is None:
+            users = np.array([f.id for f in self.factorsOption[0]], np.int32)
+        users = L.as_i32(users)
+        ids, sc, cnt = self._ctx.recommend(users, num, side=L.SIDE_USER, exclude=exclude)
+        return {int(u): [(int(u), int(ids[j, x]), float(sc[j, x])) for x in range(int(cnt[j]))]
+                for j, u in enumerate(users)}
+
     def rmse(self, labeled) -> Tuple[float, int]:
         self._require_fit()
         u, i, r = _columns(labeled)
