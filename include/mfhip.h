@@ -70,6 +70,10 @@ extern "C" {
 #define MF_INIT_PSEUDO_RANDOM 0  /* new Random(id), k x nextDouble   (:23-27)           */
 #define MF_INIT_SEEDED 1         /* new Random(id ^ seed), as DSGD init (DSGDforMF.scala:548) */
 
+/* ALS regularisation (mf_als_run). */
+#define MF_ALS_REG_WEIGHTED 0 /* lambda * n_row on the diagonal: MLlib's ALS-WR, what ALS.train does */
+#define MF_ALS_REG_PLAIN 1    /* lambda on the diagonal                                            */
+
 #define MF_UID_BYTES 128         /* RCCL unique id */
 
 /* Parameters mirror MatrixFactorization.scala:201-223 and DSGDforMF.scala:163-169;
@@ -201,6 +205,39 @@ int mf_recommend(mf_ctx* ctx, int query_side, const int32_t* queries, int64_t n_
                  int32_t top_n,
                  const int32_t* excl_query, const int32_t* excl_cand, int64_t n_excl,
                  int32_t* ids_out, double* scores_out, int32_t* counts_out);
+
+/* ALS.train(ratings, rank = params.num_factors, iterations, lambda), the "ALS" branch of
+   OnlineSpark.buildModelCombineOffline (sp/OnlineSpark.scala:125-131), as alternating least squares
+   on the device.  mf_als_prepare keeps the ratings on the device as one CSR per side (the ratings of
+   a row in the order of the caller's arrays); mf_als_run runs half-sweeps; mf_als_fit is
+   mf_als_prepare followed by mf_als_run(2 * iterations).  n == 0 makes mf_als_fit a no-op.
+   Order and arithmetic.  A half-sweep solves, for every row a of one side with at least one rating,
+       (sum_j q_j q_j^T + lambda' I) x = sum_j r_j q_j
+   over that row's ratings j (duplicate pairs included), q_j the counterpart's row as it stands when
+   the half-sweep begins; lambda' = lambda * n_a (n_a = the row's rating count) for
+   MF_ALS_REG_WEIGHTED and lambda' = lambda for MF_ALS_REG_PLAIN.  The solve is a Cholesky
+   factorisation and two triangular solves; a pivot that is not a positive finite number makes that
+   row NaN.  Half-sweep 0 solves the item side from the user factors, half-sweep 1 the user side from
+   the item factors, and so on alternately (MLlib's order); the counter starts at 0 in mf_als_prepare
+   and continues across mf_als_run calls.  MF_MODE_DETERMINISTIC_F64 contexts compute in f64,
+   MF_MODE_FAST_F32 contexts in f32 throughout (ratings and lambda rounded to f32).  Results are
+   bitwise reproducible from run to run.
+   Model.  Rows the context already holds are kept (a warm start: the online + offline combination);
+   ids not yet in the model are inserted under mf_online_update's rules for a fitted or prepared
+   context, with the initial values mf_dsgd_fit gives them (k x nextDouble of new Random(id ^ seed)).
+   Rows with no rating in the data are left untouched.  After a run the context is fitted.
+   MLlib's own initial factors (normalised |Gaussian| draws from a per-partition XORShift stream)
+   are NOT reproduced: MLlib is not part of the reference tree and its stream depends on Spark's
+   partitioning, so factors agree with MLlib's in quality, not in bits.
+   Errors.  MF_ERR_INVALID: lambda <= 0, a negative count, an unknown reg, or a rank above 128 (the
+   k x k normal matrix of a row is kept in LDS).  MF_ERR_STATE: mf_als_run before mf_als_prepare (or
+   after a later mf_dsgd_prepare / mf_dsgd_fit, which rebuilds the rows), a rank-mode context, or a
+   context on more than one device. */
+int mf_als_fit(mf_ctx* ctx, const int32_t* users, const int32_t* items, const double* ratings, int64_t n,
+               int32_t iterations, double lambda, int32_t reg);
+int mf_als_prepare(mf_ctx* ctx, const int32_t* users, const int32_t* items, const double* ratings,
+                   int64_t n);
+int mf_als_run(mf_ctx* ctx, int64_t half_sweeps, double lambda, int32_t reg);
 
 /* Exact updateLocalFactors replacement (DSGDforMF.scala:378-418) on caller buffers:
    users[nu x k], items[ni x k] are updated in place; omegas are per row.  Reentrant

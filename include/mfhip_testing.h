@@ -56,6 +56,13 @@ int32_t mf_debug_build_flags(void);
 /* Device memory this process holds through the library: out[0] = live bytes, out[1] = the
    high-water mark since the library was loaded (rank rehearsals report it per rank). */
 int mf_debug_device_bytes(int64_t out[2]);
+/* mf_debug_als_normal_eq: after mf_als_prepare, the system an ALS half-sweep would solve for `id` of
+   `side` from the current factors: A_out[k * k] = sum q q^T + lambda' I (full symmetric, row-major)
+   and b_out[k] = sum r q, as the device accumulates them -- through the sweep's own kernels, the
+   chunked path of a long row included -- widened to f64.  The factors are not changed.
+   MF_ERR_INVALID for an id that is unknown or has no rating in the prepared data. */
+int mf_debug_als_normal_eq(mf_ctx* ctx, int side, int32_t id, double lambda, int32_t reg, double* A_out,
+                           double* b_out);
 
 #ifdef __cplusplus
 }

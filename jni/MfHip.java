@@ -32,6 +32,10 @@ public final class MfHip {
   public static native void dsgdRun(long ctx, long supersteps);
   public static native void dsgdRestart(long ctx);
   public static native void sync(long ctx);
+  // ALS.train(ratings, rank = numFactors, iterations, lambda) (OnlineSpark.scala:125-131);
+  // reg: 0 = lambda * n_row (ALS-WR, what ALS.train does), 1 = plain lambda
+  public static native void alsFit(long ctx, int[] users, int[] items, double[] ratings,
+                                   int iterations, double lambda, int reg);
   // unblock (DSGDforMF.scala:245-255) and checkpoint restore
   public static native long numFactors(long ctx, int side);
   public static native long getFactors(long ctx, int side, int[] idsOut, double[] vecsOut);

@@ -167,6 +167,24 @@ JNIEXPORT void JNICALL JFN(dsgdPrepare)(JNIEnv* env, jclass c, jlong h, jintArra
   with_ratings(env, h, u, i, r, mf_dsgd_prepare);
 }
 
+/* ALS.train(ratings, rank, iterations, lambda) (sp/OnlineSpark.scala:125-131): mf_als_fit */
+JNIEXPORT void JNICALL JFN(alsFit)(JNIEnv* env, jclass c, jlong h, jintArray u, jintArray i, jdoubleArray r,
+                                   jint iterations, jdouble lambda, jint reg) {
+  jsize n = 0;
+  if (rating_columns(env, u, i, r, &n)) return;
+  Elems eu = {0}, ei = {0}, er = {0};
+  if (acquire(env, &eu, u, kInt) || acquire(env, &ei, i, kInt) || acquire(env, &er, r, kDouble)) {
+    release(env, &eu, JNI_ABORT);
+    release(env, &ei, JNI_ABORT);
+    return;
+  }
+  int st = mf_als_fit(CTX(h), (const int32_t*)eu.p, (const int32_t*)ei.p, (const double*)er.p, n, iterations, lambda, reg);
+  release(env, &er, JNI_ABORT);
+  release(env, &ei, JNI_ABORT);
+  release(env, &eu, JNI_ABORT);
+  check(env, st);
+}
+
 JNIEXPORT void JNICALL JFN(dsgdRun)(JNIEnv* env, jclass c, jlong h, jlong supersteps) {
   check(env, mf_dsgd_run(CTX(h), supersteps));
 }

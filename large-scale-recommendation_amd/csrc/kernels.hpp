@@ -234,4 +234,28 @@ void device_fast_schedule(hipStream_t st, const DevRatingBlocks& dr, const Ratin
 void launch_jvm_init_rows(hipStream_t st, const int32_t* ids, int64_t rows, int k, bool xor_seed, int64_t seed,
                           const uint64_t* jump, void* out, bool f64);
 
+// ALS half-sweep (kernels_als.hip).  A work item is a whole row of the side being solved (slot < 0:
+// its system is solved in the kernel and x stored to X[row]) or one chunk of a long row (slot >= 0:
+// its partial matrix and right-hand side go to partial[slot], als_partial_elems(k) elements each);
+// an AlsSplit names a long row's partials [slot0, slot0 + chunks), added in that order and solved.
+// cols / vals: the side's CSR (counterpart rows of Q, ratings in the context's precision).
+// dump != null (the testing hook, one row): the row's k x k matrix and right-hand side are
+// stored there instead of being solved.
+constexpr int kAlsMaxRank = 128;
+struct AlsItem {
+  int64_t begin;  // first rating of the item in cols / vals
+  int32_t row;
+  int32_t count;  // ratings of the item (of the whole row when slot < 0)
+  int32_t slot;
+  int32_t pad;
+};
+struct AlsSplit {
+  int32_t row, slot0, chunks;
+  int32_t count;  // ratings of the whole row (lambda' = lambda * count when weighted)
+};
+size_t als_partial_elems(int k);
+void launch_als(hipStream_t st, const AlsItem* items, int n_items, const AlsSplit* splits, int n_splits,
+                const int32_t* cols, const void* vals, const void* Q, void* X, int k, double lambda, bool weighted,
+                bool f64, void* partial, void* dump);
+
 }  // namespace mfhip

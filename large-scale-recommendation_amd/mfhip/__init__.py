@@ -5,6 +5,7 @@ this package is the Python equivalent of the Scala entry points that bind it.
 """
 from . import _lib, jvm, synth
 from ._lib import MFError, MFNoDeviceError, device_count, version
+from .als import ALS, MatrixFactorizationModel
 from .context import Context, block_update
 from .core import (FactorInitializer, FactorInitializerDescriptor, Factors, FactorUpdater, FactorVector,
                    ItemUpdate, MockFactorUpdater, PseudoRandomFactorInitializer,
@@ -19,5 +20,5 @@ __all__ = [
     "LearningRateMethod", "OnlineMF", "Rating", "FactorVector", "Factors", "FactorUpdater", "SGDUpdater",
     "MockFactorUpdater", "FactorInitializer", "FactorInitializerDescriptor", "PseudoRandomFactorInitializer",
     "PseudoRandomFactorInitializerDescriptor", "RandomFactorInitializer", "RandomFactorInitializerDescriptor",
-    "UserUpdate", "ItemUpdate", "read_ratings",
+    "UserUpdate", "ItemUpdate", "read_ratings", "ALS", "MatrixFactorizationModel",
 ]

@@ -37,6 +37,9 @@ INIT_PSEUDO_RANDOM = 0
 INIT_SEEDED = 1
 UID_BYTES = 128
 RECOMMEND_MAX_TOP = 128
+ALS_REG_WEIGHTED = 0
+ALS_REG_PLAIN = 1
+ALS_MAX_RANK = 128
 
 
 class MFError(RuntimeError):
@@ -95,13 +98,14 @@ EXPORTS = [
     "mf_block_update", "mf_online_update", "mf_lookup", "mf_set_profiling", "mf_get_stats",
     "mf_reset_stats", "mf_jvm_shuffle", "mf_jvm_block_of", "mf_jvm_random_factors",
     "mf_learning_rate", "mf_get_params", "mf_read_ratings", "mf_save_model", "mf_load_model",
-    "mf_dsgd_restart", "mf_online_update_out", "mf_recommend",
+    "mf_dsgd_restart", "mf_online_update_out", "mf_recommend", "mf_als_fit", "mf_als_prepare",
+    "mf_als_run",
 ]
 # The test hooks include/mfhip_testing.h declares (not product surface; same library).
 TESTING_EXPORTS = [
     "mf_debug_levels", "mf_debug_fast_schedule", "mf_debug_fast_split", "mf_debug_ring_schedule",
     "mf_debug_plan_digest", "mf_fast_plan_window", "mf_fast_kernel_name", "mf_debug_build_flags",
-    "mf_debug_device_bytes",
+    "mf_debug_device_bytes", "mf_debug_als_normal_eq",
 ]
 
 _i32p = C.POINTER(C.c_int32)
@@ -172,6 +176,10 @@ def lib() -> C.CDLL:
                                            _f64p, _f64p]),
         "mf_recommend": (C.c_int, [_ctxp, C.c_int, _i32p, C.c_int64, C.c_int32, _i32p, _i32p, C.c_int64, _i32p, _f64p,
                                    _i32p]),
+        "mf_als_fit": (C.c_int, [_ctxp, _i32p, _i32p, _f64p, C.c_int64, C.c_int32, C.c_double, C.c_int32]),
+        "mf_als_prepare": (C.c_int, [_ctxp, _i32p, _i32p, _f64p, C.c_int64]),
+        "mf_als_run": (C.c_int, [_ctxp, C.c_int64, C.c_double, C.c_int32]),
+        "mf_debug_als_normal_eq": (C.c_int, [_ctxp, C.c_int, C.c_int32, C.c_double, C.c_int32, _f64p, _f64p]),
         "mf_debug_ring_schedule": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, _i32p, _i32p, _i32p, _i32p]),
         "mf_debug_plan_digest": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
         "mf_debug_build_flags": (C.c_int32, []),

@@ -1,0 +1,93 @@
+"""Mirror of the Spark MLlib entry point the reference's offline "ALS" branch calls
+(sp/OnlineSpark.scala:125-131): ALS.train(ratings, rank, iterations, lambda) returning a
+MatrixFactorizationModel, backed by mf_als_fit (alternating least squares on the device).
+
+    model = ALS.train(ratings, rank=10, iterations=10, lambda_=0.1)
+    model.predict(user, product)
+    model.recommendProducts(user, 10)
+
+Weighted-lambda regularisation (ALS-WR), as ALS.train uses.  The initial factors are this library's
+(k x nextDouble of new Random(id ^ seed)), not MLlib's partition-dependent XORShift draws.
+"""
+from __future__ import annotations
+
+from typing import List, Tuple
+
+import numpy as np
+
+from . import _lib as L
+from .context import Context
+from .dsgd import _columns, _pairs
+
+
+class MatrixFactorizationModel:
+    """org.apache.spark.mllib.recommendation.MatrixFactorizationModel over a fitted Context;
+    Rating(user, product, rating) is the tuple (user, product, rating)."""
+
+    def __init__(self, ctx: Context):
+        self._ctx = ctx
+        self.rank = ctx.k
+
+    @property
+    def context(self) -> Context:
+        return self._ctx
+
+    def close(self) -> None:
+        self._ctx.close()
+
+    def userFeatures(self) -> List[Tuple[int, np.ndarray]]:
+        ids, vecs = self._ctx.factors(L.SIDE_USER)
+        return [(int(x), v) for x, v in zip(ids, vecs)]
+
+    def productFeatures(self) -> List[Tuple[int, np.ndarray]]:
+        ids, vecs = self._ctx.factors(L.SIDE_ITEM)
+        return [(int(x), v) for x, v in zip(ids, vecs)]
+
+    def predict(self, user, product=None):
+        """predict(user, product) -> float; predict(pairs) -> [(user, product, rating)], unknown ids dropped."""
+        if product is not None:
+            pred, found = self._ctx.predict([int(user)], [int(product)])
+            if not found[0]:
+                raise KeyError(f"unknown user or product: ({user}, {product})")
+            return float(pred[0])
+        u, i = _pairs(user)
+        pred, found = self._ctx.predict(u, i)
+        return [(int(a), int(b), float(c)) for a, b, c, f in zip(u, i, pred, found) if f]
+
+    def recommendProducts(self, user: int, num: int) -> List[Tuple[int, int, float]]:
+        ids, sc, cnt = self._ctx.recommend([int(user)], num, side=L.SIDE_USER)
+        return [(int(user), int(ids[0, x]), float(sc[0, x])) for x in range(int(cnt[0]))]
+
+    def recommendUsers(self, product: int, num: int) -> List[Tuple[int, int, float]]:
+        ids, sc, cnt = self._ctx.recommend([int(product)], num, side=L.SIDE_ITEM)
+        return [(int(ids[0, x]), int(product), float(sc[0, x])) for x in range(int(cnt[0]))]
+
+    def recommendProductsForUsers(self, num: int, users=None, exclude=None) -> dict:
+        """users=None: every user of the model.  exclude: (user ids, item ids) pairs never recommended."""
+        if users is None:
+            users, _ = self._ctx.factors(L.SIDE_USER)
+        users = L.as_i32(users)
+        ids, sc, cnt = self._ctx.recommend(users, num, side=L.SIDE_USER, exclude=exclude)
+        return {int(u): [(int(u), int(ids[j, x]), float(sc[j, x])) for x in range(int(cnt[j]))]
+                for j, u in enumerate(users)}
+
+
+class ALS:
+    @staticmethod
+    def train(ratings, rank: int, iterations: int = 10, lambda_: float = 0.01, mode: str = "deterministic",
+              seed: int = 0) -> MatrixFactorizationModel:
+        """ALS.train(ratings, rank, iterations, lambda); ratings: (user, product, rating) tuples or
+        three arrays."""
+        u, i, r = _columns(ratings)
+        p = L.default_params()
+        p.num_factors = int(rank)
+        p.has_seed = 1
+        p.seed = int(seed)
+        p.mode = L.MODE_FAST_F32 if mode == "fast" else L.MODE_DETERMINISTIC_F64
+        ctx = Context(p)
+        try:
+            ctx.als_fit(u, i, r, int(iterations), float(lambda_), L.ALS_REG_WEIGHTED)
+        except Exception:
+            ctx.close()
+            raise
+        return MatrixFactorizationModel(ctx)

@@ -7,7 +7,8 @@ factors: every micro-batch either
     -- and emits the touched user and item vectors (UpdateSeparatedHashMap.updates, :33-67), or,
   * every `offline_every`-th batch, refits from scratch on the whole rating history --
     OfflineSpark.offlineDSGD with empty initial factors and `iterations` sweeps (:68-89) -- and
-    emits every vector.
+    emits every vector.  With offline_algorithm="ALS" the refit is the reference's other branch,
+    ALS.train(history, numFactors, iterations, 0.1) (OnlineSpark.scala:125-131; mf_als_fit).
 The counters follow the reference (decrement, fire at <= 0, reset).  Every `checkpoint_every`-th
 batch the model is written as an mf_save_model snapshot when `snapshot_dir` is given: the
 localCheckpoint of the reference (:93-99) cuts RDD lineage; here it is a restartable file.
@@ -27,7 +28,10 @@ class OnlineOfflineSpark:
     def __init__(self, num_factors: int, learning_rate: float = 0.01, num_partitions: int = 4,
                  offline_every: int = 10, checkpoint_every: int = 10, iterations: int = 10,
                  init: str = "pseudo_random", seed: int = 0, mode: str = "deterministic",
-                 snapshot_dir: Optional[str] = None):
+                 snapshot_dir: Optional[str] = None, offline_algorithm: str = "DSGD"):
+        if offline_algorithm not in ("DSGD", "ALS"):
+            raise ValueError(f'offline_algorithm must be "DSGD" or "ALS", got {offline_algorithm!r}')
+        self.offline_algorithm = offline_algorithm
         self.k = num_factors
         self.P = num_partitions
         self.offline_every = offline_every
@@ -72,8 +76,11 @@ class OnlineOfflineSpark:
         else:
             hu, hi, hr = (np.concatenate(x) for x in self._hist)
             fresh = Context(self._params)
-            for _ in range(self.iterations):
-                fresh.online_update(hu, hi, hr, L.ONLINE_SPARK_SWEEP, self.P)
+            if self.offline_algorithm == "ALS":
+                fresh.als_fit(hu, hi, hr, self.iterations, 0.1)
+            else:
+                for _ in range(self.iterations):
+                    fresh.online_update(hu, hi, hr, L.ONLINE_SPARK_SWEEP, self.P)
             self.ctx.close()
             self.ctx = fresh
             users, items = np.unique(hu), np.unique(hi)

@@ -85,6 +85,32 @@ class Context:
     def superstep(self, done: int) -> None:
         check(L.lib().mf_dsgd_set_superstep(self._h, int(done)))
 
+    # -- ALS -------------------------------------------------------------------
+    def als_prepare(self, u, i, r) -> None:
+        """mf_als_prepare: ids resolved (unseen ones inserted), both CSRs on the device, counter 0."""
+        u, i, r = as_i32(u), as_i32(i), as_f64(r)
+        same_length(u, i, r)
+        check(L.lib().mf_als_prepare(self._h, ptr(u, C.c_int32), ptr(i, C.c_int32), ptr(r, C.c_double), len(u)))
+
+    def als_run(self, half_sweeps: int, lam: float, reg: int = L.ALS_REG_WEIGHTED) -> None:
+        """mf_als_run: half-sweeps alternate, the item side first; the counter continues across calls."""
+        check(L.lib().mf_als_run(self._h, int(half_sweeps), float(lam), int(reg)))
+
+    def als_fit(self, u, i, r, iterations: int, lam: float, reg: int = L.ALS_REG_WEIGHTED) -> None:
+        """mf_als_fit: als_prepare + als_run(2 * iterations) (ALS.train, OnlineSpark.scala:125-131)."""
+        u, i, r = as_i32(u), as_i32(i), as_f64(r)
+        same_length(u, i, r)
+        check(L.lib().mf_als_fit(self._h, ptr(u, C.c_int32), ptr(i, C.c_int32), ptr(r, C.c_double), len(u),
+                                 int(iterations), float(lam), int(reg)))
+
+    def als_normal_eq(self, side: int, id_: int, lam: float, reg: int = L.ALS_REG_WEIGHTED):
+        """(A [k, k], b [k]) of one row as the device accumulates them (mf_debug_als_normal_eq)."""
+        A = np.empty((self.k, self.k), np.float64)
+        b = np.empty(self.k, np.float64)
+        check(L.lib().mf_debug_als_normal_eq(self._h, int(side), int(id_), float(lam), int(reg), ptr(A, C.c_double),
+                                             ptr(b, C.c_double)))
+        return A, b
+
     # -- factors ---------------------------------------------------------------
     def num_factors(self, side: int) -> int:
         v = C.c_int64(0)

@@ -1,0 +1,140 @@
+#!/usr/bin/env python3
+"""ALS iterations on the NFLX-shaped synthetic (480,189 x 17,770, the training split, k = 128), fast mode.
+
+mf_als_prepare once (its host time is reported), one warm-up iteration, then --iters full iterations
+(item half-sweep + user half-sweep) timed twice over: with the host clock around the blocking
+mf_als_run call, and with the library's device events around every half-sweep's launches
+(mf_set_profiling).  The Gram accumulation and the solve of a row run in one kernel, so they are not
+timed apart; the item and user half-sweeps are.
+
+FLOP convention, per half-sweep: 2 * nnz * k^2 for the normal matrices (the full k x k product per
+rating; the kernel computes the lower-triangle 32 x 32 blocks only, 10 of 16 at k = 128) plus
+(2/3) * k^3 * rows for the factorisations, rows = the rated rows of the side solved.  TFLOP/s is that
+count over the device-event time.
+
+--chunks N[,N...] repeats the measurement with MFHIP_TEST als_chunk=N (ratings per work item of a
+long row).  --dsgd also times one fast DSGD epoch (numBlocks 8) on the same data in the same
+process, the baseline the README records beside the ALS iteration.
+
+Writes profiles/als_bench.json.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "large-scale-recommendation_amd"))
+
+F32_MFMA_PEAK = 157.3e12  # MI355X, v_mfma_f32_32x32x2_f32 (f32 in, f32 accumulate)
+
+
+def als_run(train, k, iters, lam, chunk):
+    from mfhip import _lib as L
+    from mfhip.context import Context
+
+    u, i, r = train
+    if chunk:
+        os.environ["MFHIP_TEST"] = f"als_chunk={chunk}"
+    else:
+        os.environ.pop("MFHIP_TEST", None)
+    p = L.default_params()
+    p.num_factors = k
+    p.mode = L.MODE_FAST_F32
+    nnz = len(u)
+    rows = {"item": len(np.unique(i)), "user": len(np.unique(u))}
+    flop = {s: 2.0 * nnz * k * k + (2.0 / 3.0) * k ** 3 * rows[s] for s in rows}
+    res = {"chunk": chunk or "default", "nnz": nnz, "rows": rows, "k": k, "iters": iters, "lambda": lam,
+           "flop_per_half_sweep": flop}
+    with Context(p) as ctx:
+        t0 = time.perf_counter()
+        ctx.als_prepare(u, i, r)
+        res["prepare_host_s"] = time.perf_counter() - t0
+        ctx.als_run(2, lam)  # warm-up
+        ctx.set_profiling(True)
+        half = {"item": [], "user": []}
+        wall = []
+        for _ in range(iters):
+            t0 = time.perf_counter()
+            for side in ("item", "user"):
+                ctx.reset_stats()
+                ctx.als_run(1, lam)
+                half[side].append(ctx.stats()["kernel_ms"])
+            wall.append(time.perf_counter() - t0)
+        ctx.set_profiling(False)
+        rmse, _ = ctx.rmse(u[:2_000_000], i[:2_000_000], r[:2_000_000])
+    res["train_rmse_sample"] = rmse
+    ms = {s: float(np.median(half[s])) for s in half}
+    res["half_sweep_ms"] = {s: {"median": ms[s], "all": half[s]} for s in half}
+    res["iteration_ms_device"] = ms["item"] + ms["user"]
+    res["iteration_ms_host_call"] = float(np.median(wall)) * 1e3
+    res["tflops"] = {s: flop[s] / (ms[s] * 1e-3) / 1e12 for s in half}
+    res["tflops"]["iteration"] = (flop["item"] + flop["user"]) / (res["iteration_ms_device"] * 1e-3) / 1e12
+    res["fraction_of_f32_mfma_peak"] = res["tflops"]["iteration"] * 1e12 / F32_MFMA_PEAK
+    print(f"ALS chunk {res['chunk']}: {res['iteration_ms_device']:.1f} ms / iteration on the device "
+          f"(item half {ms['item']:.1f} ms, {res['tflops']['item']:.1f} TFLOP/s; user half {ms['user']:.1f} ms, "
+          f"{res['tflops']['user']:.1f} TFLOP/s), host call {res['iteration_ms_host_call']:.1f} ms; "
+          f"{res['tflops']['iteration']:.1f} TFLOP/s by 2*nnz*k^2 + (2/3)*k^3*rows per half-sweep = "
+          f"{100 * res['fraction_of_f32_mfma_peak']:.1f} % of the f32 MFMA peak; prepare {res['prepare_host_s']:.1f} s; "
+          f"rmse {rmse:.4f}", flush=True)
+    return res
+
+
+def dsgd_epoch(train, k, nb):
+    from mfhip import _lib as L
+    from mfhip.context import Context
+
+    os.environ.pop("MFHIP_TEST", None)
+    p = L.default_params()
+    p.num_factors = k
+    p.num_blocks = nb
+    p.mode = L.MODE_FAST_F32
+    with Context(p) as ctx:
+        ctx.prepare(*train)
+        ctx.run(nb)
+        ctx.sync()
+        t = []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            ctx.run(nb)
+            ctx.sync()
+            t.append(time.perf_counter() - t0)
+    ms = float(np.median(t)) * 1e3
+    print(f"fast DSGD epoch (numBlocks {nb}) on the same data: {ms:.1f} ms", flush=True)
+    return {"epoch_ms": ms, "all_s": t, "n_blocks": nb}
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--iters", type=int, default=3)
+    ap.add_argument("--lam", type=float, default=0.1)
+    ap.add_argument("--chunks", default="", help="comma-separated als_chunk values (empty: the default only)")
+    ap.add_argument("--dsgd", action="store_true", help="also time a fast DSGD epoch on the same data")
+    ap.add_argument("--scale", type=float, default=1.0, help="shrink the synthetic (rehearsal only)")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "als_bench.json"))
+    a = ap.parse_args()
+    from mfhip import _lib as L
+    from mfhip import synth
+    try:
+        if L.device_count() < 1:
+            raise L.MFNoDeviceError(L.MF_ERR_NO_DEVICE, "no device")
+    except L.MFNoDeviceError:
+        sys.exit("als_bench needs a GPU: there is no CPU path to time")
+    nu, ni, nr, k, nb = synth.CONFIGS["NFLX"]
+    train, _ = synth.generate(max(1, int(nu * a.scale)), max(1, int(ni * a.scale)), max(1, int(nr * a.scale))).split()
+    out = {"shape": "NFLX", "scale": a.scale, "runs": []}
+    for c in [int(x) for x in a.chunks.split(",") if x] or [0]:
+        out["runs"].append(als_run(train, k, a.iters, a.lam, c))
+    if a.dsgd:
+        out["dsgd_fast"] = dsgd_epoch(train, k, nb)
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+    print("wrote", a.out)
+
+
+if __name__ == "__main__":
+    main()
