@@ -4,9 +4,15 @@
 // groups; in rotation sub-step t, wave g of a block sweeps cell (item group g, user group
 // (g+t) mod G).  Cells of one sub-step share no user or item row (conflict-free batching).
 //
-// Two drivers of the same schedule (identical results, bit for bit):
-//  * k_fast_superstep (default): ONE persistent launch per superstep.  Wave g sweeps its G
-//    cells in order; before cell t it waits until wave g+1 has finished cell t-1 -- the only
+// This file sweeps every rank the pair kernels (kernels_pair.hip: k = 64, 128, 256) do not take,
+// and those three with MFHIP_TEST fast_kernel=cell (mfhip.cpp choose_fast_kernel).
+//
+// Two drivers of the same schedule (identical results, bit for bit:
+// tests/test_gpu_fast_cell.py test_persistent_driver_equals_cell):
+//  * k_fast_substep (the default): one launch per sub-step (kernel boundaries order the sub-steps).
+//  * k_fast_superstep (only with MFHIP_TEST fast_kernel=persistent): ONE persistent launch per
+//    superstep.  Wave g sweeps its G cells in order; before cell t it waits until wave g+1 has
+//    finished cell t-1 -- the only
 //    earlier user of user group (g+t) mod G in this superstep -- so the rotation runs as a
 //    systolic pipeline instead of G grid-wide barriers, and a wave holding a hot item never
 //    waits for the slowest cell of every sub-step.  Hand-off (MI355X_MICROARCH.md, Valid
@@ -14,7 +20,6 @@
 //    bypass), the wave drains with s_waitcnt vmcnt(0), then one lane stores the progress word
 //    with an agent-scope relaxed atomic; the consumer polls that word with sc1 loads.  Each
 //    workgroup is one wave.  Spins are bounded by s_memrealtime; a timeout sets err[0].
-//  * k_fast_substep: one launch per sub-step (kernel boundaries order the sub-steps).
 //
 // Inside a cell the ratings form one contiguous run per item: the item row lives in VGPRs
 // for the whole run (hot items never leave registers), user rows are gathered D ratings ahead
