@@ -1,0 +1,446 @@
+// abi.cpp -- the C ABI of libmfhip.so: every entry point of include/mfhip.h and
+// include/mfhip_testing.h, as a thin wrapper that checks its arguments and calls the feature's
+// function (mfhip.cpp, online.cpp, eval.cpp, als.cpp; declared in context.hpp) under `guarded`.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "common.hpp"
+#include "context.hpp"
+#include "jvm_random.hpp"
+#include "kernels.hpp"
+#include "plan.hpp"
+
+using namespace mfhip;
+
+extern "C" {
+
+void mf_params_init(mf_params* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof(*p));
+  p->num_factors = 10;        // MatrixFactorization.scala:201-203
+  p->iterations = 10;         // :209-211
+  p->lambda = 1.0;            // :205-207
+  p->learning_rate = 0.001;   // DSGDforMF.scala:163-165
+  p->lr_method = MF_LR_DEFAULT;  // :167-169
+  p->lr_arg = 0.0;
+  p->num_blocks = 1;          // Blocks None -> getOrElse(1) (:270)
+  p->seed = 0;                // Seed Some(0L) (:217-219)
+  p->has_seed = 1;
+  p->mode = MF_MODE_DETERMINISTIC_F64;
+  p->online_learning_rate = 0.01;  // SparkExample.scala:33 SGDUpdater(0.01)
+  p->online_init = MF_INIT_PSEUDO_RANDOM;
+  p->fast_waves = 0;
+}
+
+const char* mf_last_error(void) { return g_last_error.c_str(); }
+const char* mf_version(void) { return "mfhip 0.1.0 (gfx950)"; }
+
+int mf_device_count(int* n) {
+  return guarded([&] {
+    MF_REQUIRE(n, "null");
+    int c = 0;
+    hipError_t e = hipGetDeviceCount(&c);
+    *n = (e == hipSuccess) ? c : 0;
+  });
+}
+
+int mf_create(const mf_params* p, const int* device_ids, int n_devices, mf_ctx** out) {
+  return guarded([&] {
+    MF_REQUIRE(out, "out is null");
+    *out = nullptr;
+    *out = create_ctx(p, device_ids, n_devices);
+  });
+}
+
+int mf_comm_unique_id(uint8_t uid_out[MF_UID_BYTES]) {
+  return guarded([&] {
+    MF_REQUIRE(uid_out, "null");
+    static_assert(sizeof(ncclUniqueId) <= MF_UID_BYTES, "uid size");
+    ncclUniqueId id;
+    MF_NCCL(ncclGetUniqueId(&id));
+    std::memset(uid_out, 0, MF_UID_BYTES);
+    std::memcpy(uid_out, &id, sizeof(id));
+  });
+}
+
+int mf_create_rank(const mf_params* p, int device_id, int nranks, int rank, const uint8_t uid[MF_UID_BYTES],
+                   mf_ctx** out) {
+  return guarded([&] {
+    MF_REQUIRE(out && uid, "null argument");
+    *out = nullptr;
+    *out = create_rank_ctx(p, device_id, nranks, rank, uid);
+  });
+}
+
+int mf_destroy(mf_ctx* ctx) {
+  return guarded([&] {
+    if (ctx) destroy_ctx(ctx);
+  });
+}
+
+int mf_dsgd_prepare(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n) {
+  return guarded([&] {
+    MF_REQUIRE(ctx, "null context");
+    prepare(ctx, u, i, r, n);
+  });
+}
+
+int mf_dsgd_run(mf_ctx* ctx, int64_t supersteps) {
+  return guarded([&] {
+    MF_REQUIRE(ctx, "null context");
+    MF_REQUIRE(supersteps >= 0, "negative superstep count");
+    run_supersteps(ctx, supersteps);
+  });
+}
+
+int mf_dsgd_superstep(mf_ctx* ctx, int64_t* done) {
+  return guarded([&] {
+    MF_REQUIRE(ctx && done, "null argument");
+    *done = ctx->superstep_done;
+  });
+}
+
+int mf_dsgd_set_superstep(mf_ctx* ctx, int64_t done) {
+  return guarded([&] {
+    MF_REQUIRE(ctx && done >= 0, "bad argument");
+    MF_REQUIRE(ctx->prepared, "mf_dsgd_set_superstep before mf_dsgd_prepare");
+    det_spec_wait(ctx, true);
+    sync_all(ctx);
+    ctx->superstep_done = done;
+    reset_item_loc(ctx);
+  });
+}
+
+int mf_dsgd_restart(mf_ctx* ctx) {
+  return guarded([&] {
+    MF_REQUIRE(ctx, "null context");
+    MF_REQUIRE(ctx->prepared, "mf_dsgd_restart before mf_dsgd_prepare");
+    det_spec_wait(ctx, true);
+    ctx->failed.clear();
+    sync_all(ctx);
+    init_factors(ctx);
+    ctx->superstep_done = 0;
+    reset_item_loc(ctx);
+  });
+}
+
+int mf_sync(mf_ctx* ctx) {
+  return guarded([&] {
+    MF_REQUIRE(ctx, "null context");
+    sync_all(ctx);
+  });
+}
+
+int mf_dsgd_fit(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n) {
+  return guarded([&] {
+    MF_REQUIRE(ctx, "null context");
+    prepare(ctx, u, i, r, n);
+    run_supersteps(ctx, static_cast<int64_t>(ctx->P.iterations) * ctx->nb);
+    sync_all(ctx);
+  });
+}
+
+int mf_num_factors(mf_ctx* ctx, int side, int64_t* count) {
+  return guarded([&] {
+    MF_REQUIRE(ctx && count, "null argument");
+    MF_REQUIRE(side == MF_SIDE_USER || side == MF_SIDE_ITEM, "bad side");
+    const SideLayout& S = side_of(ctx, side);
+    if (!ctx->rank_mode || side == MF_SIDE_ITEM || !ctx->prepared) { *count = S.rows(); return; }
+    const int me = ctx->shards[0].index;
+    *count = S.block_start[(me + 1) * ctx->c] - S.block_start[me * ctx->c];
+  });
+}
+
+int mf_get_factors(mf_ctx* ctx, int side, int32_t* ids, double* vecs, int64_t cap, int64_t* written) {
+  return guarded([&] {
+    MF_REQUIRE(ctx, "null context");
+    MF_REQUIRE(side == MF_SIDE_USER || side == MF_SIDE_ITEM, "bad side");
+    get_factors(ctx, side, ids, vecs, cap, written);
+  });
+}
+
+int mf_set_factors(mf_ctx* ctx, int side, const int32_t* ids, const double* vecs, int64_t n) {
+  return guarded([&] {
+    MF_REQUIRE(ctx && (n == 0 || (ids && vecs)), "null argument");
+    MF_REQUIRE(side == MF_SIDE_USER || side == MF_SIDE_ITEM, "bad side");
+    set_factors(ctx, side, ids, vecs, n);
+  });
+}
+
+int mf_get_params(mf_ctx* ctx, mf_params* out) {
+  return guarded([&] {
+    MF_REQUIRE(ctx && out, "null argument");
+    *out = ctx->P;
+  });
+}
+
+int mf_predict(mf_ctx* ctx, const int32_t* u, const int32_t* i, int64_t n, double* out, uint8_t* found) {
+  return guarded([&] {
+    MF_REQUIRE(ctx, "null context");
+    MF_REQUIRE(n == 0 || (u && i && out && found), "null argument");
+    evaluate(ctx, u, i, nullptr, n, nullptr, 0.0, out, found);
+  });
+}
+
+int mf_rmse(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n, double* rmse,
+            int64_t* matched) {
+  return guarded([&] {
+    MF_REQUIRE(ctx && rmse, "null argument");
+    MF_REQUIRE(n == 0 || (u && i && r), "null argument");
+    EvalOut e = evaluate(ctx, u, i, r, n, nullptr, 0.0, nullptr, nullptr);
+    *rmse = e.cnt > 0 ? std::sqrt(e.sse / e.cnt) : std::nan("");
+    if (matched) *matched = static_cast<int64_t>(e.cnt);
+  });
+}
+
+int mf_empirical_risk(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n,
+                      double lambda, double* risk) {
+  return guarded([&] {
+    MF_REQUIRE(ctx && risk, "null argument");
+    MF_REQUIRE(n == 0 || (u && i && r), "null argument");
+    // the (user, item)-keyed join multiplies duplicate pairs (MatrixFactorization.scala:175)
+    std::vector<uint64_t> key(n);
+    for (int64_t j = 0; j < n; ++j)
+      key[j] = (static_cast<uint64_t>(static_cast<uint32_t>(u[j])) << 32) | static_cast<uint32_t>(i[j]);
+    std::vector<uint64_t> sorted = key;
+    std::sort(sorted.begin(), sorted.end());
+    std::vector<int32_t> mult(n);
+    for (int64_t j = 0; j < n; ++j) {
+      auto rg = std::equal_range(sorted.begin(), sorted.end(), key[j]);
+      mult[j] = static_cast<int32_t>(rg.second - rg.first);
+    }
+    EvalOut e = evaluate(ctx, u, i, r, n, mult.data(), lambda, nullptr, nullptr);
+    *risk = e.risk;
+  });
+}
+
+int mf_recommend(mf_ctx* ctx, int query_side, const int32_t* queries, int64_t n_queries, int32_t top_n,
+                 const int32_t* excl_query, const int32_t* excl_cand, int64_t n_excl, int32_t* ids_out,
+                 double* scores_out, int32_t* counts_out) {
+  return guarded([&] {
+    MF_REQUIRE(ctx, "null context");
+    MF_REQUIRE(query_side == MF_SIDE_USER || query_side == MF_SIDE_ITEM, "bad side");
+    MF_REQUIRE(top_n >= 1 && top_n <= MF_RECOMMEND_MAX_TOP,
+               "top_n must be in [1, " + std::to_string(MF_RECOMMEND_MAX_TOP) + "]");
+    MF_REQUIRE(n_queries >= 0 && n_excl >= 0, "negative count");
+    MF_REQUIRE(n_excl == 0 || (excl_query && excl_cand), "null exclusion list");
+    if (ctx->rank_mode)
+      fail(MF_ERR_STATE, "mf_recommend runs on a single-process context; a rank-mode context (mf_create_rank) "
+                         "holds only its own users' rows");
+    if (!ctx->have_model)
+      fail(MF_ERR_NOT_FITTED, "The MatrixFactorization model has not been fitted to data. "
+                              "Prior to predicting values, it has to be trained on data.");
+    require_healthy(ctx);
+    if (n_queries == 0) return;
+    MF_REQUIRE(queries && ids_out && counts_out, "null argument");
+    recommend(ctx, query_side, queries, n_queries, top_n, excl_query, excl_cand, n_excl, ids_out, scores_out,
+              counts_out);
+  });
+}
+
+int mf_als_prepare(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n) {
+  return guarded([&] {
+    MF_REQUIRE(ctx, "null context");
+    als_prepare(ctx, u, i, r, n);
+  });
+}
+
+int mf_als_run(mf_ctx* ctx, int64_t half_sweeps, double lambda, int32_t reg) {
+  return guarded([&] {
+    MF_REQUIRE(ctx, "null context");
+    als_run(ctx, half_sweeps, lambda, reg);
+  });
+}
+
+int mf_als_fit(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n, int32_t iterations,
+               double lambda, int32_t reg) {
+  return guarded([&] {
+    MF_REQUIRE(ctx, "null context");
+    MF_REQUIRE(n >= 0 && iterations >= 0, "negative count");
+    als_check_run(lambda, reg);
+    als_check(ctx);
+    if (n == 0) return;
+    als_prepare(ctx, u, i, r, n);
+    als_run(ctx, 2 * static_cast<int64_t>(iterations), lambda, reg);
+  });
+}
+
+int mf_debug_als_normal_eq(mf_ctx* ctx, int side, int32_t id, double lambda, int32_t reg, double* A_out,
+                           double* b_out) {
+  return guarded([&] {
+    MF_REQUIRE(ctx && A_out && b_out, "null argument");
+    MF_REQUIRE(side == MF_SIDE_USER || side == MF_SIDE_ITEM, "bad side");
+    als_normal_eq(ctx, side, id, lambda, reg, A_out, b_out);
+  });
+}
+
+int mf_block_update(mf_ctx* ctx, const double* r, const int32_t* uidx, const int32_t* iidx, int64_t len,
+                    double* users, const int32_t* uomega, int64_t nu, double* items, const int32_t* iomega,
+                    int64_t ni, int k, int iteration, int rating_block_id, int64_t seed, double lr,
+                    int lr_method, double lr_arg, double lambda) {
+  return guarded([&] {
+    MF_REQUIRE(ctx, "null context");
+    block_update(ctx, r, uidx, iidx, len, users, uomega, nu, items, iomega, ni, k, iteration, rating_block_id, seed,
+                 lr, lr_method, lr_arg, lambda);
+  });
+}
+
+int mf_online_update(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n, int flavour,
+                     int num_partitions, int64_t* touched_users, int64_t* touched_items) {
+  return guarded([&] {
+    MF_REQUIRE(ctx, "null context");
+    det_spec_wait(ctx, true);  // new ids change the layouts the builds read
+    online_update(ctx, u, i, r, n, flavour, num_partitions, touched_users, touched_items);
+  });
+}
+
+int mf_online_update_out(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n, int flavour,
+                         int num_partitions, int64_t* touched_users, int64_t* touched_items, double* user_out,
+                         double* item_out) {
+  return guarded([&] {
+    MF_REQUIRE(ctx, "null context");
+    det_spec_wait(ctx, true);  // new ids change the layouts the builds read
+    online_update(ctx, u, i, r, n, flavour, num_partitions, touched_users, touched_items, user_out, item_out);
+  });
+}
+
+int mf_lookup(mf_ctx* ctx, int side, const int32_t* ids, int64_t n, double* vecs_out, uint8_t* found) {
+  return guarded([&] {
+    MF_REQUIRE(ctx && (n == 0 || (ids && vecs_out && found)), "null argument");
+    MF_REQUIRE(side == MF_SIDE_USER || side == MF_SIDE_ITEM, "bad side");
+    lookup_factors(ctx, side, ids, n, vecs_out, found);
+  });
+}
+
+int mf_set_profiling(mf_ctx* ctx, int on) {
+  return guarded([&] {
+    MF_REQUIRE(ctx, "null context");
+    sync_all(ctx);
+    ctx->profiling = on != 0;
+  });
+}
+
+int mf_get_stats(mf_ctx* ctx, mf_stats* out) {
+  return guarded([&] {
+    MF_REQUIRE(ctx && out, "null argument");
+    sync_all(ctx);
+    ctx->stats.algorithmic_bytes = static_cast<double>(ctx->stats.updates) * bytes_per_update(ctx);
+    *out = ctx->stats;
+  });
+}
+
+int mf_reset_stats(mf_ctx* ctx) {
+  return guarded([&] {
+    MF_REQUIRE(ctx, "null context");
+    sync_all(ctx);
+    const int32_t groups = ctx->stats.groups;
+    const int64_t pads = ctx->stats.pads;
+    ctx->stats = mf_stats{};
+    ctx->stats.groups = groups;
+    ctx->stats.pads = pads;
+  });
+}
+
+int mf_jvm_shuffle(int64_t seed, int64_t len, int32_t* out) {
+  return guarded([&] {
+    MF_REQUIRE(len >= 0 && (len == 0 || out), "bad argument");
+    JavaRandom rng(seed);
+    scala_shuffle(rng, out, len);
+  });
+}
+
+int mf_jvm_block_of(int32_t id, int64_t seed, int32_t n_blocks, int32_t* out) {
+  return guarded([&] {
+    MF_REQUIRE(out && n_blocks >= 1, "bad argument");
+    JavaRandom rng(static_cast<int64_t>(id) ^ seed);
+    *out = rng.nextInt(n_blocks);
+  });
+}
+
+int mf_jvm_random_factors(int64_t rng_seed, int32_t k, double* out) {
+  return guarded([&] {
+    MF_REQUIRE(out && k >= 0, "bad argument");
+    JavaRandom rng(rng_seed);
+    for (int32_t f = 0; f < k; ++f) out[f] = rng.nextDouble();
+  });
+}
+
+int mf_debug_levels(const uint32_t* urow, const uint32_t* irow, const int32_t* order, int64_t n, int32_t* level_out) {
+  return guarded([&] {
+    debug_levels(urow, irow, order, n, level_out);
+  });
+}
+
+int mf_debug_fast_schedule(const int32_t* u, const int32_t* i, int64_t n, int32_t n_blocks, int64_t seed,
+                           int32_t groups, int32_t blocking, int32_t window, int32_t k, int32_t* block_out,
+                           int32_t* substep_out, int32_t* group_out, int64_t* pos_out) {
+  return mf_debug_fast_split(u, i, n, n_blocks, seed, groups, blocking, window, k, 0, block_out, substep_out, group_out,
+                             pos_out, nullptr);
+}
+
+int mf_debug_fast_split(const int32_t* u, const int32_t* i, int64_t n, int32_t n_blocks, int64_t seed,
+                        int32_t groups, int32_t blocking, int32_t window, int32_t k, int32_t item_split,
+                        int32_t* block_out, int32_t* substep_out, int32_t* group_out, int64_t* pos_out,
+                        int32_t* replica_out) {
+  return mfhip::debug_fast_plan(u, i, n, n_blocks, seed, groups, blocking, window, k, item_split, block_out,
+                                substep_out, group_out, pos_out, replica_out);
+}
+
+const char* mf_fast_kernel_name(int32_t k) {
+  switch (choose_fast_kernel(k)) {
+    case FastKernel::kPair: return want_pair_sys() ? "k_sweep_pair_sys" : "k_sweep_pair";
+    case FastKernel::kPersistent: return "k_fast_superstep";
+    default: return "k_fast_substep";
+  }
+}
+
+int32_t mf_debug_build_flags(void) { return mfhip::kExperiments ? 1 : 0; }
+
+int mf_debug_device_bytes(int64_t out[2]) {
+  if (!out) return MF_ERR_INVALID;
+  out[0] = mfhip::dev_bytes_live().load();
+  out[1] = mfhip::dev_bytes_peak().load();
+  return MF_OK;
+}
+
+int mf_debug_plan_digest(mf_ctx* ctx, uint64_t out[2]) {
+  return guarded([&] {
+    MF_REQUIRE(ctx && out, "null argument");
+    plan_digest(ctx, out);
+  });
+}
+
+int mf_debug_ring_schedule(int32_t rank, int32_t world, int32_t n_blocks, int64_t superstep, int32_t* out_blk,
+                           int32_t* in_blk, int32_t* dst, int32_t* src) {
+  return guarded([&] {
+    MF_REQUIRE(out_blk && in_blk && dst && src, "null argument");
+    MF_REQUIRE(world >= 1 && rank >= 0 && rank < world && n_blocks >= 1 && n_blocks % world == 0 && superstep >= 1,
+               "bad ring arguments (n_blocks must be a multiple of world, superstep >= 1)");
+    const RingStep rs = ring_step(rank, world, n_blocks / world, n_blocks, superstep);
+    *out_blk = rs.out_blk;
+    *in_blk = rs.in_blk;
+    *dst = rs.dst;
+    *src = rs.src;
+  });
+}
+
+int mf_fast_plan_window(int32_t k, int32_t* window_out) {
+  return guarded([&] {
+    MF_REQUIRE(window_out, "null");
+    const FastKernel fk = choose_fast_kernel(k);
+    *window_out = fk == FastKernel::kPair ? plan_window(k) : kHazardWindow;
+  });
+}
+
+int mf_learning_rate(int method, double lr, int32_t iteration, double lambda, double arg, double* out) {
+  return guarded([&] {
+    MF_REQUIRE(out, "null");
+    MF_REQUIRE(method >= MF_LR_DEFAULT && method <= MF_LR_XU, "unknown lr_method");
+    *out = learning_rate(method, lr, iteration, lambda, arg);
+  });
+}
+
+}  // extern "C"

@@ -1,0 +1,248 @@
+// als.cpp -- ALS training (mf_als_prepare / mf_als_run / mf_als_fit) and its testing hook.
+#include <algorithm>
+#include <atomic>
+#include <cmath>
+#include <cstring>
+#include <numeric>
+#include <random>
+#include <string>
+#include <vector>
+
+#include "common.hpp"
+#include "context.hpp"
+#include "jvm_random.hpp"
+#include "kernels.hpp"
+#include "plan.hpp"
+
+namespace mfhip {
+
+// ---------------------------------------------------------------------------------------
+// ALS (mf_als_prepare / mf_als_run; kernels_als.hip), single shard.  prepare resolves the ids
+// (unseen ones get rows as in an online batch, initialised like a DSGD fit's), builds each side's
+// CSR on the host with a stable counting sort (ratings of a row in the caller's order) and uploads
+// it with the work lists; a half-sweep is then launches only.
+constexpr int64_t kAlsChunk = 16384;     // ratings per work item of a long row (MFHIP_TEST als_chunk=N)
+constexpr int64_t kAlsBatch = 16384;     // rows per launch (MFHIP_TEST als_batch=B)
+constexpr int64_t kAlsBatchSlots = 2048; // partial systems per launch: a new launch starts past this
+
+void als_check(const mf_ctx* ctx) {
+  if (ctx->rank_mode || ctx->shards.size() != 1)
+    fail(MF_ERR_STATE, "ALS runs on a single-process context on one device");
+  MF_REQUIRE(ctx->P.num_factors <= kAlsMaxRank,
+             "ALS supports a rank of at most " + std::to_string(kAlsMaxRank) +
+                 " (the k x k normal matrix of a row is kept in LDS); this context has k = " +
+                 std::to_string(ctx->P.num_factors));
+}
+
+void als_check_run(double lambda, int32_t reg) {
+  MF_REQUIRE(lambda > 0.0 && std::isfinite(lambda), "ALS needs lambda > 0");
+  MF_REQUIRE(reg == MF_ALS_REG_WEIGHTED || reg == MF_ALS_REG_PLAIN, "unknown ALS regularisation (reg)");
+}
+
+namespace {
+
+template <typename T>
+void als_build_side(mf_ctx* ctx, Shard& s, int side, const std::vector<uint32_t>& xr, const std::vector<uint32_t>& yr,
+                    const double* r, int64_t n, int64_t rows, int64_t chunk, int64_t batch) {
+  std::vector<int64_t> off(static_cast<size_t>(rows) + 1, 0);
+  for (int64_t j = 0; j < n; ++j) ++off[xr[j] + 1];
+  for (int64_t x = 0; x < rows; ++x) off[x + 1] += off[x];
+  std::vector<int32_t> cols(static_cast<size_t>(n));
+  std::vector<T> vals(static_cast<size_t>(n));
+  {
+    std::vector<int64_t> pos(off.begin(), off.end() - 1);
+    for (int64_t j = 0; j < n; ++j) {
+      const int64_t p = pos[xr[j]]++;
+      cols[p] = static_cast<int32_t>(yr[j]);
+      vals[p] = static_cast<T>(r[j]);
+    }
+  }
+  mf_ctx::AlsSide& A = ctx->als[side];
+  A = mf_ctx::AlsSide();
+  mf_ctx::AlsBatch cur{0, 0, 0, 0};
+  int64_t cur_rows = 0, cur_slots = 0;
+  auto close = [&]() {
+    if (cur.items > 0) A.batches.push_back(cur);
+    A.max_slots = std::max(A.max_slots, cur_slots);
+    cur = {static_cast<int64_t>(A.items.size()), 0, static_cast<int64_t>(A.splits.size()), 0};
+    cur_rows = cur_slots = 0;
+  };
+  for (int64_t row = 0; row < rows; ++row) {
+    const int64_t c = off[row + 1] - off[row];
+    if (c == 0) continue;
+    MF_REQUIRE(c <= INT32_MAX, "ALS: a row has more than 2^31 - 1 ratings");
+    const int64_t nch = c <= chunk ? 1 : (c + chunk - 1) / chunk;
+    if (cur_rows >= batch || (nch > 1 && cur_slots > 0 && cur_slots + nch > kAlsBatchSlots)) close();
+    if (nch == 1) {
+      A.items.push_back({off[row], static_cast<int32_t>(row), static_cast<int32_t>(c), -1, 0});
+      cur.items += 1;
+    } else {
+      for (int64_t ch = 0; ch < nch; ++ch)
+        A.items.push_back({off[row] + ch * chunk, static_cast<int32_t>(row),
+                           static_cast<int32_t>(std::min(chunk, c - ch * chunk)), static_cast<int32_t>(cur_slots + ch), 0});
+      A.splits.push_back({static_cast<int32_t>(row), static_cast<int32_t>(cur_slots), static_cast<int32_t>(nch),
+                          static_cast<int32_t>(c)});
+      cur.items += nch;
+      cur.splits += 1;
+      cur_slots += nch;
+    }
+    ++cur_rows;
+  }
+  close();
+  DeviceGuard g(s.device);
+  auto up = [&](DevBuf& d, const void* src, size_t bytes) {
+    d.alloc(std::max<size_t>(bytes, 16));
+    if (bytes) MF_HIP(hipMemcpy(d.get(), src, bytes, hipMemcpyHostToDevice));
+  };
+  up(s.als_cols[side], cols.data(), cols.size() * 4);
+  up(s.als_vals[side], vals.data(), vals.size() * sizeof(T));
+  up(s.als_items[side], A.items.data(), A.items.size() * sizeof(AlsItem));
+  up(s.als_splits[side], A.splits.data(), A.splits.size() * sizeof(AlsSplit));
+}
+
+}  // namespace
+
+void als_prepare(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n) {
+  MF_REQUIRE(n >= 0, "negative rating count");
+  MF_REQUIRE(n == 0 || (u && i && r), "null rating arrays");
+  als_check(ctx);
+  require_healthy(ctx);
+  det_spec_wait(ctx, true);  // new ids change the layouts the builds read
+  sync_all(ctx);
+  Shard& s = ctx->shards[0];
+  ctx->als_prepared = false;
+  if (!ctx->have_model) {
+    ctx->U = SideLayout();
+    ctx->I = SideLayout();
+    ctx->have_model = true;
+    ++ctx->layout_gen;
+  }
+  const int k = ctx->P.num_factors;
+  const int64_t u0 = ctx->U.rows(), i0 = ctx->I.rows();
+  constexpr uint32_t kMiss = 0xFFFFFFFFu;
+  std::vector<uint32_t> ur, ir;
+  lookup_rows(ctx->U, u, n, ur);
+  lookup_rows(ctx->I, i, n, ir);
+  std::vector<int32_t> fu, fi;
+  for (int64_t j = 0; j < n; ++j) {  // unseen ids take new rows in order of appearance
+    if (ur[j] == kMiss) ur[j] = static_cast<uint32_t>(online_row(ctx, ctx->U, u[j], fu));
+    if (ir[j] == kMiss) ir[j] = static_cast<uint32_t>(online_row(ctx, ctx->I, i[j], fi));
+  }
+  // as in an online batch: new rows take the slab rows a fast DSGD schedule keeps zeroed
+  if (ctx->prepared && !ctx->f64 && (!fu.empty() || !fi.empty())) ctx->prepared = false;
+  // the initial factors a DSGD fit gives these ids: new Random(id ^ seed) (DSGDforMF.scala:548-549)
+  if (ctx->P.has_seed) {
+    ctx->init_seed = ctx->P.seed;
+  } else if (ctx->init_seed == 0) {
+    std::random_device rd;
+    ctx->init_seed = (static_cast<int64_t>(rd()) << 32) ^ rd();
+  }
+  for (int side = 0; side < 2; ++side) {
+    const std::vector<int32_t>& fresh = side == kSideU ? fu : fi;
+    ensure_rows(ctx, s, side, std::max<int64_t>(side_of(ctx, side).rows(), 1));
+    if (fresh.empty()) continue;
+    std::vector<double> vec;
+    init_vectors(fresh.data(), static_cast<int64_t>(fresh.size()), k, true, ctx->init_seed, vec);
+    upload_rows(ctx, s, side, side == kSideU ? u0 : i0, vec.data(), static_cast<int64_t>(fresh.size()));
+  }
+  int64_t chunk = kAlsChunk, batch = kAlsBatch;
+  if (const std::string v = test_knob("als_chunk"); !v.empty()) chunk = std::max<int64_t>(1, std::atoll(v.c_str()));
+  if (const std::string v = test_knob("als_batch"); !v.empty()) batch = std::max<int64_t>(1, std::atoll(v.c_str()));
+  if (ctx->f64) {
+    als_build_side<double>(ctx, s, kSideU, ur, ir, r, n, ctx->U.rows(), chunk, batch);
+    als_build_side<double>(ctx, s, MF_SIDE_ITEM, ir, ur, r, n, ctx->I.rows(), chunk, batch);
+  } else {
+    als_build_side<float>(ctx, s, kSideU, ur, ir, r, n, ctx->U.rows(), chunk, batch);
+    als_build_side<float>(ctx, s, MF_SIDE_ITEM, ir, ur, r, n, ctx->I.rows(), chunk, batch);
+  }
+  ctx->als_prepared = true;
+  ctx->als_half_sweeps = 0;
+}
+
+namespace {
+
+// One side solved from the other.  only_row >= 0 (the testing hook): that row's work items alone,
+// its system stored to s.als_dump instead of being solved; false if the row has no rating.
+bool als_half(mf_ctx* ctx, int side, double lambda, int32_t reg, int64_t only_row = -1) {
+  Shard& s = ctx->shards[0];
+  DeviceGuard g(s.device);
+  const mf_ctx::AlsSide& A = ctx->als[side];
+  const int k = ctx->P.num_factors;
+  s.als_part.alloc(std::max<size_t>(static_cast<size_t>(A.max_slots) * als_partial_elems(k) * ctx->es, 16));
+  const void* Q = side == kSideU ? s.itf.get() : s.uf.get();
+  void* X = side == kSideU ? s.uf.get() : s.itf.get();
+  const AlsItem* d_items = s.als_items[side].as<AlsItem>();
+  const AlsSplit* d_splits = s.als_splits[side].as<AlsSplit>();
+  const bool weighted = reg == MF_ALS_REG_WEIGHTED;
+  if (only_row >= 0) {
+    auto lo = std::lower_bound(A.items.begin(), A.items.end(), only_row,
+                               [](const AlsItem& a, int64_t row) { return a.row < row; });
+    if (lo == A.items.end() || lo->row != only_row) return false;
+    auto hi = lo;
+    while (hi != A.items.end() && hi->row == only_row) ++hi;
+    auto sp = std::lower_bound(A.splits.begin(), A.splits.end(), only_row,
+                               [](const AlsSplit& a, int64_t row) { return a.row < row; });
+    const bool split = sp != A.splits.end() && sp->row == only_row;
+    s.als_dump.alloc((static_cast<size_t>(k) * k + k) * ctx->es);
+    launch_als(s.stream, d_items + (lo - A.items.begin()), static_cast<int>(hi - lo),
+               d_splits + (sp - A.splits.begin()), split ? 1 : 0, s.als_cols[side].as<int32_t>(),
+               s.als_vals[side].get(), Q, X, k, lambda, weighted, ctx->f64, s.als_part.get(), s.als_dump.get());
+    MF_HIP(hipGetLastError());
+    return true;
+  }
+  LaunchTimer t(s, ctx->profiling);
+  for (const mf_ctx::AlsBatch& b : A.batches) {
+    launch_als(s.stream, d_items + b.item0, static_cast<int>(b.items), d_splits + b.split0, static_cast<int>(b.splits),
+               s.als_cols[side].as<int32_t>(), s.als_vals[side].get(), Q, X, k, lambda, weighted, ctx->f64,
+               s.als_part.get(), nullptr);
+    MF_HIP(hipGetLastError());
+    ctx->stats.kernel_launches += 1 + (b.splits > 0);
+  }
+  return true;
+}
+
+}  // namespace
+
+void als_run(mf_ctx* ctx, int64_t half_sweeps, double lambda, int32_t reg) {
+  MF_REQUIRE(half_sweeps >= 0, "negative half-sweep count");
+  als_check_run(lambda, reg);
+  als_check(ctx);
+  if (!ctx->als_prepared) fail(MF_ERR_STATE, "mf_als_run before mf_als_prepare");
+  require_healthy(ctx);
+  sync_all(ctx);
+  for (int64_t h = 0; h < half_sweeps; ++h) {
+    // MLlib's order: the item side from the user factors first
+    als_half(ctx, ctx->als_half_sweeps % 2 == 0 ? MF_SIDE_ITEM : kSideU, lambda, reg);
+    ++ctx->als_half_sweeps;
+  }
+  DeviceGuard g(ctx->shards[0].device);
+  MF_HIP(hipStreamSynchronize(ctx->shards[0].stream));
+}
+
+// The normal equations of one row as the kernel accumulates them (mf_debug_als_normal_eq).
+void als_normal_eq(mf_ctx* ctx, int side, int32_t id, double lambda, int32_t reg, double* A_out, double* b_out) {
+  als_check_run(lambda, reg);
+  als_check(ctx);
+  if (!ctx->als_prepared) fail(MF_ERR_STATE, "mf_debug_als_normal_eq before mf_als_prepare");
+  require_healthy(ctx);
+  sync_all(ctx);
+  const int32_t row = side_of(ctx, side).index.find(id);
+  MF_REQUIRE(row >= 0, "unknown id");
+  MF_REQUIRE(als_half(ctx, side, lambda, reg, row), "the id has no rating in the prepared data");
+  Shard& s = ctx->shards[0];
+  DeviceGuard g(s.device);
+  MF_HIP(hipStreamSynchronize(s.stream));
+  const size_t k = static_cast<size_t>(ctx->P.num_factors), m = k * k + k;
+  std::vector<double> h(m);
+  if (ctx->f64) {
+    MF_HIP(hipMemcpy(h.data(), s.als_dump.get(), m * 8, hipMemcpyDeviceToHost));
+  } else {
+    std::vector<float> f(m);
+    MF_HIP(hipMemcpy(f.data(), s.als_dump.get(), m * 4, hipMemcpyDeviceToHost));
+    for (size_t x = 0; x < m; ++x) h[x] = static_cast<double>(f[x]);
+  }
+  std::memcpy(A_out, h.data(), k * k * 8);
+  std::memcpy(b_out, h.data() + k * k, k * 8);
+}
+
+}  // namespace mfhip

@@ -1,0 +1,326 @@
+// context.hpp -- the context (mf_ctx), its shards, and the helpers more than one host translation
+// unit uses.  Private to the host side: included by the .cpp files only (mfhip.cpp, abi.cpp,
+// online.cpp, eval.cpp, als.cpp), never by a .hip file or by kernels.hpp / plan.hpp.
+#pragma once
+
+#include <array>
+#include <rccl/rccl.h>
+
+#include <atomic>
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <future>
+#include <string>
+#include <vector>
+
+#include "common.hpp"
+#include "kernels.hpp"
+#include "plan.hpp"
+
+namespace mfhip {
+
+struct DeviceGuard {
+  int prev = 0;
+  explicit DeviceGuard(int dev) {
+    (void)hipGetDevice(&prev);
+    MF_HIP(hipSetDevice(dev));
+  }
+  ~DeviceGuard() { (void)hipSetDevice(prev); }
+};
+
+#define MF_NCCL(call)                                                                     \
+  do {                                                                                    \
+    ncclResult_t _r = (call);                                                             \
+    if (_r != ncclSuccess) ::mfhip::fail(MF_ERR_COMM, std::string(#call) + ": " + ncclGetErrorString(_r)); \
+  } while (0)
+
+// Deterministic persistent sweep: one superstep's entries, staged in pinned memory by a host
+// thread while earlier supersteps run, then copied to the device (fixed SoA offsets).  A ring of
+// kDetSlots buffers: the host builds supersteps s+1 and s+2 (two builders at once) while the device
+// runs s.  On the GPU box (16 host threads) one NFLX build takes ~28 ms alone and about as long
+// with another beside it, i.e. ~14 ms per superstep -- the split sweep's ~14.4 ms launch; a third
+// builder does not raise that rate (three at once: ~44 ms each, the host threads are saturated).
+constexpr int kDetSlots = 3;
+struct DetBuf {
+  PinnedBuf pin;
+  DevBuf dev;
+  hipEvent_t copied = nullptr;  // the H2D from `pin` finished (pin may be rewritten)
+  hipEvent_t swept = nullptr;   // the sweep that read `dev` finished (dev may be rewritten)
+  bool pending = false;         // `copied` was recorded and not yet waited for
+  bool dev_built = false;       // det_build left only the shuffle here: the device builds the entries
+  int64_t n = 0, nw = 0;
+  DetStepScratch scratch;  // build_det_step's gathers for this slot (kept: no page faults per superstep)
+};
+
+// A device mirror of one side's IdIndex (same slots), for the online batch's id lookup.
+struct DevIndex {
+  DevBuf slots, upd_pos, upd_val;
+  uint64_t gen = 0, cap = 0;
+  size_t applied = 0;  // entries of the table's write log already in the mirror
+};
+
+struct Shard {
+  int device = 0;
+  int index = 0;  // global shard index (== rank in rank mode)
+  hipStream_t stream = nullptr;
+  hipStream_t copy_stream = nullptr;  // host-to-device staging beside the sweeps (deterministic mode)
+  // ring overlap (c >= 2 user blocks per shard, systolic fast sweep): the shard's last local block
+  // runs on `aux` behind the arriving item block; the leaving block moves on `comm` as soon as
+  // the launch holding the other blocks has finished
+  hipStream_t aux = nullptr, comm = nullptr;
+  hipEvent_t ev_front = nullptr;  // launch A (local blocks 0..c-2) of the latest superstep done
+  hipEvent_t ev_last = nullptr;   // launch B (local block c-1) of the latest superstep done
+  hipEvent_t ev_moved = nullptr;  // the item block this shard sent / received in the latest ring step
+  std::vector<int64_t> st_sys_block_off;  // PairPlan::sys_block_off
+  hipEvent_t done = nullptr;  // ring hand-off ordering between in-process shards
+  DevBuf uf, itf, regu, regi;
+  int64_t cap_u = 0, cap_i = 0;
+  // deterministic mode staging
+  DevBuf det_dev;
+  PinnedBuf det_pin;
+  OnlineSweepScratch online_sc;  // online micro-batches (k_online_sweep)
+  DevIndex didx[2];              // device mirrors of the user [0] / item [1] IdIndex (online id lookup)
+  PinnedBuf small_pin;           // online batch: {lookup misses, sweep error, touched users, items}, read back async
+  PinnedBuf slots_pin;           // online f64 batch: the wave table read back for det_slot_table
+  DevBuf blk_u, blk_i, blk_ru, blk_ri;  // mf_block_update: the block's factor rows and lambda / omega
+  // fast mode
+  DevBuf fast_recs, fast_cells, fast_blks;
+  DevBuf fast_prog, fast_err;  // persistent sweep: progress words + timeout flag
+  DevBuf st_recs, st_waves;    // pair schedule: records and per-cell wave table
+  int64_t st_nrecs = 0;        // pair records in st_recs
+  std::vector<int64_t> st_sub_off;
+  std::vector<WaveDesc> st_waves_host;  // kept only when tracing
+  DevBuf st_sys, st_sysw;               // systolic pair tables (PairPlan::sys, sys_waves)
+  DevBuf st_place;                      // per systolic wave slot: block -> wave of its launch (sys_placement)
+  std::vector<int64_t> st_place_off;     // per superstep: its first slot in st_place (nb + 1)
+  std::vector<int32_t> st_place_pad;     // per superstep: empty blocks per XCD in its launch (sys_placement)
+  std::vector<int64_t> st_sys_off;      // PairPlan::sys_off
+  std::vector<WaveDesc> st_sys_host;    // kept only when tracing
+  std::vector<SysWave> st_sysw_host;    // kept only when tracing
+  uint32_t sys_base = 0;                // progress-word base of the next systolic launch
+  uint32_t sys_step = 1;                // base advance per launch (> the largest G_j)
+  DevBuf st_trace;                      // MFHIP_WAVE_TRACE: {start, end} per wave
+  DevBuf st_split;                      // hot-item replicas (SplitItem), superstep-major
+  std::vector<int64_t> st_split_off;    // per superstep (n + 1)
+  std::vector<double> sm_bytes;         // per superstep index (s-1) mod n: bytes the sweep requests
+  // deterministic persistent sweep (kernels_detsweep.hip)
+  DetSweepLayout det_layout;
+  DetBuf det_buf[kDetSlots];
+  DevBuf det_ticket, det_err, det_scratch;
+  int64_t det_n_max = 0, det_nw_max = 0;
+  // the superstep's input built on the device (det_device_build; MFHIP_TEST det_build=host: on the
+  // host): the rating blocks' 16-B records, the blocks' item -> wave maps, per superstep index
+  // (s-1) mod n its block table and its wave / slot table (both fixed: a wave's count is the sum
+  // of its items' counts), the uploaded shuffle permutation, and the build's scratch
+  DevBuf det_aos_dev, det_iw, det_bt, det_ord;
+  DetBuildScratch det_bs;
+  std::vector<std::vector<DetWave>> det_sm_slots;
+  std::vector<int64_t> det_sm_n;
+  std::vector<int32_t> det_sm_nblk;
+  uint32_t det_wave_bound = 1;
+  // evaluation scratch
+  DevBuf ev_u, ev_i, ev_r, ev_mult, ev_out, ev_part;
+  // recommendation (mf_recommend): the row -> id table of each side (valid while rec_id_gen matches
+  // the context's layout_gen), the query rows and exclusion CSR of a call, and a batch's partial
+  // lists and results
+  DevBuf rec_id[2];
+  uint64_t rec_id_gen[2] = {0, 0};
+  DevBuf rec_q, rec_eoff, rec_erows, rec_part, rec_ids, rec_scores, rec_counts;
+  // ALS (mf_als_prepare): per solved side [user, item] the CSR (counterpart rows, ratings) and the
+  // work lists; the long rows' partial systems of one launch; the testing hook's output
+  DevBuf als_cols[2], als_vals[2], als_items[2], als_splits[2], als_part, als_dump;
+  // profiling
+  std::vector<hipEvent_t> ev;
+  size_t ev_used = 0;
+  int64_t ev_launches = 0;
+};
+
+}  // namespace mfhip
+
+struct mf_ctx {
+  mfhip::Reaper reaper;  // host plan buffers being released in the background (first member: joined last)
+  mf_params P{};
+  std::vector<uint32_t> on_ur, on_ir;  // online batches: factor rows per rating (kept: no page faults per batch)
+  bool f64 = true;
+  size_t es = 8;  // bytes per factor element
+  int G = 1;      // global shard count
+  bool rank_mode = false;
+  ncclComm_t comm = nullptr;
+  std::vector<mfhip::Shard> shards;  // local shards
+  mfhip::SideLayout U, I;
+  bool have_model = false;
+  bool prepared = false;
+  int32_t nb = 1;
+  int32_t c = 1;  // user blocks per shard
+  int64_t superstep_done = 0;
+  std::vector<int> item_loc;  // item block -> shard holding it
+  mfhip::RatingBlocks rb;     // deterministic mode keeps the rating blocks on the host
+  int32_t G_fast = 0;
+  uint32_t fast_dummy_u = 0, fast_dummy_i = 0;  // zeroed rows past the real ones (padding / idle prefetch)
+  int32_t fast_prio_len = 1 << 30;  // cells at least this long run at raised priority
+  bool fast_persistent = false;  // MFHIP_TEST fast_kernel=persistent selects the systolic single launch
+  bool fast_pair = false;         // two updates per step (kernels_pair.hip), k in {64, 128, 256}
+  bool fast_sys = false;          // pair cells as one systolic launch per superstep (k_sweep_pair_sys)
+  bool det_sweep = false;         // deterministic mode: one persistent k_det_sweep launch per superstep
+  bool det_split = false;         // ... with single-item chains split over two waves (k_det_sweep_split)
+  bool det_dev_build = false;     // ... its input built on the device from the host's shuffle (det_device_build)
+  bool det_dev_ready = false;     // ... the device build prepared (the switch below may turn it on)
+  bool det_mixed = false;         // ... MFHIP_TEST det_build=mixed: switch from the third superstep on
+  std::atomic<bool> det_switch{false};  // ... the host builds fell behind the device: device builds from now on
+  int det_idle = 0;               // ... consecutive supersteps whose build the device had to wait for
+  bool det_alone = true;          // ... the longest chains on CUs of their own (det_slot_table)
+  int64_t det_split_blocks = 0;   // resident blocks of k_det_sweep_split (per device share)
+  int64_t det_cu_period = 256;    // CUs of the device: blocks b and b + period share a CU
+  bool ring_overlap = false;      // fast systolic sweep, >1 shard, c >= 2: the ring step overlaps the sweep
+  // fast-mode hot-item replicas (plan.hpp SplitItem), an experiment outside the product surface:
+  // MFHIP_ITEM_SPLIT=m sweeps an item with more than m ratings in one rating block as ceil(r / m)
+  // chains averaged when the superstep ends (read at prepare; 0 / unset = off)
+  int32_t item_split = 0;
+  std::vector<int64_t> fast_rb_size;  // per rating block (fast mode)
+  mf_stats stats{};
+  bool profiling = false;
+  std::vector<int32_t> rows_by_id_u, rows_by_id_i;  // ascending-id row permutations
+  bool order_dirty = true;
+  uint64_t layout_gen = 1;  // bumped wherever a side's rows change (with order_dirty): device row -> id tables
+  int64_t init_seed = 0;      // seed of the initial factors (P.seed, or a random one when unseeded)
+  std::string failed;         // non-empty: a device-side bound tripped; the fit must be prepared again
+  // deterministic sweep: the next run's first supersteps, built on worker threads when a run ends
+  // (a superstep's schedule depends only on its number and the training data): det_spec_s[slot] =
+  // the superstep built into det_buf[slot], -1 = none (det_run takes them over; det_spec_wait
+  // joins them where the data, layouts or superstep change)
+  // ALS (mf_als_prepare / mf_als_run): per solved side the work lists (host copies of the device
+  // arrays) cut into launches; the CSR itself lives on the device only
+  struct AlsBatch { int64_t item0, items, split0, splits; };
+  struct AlsSide {
+    std::vector<mfhip::AlsItem> items;
+    std::vector<mfhip::AlsSplit> splits;
+    std::vector<AlsBatch> batches;
+    int64_t max_slots = 0;
+  } als[2];
+  bool als_prepared = false;
+  int64_t als_half_sweeps = 0;  // half-sweeps run since mf_als_prepare (even: the item side is next)
+  std::future<void> det_spec[mfhip::kDetSlots];
+  int64_t det_spec_s[mfhip::kDetSlots] = {-1, -1, -1};
+};
+
+namespace mfhip {
+
+constexpr int kSideU = MF_SIDE_USER;
+
+enum class FastKernel { kPair, kCell, kPersistent };
+
+inline SideLayout& side_of(mf_ctx* ctx, int side) { return side == kSideU ? ctx->U : ctx->I; }
+
+// ---------------------------------------------------------------------------------------
+// profiling: a pair of HIP events around every sweep-kernel launch on the shard's stream.
+// ext = true: the launch records the pair itself (hipExtLaunchKernel start/stop events, part
+// of the dispatch packet, so timing adds no commands between kernels); start() / stop() give
+// the events, or null when profiling is off.
+struct LaunchTimer {
+  Shard& s;
+  bool on, ext;
+  size_t slot = 0;
+  LaunchTimer(Shard& sh, bool enabled, bool ext_events = false) : s(sh), on(enabled), ext(ext_events) {
+    if (!on) return;
+    if (s.ev_used + 2 > s.ev.size()) {
+      for (int x = 0; x < 512; ++x) {
+        hipEvent_t e;
+        MF_HIP(hipEventCreate(&e));
+        s.ev.push_back(e);
+      }
+    }
+    slot = s.ev_used;
+    s.ev_used += 2;
+    if (!ext) MF_HIP(hipEventRecord(s.ev[slot], s.stream));
+  }
+  hipEvent_t start() const { return on ? s.ev[slot] : nullptr; }
+  hipEvent_t stop() const { return on ? s.ev[slot + 1] : nullptr; }
+  ~LaunchTimer() {
+    if (on) {
+      if (!ext) (void)hipEventRecord(s.ev[slot + 1], s.stream);
+      s.ev_launches++;
+    }
+  }
+};
+
+// MFHIP_TIMING=1: host phases of prepare on stderr.
+struct PhaseClock {
+  bool on = std::getenv("MFHIP_TIMING") != nullptr;
+  std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
+  void lap(const char* what) {
+    if (!on) return;
+    const auto now = std::chrono::steady_clock::now();
+    std::fprintf(stderr, "[mfhip] %-28s %10.3f ms\n", what, 1e3 * std::chrono::duration<double>(now - t).count());
+    t = now;
+  }
+};
+
+struct RingStep {
+  int32_t out_blk, in_blk, dst, src;
+};
+
+// Evaluation: resolve ids on the host, gather-dot on the device.
+struct EvalOut {
+  double sse = 0, cnt = 0, risk = 0;
+};
+
+// mfhip.cpp: context lifetime, slabs, health, the DSGD driver
+mf_ctx* create_ctx(const mf_params* p, const int* device_ids, int n_devices);
+mf_ctx* create_rank_ctx(const mf_params* p, int device_id, int nranks, int rank, const uint8_t* uid);
+void destroy_ctx(mf_ctx* ctx);
+bool want_pair_sys();
+FastKernel choose_fast_kernel(int k);
+int32_t plan_window(int32_t k);
+double bytes_per_update(const mf_ctx* ctx);
+void ensure_rows(mf_ctx* ctx, Shard& s, int side, int64_t rows);
+void upload_rows(mf_ctx* ctx, Shard& s, int side, int64_t row0, const double* src, int64_t n);
+void upload_regs(mf_ctx* ctx, Shard& s, int side, int64_t row0, const double* src, int64_t n);
+void download_rows(mf_ctx* ctx, Shard& s, int side, int64_t row0, int64_t n, double* out);
+void init_vectors(const int32_t* ids, int64_t n, int k, bool xor_seed, int64_t seed, std::vector<double>& out);
+void init_factors(mf_ctx* ctx);
+void det_spec_wait(mf_ctx* ctx, bool invalidate);
+void sync_all(mf_ctx* ctx);
+void require_healthy(const mf_ctx* ctx);
+void ensure_order(mf_ctx* ctx);
+void consolidate(mf_ctx* ctx, Shard& dst);
+int32_t online_row(mf_ctx* ctx, SideLayout& S, int32_t id, std::vector<int32_t>& fresh);
+int64_t device_cu_count(int dev);
+int64_t det_slot_room(int64_t nw);
+int64_t det_slot_table(DetWave* waves, int64_t nw, int64_t max_blocks, bool alone, int64_t period);
+RingStep ring_step(int32_t g, int32_t G, int32_t c, int32_t n, int64_t superstep);
+void reset_item_loc(mf_ctx* ctx);
+void prepare(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n);
+void run_supersteps(mf_ctx* ctx, int64_t count);
+void debug_levels(const uint32_t* urow, const uint32_t* irow, const int32_t* order, int64_t n, int32_t* level_out);
+int debug_fast_plan(const int32_t* u, const int32_t* i, int64_t n, int32_t n_blocks, int64_t seed, int32_t groups,
+                    int32_t blocking, int32_t window, int32_t k, int32_t item_split, int32_t* block_out, int32_t* substep_out, int32_t* group_out, int64_t* pos_out,
+                    int32_t* replica_out);
+void plan_digest(mf_ctx* ctx, uint64_t out[2]);
+
+// online.cpp
+void online_update(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n, int flavour,
+                   int num_partitions, int64_t* tu, int64_t* ti, double* uout = nullptr, double* iout = nullptr);
+void block_update(mf_ctx* ctx, const double* r, const int32_t* uidx, const int32_t* iidx, int64_t len, double* users,
+                  const int32_t* uomega, int64_t nu, double* items, const int32_t* iomega, int64_t ni, int k,
+                  int iteration, int rating_block_id, int64_t seed, double lr, int lr_method, double lr_arg,
+                  double lambda);
+void set_factors(mf_ctx* ctx, int side, const int32_t* ids, const double* vecs, int64_t n);
+
+// eval.cpp
+void allgather_items(mf_ctx* ctx);
+EvalOut evaluate(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n,
+                 const int32_t* mult, double lambda, double* pred_out, uint8_t* found_out);
+void recommend(mf_ctx* ctx, int qside, const int32_t* queries, int64_t nq, int32_t top_n, const int32_t* eq,
+               const int32_t* ec, int64_t ne, int32_t* ids_out, double* scores_out, int32_t* counts_out);
+void get_factors(mf_ctx* ctx, int side, int32_t* ids, double* vecs, int64_t cap, int64_t* written);
+void lookup_factors(mf_ctx* ctx, int side, const int32_t* ids, int64_t n, double* vecs_out, uint8_t* found);
+
+// als.cpp
+void als_check(const mf_ctx* ctx);
+void als_check_run(double lambda, int32_t reg);
+void als_prepare(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n);
+void als_run(mf_ctx* ctx, int64_t half_sweeps, double lambda, int32_t reg);
+void als_normal_eq(mf_ctx* ctx, int side, int32_t id, double lambda, int32_t reg, double* A_out, double* b_out);
+
+}  // namespace mfhip

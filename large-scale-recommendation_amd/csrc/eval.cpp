@@ -1,0 +1,296 @@
+// eval.cpp -- reading the model out: evaluation (mf_predict / mf_rmse / mf_empirical_risk),
+// top-N recommendation (mf_recommend) and the factor read-outs (mf_get_factors, mf_lookup).
+#include <algorithm>
+#include <atomic>
+#include <cmath>
+#include <cstring>
+#include <numeric>
+#include <random>
+#include <string>
+#include <vector>
+
+#include "common.hpp"
+#include "context.hpp"
+#include "jvm_random.hpp"
+#include "kernels.hpp"
+#include "plan.hpp"
+
+namespace mfhip {
+
+// Rank mode: broadcast each item block from its holder so every rank has all items.
+void allgather_items(mf_ctx* ctx) {
+  if (!ctx->rank_mode || ctx->G <= 1) return;
+  // The last superstep may still be running: with the ring overlap its second launch is on
+  // `aux` and the item block's send/recv on `comm`.  The broadcast below reads and writes item
+  // rows on `stream`, and two RCCL operations of one communicator must not run on unordered
+  // streams, so every stream of the rank drains first (and a sweep timeout surfaces here).
+  sync_all(ctx);
+  require_healthy(ctx);
+  Shard& s = ctx->shards[0];
+  DeviceGuard g(s.device);
+  const size_t k = static_cast<size_t>(ctx->P.num_factors);
+  MF_NCCL(ncclGroupStart());
+  for (int32_t b = 0; b < ctx->nb; ++b) {
+    const int64_t r0 = ctx->I.block_start[b], cnt = ctx->I.block_start[b + 1] - r0;
+    if (cnt == 0) continue;
+    char* p = s.itf.as<char>() + static_cast<size_t>(r0) * k * ctx->es;
+    MF_NCCL(ncclBroadcast(p, p, cnt * k, ctx->f64 ? ncclFloat64 : ncclFloat32, ctx->item_loc[b], ctx->comm, s.stream));
+  }
+  MF_NCCL(ncclGroupEnd());
+  MF_HIP(hipStreamSynchronize(s.stream));
+  // item_loc keeps tracking the ring (all ranks simulate it identically); copies made here
+  // are read-only snapshots for evaluation.
+}
+
+EvalOut evaluate(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n,
+                 const int32_t* mult, double lambda, double* pred_out, uint8_t* found_out) {
+  MF_REQUIRE(ctx->have_model, "The MatrixFactorization model has not been fitted to data. "
+                              "Prior to predicting values, it has to be trained on data.");
+  MF_REQUIRE(n >= 0, "negative count");
+  require_healthy(ctx);
+  EvalOut res;
+  if (n == 0) return res;
+  Shard& s = ctx->shards[0];
+  if (ctx->rank_mode) allgather_items(ctx);
+  else consolidate(ctx, s);
+  std::vector<uint32_t> ur, ir;
+  lookup_rows(ctx->U, u, n, ur);
+  lookup_rows(ctx->I, i, n, ir);
+  std::vector<int32_t> urow(n), irow(n);
+  const int me = s.index;
+  for (int64_t j = 0; j < n; ++j) {
+    int32_t a = static_cast<int32_t>(ur[j]), b = static_cast<int32_t>(ir[j]);
+    if (ctx->rank_mode && a >= 0 && ctx->U.row_block[a] / ctx->c != me) a = -1;  // not my user
+    urow[j] = a;
+    irow[j] = b;
+  }
+  DeviceGuard g(s.device);
+  MF_HIP(hipStreamSynchronize(s.stream));
+  s.ev_u.alloc(n * 4);
+  s.ev_i.alloc(n * 4);
+  MF_HIP(hipMemcpy(s.ev_u.get(), urow.data(), n * 4, hipMemcpyHostToDevice));
+  MF_HIP(hipMemcpy(s.ev_i.get(), irow.data(), n * 4, hipMemcpyHostToDevice));
+  double* dout = nullptr;
+  if (pred_out) { s.ev_out.alloc(n * 8); dout = s.ev_out.as<double>(); }
+  const double* dr = nullptr;
+  const int32_t* dm = nullptr;
+  double* dpart = nullptr;
+  const int grid = predict_grid(n);
+  if (r) {
+    s.ev_r.alloc(n * 8);
+    MF_HIP(hipMemcpy(s.ev_r.get(), r, n * 8, hipMemcpyHostToDevice));
+    dr = s.ev_r.as<double>();
+    s.ev_part.alloc(static_cast<size_t>(grid) * 3 * 8);
+    dpart = s.ev_part.as<double>();
+    if (mult) {
+      s.ev_mult.alloc(n * 4);
+      MF_HIP(hipMemcpy(s.ev_mult.get(), mult, n * 4, hipMemcpyHostToDevice));
+      dm = s.ev_mult.as<int32_t>();
+    }
+  }
+  launch_predict(s.stream, s.ev_u.as<int32_t>(), s.ev_i.as<int32_t>(), n, s.uf.get(), s.itf.get(),
+                 ctx->P.num_factors, ctx->f64, dout, dr, dm, lambda, dpart);
+  MF_HIP(hipGetLastError());
+  MF_HIP(hipStreamSynchronize(s.stream));
+  if (pred_out) {
+    MF_HIP(hipMemcpy(pred_out, dout, n * 8, hipMemcpyDeviceToHost));
+    for (int64_t j = 0; j < n; ++j) found_out[j] = (urow[j] >= 0 && irow[j] >= 0) ? 1 : 0;
+  }
+  if (r) {
+    std::vector<double> part(static_cast<size_t>(grid) * 3);
+    MF_HIP(hipMemcpy(part.data(), dpart, part.size() * 8, hipMemcpyDeviceToHost));
+    for (int w = 0; w < grid; ++w) {
+      res.sse += part[3 * w];
+      res.cnt += part[3 * w + 1];
+      res.risk += part[3 * w + 2];
+    }
+  }
+  if (ctx->rank_mode && ctx->G > 1) {
+    // combine per-rank results: predictions (owner rank writes, others contribute 0), sums
+    DevBuf red;
+    const int64_t m = 3 + (pred_out ? 2 * n : 0);
+    std::vector<double> h(m, 0.0);
+    h[0] = res.sse; h[1] = res.cnt; h[2] = res.risk;
+    if (pred_out)
+      for (int64_t j = 0; j < n; ++j) { h[3 + j] = found_out[j] ? pred_out[j] : 0.0; h[3 + n + j] = found_out[j]; }
+    red.alloc(m * 8);
+    MF_HIP(hipMemcpy(red.get(), h.data(), m * 8, hipMemcpyHostToDevice));
+    MF_NCCL(ncclAllReduce(red.get(), red.get(), m, ncclFloat64, ncclSum, ctx->comm, s.stream));
+    MF_HIP(hipStreamSynchronize(s.stream));
+    MF_HIP(hipMemcpy(h.data(), red.get(), m * 8, hipMemcpyDeviceToHost));
+    res.sse = h[0]; res.cnt = h[1]; res.risk = h[2];
+    if (pred_out)
+      for (int64_t j = 0; j < n; ++j) { pred_out[j] = h[3 + j]; found_out[j] = h[3 + n + j] > 0.5 ? 1 : 0; }
+  }
+  return res;
+}
+
+// ---------------------------------------------------------------------------------------
+// Top-N recommendation (mf_recommend): ids resolved on the host, score + select on the device
+// (kernels_recommend.hip), on shard 0 like evaluate.  Distinct known query rows are scored once, in
+// batches that bound the device scratch at batch x S x top_n keys (S = candidate splits, chosen so
+// that a small batch against a large catalogue still fills the device); every position of
+// queries[] then takes its row's result.  MFHIP_TEST rec_batch=B / rec_split=S override both.
+void recommend(mf_ctx* ctx, int qside, const int32_t* queries, int64_t nq, int32_t top_n, const int32_t* eq,
+               const int32_t* ec, int64_t ne, int32_t* ids_out, double* scores_out, int32_t* counts_out) {
+  Shard& s = ctx->shards[0];
+  consolidate(ctx, s);
+  sync_all(ctx);  // a run may still be sweeping (mf_dsgd_run returns early)
+  const int cside = 1 - qside;
+  const SideLayout& QS = side_of(ctx, qside);
+  const SideLayout& CS = side_of(ctx, cside);
+  const int64_t C = CS.rows();
+  const int k = ctx->P.num_factors;
+  const size_t N = static_cast<size_t>(top_n);
+  constexpr uint32_t kMiss = 0xFFFFFFFFu;
+
+  // distinct known query rows, ascending; pos[j] = queries[j]'s index among them (-1: unknown id)
+  std::vector<uint32_t> qr;
+  lookup_rows(QS, queries, nq, qr);
+  std::vector<int32_t> uniq;
+  uniq.reserve(qr.size());
+  for (uint32_t r : qr)
+    if (r != kMiss) uniq.push_back(static_cast<int32_t>(r));
+  std::sort(uniq.begin(), uniq.end());
+  uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
+  const int64_t nu = static_cast<int64_t>(uniq.size());
+  auto upos = [&](uint32_t row) -> int64_t {
+    if (row == kMiss) return -1;
+    auto it = std::lower_bound(uniq.begin(), uniq.end(), static_cast<int32_t>(row));
+    return it != uniq.end() && *it == static_cast<int32_t>(row) ? it - uniq.begin() : -1;
+  };
+
+  // exclusion CSR: one row per distinct query, sorted candidate rows inside it
+  std::vector<int64_t> eoff(static_cast<size_t>(nu) + 1, 0);
+  std::vector<int32_t> erows;
+  if (ne > 0 && nu > 0 && C > 0) {
+    std::vector<uint32_t> er_q, er_c;
+    lookup_rows(QS, eq, ne, er_q);
+    lookup_rows(CS, ec, ne, er_c);
+    std::vector<uint64_t> pairs;
+    pairs.reserve(static_cast<size_t>(ne));
+    for (int64_t e = 0; e < ne; ++e) {
+      const int64_t u = upos(er_q[e]);
+      if (u < 0 || er_c[e] == kMiss) continue;
+      pairs.push_back((static_cast<uint64_t>(u) << 32) | er_c[e]);
+    }
+    std::sort(pairs.begin(), pairs.end());
+    pairs.erase(std::unique(pairs.begin(), pairs.end()), pairs.end());
+    erows.resize(pairs.size());
+    for (size_t x = 0; x < pairs.size(); ++x) {
+      ++eoff[(pairs[x] >> 32) + 1];
+      erows[x] = static_cast<int32_t>(pairs[x] & 0xFFFFFFFFu);
+    }
+    for (int64_t u = 0; u < nu; ++u) eoff[u + 1] += eoff[u];
+  }
+
+  std::vector<int32_t> uid(static_cast<size_t>(nu) * N, 0), ucnt(static_cast<size_t>(nu), 0);
+  std::vector<double> usc(scores_out ? static_cast<size_t>(nu) * N : 0, 0.0);
+  if (nu > 0 && C > 0) {
+    DeviceGuard g(s.device);
+    if (s.rec_id_gen[cside] != ctx->layout_gen || s.rec_id[cside].bytes() < static_cast<size_t>(C) * 4) {
+      s.rec_id[cside].alloc(static_cast<size_t>(C) * 4);
+      MF_HIP(hipMemcpy(s.rec_id[cside].get(), CS.row_id.data(), static_cast<size_t>(C) * 4, hipMemcpyHostToDevice));
+      s.rec_id_gen[cside] = ctx->layout_gen;
+    }
+    s.rec_q.alloc(static_cast<size_t>(nu) * 4);
+    s.rec_eoff.alloc(eoff.size() * 8);
+    s.rec_erows.alloc(std::max<size_t>(erows.size(), 1) * 4);
+    MF_HIP(hipMemcpy(s.rec_q.get(), uniq.data(), static_cast<size_t>(nu) * 4, hipMemcpyHostToDevice));
+    MF_HIP(hipMemcpy(s.rec_eoff.get(), eoff.data(), eoff.size() * 8, hipMemcpyHostToDevice));
+    if (!erows.empty()) MF_HIP(hipMemcpy(s.rec_erows.get(), erows.data(), erows.size() * 4, hipMemcpyHostToDevice));
+
+    int64_t batch = 8192;
+    if (const std::string v = test_knob("rec_batch"); !v.empty()) batch = std::max<int64_t>(1, std::atoll(v.c_str()));
+    batch = std::min(batch, nu);
+    // S: enough workgroups for two per CU, each split at least one candidate tile of 128 rows
+    const int qt = recommend_query_tile(top_n, ctx->f64);
+    const int64_t qtiles = (batch + qt - 1) / qt;
+    int64_t S = std::min<int64_t>((512 + qtiles - 1) / qtiles, (C + 127) / 128);
+    if (const std::string v = test_knob("rec_split"); !v.empty()) S = std::atoll(v.c_str());
+    S = std::max<int64_t>(1, std::min<int64_t>({S, 64, C}));
+
+    s.rec_part.alloc(static_cast<size_t>(batch) * S * N * recommend_key_bytes(ctx->f64));
+    s.rec_ids.alloc(static_cast<size_t>(batch) * N * 4);
+    s.rec_scores.alloc(static_cast<size_t>(batch) * N * 8);
+    s.rec_counts.alloc(static_cast<size_t>(batch) * 4);
+    const void* Q = qside == kSideU ? s.uf.get() : s.itf.get();
+    const void* Cf = cside == kSideU ? s.uf.get() : s.itf.get();
+    for (int64_t b0 = 0; b0 < nu; b0 += batch) {
+      const int64_t nb = std::min(batch, nu - b0);
+      launch_recommend(s.stream, Q, Cf, s.rec_q.as<int32_t>() + b0, static_cast<int>(nb), static_cast<int32_t>(C),
+                       static_cast<int>(S), k, top_n, ctx->f64, s.rec_id[cside].as<int32_t>(),
+                       s.rec_eoff.as<int64_t>() + b0, s.rec_erows.as<int32_t>(), s.rec_part.get(),
+                       s.rec_ids.as<int32_t>(), s.rec_scores.as<double>(), s.rec_counts.as<int32_t>());
+      MF_HIP(hipGetLastError());
+      MF_HIP(hipStreamSynchronize(s.stream));
+      MF_HIP(hipMemcpy(uid.data() + static_cast<size_t>(b0) * N, s.rec_ids.get(), static_cast<size_t>(nb) * N * 4,
+                       hipMemcpyDeviceToHost));
+      if (scores_out)
+        MF_HIP(hipMemcpy(usc.data() + static_cast<size_t>(b0) * N, s.rec_scores.get(), static_cast<size_t>(nb) * N * 8,
+                         hipMemcpyDeviceToHost));
+      MF_HIP(hipMemcpy(ucnt.data() + b0, s.rec_counts.get(), static_cast<size_t>(nb) * 4, hipMemcpyDeviceToHost));
+    }
+  }
+  parallel_for(nq, [&](int64_t b, int64_t e, int) {
+    for (int64_t j = b; j < e; ++j) {
+      const int64_t u = upos(qr[j]);
+      int32_t* io = ids_out + static_cast<size_t>(j) * N;
+      if (u < 0) {
+        counts_out[j] = 0;
+        std::fill(io, io + N, 0);
+        if (scores_out) std::fill(scores_out + static_cast<size_t>(j) * N, scores_out + static_cast<size_t>(j + 1) * N, 0.0);
+        continue;
+      }
+      counts_out[j] = ucnt[u];
+      std::memcpy(io, uid.data() + static_cast<size_t>(u) * N, N * 4);
+      if (scores_out) std::memcpy(scores_out + static_cast<size_t>(j) * N, usc.data() + static_cast<size_t>(u) * N, N * 8);
+    }
+  });
+}
+
+// Every row of a side (rank mode: the rank's own users), ascending by id (mf_get_factors).
+void get_factors(mf_ctx* ctx, int side, int32_t* ids, double* vecs, int64_t cap, int64_t* written) {
+  MF_REQUIRE(ctx->have_model, "The MatrixFactorization model has not been fitted to data.");
+  require_healthy(ctx);
+  Shard& s = ctx->shards[0];
+  if (ctx->rank_mode) { if (side == MF_SIDE_ITEM) allgather_items(ctx); }
+  else consolidate(ctx, s);
+  sync_all(ctx);
+  ensure_order(ctx);
+  const SideLayout& S = side_of(ctx, side);
+  const int k = ctx->P.num_factors;
+  std::vector<double> all(static_cast<size_t>(std::max<int64_t>(S.rows(), 1)) * k);
+  download_rows(ctx, s, side, 0, S.rows(), all.data());
+  const auto& ord = side == kSideU ? ctx->rows_by_id_u : ctx->rows_by_id_i;
+  int64_t w = 0;
+  const int me = s.index;
+  for (int64_t x = 0; x < S.rows(); ++x) {
+    const int32_t row = ord[x];
+    if (ctx->rank_mode && side == kSideU && S.row_block[row] / ctx->c != me) continue;
+    if (w >= cap) fail(MF_ERR_CAPACITY, "output capacity too small");
+    if (ids) ids[w] = S.row_id[row];
+    if (vecs) std::memcpy(vecs + static_cast<size_t>(w) * k, all.data() + static_cast<size_t>(row) * k, sizeof(double) * k);
+    ++w;
+  }
+  if (written) *written = w;
+}
+
+void lookup_factors(mf_ctx* ctx, int side, const int32_t* ids, int64_t n, double* vecs_out, uint8_t* found) {
+  MF_REQUIRE(ctx->have_model, "no model");
+  Shard& s = ctx->shards[0];
+  if (!ctx->rank_mode) consolidate(ctx, s);
+  else if (side == MF_SIDE_ITEM) allgather_items(ctx);
+  sync_all(ctx);
+  const SideLayout& S = side_of(ctx, side);
+  const int k = ctx->P.num_factors;
+  std::vector<double> row(k);
+  for (int64_t j = 0; j < n; ++j) {
+    const int32_t x = S.index.find(ids[j]);
+    found[j] = x >= 0;
+    if (x < 0) { std::fill(vecs_out + j * k, vecs_out + (j + 1) * k, 0.0); continue; }
+    download_rows(ctx, s, side, x, 1, vecs_out + static_cast<size_t>(j) * k);
+  }
+}
+
+}  // namespace mfhip

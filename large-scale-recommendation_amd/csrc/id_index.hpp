@@ -29,7 +29,7 @@ class IdIndex {
   void clear() { slots_.clear(); size_ = 0; mask_ = 0; gen_ = next_gen(); log_.clear(); }
   int64_t size() const { return size_; }
 
-  // The device mirror of the table (mfhip.cpp DevIndex, the online batch's id lookup on the GPU)
+  // The device mirror of the table (online.cpp sync_dev_index, the online batch's id lookup on the GPU)
   // copies slots() whole when gen() changed (a rehash or clear: every slot may have moved) and
   // otherwise only the slots written since, listed in log() in write order.  gen() is unique
   // across all tables of the process, so a table replaced by another never matches a stale mirror.

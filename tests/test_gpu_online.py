@@ -275,3 +275,57 @@ def test_device_id_lookup_equals_host_lookup(monkeypatch, mode):
     for side in (0, 1):
         assert np.array_equal(res["host"][side][0], res["device"][side][0])
         assert np.array_equal(res["host"][side][1], res["device"][side][1])
+
+
+_SWEEP, _LEVEL = "sweep", "level"
+
+
+@pytest.mark.parametrize("mode,k,knobs,call,expect", [
+    (L.MODE_FAST_F32, 64, {}, "update", _SWEEP),                           # k_online_f32, queued behind the lookup
+    (L.MODE_DETERMINISTIC_F64, 64, {}, "update", _SWEEP),                  # the deterministic split sweep
+    (L.MODE_DETERMINISTIC_F64, 200, {}, "update", _SWEEP),                 # k_online_sweep (no split sweep at k = 200)
+    (L.MODE_FAST_F32, 300, {}, "update", _SWEEP),                          # k_online_sweep (past k_online_f32)
+    (L.MODE_FAST_F32, 64, {"offset_limit": "1"}, "update", _SWEEP),        # k_online_sweep (offset-limit fallback)
+    (L.MODE_FAST_F32, 64, {}, "spark", _SWEEP),                            # staged Spark-sweep order
+    (L.MODE_DETERMINISTIC_F64, 64, {}, "spark", _SWEEP),
+    (L.MODE_FAST_F32, 64, {"online_kernel": "level"}, "update", _LEVEL),
+    (L.MODE_DETERMINISTIC_F64, 64, {"online_kernel": "level"}, "update", _LEVEL),
+    (L.MODE_DETERMINISTIC_F64, 64, {}, "out", _LEVEL),                     # per-rating outputs: always the replay
+])
+def test_online_dispatch_counts(monkeypatch, mode, k, knobs, call, expect):
+    """Which kind of kernel an online batch ran, read from mf_get_stats: every sweep path is one
+    launch and no level, the level replay one launch per level.  (The other tests here compare the
+    sweeps with the level replay bit for bit, so a dispatch that sent every batch to the replay
+    would pass them.)  The second batch brings ids the model has not seen: on the device-lookup
+    path the queued sweep is skipped on the device and runs again after the host has given the
+    new ids rows -- still exactly one launch counted."""
+    rng = np.random.default_rng(5)
+    n, hot = 2000, 50
+    batches = []
+    for shift_u, shift_i in ((0, 0), (30, 10)):  # second batch: about a tenth of the ids are new
+        u = (rng.integers(0, 300, n) + shift_u).astype(np.int32)
+        i = (rng.integers(0, 100, n) + shift_i).astype(np.int32)
+        i[::17] = hot  # a hot item: the f32 single-item path, the f64 chain / helper pair
+        batches.append((u, i, rng.integers(1, 6, n).astype(np.float64)))
+    for key, value in knobs.items():
+        set_knob(monkeypatch, key, value)
+    p = L.default_params()
+    p.num_factors, p.mode, p.online_learning_rate = k, mode, 0.01
+    with mfhip.Context(p) as ctx:
+        for b, (u, i, r) in enumerate(batches):
+            new_ids = len(np.setdiff1d(u, batches[0][0])) + len(np.setdiff1d(i, batches[0][1])) if b else None
+            assert new_ids is None or new_ids > 0
+            ctx.reset_stats()
+            if call == "out":
+                ctx.online_update_out(u, i, r, L.ONLINE_NEXT_FACTORS)
+            elif call == "spark":
+                ctx.online_update(u, i, r, L.ONLINE_SPARK_SWEEP, num_partitions=4)
+            else:
+                ctx.online_update(u, i, r, L.ONLINE_NEXT_FACTORS)
+            st = ctx.stats()
+            print(f"batch {b}: launches {st['kernel_launches']} levels {st['levels']} updates {st['updates']}")
+            assert st["updates"] == n
+            if expect == _SWEEP:
+                assert (st["kernel_launches"], st["levels"]) == (1, 0), (b, st)
+            else:
+                assert st["levels"] >= 1 and st["kernel_launches"] == st["levels"], (b, st)

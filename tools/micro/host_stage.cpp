@@ -1,4 +1,4 @@
-// Host side of one online micro-batch upload (mfhip.cpp online_update): the batch's three arrays
+// Host side of one online micro-batch upload (online.cpp stage_and_lookup_device): the batch's three arrays
 // (user ids, item ids, ratings: 16 B per rating) copied into the pinned upload buffer by host
 // threads, then one H2D copy.  Measures, on the box's CPU: thread spawn per call (parallel_for as
 // of round 6) against a persistent worker pool (common.hpp WorkerPool), the copy itself at 4-16
