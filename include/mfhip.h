@@ -239,6 +239,37 @@ int mf_als_prepare(mf_ctx* ctx, const int32_t* users, const int32_t* items, cons
                    int64_t n);
 int mf_als_run(mf_ctx* ctx, int64_t half_sweeps, double lambda, int32_t reg);
 
+/* ALS.trainImplicit(ratings, rank, iterations, lambda, alpha): the confidence-weighted factorisation
+   of implicit feedback (Hu, Koren, Volinsky 2008) as MLlib runs it.  mf_als_prepare is shared and
+   unchanged; mf_als_run_implicit runs half-sweeps on the prepared data, mf_als_fit_implicit is
+   mf_als_prepare followed by mf_als_run_implicit(2 * iterations) (n == 0: a no-op).
+   Arithmetic.  A half-sweep solves, for every row a of one side with at least one rating,
+       (G + sum_j w_j q_j q_j^T + lambda' I) x = sum_{j : r_j > 0} (1 + w_j) q_j,   w_j = alpha * |r_j|
+   The sums run over that row's ratings j in CSR order, duplicate pairs included; q_j is the
+   counterpart's row as it stands when the half-sweep begins.  G = sum_b y_b y_b^T runs over the
+   counterpart rows b with at least one rating in the prepared data (the rows MLlib has factors
+   for): rows the context holds but the data does not name take no part in G and are left untouched.
+   This is MLlib's rule (c1 = alpha * |r|; ls.add(q, if r > 0 then 1 + c1 else 0, c1)): a rating of 0
+   contributes nothing, a negative rating adds confidence to a preference of 0.
+   lambda' = lambda * n+_a for MF_ALS_REG_WEIGHTED, n+_a the number of the row's ratings with r > 0
+   (MLlib's numExplicits), and lambda' = lambda for MF_ALS_REG_PLAIN.  A row whose ratings are all
+   <= 0 has a zero right-hand side: it is set to zero without factorising (the exact solution of a
+   nonsingular system, also where lambda' = 0).
+   Order.  The rating sum is taken per chunk in CSR order, chunks ascending, exactly as mf_als_run
+   takes it; then + G; then + lambda' on the diagonal.  Only the lower triangle is formed, the weight
+   multiplying one operand -- (w_j q_j[a]) * q_j[b] with a >= b -- so the matrix is symmetric by
+   construction.  G itself is summed over the rated rows in ascending row order, in slices of 1024
+   rows whose partial sums are added in ascending order.  Deterministic contexts compute in f64,
+   fast contexts in f32 throughout (alpha, lambda and the ratings rounded to f32).  Results are
+   bitwise reproducible from run to run.  mf_als_run's rule for a pivot that is not a positive
+   finite number holds.  The half-sweep order and the counter are mf_als_run's, and the two kinds
+   of run call share the counter: the item side first, 0 after mf_als_prepare, continuing across calls.
+   Errors.  MF_ERR_INVALID: alpha < 0 or not finite (alpha = 0 is valid); otherwise exactly
+   mf_als_run's / mf_als_fit's. */
+int mf_als_run_implicit(mf_ctx* ctx, int64_t half_sweeps, double lambda, int32_t reg, double alpha);
+int mf_als_fit_implicit(mf_ctx* ctx, const int32_t* users, const int32_t* items, const double* ratings,
+                        int64_t n, int32_t iterations, double lambda, int32_t reg, double alpha);
+
 /* Exact updateLocalFactors replacement (DSGDforMF.scala:378-418) on caller buffers:
    users[nu x k], items[ni x k] are updated in place; omegas are per row.  Reentrant
    on disjoint buffers with distinct contexts, as Flink calls it per task slot. */

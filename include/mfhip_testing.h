@@ -63,6 +63,15 @@ int mf_debug_device_bytes(int64_t out[2]);
    MF_ERR_INVALID for an id that is unknown or has no rating in the prepared data. */
 int mf_debug_als_normal_eq(mf_ctx* ctx, int side, int32_t id, double lambda, int32_t reg, double* A_out,
                            double* b_out);
+/* mf_debug_als_gram: after mf_als_prepare, G_out[k * k] = sum of y y^T over the rows of `side` that
+   have a rating in the prepared data, from the current factors, through the implicit half-sweep's
+   own two launches (k_als_gram and its reduction), widened to f64.
+   mf_debug_als_normal_eq_implicit: as mf_debug_als_normal_eq for the system mf_als_run_implicit
+   would solve: A_out = G + sum w q q^T + lambda' I, b_out = sum_{r > 0} (1 + w) q.  A row with no
+   positive rating reports its system (b_out zero); the half-sweep sets that row to zero unsolved. */
+int mf_debug_als_gram(mf_ctx* ctx, int side, double* G_out);
+int mf_debug_als_normal_eq_implicit(mf_ctx* ctx, int side, int32_t id, double lambda, int32_t reg, double alpha,
+                                    double* A_out, double* b_out);
 
 #ifdef __cplusplus
 }

@@ -36,6 +36,10 @@ public final class MfHip {
   // reg: 0 = lambda * n_row (ALS-WR, what ALS.train does), 1 = plain lambda
   public static native void alsFit(long ctx, int[] users, int[] items, double[] ratings,
                                    int iterations, double lambda, int reg);
+  // ALS.trainImplicit(ratings, rank = numFactors, iterations, lambda, alpha): confidences
+  // 1 + alpha |r|, preferences r > 0; reg as above, with n_row counting the ratings r > 0
+  public static native void alsFitImplicit(long ctx, int[] users, int[] items, double[] ratings,
+                                           int iterations, double lambda, int reg, double alpha);
   // unblock (DSGDforMF.scala:245-255) and checkpoint restore
   public static native long numFactors(long ctx, int side);
   public static native long getFactors(long ctx, int side, int[] idsOut, double[] vecsOut);

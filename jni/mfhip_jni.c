@@ -185,6 +185,25 @@ JNIEXPORT void JNICALL JFN(alsFit)(JNIEnv* env, jclass c, jlong h, jintArray u, 
   check(env, st);
 }
 
+/* ALS.trainImplicit(ratings, rank, iterations, lambda, alpha): mf_als_fit_implicit */
+JNIEXPORT void JNICALL JFN(alsFitImplicit)(JNIEnv* env, jclass c, jlong h, jintArray u, jintArray i, jdoubleArray r,
+                                           jint iterations, jdouble lambda, jint reg, jdouble alpha) {
+  jsize n = 0;
+  if (rating_columns(env, u, i, r, &n)) return;
+  Elems eu = {0}, ei = {0}, er = {0};
+  if (acquire(env, &eu, u, kInt) || acquire(env, &ei, i, kInt) || acquire(env, &er, r, kDouble)) {
+    release(env, &eu, JNI_ABORT);
+    release(env, &ei, JNI_ABORT);
+    return;
+  }
+  int st = mf_als_fit_implicit(CTX(h), (const int32_t*)eu.p, (const int32_t*)ei.p, (const double*)er.p, n, iterations,
+                               lambda, reg, alpha);
+  release(env, &er, JNI_ABORT);
+  release(env, &ei, JNI_ABORT);
+  release(env, &eu, JNI_ABORT);
+  check(env, st);
+}
+
 JNIEXPORT void JNICALL JFN(dsgdRun)(JNIEnv* env, jclass c, jlong h, jlong supersteps) {
   check(env, mf_dsgd_run(CTX(h), supersteps));
 }

@@ -268,6 +268,46 @@ int mf_als_fit(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r,
   });
 }
 
+int mf_als_run_implicit(mf_ctx* ctx, int64_t half_sweeps, double lambda, int32_t reg, double alpha) {
+  return guarded([&] {
+    MF_REQUIRE(ctx, "null context");
+    als_check_alpha(alpha);
+    als_run(ctx, half_sweeps, lambda, reg, alpha);
+  });
+}
+
+int mf_als_fit_implicit(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n,
+                        int32_t iterations, double lambda, int32_t reg, double alpha) {
+  return guarded([&] {
+    MF_REQUIRE(ctx, "null context");
+    MF_REQUIRE(n >= 0 && iterations >= 0, "negative count");
+    als_check_alpha(alpha);
+    als_check_run(lambda, reg);
+    als_check(ctx);
+    if (n == 0) return;
+    als_prepare(ctx, u, i, r, n);
+    als_run(ctx, 2 * static_cast<int64_t>(iterations), lambda, reg, alpha);
+  });
+}
+
+int mf_debug_als_gram(mf_ctx* ctx, int side, double* G_out) {
+  return guarded([&] {
+    MF_REQUIRE(ctx && G_out, "null argument");
+    MF_REQUIRE(side == MF_SIDE_USER || side == MF_SIDE_ITEM, "bad side");
+    als_gram(ctx, side, G_out);
+  });
+}
+
+int mf_debug_als_normal_eq_implicit(mf_ctx* ctx, int side, int32_t id, double lambda, int32_t reg, double alpha,
+                                    double* A_out, double* b_out) {
+  return guarded([&] {
+    MF_REQUIRE(ctx && A_out && b_out, "null argument");
+    MF_REQUIRE(side == MF_SIDE_USER || side == MF_SIDE_ITEM, "bad side");
+    als_check_alpha(alpha);
+    als_normal_eq(ctx, side, id, lambda, reg, A_out, b_out, alpha);
+  });
+}
+
 int mf_debug_als_normal_eq(mf_ctx* ctx, int side, int32_t id, double lambda, int32_t reg, double* A_out,
                            double* b_out) {
   return guarded([&] {

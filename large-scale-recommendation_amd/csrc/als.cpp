@@ -1,4 +1,5 @@
-// als.cpp -- ALS training (mf_als_prepare / mf_als_run / mf_als_fit) and its testing hook.
+// als.cpp -- ALS training (mf_als_prepare / mf_als_run / mf_als_fit, mf_als_run_implicit /
+// mf_als_fit_implicit) and its testing hooks.
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -24,6 +25,10 @@ namespace mfhip {
 constexpr int64_t kAlsChunk = 16384;     // ratings per work item of a long row (MFHIP_TEST als_chunk=N)
 constexpr int64_t kAlsBatch = 16384;     // rows per launch (MFHIP_TEST als_batch=B)
 constexpr int64_t kAlsBatchSlots = 2048; // partial systems per launch: a new launch starts past this
+// Rated rows per workgroup of k_als_gram (MFHIP_TEST als_gram_slice=N): 32 tiles.  A constant of the
+// data, never of the device, so G's summation order is the same everywhere; at 480,189 rows it gives
+// 469 workgroups and 30 MB of f32 partials at k = 128.
+constexpr int64_t kAlsGramSlice = 1024;
 
 void als_check(const mf_ctx* ctx) {
   if (ctx->rank_mode || ctx->shards.size() != 1)
@@ -32,6 +37,10 @@ void als_check(const mf_ctx* ctx) {
              "ALS supports a rank of at most " + std::to_string(kAlsMaxRank) +
                  " (the k x k normal matrix of a row is kept in LDS); this context has k = " +
                  std::to_string(ctx->P.num_factors));
+}
+
+void als_check_alpha(double alpha) {
+  MF_REQUIRE(alpha >= 0.0 && std::isfinite(alpha), "implicit ALS needs a finite alpha >= 0");
 }
 
 void als_check_run(double lambda, int32_t reg) {
@@ -67,21 +76,25 @@ void als_build_side(mf_ctx* ctx, Shard& s, int side, const std::vector<uint32_t>
     cur = {static_cast<int64_t>(A.items.size()), 0, static_cast<int64_t>(A.splits.size()), 0};
     cur_rows = cur_slots = 0;
   };
+  std::vector<int32_t> rated;
   for (int64_t row = 0; row < rows; ++row) {
     const int64_t c = off[row + 1] - off[row];
     if (c == 0) continue;
     MF_REQUIRE(c <= INT32_MAX, "ALS: a row has more than 2^31 - 1 ratings");
+    rated.push_back(static_cast<int32_t>(row));
+    int32_t npos = 0;  // MLlib's numExplicits: the implicit half-sweep's n+
+    for (int64_t p = off[row]; p < off[row + 1]; ++p) npos += vals[p] > T(0);
     const int64_t nch = c <= chunk ? 1 : (c + chunk - 1) / chunk;
     if (cur_rows >= batch || (nch > 1 && cur_slots > 0 && cur_slots + nch > kAlsBatchSlots)) close();
     if (nch == 1) {
-      A.items.push_back({off[row], static_cast<int32_t>(row), static_cast<int32_t>(c), -1, 0});
+      A.items.push_back({off[row], static_cast<int32_t>(row), static_cast<int32_t>(c), -1, npos});
       cur.items += 1;
     } else {
       for (int64_t ch = 0; ch < nch; ++ch)
         A.items.push_back({off[row] + ch * chunk, static_cast<int32_t>(row),
-                           static_cast<int32_t>(std::min(chunk, c - ch * chunk)), static_cast<int32_t>(cur_slots + ch), 0});
+                           static_cast<int32_t>(std::min(chunk, c - ch * chunk)), static_cast<int32_t>(cur_slots + ch), npos});
       A.splits.push_back({static_cast<int32_t>(row), static_cast<int32_t>(cur_slots), static_cast<int32_t>(nch),
-                          static_cast<int32_t>(c)});
+                          static_cast<int32_t>(c), npos});
       cur.items += nch;
       cur.splits += 1;
       cur_slots += nch;
@@ -89,6 +102,7 @@ void als_build_side(mf_ctx* ctx, Shard& s, int side, const std::vector<uint32_t>
     ++cur_rows;
   }
   close();
+  A.rated = static_cast<int64_t>(rated.size());
   DeviceGuard g(s.device);
   auto up = [&](DevBuf& d, const void* src, size_t bytes) {
     d.alloc(std::max<size_t>(bytes, 16));
@@ -98,6 +112,7 @@ void als_build_side(mf_ctx* ctx, Shard& s, int side, const std::vector<uint32_t>
   up(s.als_vals[side], vals.data(), vals.size() * sizeof(T));
   up(s.als_items[side], A.items.data(), A.items.size() * sizeof(AlsItem));
   up(s.als_splits[side], A.splits.data(), A.splits.size() * sizeof(AlsSplit));
+  up(s.als_rated[side], rated.data(), rated.size() * 4);
 }
 
 }  // namespace
@@ -148,6 +163,9 @@ void als_prepare(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* 
   int64_t chunk = kAlsChunk, batch = kAlsBatch;
   if (const std::string v = test_knob("als_chunk"); !v.empty()) chunk = std::max<int64_t>(1, std::atoll(v.c_str()));
   if (const std::string v = test_knob("als_batch"); !v.empty()) batch = std::max<int64_t>(1, std::atoll(v.c_str()));
+  ctx->als_gram_slice = kAlsGramSlice;
+  if (const std::string v = test_knob("als_gram_slice"); !v.empty())
+    ctx->als_gram_slice = std::min<int64_t>(std::max<int64_t>(1, std::atoll(v.c_str())), 1 << 30);
   if (ctx->f64) {
     als_build_side<double>(ctx, s, kSideU, ur, ir, r, n, ctx->U.rows(), chunk, batch);
     als_build_side<double>(ctx, s, MF_SIDE_ITEM, ir, ur, r, n, ctx->I.rows(), chunk, batch);
@@ -161,13 +179,28 @@ void als_prepare(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* 
 
 namespace {
 
-// One side solved from the other.  only_row >= 0 (the testing hook): that row's work items alone,
-// its system stored to s.als_dump instead of being solved; false if the row has no rating.
-bool als_half(mf_ctx* ctx, int side, double lambda, int32_t reg, int64_t only_row = -1) {
+// G of `side`'s rated rows into s.als_gram, on the shard's stream: two launches.
+void als_gram_launch(mf_ctx* ctx, Shard& s, int side) {
+  const int k = ctx->P.num_factors;
+  const int m = static_cast<int>(ctx->als[side].rated), slice = static_cast<int>(ctx->als_gram_slice);
+  const size_t ge = als_gram_elems(k) * ctx->es;
+  s.als_gram_part.alloc(std::max<size_t>(static_cast<size_t>(als_gram_slices(m, slice)) * ge, 16));
+  s.als_gram.alloc(ge);
+  launch_als_gram(s.stream, s.als_rated[side].as<int32_t>(), m, slice, side == kSideU ? s.uf.get() : s.itf.get(), k,
+                  ctx->f64, s.als_gram_part.get(), s.als_gram.get());
+  MF_HIP(hipGetLastError());
+}
+
+// One side solved from the other; alpha >= 0: the implicit half-sweep, after the counterpart's Gram
+// matrix.  only_row >= 0 (the testing hook): that row's work items alone, its system stored to
+// s.als_dump instead of being solved; false if the row has no rating.
+bool als_half(mf_ctx* ctx, int side, double lambda, int32_t reg, double alpha, int64_t only_row = -1) {
   Shard& s = ctx->shards[0];
   DeviceGuard g(s.device);
   const mf_ctx::AlsSide& A = ctx->als[side];
   const int k = ctx->P.num_factors;
+  const bool implicit = alpha >= 0.0;
+  const int other = side == kSideU ? MF_SIDE_ITEM : kSideU;
   s.als_part.alloc(std::max<size_t>(static_cast<size_t>(A.max_slots) * als_partial_elems(k) * ctx->es, 16));
   const void* Q = side == kSideU ? s.itf.get() : s.uf.get();
   void* X = side == kSideU ? s.uf.get() : s.itf.get();
@@ -184,17 +217,23 @@ bool als_half(mf_ctx* ctx, int side, double lambda, int32_t reg, int64_t only_ro
                                [](const AlsSplit& a, int64_t row) { return a.row < row; });
     const bool split = sp != A.splits.end() && sp->row == only_row;
     s.als_dump.alloc((static_cast<size_t>(k) * k + k) * ctx->es);
+    if (implicit) als_gram_launch(ctx, s, other);
     launch_als(s.stream, d_items + (lo - A.items.begin()), static_cast<int>(hi - lo),
                d_splits + (sp - A.splits.begin()), split ? 1 : 0, s.als_cols[side].as<int32_t>(),
-               s.als_vals[side].get(), Q, X, k, lambda, weighted, ctx->f64, s.als_part.get(), s.als_dump.get());
+               s.als_vals[side].get(), Q, X, k, lambda, weighted, ctx->f64, s.als_part.get(), s.als_dump.get(),
+               implicit ? s.als_gram.get() : nullptr, alpha);
     MF_HIP(hipGetLastError());
     return true;
   }
   LaunchTimer t(s, ctx->profiling);
+  if (implicit && !A.batches.empty()) {
+    als_gram_launch(ctx, s, other);
+    ctx->stats.kernel_launches += 2;
+  }
   for (const mf_ctx::AlsBatch& b : A.batches) {
     launch_als(s.stream, d_items + b.item0, static_cast<int>(b.items), d_splits + b.split0, static_cast<int>(b.splits),
                s.als_cols[side].as<int32_t>(), s.als_vals[side].get(), Q, X, k, lambda, weighted, ctx->f64,
-               s.als_part.get(), nullptr);
+               s.als_part.get(), nullptr, implicit ? s.als_gram.get() : nullptr, alpha);
     MF_HIP(hipGetLastError());
     ctx->stats.kernel_launches += 1 + (b.splits > 0);
   }
@@ -203,32 +242,37 @@ bool als_half(mf_ctx* ctx, int side, double lambda, int32_t reg, int64_t only_ro
 
 }  // namespace
 
-void als_run(mf_ctx* ctx, int64_t half_sweeps, double lambda, int32_t reg) {
+void als_run(mf_ctx* ctx, int64_t half_sweeps, double lambda, int32_t reg, double alpha) {
   MF_REQUIRE(half_sweeps >= 0, "negative half-sweep count");
   als_check_run(lambda, reg);
   als_check(ctx);
-  if (!ctx->als_prepared) fail(MF_ERR_STATE, "mf_als_run before mf_als_prepare");
+  if (!ctx->als_prepared)
+    fail(MF_ERR_STATE, std::string(alpha >= 0.0 ? "mf_als_run_implicit" : "mf_als_run") + " before mf_als_prepare");
   require_healthy(ctx);
   sync_all(ctx);
   for (int64_t h = 0; h < half_sweeps; ++h) {
     // MLlib's order: the item side from the user factors first
-    als_half(ctx, ctx->als_half_sweeps % 2 == 0 ? MF_SIDE_ITEM : kSideU, lambda, reg);
+    als_half(ctx, ctx->als_half_sweeps % 2 == 0 ? MF_SIDE_ITEM : kSideU, lambda, reg, alpha);
     ++ctx->als_half_sweeps;
   }
   DeviceGuard g(ctx->shards[0].device);
   MF_HIP(hipStreamSynchronize(ctx->shards[0].stream));
 }
 
-// The normal equations of one row as the kernel accumulates them (mf_debug_als_normal_eq).
-void als_normal_eq(mf_ctx* ctx, int side, int32_t id, double lambda, int32_t reg, double* A_out, double* b_out) {
+// The normal equations of one row as the kernel accumulates them (mf_debug_als_normal_eq, and with
+// alpha >= 0 mf_debug_als_normal_eq_implicit).
+void als_normal_eq(mf_ctx* ctx, int side, int32_t id, double lambda, int32_t reg, double* A_out, double* b_out,
+                   double alpha) {
   als_check_run(lambda, reg);
   als_check(ctx);
-  if (!ctx->als_prepared) fail(MF_ERR_STATE, "mf_debug_als_normal_eq before mf_als_prepare");
+  if (!ctx->als_prepared)
+    fail(MF_ERR_STATE, std::string(alpha >= 0.0 ? "mf_debug_als_normal_eq_implicit" : "mf_debug_als_normal_eq") +
+                           " before mf_als_prepare");
   require_healthy(ctx);
   sync_all(ctx);
   const int32_t row = side_of(ctx, side).index.find(id);
   MF_REQUIRE(row >= 0, "unknown id");
-  MF_REQUIRE(als_half(ctx, side, lambda, reg, row), "the id has no rating in the prepared data");
+  MF_REQUIRE(als_half(ctx, side, lambda, reg, alpha, row), "the id has no rating in the prepared data");
   Shard& s = ctx->shards[0];
   DeviceGuard g(s.device);
   MF_HIP(hipStreamSynchronize(s.stream));
@@ -243,6 +287,31 @@ void als_normal_eq(mf_ctx* ctx, int side, int32_t id, double lambda, int32_t reg
   }
   std::memcpy(A_out, h.data(), k * k * 8);
   std::memcpy(b_out, h.data() + k * k, k * 8);
+}
+
+// G of one side's rated rows through the half-sweep's own launches (mf_debug_als_gram).
+void als_gram(mf_ctx* ctx, int side, double* G_out) {
+  als_check(ctx);
+  if (!ctx->als_prepared) fail(MF_ERR_STATE, "mf_debug_als_gram before mf_als_prepare");
+  require_healthy(ctx);
+  sync_all(ctx);
+  Shard& s = ctx->shards[0];
+  DeviceGuard g(s.device);
+  {
+    LaunchTimer t(s, ctx->profiling);
+    als_gram_launch(ctx, s, side);
+  }
+  MF_HIP(hipStreamSynchronize(s.stream));
+  const size_t k = static_cast<size_t>(ctx->P.num_factors), kp = (k + 31) / 32 * 32;
+  std::vector<double> h(kp * kp);
+  if (ctx->f64) {
+    MF_HIP(hipMemcpy(h.data(), s.als_gram.get(), kp * kp * 8, hipMemcpyDeviceToHost));
+  } else {
+    std::vector<float> f(kp * kp);
+    MF_HIP(hipMemcpy(f.data(), s.als_gram.get(), kp * kp * 4, hipMemcpyDeviceToHost));
+    for (size_t x = 0; x < kp * kp; ++x) h[x] = static_cast<double>(f[x]);
+  }
+  for (size_t a = 0; a < k; ++a) std::memcpy(G_out + a * k, h.data() + a * kp, k * 8);
 }
 
 }  // namespace mfhip

@@ -130,6 +130,8 @@ struct Shard {
   // ALS (mf_als_prepare): per solved side [user, item] the CSR (counterpart rows, ratings) and the
   // work lists; the long rows' partial systems of one launch; the testing hook's output
   DevBuf als_cols[2], als_vals[2], als_items[2], als_splits[2], als_part, als_dump;
+  // ... the implicit half-sweep: per side its rated rows, the Gram partials of one side and G itself
+  DevBuf als_rated[2], als_gram_part, als_gram;
   // profiling
   std::vector<hipEvent_t> ev;
   size_t ev_used = 0;
@@ -197,7 +199,9 @@ struct mf_ctx {
     std::vector<mfhip::AlsSplit> splits;
     std::vector<AlsBatch> batches;
     int64_t max_slots = 0;
+    int64_t rated = 0;  // rows with at least one rating (the length of Shard::als_rated)
   } als[2];
+  int64_t als_gram_slice = 0;  // rated rows per workgroup of k_als_gram (fixed in mf_als_prepare)
   bool als_prepared = false;
   int64_t als_half_sweeps = 0;  // half-sweeps run since mf_als_prepare (even: the item side is next)
   std::future<void> det_spec[mfhip::kDetSlots];
@@ -320,7 +324,11 @@ void lookup_factors(mf_ctx* ctx, int side, const int32_t* ids, int64_t n, double
 void als_check(const mf_ctx* ctx);
 void als_check_run(double lambda, int32_t reg);
 void als_prepare(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n);
-void als_run(mf_ctx* ctx, int64_t half_sweeps, double lambda, int32_t reg);
-void als_normal_eq(mf_ctx* ctx, int side, int32_t id, double lambda, int32_t reg, double* A_out, double* b_out);
+void als_check_alpha(double alpha);
+// alpha < 0: the explicit half-sweep / system; alpha >= 0: the implicit one (mf_als_run_implicit)
+void als_run(mf_ctx* ctx, int64_t half_sweeps, double lambda, int32_t reg, double alpha = -1.0);
+void als_normal_eq(mf_ctx* ctx, int side, int32_t id, double lambda, int32_t reg, double* A_out, double* b_out,
+                   double alpha = -1.0);
+void als_gram(mf_ctx* ctx, int side, double* G_out);
 
 }  // namespace mfhip

@@ -241,21 +241,32 @@ void launch_jvm_init_rows(hipStream_t st, const int32_t* ids, int64_t rows, int 
 // cols / vals: the side's CSR (counterpart rows of Q, ratings in the context's precision).
 // dump != null (the testing hook, one row): the row's k x k matrix and right-hand side are
 // stored there instead of being solved.
+// gram != null: the implicit-feedback half-sweep (mf_als_run_implicit), (G + sum w q q^T + lambda' I) x
+// = sum_{r > 0} (1 + w) q with w = alpha |r|; gram is G, als_gram_elems(k) elements (launch_als_gram),
+// lambda' = lambda * npos when weighted, and a row with npos == 0 is set to zero.
 constexpr int kAlsMaxRank = 128;
 struct AlsItem {
   int64_t begin;  // first rating of the item in cols / vals
   int32_t row;
   int32_t count;  // ratings of the item (of the whole row when slot < 0)
   int32_t slot;
-  int32_t pad;
+  int32_t npos;   // ratings r > 0 of the whole row (the implicit half-sweep's n+)
 };
 struct AlsSplit {
   int32_t row, slot0, chunks;
   int32_t count;  // ratings of the whole row (lambda' = lambda * count when weighted)
+  int32_t npos;   // of them r > 0
 };
 size_t als_partial_elems(int k);
 void launch_als(hipStream_t st, const AlsItem* items, int n_items, const AlsSplit* splits, int n_splits,
                 const int32_t* cols, const void* vals, const void* Q, void* X, int k, double lambda, bool weighted,
-                bool f64, void* partial, void* dump);
+                bool f64, void* partial, void* dump, const void* gram = nullptr, double alpha = 0.0);
+// G = sum of y y^T over rows rated[0 .. m) of Y, KP x KP (KP = k rounded up to 32, full symmetric,
+// zero past k): workgroup b sums rows [b * slice, (b + 1) * slice) into part[b] (als_gram_slices(m,
+// slice) partials of als_gram_elems(k) elements), then one launch adds them in ascending order.
+size_t als_gram_elems(int k);
+int als_gram_slices(int m, int slice);
+void launch_als_gram(hipStream_t st, const int32_t* rated, int m, int slice, const void* Y, int k, bool f64, void* part,
+                     void* G);
 
 }  // namespace mfhip

@@ -20,6 +20,14 @@
 //  for another; every loop of the factorisation and the solves is bounded by k.  A pivot that is
 //  not a positive finite number makes the whole row NaN.  The order of every sum is a function of
 //  the row's ratings (in CSR order) and the chunk alone.
+//
+// The implicit-feedback half-sweep (mf_als_run_implicit) is the same two kernels with the template
+// flag W set: (G + sum_j w_j q_j q_j^T + lambda' I) x = sum_{r_j > 0} (1 + w_j) q_j, w_j = alpha |r_j|.
+// The weights are staged in LDS beside the ratings and multiply the A operand; G, the Gram matrix of
+// the counterpart's rated rows, is read from global memory when the accumulators (whole rows) or the
+// summed partials (split rows) go to the LDS matrix.  k_als_gram computes G: each workgroup takes a
+// contiguous slice of the rated-row list through the same tiles and GramAcc and stores a KP x KP
+// partial; k_als_gram_reduce adds the partials in ascending slice order.
 #include <hip/hip_runtime.h>
 
 #include <limits>
@@ -53,8 +61,9 @@ template <> struct GramAcc<float> {
     while ((bi + 1) * (bi + 2) / 2 <= b) ++bi;  // bi <= 3
     bj = b - bi * (bi + 1) / 2;
   }
-  template <int NB>
-  __device__ void tile(const float* q, int kp, int rows) {
+  // W: w[t] (LDS) multiplies rating t's A operand
+  template <int NB, bool W = false>
+  __device__ void tile(const float* q, int kp, int rows, const float* w = nullptr) {
     constexpr int kBlocks = NB * (NB + 1) / 2;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int h = lane >> 5, c = lane & 31;
@@ -66,13 +75,19 @@ template <> struct GramAcc<float> {
       block_of(b, bi, bj);
       const float* pa = q + h * kp + 32 * bi + c;
       const float* pb = q + h * kp + 32 * bj + c;
-      for (int t = 0; t < rows; t += 2)
-        acc[x] = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[t * kp], pb[t * kp], acc[x], 0, 0, 0);
+      if constexpr (W) {
+        for (int t = 0; t < rows; t += 2)
+          acc[x] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[t + h] * pa[t * kp], pb[t * kp], acc[x], 0, 0, 0);
+      } else {
+        for (int t = 0; t < rows; t += 2)
+          acc[x] = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[t * kp], pb[t * kp], acc[x], 0, 0, 0);
+      }
     }
   }
   // accumulators -> M (row stride ld); register r of a block is row (r & 3) + 8 (r >> 2) + 4 h
-  template <int NB>
-  __device__ void store(float* M, int ld) const {
+  // ADD: plus G (row stride 32 NB) on the way
+  template <int NB, bool ADD = false>
+  __device__ void store(float* M, int ld, const float* G = nullptr) const {
     constexpr int kBlocks = NB * (NB + 1) / 2;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int h = lane >> 5, c = lane & 31;
@@ -83,7 +98,14 @@ template <> struct GramAcc<float> {
       int bi, bj;
       block_of(b, bi, bj);
 #pragma unroll
-      for (int r = 0; r < 16; ++r) M[(32 * bi + (r & 3) + 8 * (r >> 2) + 4 * h) * ld + 32 * bj + c] = acc[x][r];
+      for (int r = 0; r < 16; ++r) {
+        if constexpr (ADD) {
+          const int row = 32 * bi + (r & 3) + 8 * (r >> 2) + 4 * h;
+          M[row * ld + 32 * bj + c] = acc[x][r] + G[row * (32 * NB) + 32 * bj + c];
+        } else {
+          M[(32 * bi + (r & 3) + 8 * (r >> 2) + 4 * h) * ld + 32 * bj + c] = acc[x][r];
+        }
+      }
     }
   }
 };
@@ -97,8 +119,8 @@ template <> struct GramAcc<double> {
 #pragma unroll
       for (int b = 0; b < 8; ++b) acc[a][b] = 0.0;
   }
-  template <int NB>
-  __device__ void tile(const double* q, int kp, int rows) {
+  template <int NB, bool W = false>
+  __device__ void tile(const double* q, int kp, int rows, const double* w = nullptr) {
     const int ty = threadIdx.x >> 4, tx = threadIdx.x & 15;
     for (int t = 0; t < rows; ++t) {
       const double* row = q + t * kp;
@@ -106,6 +128,7 @@ template <> struct GramAcc<double> {
 #pragma unroll
       for (int a = 0; a < 2 * NB; ++a) {
         qa[a] = row[ty + 16 * a];
+        if constexpr (W) qa[a] *= w[t];
         qb[a] = row[tx + 16 * a];
       }
 #pragma unroll
@@ -114,13 +137,16 @@ template <> struct GramAcc<double> {
         for (int b = 0; b <= a; ++b) acc[a][b] = fma(qa[a], qb[b], acc[a][b]);
     }
   }
-  template <int NB>
-  __device__ void store(double* M, int ld) const {
+  template <int NB, bool ADD = false>
+  __device__ void store(double* M, int ld, const double* G = nullptr) const {
     const int ty = threadIdx.x >> 4, tx = threadIdx.x & 15;
 #pragma unroll
     for (int a = 0; a < 2 * NB; ++a)
 #pragma unroll
-      for (int b = 0; b <= a; ++b) M[(ty + 16 * a) * ld + tx + 16 * b] = acc[a][b];
+      for (int b = 0; b <= a; ++b) {
+        if constexpr (ADD) M[(ty + 16 * a) * ld + tx + 16 * b] = acc[a][b] + G[(ty + 16 * a) * (32 * NB) + tx + 16 * b];
+        else M[(ty + 16 * a) * ld + tx + 16 * b] = acc[a][b];
+      }
   }
 };
 
@@ -218,11 +244,15 @@ constexpr size_t als_lds_bytes(int kp) {
   return (static_cast<size_t>(kp) * (kp + 1) + 4 * kp + kTile) * sizeof(T);
 }
 
-template <typename T, int NB>
-__global__ __launch_bounds__(kThreads) void k_als(const AlsItem* __restrict__ items, const int32_t* __restrict__ cols,
-                                                   const T* __restrict__ vals, const T* __restrict__ Q,
-                                                   T* __restrict__ X, int k, T lambda, int weighted,
-                                                   T* __restrict__ partial, T* __restrict__ dump) {
+// W (the implicit half-sweep): the ratings become confidences w = alpha |r| (rv) and right-hand-side
+// coefficients 1 + w for r > 0, else 0 (cf, which borrows col: the factorisation's scratch is idle
+// while the tiles run); G is the counterpart's Gram matrix, KP x KP.  A row with no positive rating
+// has a zero right-hand side: its x is zero, and nothing is accumulated for it.
+template <typename T, int NB, bool W>
+__device__ __forceinline__ void als_item(const AlsItem* __restrict__ items, const int32_t* __restrict__ cols,
+                                         const T* __restrict__ vals, const T* __restrict__ Q, T* __restrict__ X,
+                                         int k, T lambda, int weighted, T* __restrict__ partial,
+                                         T* __restrict__ dump, const T* __restrict__ G, T alpha) {
   constexpr int KP = 32 * NB;
   constexpr int LD = KP + 1;
   extern __shared__ __align__(16) unsigned char smem_raw[];
@@ -234,6 +264,13 @@ __global__ __launch_bounds__(kThreads) void k_als(const AlsItem* __restrict__ it
   T* rv = colraw + KP;
   const AlsItem it = items[blockIdx.x];
   const int tid = threadIdx.x;
+  if constexpr (W) {
+    if (it.npos == 0 && !dump) {  // (a chunk of such a row stores no partial: k_als_reduce reads none)
+      if (it.slot < 0 && tid < k) X[static_cast<size_t>(it.row) * k + tid] = T(0);
+      return;
+    }
+  }
+  T* cf = col;
 
   GramAcc<T> g;
   g.zero();
@@ -247,12 +284,29 @@ __global__ __launch_bounds__(kThreads) void k_als(const AlsItem* __restrict__ it
       if (t < rows && f < k) v = Q[static_cast<size_t>(cols[it.begin + t0 + t]) * k + f];
       M[e] = v;
     }
-    if (tid < kTile) rv[tid] = tid < rows ? vals[it.begin + t0 + tid] : T(0);
+    if constexpr (W) {
+      if (tid < kTile) {
+        const T r = tid < rows ? vals[it.begin + t0 + tid] : T(0);
+        const T w = alpha * (r < T(0) ? -r : r);
+        rv[tid] = w;
+        cf[tid] = r > T(0) ? T(1) + w : T(0);
+      }
+    } else {
+      if (tid < kTile) rv[tid] = tid < rows ? vals[it.begin + t0 + tid] : T(0);
+    }
     __syncthreads();
     // (rows past the end are zero: the f32 path always runs whole pairs)
-    g.template tile<NB>(M, KP, (rows + 1) & ~1);
-    if (tid < KP)
-      for (int t = 0; t < rows; ++t) bacc = fma(rv[t], M[t * KP + tid], bacc);
+    g.template tile<NB, W>(M, KP, (rows + 1) & ~1, rv);
+    if constexpr (W) {
+      if (tid < KP)
+        for (int t = 0; t < rows; ++t) {
+          const T c = cf[t];
+          if (c != T(0)) bacc = fma(c, M[t * KP + tid], bacc);  // r > 0 only
+        }
+    } else {
+      if (tid < KP)
+        for (int t = 0; t < rows; ++t) bacc = fma(rv[t], M[t * KP + tid], bacc);
+    }
   }
   __syncthreads();
   if (it.slot >= 0) {  // a chunk of a long row: the partial system goes to the scratch slab
@@ -261,20 +315,39 @@ __global__ __launch_bounds__(kThreads) void k_als(const AlsItem* __restrict__ it
     if (tid < KP) P[KP * KP + tid] = bacc;
     return;
   }
-  g.template store<NB>(M, LD);
+  g.template store<NB, W>(M, LD, G);
   if (tid < KP) rhs[tid] = bacc;
   __syncthreads();
-  const T lam = weighted ? lambda * static_cast<T>(it.count) : lambda;
+  const T lam = weighted ? lambda * static_cast<T>(W ? it.npos : it.count) : lambda;
   if (tid < k) M[tid * LD + tid] += lam;
   __syncthreads();
   finish_row<T, NB>(M, LD, rhs, y, col, colraw, k, X + static_cast<size_t>(it.row) * k, dump);
 }
 
-// One workgroup per split row: partials [slot0, slot0 + chunks) added in ascending order.
 template <typename T, int NB>
-__global__ __launch_bounds__(kThreads) void k_als_reduce(const AlsSplit* __restrict__ rows, const T* __restrict__ partial,
-                                                          T* __restrict__ X, int k, T lambda, int weighted,
-                                                          T* __restrict__ dump) {
+__global__ __launch_bounds__(kThreads) void k_als(const AlsItem* __restrict__ items, const int32_t* __restrict__ cols,
+                                                   const T* __restrict__ vals, const T* __restrict__ Q,
+                                                   T* __restrict__ X, int k, T lambda, int weighted,
+                                                   T* __restrict__ partial, T* __restrict__ dump) {
+  als_item<T, NB, false>(items, cols, vals, Q, X, k, lambda, weighted, partial, dump, nullptr, T(0));
+}
+
+template <typename T, int NB>
+__global__ __launch_bounds__(kThreads) void k_als_implicit(const AlsItem* __restrict__ items,
+                                                            const int32_t* __restrict__ cols,
+                                                            const T* __restrict__ vals, const T* __restrict__ Q,
+                                                            T* __restrict__ X, int k, T lambda, int weighted,
+                                                            T* __restrict__ partial, T* __restrict__ dump,
+                                                            const T* __restrict__ G, T alpha) {
+  als_item<T, NB, true>(items, cols, vals, Q, X, k, lambda, weighted, partial, dump, G, alpha);
+}
+
+// One workgroup per split row: partials [slot0, slot0 + chunks) added in ascending order.
+// W: plus G, once, after the partial sum; a row with no positive rating is set to zero.
+template <typename T, int NB, bool W>
+__device__ __forceinline__ void als_split(const AlsSplit* __restrict__ rows, const T* __restrict__ partial,
+                                          T* __restrict__ X, int k, T lambda, int weighted, T* __restrict__ dump,
+                                          const T* __restrict__ G) {
   constexpr int KP = 32 * NB;
   constexpr int LD = KP + 1;
   extern __shared__ __align__(16) unsigned char smem_raw[];
@@ -285,55 +358,149 @@ __global__ __launch_bounds__(kThreads) void k_als_reduce(const AlsSplit* __restr
   T* colraw = col + KP;
   const AlsSplit sp = rows[blockIdx.x];
   const int tid = threadIdx.x;
+  if constexpr (W) {
+    if (sp.npos == 0 && !dump) {
+      if (tid < k) X[static_cast<size_t>(sp.row) * k + tid] = T(0);
+      return;
+    }
+  }
   constexpr size_t kStride = static_cast<size_t>(KP) * KP + KP;
   for (int e = tid; e < KP * KP + KP; e += kThreads) {
     const int i = e / KP, j = e % KP;
     if (i < KP && j > i) continue;  // only the lower triangle is defined
     T sum = T(0);
     for (int c = 0; c < sp.chunks; ++c) sum += partial[(static_cast<size_t>(sp.slot0) + c) * kStride + e];
+    if constexpr (W) {
+      if (i < KP) sum += G[e];
+    }
     if (i < KP) M[i * LD + j] = sum;
     else rhs[j] = sum;
   }
   __syncthreads();
-  const T lam = weighted ? lambda * static_cast<T>(sp.count) : lambda;
+  const T lam = weighted ? lambda * static_cast<T>(W ? sp.npos : sp.count) : lambda;
   if (tid < k) M[tid * LD + tid] += lam;
   __syncthreads();
   finish_row<T, NB>(M, LD, rhs, y, col, colraw, k, X + static_cast<size_t>(sp.row) * k, dump);
 }
 
 template <typename T, int NB>
+__global__ __launch_bounds__(kThreads) void k_als_reduce(const AlsSplit* __restrict__ rows, const T* __restrict__ partial,
+                                                          T* __restrict__ X, int k, T lambda, int weighted,
+                                                          T* __restrict__ dump) {
+  als_split<T, NB, false>(rows, partial, X, k, lambda, weighted, dump, nullptr);
+}
+
+template <typename T, int NB>
+__global__ __launch_bounds__(kThreads) void k_als_reduce_implicit(const AlsSplit* __restrict__ rows,
+                                                                   const T* __restrict__ partial, T* __restrict__ X,
+                                                                   int k, T lambda, int weighted, T* __restrict__ dump,
+                                                                   const T* __restrict__ G) {
+  als_split<T, NB, true>(rows, partial, X, k, lambda, weighted, dump, G);
+}
+
+// G = sum over the rated rows of Y of y y^T.  Workgroup b takes rows [b * slice, (b + 1) * slice) of
+// the list through the tiles and GramAcc of k_als and stores its KP x KP partial (lower-triangle
+// blocks) to part[b]; k_als_gram_reduce adds the partials in ascending slice order into the full
+// symmetric G.  The order of every sum is a function of the list and the slice length alone.
+template <typename T, int NB>
+__global__ __launch_bounds__(kThreads) void k_als_gram(const int32_t* __restrict__ rated, int m, int slice,
+                                                        const T* __restrict__ Y, int k, T* __restrict__ part) {
+  constexpr int KP = 32 * NB;
+  __shared__ T tile[kTile * KP];
+  const int tid = threadIdx.x;
+  const int64_t lo = static_cast<int64_t>(blockIdx.x) * slice;
+  const int64_t hi = min(static_cast<int64_t>(m), lo + slice);
+  GramAcc<T> g;
+  g.zero();
+  for (int64_t t0 = lo; t0 < hi; t0 += kTile) {
+    const int rows = static_cast<int>(min(static_cast<int64_t>(kTile), hi - t0));
+    __syncthreads();  // the previous tile has been read
+    for (int e = tid; e < kTile * KP; e += kThreads) {
+      const int t = e / KP, f = e % KP;
+      T v = T(0);
+      if (t < rows && f < k) v = Y[static_cast<size_t>(rated[t0 + t]) * k + f];
+      tile[e] = v;
+    }
+    __syncthreads();
+    g.template tile<NB>(tile, KP, (rows + 1) & ~1);
+  }
+  g.template store<NB>(part + static_cast<size_t>(blockIdx.x) * KP * KP, KP);
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void k_als_gram_reduce(const T* __restrict__ part, int slices, int kp,
+                                                               T* __restrict__ G) {
+  const int e = blockIdx.x * kThreads + threadIdx.x;
+  if (e >= kp * kp) return;
+  const int i = e / kp, j = e % kp;
+  const int src = i >= j ? e : j * kp + i;  // the partials hold the lower triangle
+  T sum = T(0);
+  for (int s = 0; s < slices; ++s) sum += part[static_cast<size_t>(s) * kp * kp + src];
+  G[e] = sum;
+}
+
+template <typename T, int NB>
 void launch_nb(hipStream_t st, const AlsItem* items, int n_items, const AlsSplit* splits, int n_splits,
                const int32_t* cols, const void* vals, const void* Q, void* X, int k, double lambda, int weighted,
-               void* partial, void* dump) {
+               void* partial, void* dump, const void* gram, double alpha) {
   constexpr int KP = 32 * NB;
   const size_t smem = als_lds_bytes<T>(KP);
-  const void* f1 = reinterpret_cast<const void*>(&k_als<T, NB>);
-  const void* f2 = reinterpret_cast<const void*>(&k_als_reduce<T, NB>);
+  const void* f1 = gram ? reinterpret_cast<const void*>(&k_als_implicit<T, NB>) : reinterpret_cast<const void*>(&k_als<T, NB>);
+  const void* f2 = gram ? reinterpret_cast<const void*>(&k_als_reduce_implicit<T, NB>)
+                        : reinterpret_cast<const void*>(&k_als_reduce<T, NB>);
   if (smem > 64 * 1024)
     for (const void* fn : {f1, f2})
       if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(smem)) != hipSuccess)
         fail(MF_ERR_HIP, "k_als: " + std::to_string(smem) + " bytes of LDS refused");
-  if (n_items > 0)
-    hipLaunchKernelGGL((k_als<T, NB>), dim3(static_cast<unsigned>(n_items)), dim3(kThreads), smem, st, items, cols,
+  const dim3 gi(static_cast<unsigned>(n_items)), gs(static_cast<unsigned>(n_splits));
+  if (n_items > 0 && !gram)
+    hipLaunchKernelGGL((k_als<T, NB>), gi, dim3(kThreads), smem, st, items, cols,
                        static_cast<const T*>(vals), static_cast<const T*>(Q), static_cast<T*>(X), k,
                        static_cast<T>(lambda), weighted, static_cast<T*>(partial), static_cast<T*>(dump));
-  if (n_splits > 0)
-    hipLaunchKernelGGL((k_als_reduce<T, NB>), dim3(static_cast<unsigned>(n_splits)), dim3(kThreads), smem, st, splits,
+  if (n_items > 0 && gram)
+    hipLaunchKernelGGL((k_als_implicit<T, NB>), gi, dim3(kThreads), smem, st, items, cols,
+                       static_cast<const T*>(vals), static_cast<const T*>(Q), static_cast<T*>(X), k,
+                       static_cast<T>(lambda), weighted, static_cast<T*>(partial), static_cast<T*>(dump),
+                       static_cast<const T*>(gram), static_cast<T>(alpha));
+  if (n_splits > 0 && !gram)
+    hipLaunchKernelGGL((k_als_reduce<T, NB>), gs, dim3(kThreads), smem, st, splits,
                        static_cast<const T*>(partial), static_cast<T*>(X), k, static_cast<T>(lambda), weighted,
                        static_cast<T*>(dump));
+  if (n_splits > 0 && gram)
+    hipLaunchKernelGGL((k_als_reduce_implicit<T, NB>), gs, dim3(kThreads), smem, st, splits,
+                       static_cast<const T*>(partial), static_cast<T*>(X), k, static_cast<T>(lambda), weighted,
+                       static_cast<T*>(dump), static_cast<const T*>(gram));
 }
 
 template <typename T>
 void launch_t(hipStream_t st, const AlsItem* items, int n_items, const AlsSplit* splits, int n_splits,
               const int32_t* cols, const void* vals, const void* Q, void* X, int k, double lambda, int weighted,
-              void* partial, void* dump) {
+              void* partial, void* dump, const void* gram, double alpha) {
   switch ((k + 31) / 32) {
-    case 1: return launch_nb<T, 1>(st, items, n_items, splits, n_splits, cols, vals, Q, X, k, lambda, weighted, partial, dump);
-    case 2: return launch_nb<T, 2>(st, items, n_items, splits, n_splits, cols, vals, Q, X, k, lambda, weighted, partial, dump);
-    case 3: return launch_nb<T, 3>(st, items, n_items, splits, n_splits, cols, vals, Q, X, k, lambda, weighted, partial, dump);
-    case 4: return launch_nb<T, 4>(st, items, n_items, splits, n_splits, cols, vals, Q, X, k, lambda, weighted, partial, dump);
+    case 1: return launch_nb<T, 1>(st, items, n_items, splits, n_splits, cols, vals, Q, X, k, lambda, weighted, partial, dump, gram, alpha);
+    case 2: return launch_nb<T, 2>(st, items, n_items, splits, n_splits, cols, vals, Q, X, k, lambda, weighted, partial, dump, gram, alpha);
+    case 3: return launch_nb<T, 3>(st, items, n_items, splits, n_splits, cols, vals, Q, X, k, lambda, weighted, partial, dump, gram, alpha);
+    case 4: return launch_nb<T, 4>(st, items, n_items, splits, n_splits, cols, vals, Q, X, k, lambda, weighted, partial, dump, gram, alpha);
     default: fail(MF_ERR_INVALID, "ALS supports a rank of at most " + std::to_string(kAlsMaxRank));
   }
+}
+
+template <typename T>
+void launch_gram_t(hipStream_t st, const int32_t* rated, int m, int slice, const void* Y, int k, void* part, void* G) {
+  const int nb = (k + 31) / 32, kp = 32 * nb;
+  const int slices = als_gram_slices(m, slice);
+  const dim3 grid(static_cast<unsigned>(slices)), block(kThreads);
+  const T* y = static_cast<const T*>(Y);
+  T* p = static_cast<T*>(part);
+  if (slices > 0) switch (nb) {
+    case 1: hipLaunchKernelGGL((k_als_gram<T, 1>), grid, block, 0, st, rated, m, slice, y, k, p); break;
+    case 2: hipLaunchKernelGGL((k_als_gram<T, 2>), grid, block, 0, st, rated, m, slice, y, k, p); break;
+    case 3: hipLaunchKernelGGL((k_als_gram<T, 3>), grid, block, 0, st, rated, m, slice, y, k, p); break;
+    case 4: hipLaunchKernelGGL((k_als_gram<T, 4>), grid, block, 0, st, rated, m, slice, y, k, p); break;
+    default: fail(MF_ERR_INVALID, "ALS supports a rank of at most " + std::to_string(kAlsMaxRank));
+  }
+  hipLaunchKernelGGL((k_als_gram_reduce<T>), dim3(static_cast<unsigned>((kp * kp + kThreads - 1) / kThreads)), block, 0,
+                     st, static_cast<const T*>(part), slices, kp, static_cast<T*>(G));
 }
 
 }  // namespace
@@ -343,11 +510,24 @@ size_t als_partial_elems(int k) {
   return kp * kp + kp;
 }
 
+size_t als_gram_elems(int k) {
+  const size_t kp = static_cast<size_t>((k + 31) / 32) * 32;
+  return kp * kp;
+}
+
+int als_gram_slices(int m, int slice) { return static_cast<int>((static_cast<int64_t>(m) + slice - 1) / slice); }
+
 void launch_als(hipStream_t st, const AlsItem* items, int n_items, const AlsSplit* splits, int n_splits,
                 const int32_t* cols, const void* vals, const void* Q, void* X, int k, double lambda, bool weighted,
-                bool f64, void* partial, void* dump) {
-  if (f64) launch_t<double>(st, items, n_items, splits, n_splits, cols, vals, Q, X, k, lambda, weighted ? 1 : 0, partial, dump);
-  else launch_t<float>(st, items, n_items, splits, n_splits, cols, vals, Q, X, k, lambda, weighted ? 1 : 0, partial, dump);
+                bool f64, void* partial, void* dump, const void* gram, double alpha) {
+  if (f64) launch_t<double>(st, items, n_items, splits, n_splits, cols, vals, Q, X, k, lambda, weighted ? 1 : 0, partial, dump, gram, alpha);
+  else launch_t<float>(st, items, n_items, splits, n_splits, cols, vals, Q, X, k, lambda, weighted ? 1 : 0, partial, dump, gram, alpha);
+}
+
+void launch_als_gram(hipStream_t st, const int32_t* rated, int m, int slice, const void* Y, int k, bool f64, void* part,
+                     void* G) {
+  if (f64) launch_gram_t<double>(st, rated, m, slice, Y, k, part, G);
+  else launch_gram_t<float>(st, rated, m, slice, Y, k, part, G);
 }
 
 }  // namespace mfhip

@@ -99,13 +99,13 @@ EXPORTS = [
     "mf_reset_stats", "mf_jvm_shuffle", "mf_jvm_block_of", "mf_jvm_random_factors",
     "mf_learning_rate", "mf_get_params", "mf_read_ratings", "mf_save_model", "mf_load_model",
     "mf_dsgd_restart", "mf_online_update_out", "mf_recommend", "mf_als_fit", "mf_als_prepare",
-    "mf_als_run",
+    "mf_als_run", "mf_als_run_implicit", "mf_als_fit_implicit",
 ]
 # The test hooks include/mfhip_testing.h declares (not product surface; same library).
 TESTING_EXPORTS = [
     "mf_debug_levels", "mf_debug_fast_schedule", "mf_debug_fast_split", "mf_debug_ring_schedule",
     "mf_debug_plan_digest", "mf_fast_plan_window", "mf_fast_kernel_name", "mf_debug_build_flags",
-    "mf_debug_device_bytes", "mf_debug_als_normal_eq",
+    "mf_debug_device_bytes", "mf_debug_als_normal_eq", "mf_debug_als_gram", "mf_debug_als_normal_eq_implicit",
 ]
 
 _i32p = C.POINTER(C.c_int32)
@@ -180,6 +180,12 @@ def lib() -> C.CDLL:
         "mf_als_prepare": (C.c_int, [_ctxp, _i32p, _i32p, _f64p, C.c_int64]),
         "mf_als_run": (C.c_int, [_ctxp, C.c_int64, C.c_double, C.c_int32]),
         "mf_debug_als_normal_eq": (C.c_int, [_ctxp, C.c_int, C.c_int32, C.c_double, C.c_int32, _f64p, _f64p]),
+        "mf_als_run_implicit": (C.c_int, [_ctxp, C.c_int64, C.c_double, C.c_int32, C.c_double]),
+        "mf_als_fit_implicit": (C.c_int, [_ctxp, _i32p, _i32p, _f64p, C.c_int64, C.c_int32, C.c_double, C.c_int32,
+                                          C.c_double]),
+        "mf_debug_als_gram": (C.c_int, [_ctxp, C.c_int, _f64p]),
+        "mf_debug_als_normal_eq_implicit": (C.c_int, [_ctxp, C.c_int, C.c_int32, C.c_double, C.c_int32, C.c_double,
+                                                      _f64p, _f64p]),
         "mf_debug_ring_schedule": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, _i32p, _i32p, _i32p, _i32p]),
         "mf_debug_plan_digest": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
         "mf_debug_build_flags": (C.c_int32, []),

@@ -6,6 +6,9 @@ MatrixFactorizationModel, backed by mf_als_fit (alternating least squares on the
     model.predict(user, product)
     model.recommendProducts(user, 10)
 
+ALS.trainImplicit(ratings, rank, iterations, lambda, alpha) is the implicit-feedback sibling
+(mf_als_fit_implicit): confidences 1 + alpha |r|, preferences r > 0.
+
 Weighted-lambda regularisation (ALS-WR), as ALS.train uses.  The initial factors are this library's
 (k x nextDouble of new Random(id ^ seed)), not MLlib's partition-dependent XORShift draws.
 """
@@ -79,15 +82,33 @@ class ALS:
         """ALS.train(ratings, rank, iterations, lambda); ratings: (user, product, rating) tuples or
         three arrays."""
         u, i, r = _columns(ratings)
-        p = L.default_params()
-        p.num_factors = int(rank)
-        p.has_seed = 1
-        p.seed = int(seed)
-        p.mode = L.MODE_FAST_F32 if mode == "fast" else L.MODE_DETERMINISTIC_F64
-        ctx = Context(p)
+        ctx = ALS._context(rank, mode, seed)
         try:
             ctx.als_fit(u, i, r, int(iterations), float(lambda_), L.ALS_REG_WEIGHTED)
         except Exception:
             ctx.close()
             raise
         return MatrixFactorizationModel(ctx)
+
+    @staticmethod
+    def trainImplicit(ratings, rank: int, iterations: int = 10, lambda_: float = 0.01, alpha: float = 0.01,
+                      mode: str = "deterministic", seed: int = 0) -> MatrixFactorizationModel:
+        """ALS.trainImplicit(ratings, rank, iterations, lambda, alpha) with MLlib's defaults; the ratings
+        are implicit feedback (counts, possibly zero or negative)."""
+        u, i, r = _columns(ratings)
+        ctx = ALS._context(rank, mode, seed)
+        try:
+            ctx.als_fit_implicit(u, i, r, int(iterations), float(lambda_), float(alpha), L.ALS_REG_WEIGHTED)
+        except Exception:
+            ctx.close()
+            raise
+        return MatrixFactorizationModel(ctx)
+
+    @staticmethod
+    def _context(rank: int, mode: str, seed: int) -> Context:
+        p = L.default_params()
+        p.num_factors = int(rank)
+        p.has_seed = 1
+        p.seed = int(seed)
+        p.mode = L.MODE_FAST_F32 if mode == "fast" else L.MODE_DETERMINISTIC_F64
+        return Context(p)

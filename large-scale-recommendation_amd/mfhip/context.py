@@ -111,6 +111,33 @@ class Context:
                                              ptr(b, C.c_double)))
         return A, b
 
+    def als_run_implicit(self, half_sweeps: int, lam: float, alpha: float, reg: int = L.ALS_REG_WEIGHTED) -> None:
+        """mf_als_run_implicit: confidence-weighted half-sweeps (w = alpha |r|) on the prepared data; the
+        order and the counter are als_run's, and the two share the counter."""
+        check(L.lib().mf_als_run_implicit(self._h, int(half_sweeps), float(lam), int(reg), float(alpha)))
+
+    def als_fit_implicit(self, u, i, r, iterations: int, lam: float, alpha: float,
+                         reg: int = L.ALS_REG_WEIGHTED) -> None:
+        """mf_als_fit_implicit: als_prepare + als_run_implicit(2 * iterations) (ALS.trainImplicit)."""
+        u, i, r = as_i32(u), as_i32(i), as_f64(r)
+        same_length(u, i, r)
+        check(L.lib().mf_als_fit_implicit(self._h, ptr(u, C.c_int32), ptr(i, C.c_int32), ptr(r, C.c_double), len(u),
+                                          int(iterations), float(lam), int(reg), float(alpha)))
+
+    def als_gram(self, side: int) -> np.ndarray:
+        """G [k, k] = sum of y y^T over `side`'s rows rated in the prepared data (mf_debug_als_gram)."""
+        G = np.empty((self.k, self.k), np.float64)
+        check(L.lib().mf_debug_als_gram(self._h, int(side), ptr(G, C.c_double)))
+        return G
+
+    def als_normal_eq_implicit(self, side: int, id_: int, lam: float, alpha: float, reg: int = L.ALS_REG_WEIGHTED):
+        """(A [k, k], b [k]) of one row of the implicit half-sweep (mf_debug_als_normal_eq_implicit)."""
+        A = np.empty((self.k, self.k), np.float64)
+        b = np.empty(self.k, np.float64)
+        check(L.lib().mf_debug_als_normal_eq_implicit(self._h, int(side), int(id_), float(lam), int(reg), float(alpha),
+                                                      ptr(A, C.c_double), ptr(b, C.c_double)))
+        return A, b
+
     # -- factors ---------------------------------------------------------------
     def num_factors(self, side: int) -> int:
         v = C.c_int64(0)

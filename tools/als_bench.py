@@ -14,7 +14,11 @@ count over the device-event time.
 
 --chunks N[,N...] repeats the measurement with MFHIP_TEST als_chunk=N (ratings per work item of a
 long row).  --dsgd also times one fast DSGD epoch (numBlocks 8) on the same data in the same
-process, the baseline the README records beside the ALS iteration.
+process, the baseline the README records beside the ALS iteration.  --implicit also times implicit
+iterations (mf_als_run_implicit, alpha --alpha) after the explicit ones, on the same data in the same
+process with the ratings shifted by -3 so that they straddle zero (all three rating signs occur).  The
+two Gram launches of a half-sweep are inside its time; they are also timed alone, through
+mf_debug_als_gram under the same device events.
 
 Writes profiles/als_bench.json.
 """
@@ -32,7 +36,8 @@ sys.path.insert(0, os.path.join(ROOT, "large-scale-recommendation_amd"))
 F32_MFMA_PEAK = 157.3e12  # MI355X, v_mfma_f32_32x32x2_f32 (f32 in, f32 accumulate)
 
 
-def als_run(train, k, iters, lam, chunk):
+def als_run(train, k, iters, lam, chunk, alpha=None):
+    """alpha None: explicit iterations; else implicit ones on the ratings as given."""
     from mfhip import _lib as L
     from mfhip.context import Context
 
@@ -49,11 +54,21 @@ def als_run(train, k, iters, lam, chunk):
     flop = {s: 2.0 * nnz * k * k + (2.0 / 3.0) * k ** 3 * rows[s] for s in rows}
     res = {"chunk": chunk or "default", "nnz": nnz, "rows": rows, "k": k, "iters": iters, "lambda": lam,
            "flop_per_half_sweep": flop}
+    if alpha is not None:
+        res["alpha"] = alpha
+        res["rating_signs"] = {"negative": int((r < 0).sum()), "zero": int((r == 0).sum()),
+                               "positive": int((r > 0).sum())}
     with Context(p) as ctx:
         t0 = time.perf_counter()
         ctx.als_prepare(u, i, r)
         res["prepare_host_s"] = time.perf_counter() - t0
-        ctx.als_run(2, lam)  # warm-up
+        def run(n):
+            if alpha is None:
+                ctx.als_run(n, lam)
+            else:
+                ctx.als_run_implicit(n, lam, alpha)
+
+        run(2)  # warm-up
         ctx.set_profiling(True)
         half = {"item": [], "user": []}
         wall = []
@@ -61,9 +76,19 @@ def als_run(train, k, iters, lam, chunk):
             t0 = time.perf_counter()
             for side in ("item", "user"):
                 ctx.reset_stats()
-                ctx.als_run(1, lam)
+                run(1)
                 half[side].append(ctx.stats()["kernel_ms"])
             wall.append(time.perf_counter() - t0)
+        if alpha is not None:
+            # the Gram launches alone: the item half-sweep takes G of the user rows, the user one of the items
+            gram = {"item": [], "user": []}
+            for _ in range(iters):
+                for side, of in (("item", L.SIDE_USER), ("user", L.SIDE_ITEM)):
+                    ctx.reset_stats()
+                    ctx.als_gram(of)
+                    gram[side].append(ctx.stats()["kernel_ms"])
+            res["gram_ms"] = {s: {"median": float(np.median(gram[s])), "all": gram[s]} for s in gram}
+            res["gram_flop"] = {"item": 2.0 * rows["user"] * k * k, "user": 2.0 * rows["item"] * k * k}
         ctx.set_profiling(False)
         rmse, _ = ctx.rmse(u[:2_000_000], i[:2_000_000], r[:2_000_000])
     res["train_rmse_sample"] = rmse
@@ -74,12 +99,17 @@ def als_run(train, k, iters, lam, chunk):
     res["tflops"] = {s: flop[s] / (ms[s] * 1e-3) / 1e12 for s in half}
     res["tflops"]["iteration"] = (flop["item"] + flop["user"]) / (res["iteration_ms_device"] * 1e-3) / 1e12
     res["fraction_of_f32_mfma_peak"] = res["tflops"]["iteration"] * 1e12 / F32_MFMA_PEAK
-    print(f"ALS chunk {res['chunk']}: {res['iteration_ms_device']:.1f} ms / iteration on the device "
+    kind = "ALS" if alpha is None else f"implicit ALS (alpha {alpha})"
+    print(f"{kind} chunk {res['chunk']}: {res['iteration_ms_device']:.1f} ms / iteration on the device "
           f"(item half {ms['item']:.1f} ms, {res['tflops']['item']:.1f} TFLOP/s; user half {ms['user']:.1f} ms, "
           f"{res['tflops']['user']:.1f} TFLOP/s), host call {res['iteration_ms_host_call']:.1f} ms; "
           f"{res['tflops']['iteration']:.1f} TFLOP/s by 2*nnz*k^2 + (2/3)*k^3*rows per half-sweep = "
           f"{100 * res['fraction_of_f32_mfma_peak']:.1f} % of the f32 MFMA peak; prepare {res['prepare_host_s']:.1f} s; "
           f"rmse {rmse:.4f}", flush=True)
+    if alpha is not None:
+        g = res["gram_ms"]
+        print(f"  of which the Gram launches: item half {g['item']['median']:.3f} ms ({rows['user']} rows), "
+              f"user half {g['user']['median']:.3f} ms ({rows['item']} rows)", flush=True)
     return res
 
 
@@ -113,6 +143,8 @@ def main():
     ap.add_argument("--lam", type=float, default=0.1)
     ap.add_argument("--chunks", default="", help="comma-separated als_chunk values (empty: the default only)")
     ap.add_argument("--dsgd", action="store_true", help="also time a fast DSGD epoch on the same data")
+    ap.add_argument("--implicit", action="store_true", help="also time implicit iterations on the shifted ratings")
+    ap.add_argument("--alpha", type=float, default=1.0, help="the implicit runs' alpha")
     ap.add_argument("--scale", type=float, default=1.0, help="shrink the synthetic (rehearsal only)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "als_bench.json"))
     a = ap.parse_args()
@@ -128,6 +160,11 @@ def main():
     out = {"shape": "NFLX", "scale": a.scale, "runs": []}
     for c in [int(x) for x in a.chunks.split(",") if x] or [0]:
         out["runs"].append(als_run(train, k, a.iters, a.lam, c))
+    if a.implicit:
+        u, i, r = train
+        shifted = (u, i, np.asarray(r, np.float64) - 3.0)
+        out["implicit_runs"] = [als_run(shifted, k, a.iters, a.lam, c, a.alpha)
+                                for c in [int(x) for x in a.chunks.split(",") if x] or [0]]
     if a.dsgd:
         out["dsgd_fast"] = dsgd_epoch(train, k, nb)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
