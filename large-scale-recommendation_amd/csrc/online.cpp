@@ -218,6 +218,10 @@ void choose_online_path(OnlineBatch& b) {
   if (b.sweeps()) {
     int64_t wmax = 4096;
     if (const char* v = exp_knob("MFHIP_ONLINE_WAVES")) wmax = std::max(1, std::atoi(v));
+    // MFHIP_TEST online_waves=<W>: at most W waves, so that a small batch puts many items and many
+    // updates on each wave (tests/test_gpu_online_ranks.py)
+    if (const std::string v = test_knob("online_waves"); !v.empty())
+      wmax = std::min<int64_t>(wmax, std::max(1, std::atoi(v.c_str())));
     b.W = std::max<int64_t>(1, std::min<int64_t>({static_cast<int64_t>(b.cap / 2), wmax, b.n}));
   }
   b.direct = b.sweeps() && b.flavour != MF_ONLINE_SPARK_SWEEP;

@@ -1,4 +1,9 @@
-"""Online micro-batch path on the GPU vs the oracle (SGDUpdater arithmetic, bit-exact in f64)."""
+"""Online micro-batch path on the GPU vs the oracle (SGDUpdater arithmetic, bit-exact in f64).
+
+The f32 comparisons here are device against device: the sweeps against the level replay, which
+shares online_f32.hpp with them, so they show that the paths agree (plans, tickets, lookups, large
+batches), not that the shared arithmetic is right.  That check is tests/test_gpu_online_ranks.py:
+every f32 and f64 online kernel instance bitwise against a host replay (tests/online_emu.py)."""
 import os
 
 import numpy as np
