@@ -1,5 +1,5 @@
-// kernels.hpp -- host-side launch wrappers of the HIP kernels (kernels_det.hip, kernels_fast.hip,
-// kernels_eval.hip).  All launches are asynchronous on the given stream.
+// kernels.hpp -- host-side launch wrappers of the HIP kernels, grouped by the kernel file that
+// defines them (kernels_*.hip).  All launches are asynchronous on the given stream.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -9,6 +9,7 @@
 
 namespace mfhip {
 
+// ---- kernels_det.hip: level replay, ticket sweep, evaluation, initial rows ----------------------
 // Update arithmetic of one replayed rating.
 enum class Arith : int {
   kDsgd = 0,     // DSGDforMF.updateLocalFactors body (:405-413), regularised
@@ -27,6 +28,62 @@ void launch_level(hipStream_t st, const DetEntry* entries, int64_t n, void* U, v
 int online_sweep_capacity(int k, bool f64);
 void launch_online_sweep(hipStream_t st, int nw, const int64_t* wbeg, const DetEntry* ent, const uint32_t* useq,
                          void* U, void* I, int k, double eta, bool f64, int32_t* ticket, int32_t* err);
+// Per-rating records of the online operators (mf_online_update_out), f64 rows of k at
+// [src[entry] * k]: kOutNext = (user', item') (FlinkOnlineMF.scala:131-135), kOutDelta =
+// (user + deltaItem, deltaItem) with user before the update (PSOfflineOnlineMF.scala:174-176).
+enum class OnlineOut : int { kNone = 0, kOutNext = 1, kOutDelta = 2 };
+void launch_level_out(hipStream_t st, const DetEntry* entries, int64_t n, void* U, void* I, int k, double eta, bool f64,
+                      OnlineOut mode, const int32_t* src, double* uout, double* iout);
+// Gather-dot over resolved pairs (row -1 = unknown id).  out[j] = p.q summed left to right in
+// f64 (predictRating's ddot).  When r != nullptr every workgroup writes partials[3*wg + c]:
+//   c=0: sum (r - p.q)^2, c=1: matched count, c=2: sum mult*((r-p.q)^2 + lambda*(p.p + q.q)).
+// The grid has predict_grid(n) workgroups; the host adds the partials in a fixed order.
+int predict_grid(int64_t n);
+void launch_predict(hipStream_t st, const int32_t* urow, const int32_t* irow, int64_t n,
+                    const void* U, const void* I, int k, bool f64, double* out, const double* r,
+                    const int32_t* mult, double lambda, double* partials);
+// Initial factor rows on the device (DSGDforMF.scala:548-549, MatrixFactorization.scala:278-280):
+// row x, factor f = the f-th nextDouble of new Random(ids[x] ^ seed) (xor_seed) or of
+// new Random(ids[x]).  One thread per element: the JVM LCG state after m steps is
+// jump[2(m-1)] * s0 + jump[2(m-1)+1] mod 2^48 (host table, m = 1..2k), so every element is
+// computed independently and written coalesced; bit-exact with JavaRandom::nextDouble.
+// out: rows x k, double (f64) or float (rounded from the same double).
+void launch_jvm_init_rows(hipStream_t st, const int32_t* ids, int64_t rows, int k, bool xor_seed, int64_t seed,
+                          const uint64_t* jump, void* out, bool f64);
+
+// ---- kernels_detsweep.hip: the deterministic f64 sweep, one launch per superstep ----------------
+// Deterministic persistent sweep (kernels_detsweep.hip): one launch per superstep, nw waves of
+// 64 lanes, all of which must be resident at once (nw <= det_sweep_capacity(k)).  Entries are
+// build_det_step's SoA arrays; ticket: one int32 per user row, zero before the launch; err[0]
+// set when a wave gave up waiting.  ev0 / ev1 (may be null): dispatch-recorded timing events.
+int det_sweep_capacity(int k);
+// Entry arrays are read in 64-entry chunks up to 192 entries past a wave's end (kDetPad slack).
+// u_bytes / i_bytes: slab sizes (< 4 GiB, 32-bit row offsets); dummy_ticket: 16 scratch words
+// per wave (nw * 16 int32).
+constexpr int64_t kDetPad = 256;
+void launch_det_sweep(hipStream_t st, const DetWave* waves, int nw, const uint32_t* eu, const uint32_t* ei,
+                      const uint32_t* eq, const double* er, double* U, double* I, uint64_t u_bytes, uint64_t i_bytes,
+                      const double* regU, const double* regI, int k, double eta, int32_t* ticket,
+                      int32_t* dummy_ticket, int32_t* err, hipEvent_t ev0, hipEvent_t ev1);
+
+// Split single-item chains (k = 64, 128, 256; kernels_detsweep.hip k_det_sweep_split): blocks of
+// two wave slots, slots[2b + w] for wave w (nslots even, nslots / 2 blocks, all resident at once:
+// nslots <= det_split_capacity(k), counted in wave slots; 0 = k not supported).  A block whose
+// slot 0 is a single-item wave runs it as a chain wave plus a helper wave (slot 1 ignored, by
+// convention kDetWaveHelper); any other slot is an ordinary k_det_sweep2 wave (count 0: none).
+int det_split_capacity(int k);
+// The same split sweep with SGDUpdater.nextFactors' update (the online f64 batch, no lambda /
+// omega); k = 64, 128, 256 (capacity 0 otherwise).
+int online_det_capacity(int k);
+void launch_online_det(hipStream_t st, const DetWave* slots, int nslots, const uint32_t* eu, const uint32_t* ei,
+                       const uint32_t* eq, const double* er, double* U, double* I, uint64_t u_bytes, uint64_t i_bytes,
+                       int k, double eta, int32_t* ticket, int32_t* err, hipEvent_t ev0, hipEvent_t ev1);
+void launch_det_sweep_split(hipStream_t st, const DetWave* slots, int nslots, const uint32_t* eu, const uint32_t* ei,
+                            const uint32_t* eq, const double* er, double* U, double* I, uint64_t u_bytes,
+                            uint64_t i_bytes, const double* regU, const double* regI, int k, double eta,
+                            int32_t* ticket, int32_t* err, hipEvent_t ev0, hipEvent_t ev1);
+
+// ---- kernels_online_sweep.hip: the f32 online batch, one launch ---------------------------------
 // The f32 batch at k <= 256 (k_online_f32, kernels_online_sweep.hip): the same plan and tickets,
 // rows and tickets pipelined two updates deep, the dot product of online_f32.hpp (the f32 level
 // replay's).  dummy_ticket: 16 int32 per wave of scratch.  skip (may be null): the launch does
@@ -37,6 +94,8 @@ void launch_online_f32(hipStream_t st, int nw, const int64_t* wbeg, const DetEnt
                        float* I, uint64_t u_bytes, uint64_t i_bytes, int k, double eta, int32_t* ticket,
                        int32_t* dummy_ticket, int32_t* err, int nsingle, const int32_t* skip, hipEvent_t ev0,
                        hipEvent_t ev1);
+
+// ---- kernels_online.hip: the sweeps' inputs built on the device ---------------------------------
 // k_online_sweep's inputs from one batch in sequence order (eu / ei / er: user row, item row,
 // rating of update x; device arrays), on the device (kernels_online.hip): ent / useq (n each,
 // grouped by wave = item row mod W, sequence order inside a wave, useq = the update's rank among
@@ -82,13 +141,8 @@ void det_device_build_reserve(DetBuildScratch& sc, int64_t n_max, uint32_t wave_
 void det_device_build(hipStream_t st, DetBuildScratch& sc, const int32_t* ord, int64_t n, const DetBuildBlock* blocks,
                       int nblk, const DetEntry* aos, const int32_t* item_wave, uint32_t wave_bound,
                       uint32_t user_rows, uint32_t* ou, uint32_t* oi, uint32_t* oq, double* orr);
-// Per-rating records of the online operators (mf_online_update_out), f64 rows of k at
-// [src[entry] * k]: kOutNext = (user', item') (FlinkOnlineMF.scala:131-135), kOutDelta =
-// (user + deltaItem, deltaItem) with user before the update (PSOfflineOnlineMF.scala:174-176).
-enum class OnlineOut : int { kNone = 0, kOutNext = 1, kOutDelta = 2 };
-void launch_level_out(hipStream_t st, const DetEntry* entries, int64_t n, void* U, void* I, int k, double eta, bool f64,
-                      OnlineOut mode, const int32_t* src, double* uout, double* iout);
 
+// ---- kernels_fast.hip: fast-mode sweep, one update per step (every rank) ------------------------
 // Fast-mode sweep, one rotation sub-step t for nblk rating blocks of one superstep.
 struct FastBlk {
   int64_t rec_base;   // first record of the rating block
@@ -111,6 +165,7 @@ void launch_fast_superstep(hipStream_t st, const FastBlk* blks, int nblk, int G,
                            uint64_t i_bytes, uint32_t dummy_u_off, uint32_t dummy_i_off, int32_t* progress,
                            int32_t* err);
 
+// ---- kernels_pair.hip: fast-mode sweep, pair schedule (k = 64, 128, 256) ------------------------
 // Fast-mode sweep, pair schedule (kernels_pair.hip): one launch per sub-step, one wave per
 // cell, two updates of one item per step (build_pair_plan).  k in {64, 128, 256}; the plan
 // window must be >= 2 * pair_ring(pair_kpl(k)) (plan.hpp pair_window).
@@ -126,10 +181,6 @@ void launch_sweep_pair(hipStream_t st, const WaveDesc* waves, int nwaves, const 
 // err[0] is set when a wave gave up waiting.  trace (may be null): per cell {start, end} at
 // [2*(cell index in sys)].
 int sweep_pair_sys_capacity(int k);
-// Hot-item replicas around a fast superstep (plan.hpp SplitItem): fork before the sweep, join
-// after it, on the sweep's stream; n split items, f32 rows of k.
-void launch_split_fork(hipStream_t st, const SplitItem* sp, int n, float* I, int k);
-void launch_split_join(hipStream_t st, const SplitItem* sp, int n, float* I, int k);
 // lbase: index of sw[0] among the superstep's waves (a superstep may be split over two launches,
 // see mfhip.cpp ring overlap); prog and SysWave::nbr count from the superstep's first wave.
 // place (may be null): block b of the launch sweeps wave sw[place[b]] (sys_placement, mfhip.cpp);
@@ -138,60 +189,12 @@ void launch_sweep_pair_sys(hipStream_t st, const SysWave* sw, const WaveDesc* sy
                            const PairRec* recs, float* U, float* I, uint64_t u_bytes, uint64_t i_bytes, int k, float eta,
                            int32_t* prog, uint32_t base, int32_t* err, uint64_t* trace, hipEvent_t ev0, hipEvent_t ev1,
                            const int32_t* place = nullptr);
+// Hot-item replicas around a fast superstep (plan.hpp SplitItem): fork before the sweep, join
+// after it, on the sweep's stream; n split items, f32 rows of k.
+void launch_split_fork(hipStream_t st, const SplitItem* sp, int n, float* I, int k);
+void launch_split_join(hipStream_t st, const SplitItem* sp, int n, float* I, int k);
 
-// Deterministic persistent sweep (kernels_detsweep.hip): one launch per superstep, nw waves of
-// 64 lanes, all of which must be resident at once (nw <= det_sweep_capacity(k)).  Entries are
-// build_det_step's SoA arrays; ticket: one int32 per user row, zero before the launch; err[0]
-// set when a wave gave up waiting.  ev0 / ev1 (may be null): dispatch-recorded timing events.
-int det_sweep_capacity(int k);
-// Entry arrays are read in 64-entry chunks up to 192 entries past a wave's end (kDetPad slack).
-// u_bytes / i_bytes: slab sizes (< 4 GiB, 32-bit row offsets); dummy_ticket: 16 scratch words
-// per wave (nw * 16 int32).
-constexpr int64_t kDetPad = 256;
-void launch_det_sweep(hipStream_t st, const DetWave* waves, int nw, const uint32_t* eu, const uint32_t* ei,
-                      const uint32_t* eq, const double* er, double* U, double* I, uint64_t u_bytes, uint64_t i_bytes,
-                      const double* regU, const double* regI, int k, double eta, int32_t* ticket,
-                      int32_t* dummy_ticket, int32_t* err, hipEvent_t ev0, hipEvent_t ev1);
-
-// Split single-item chains (k = 64, 128, 256; kernels_detsweep.hip k_det_sweep_split): blocks of
-// two wave slots, slots[2b + w] for wave w (nslots even, nslots / 2 blocks, all resident at once:
-// nslots <= det_split_capacity(k), counted in wave slots; 0 = k not supported).  A block whose
-// slot 0 is a single-item wave runs it as a chain wave plus a helper wave (slot 1 ignored, by
-// convention kDetWaveHelper); any other slot is an ordinary k_det_sweep2 wave (count 0: none).
-int det_split_capacity(int k);
-// The same split sweep with SGDUpdater.nextFactors' update (the online f64 batch, no lambda /
-// omega); k = 64, 128, 256 (capacity 0 otherwise).
-int online_det_capacity(int k);
-void launch_online_det(hipStream_t st, const DetWave* slots, int nslots, const uint32_t* eu, const uint32_t* ei,
-                       const uint32_t* eq, const double* er, double* U, double* I, uint64_t u_bytes, uint64_t i_bytes,
-                       int k, double eta, int32_t* ticket, int32_t* err, hipEvent_t ev0, hipEvent_t ev1);
-void launch_det_sweep_split(hipStream_t st, const DetWave* slots, int nslots, const uint32_t* eu, const uint32_t* ei,
-                            const uint32_t* eq, const double* er, double* U, double* I, uint64_t u_bytes,
-                            uint64_t i_bytes, const double* regU, const double* regI, int k, double eta,
-                            int32_t* ticket, int32_t* err, hipEvent_t ev0, hipEvent_t ev1);
-
-// Gather-dot over resolved pairs (row -1 = unknown id).  out[j] = p.q summed left to right in
-// f64 (predictRating's ddot).  When r != nullptr every workgroup writes partials[3*wg + c]:
-//   c=0: sum (r - p.q)^2, c=1: matched count, c=2: sum mult*((r-p.q)^2 + lambda*(p.p + q.q)).
-// The grid has predict_grid(n) workgroups; the host adds the partials in a fixed order.
-int predict_grid(int64_t n);
-void launch_predict(hipStream_t st, const int32_t* urow, const int32_t* irow, int64_t n,
-                    const void* U, const void* I, int k, bool f64, double* out, const double* r,
-                    const int32_t* mult, double lambda, double* partials);
-
-// Top-N recommendation (kernels_recommend.hip): for each of the nq query rows qrows[] of slab Q (all
-// valid rows) the top_n best of candidate rows [0, C) of slab Cf by p.q, as ids / scores / counts
-// ([nq][top_n], [nq]; device).  f64: the sequential pq = pq + a*b chain (k_predict's value); f32:
-// the fmaf chain over f = 0..k-1 on the f32-input MFMA.  cand_id: row -> id of the candidate side.
-// excl_off (nq + 1) / excl_rows: per query the sorted candidate rows never returned.  The candidate
-// rows are walked in S <= 64 splits; part: nq * S * top_n keys of recommend_key_bytes(f64) scratch.
-// recommend_query_tile: the queries one workgroup owns (the host sizes S by it).
-size_t recommend_key_bytes(bool f64);
-int recommend_query_tile(int top_n, bool f64);
-void launch_recommend(hipStream_t st, const void* Q, const void* Cf, const int32_t* qrows, int nq, int32_t C, int S,
-                      int k, int top_n, bool f64, const int32_t* cand_id, const int64_t* excl_off,
-                      const int32_t* excl_rows, void* part, int32_t* ids, double* scores, int32_t* counts);
-
+// ---- kernels_block.hip: DSGD blocking -----------------------------------------------------------
 // DSGD blocking on the device (kernels_block.hip): both SideLayouts (initFactorBlockAndIndices,
 // DSGDforMF.scala:513-588, the reference's seeded blocking) and the rating blocks of user blocks
 // [ub_lo, ub_hi) (:301-327; sort_ui: (user, item) order inside a block), bitwise what
@@ -205,6 +208,8 @@ struct DevRatingBlocks;
 void device_blocking(hipStream_t st, const int32_t* u, const int32_t* i, const double* r, int64_t n, int32_t nb,
                      int64_t seed, int32_t ub_lo, int32_t ub_hi, bool sort_ui, SideLayout& U, SideLayout& I,
                      RatingBlocks& rb, DevRatingBlocks* keep = nullptr, bool host_arrays = true);
+
+// ---- kernels_plan.hip: the fast schedule --------------------------------------------------------
 void fetch_rating_blocks(hipStream_t st, const DevRatingBlocks& dr, RatingBlocks& rb);
 // Per rating block (n*n): the rating count of its most rated item, from the device arrays.
 std::vector<int64_t> device_block_tops(hipStream_t st, const DevRatingBlocks& dr, const RatingBlocks& rb,
@@ -225,15 +230,21 @@ void device_fast_schedule(hipStream_t st, const DevRatingBlocks& dr, const Ratin
                           FastPlan& fp, int32_t c, int32_t shard, int32_t k, uint32_t dummy_row, int32_t window,
                           PairPlan& pp, DevBuf& d_pairs);
 
-// Initial factor rows on the device (DSGDforMF.scala:548-549, MatrixFactorization.scala:278-280):
-// row x, factor f = the f-th nextDouble of new Random(ids[x] ^ seed) (xor_seed) or of
-// new Random(ids[x]).  One thread per element: the JVM LCG state after m steps is
-// jump[2(m-1)] * s0 + jump[2(m-1)+1] mod 2^48 (host table, m = 1..2k), so every element is
-// computed independently and written coalesced; bit-exact with JavaRandom::nextDouble.
-// out: rows x k, double (f64) or float (rounded from the same double).
-void launch_jvm_init_rows(hipStream_t st, const int32_t* ids, int64_t rows, int k, bool xor_seed, int64_t seed,
-                          const uint64_t* jump, void* out, bool f64);
+// ---- kernels_recommend.hip: top-N recommendation ------------------------------------------------
+// Top-N recommendation (kernels_recommend.hip): for each of the nq query rows qrows[] of slab Q (all
+// valid rows) the top_n best of candidate rows [0, C) of slab Cf by p.q, as ids / scores / counts
+// ([nq][top_n], [nq]; device).  f64: the sequential pq = pq + a*b chain (k_predict's value); f32:
+// the fmaf chain over f = 0..k-1 on the f32-input MFMA.  cand_id: row -> id of the candidate side.
+// excl_off (nq + 1) / excl_rows: per query the sorted candidate rows never returned.  The candidate
+// rows are walked in S <= 64 splits; part: nq * S * top_n keys of recommend_key_bytes(f64) scratch.
+// recommend_query_tile: the queries one workgroup owns (the host sizes S by it).
+size_t recommend_key_bytes(bool f64);
+int recommend_query_tile(int top_n, bool f64);
+void launch_recommend(hipStream_t st, const void* Q, const void* Cf, const int32_t* qrows, int nq, int32_t C, int S,
+                      int k, int top_n, bool f64, const int32_t* cand_id, const int64_t* excl_off,
+                      const int32_t* excl_rows, void* part, int32_t* ids, double* scores, int32_t* counts);
 
+// ---- kernels_als.hip: ALS half-sweeps -----------------------------------------------------------
 // ALS half-sweep (kernels_als.hip).  A work item is a whole row of the side being solved (slot < 0:
 // its system is solved in the kernel and x stored to X[row]) or one chunk of a long row (slot >= 0:
 // its partial matrix and right-hand side go to partial[slot], als_partial_elems(k) elements each);

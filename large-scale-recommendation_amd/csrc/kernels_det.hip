@@ -16,19 +16,17 @@
 #include <algorithm>
 
 #include "kernels.hpp"
+#include "online_f32.hpp"
+#include "seq_fold.hpp"
+#include "ticket_wait.hpp"
+#include "wave_device.hpp"
 
 namespace mfhip {
 namespace {
+using namespace dev;
 
-__device__ __forceinline__ double readlane(double v, int l) {
-  const unsigned long long b = static_cast<unsigned long long>(__double_as_longlong(v));
-  const unsigned lo = static_cast<unsigned>(__builtin_amdgcn_readlane(static_cast<int>(b & 0xffffffffu), l));
-  const unsigned hi = static_cast<unsigned>(__builtin_amdgcn_readlane(static_cast<int>(b >> 32), l));
-  return __longlong_as_double(static_cast<long long>((static_cast<unsigned long long>(hi) << 32) | lo));
-}
-__device__ __forceinline__ float readlane(float v, int l) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
-}
+__device__ __forceinline__ double readlane(double v, int l) { return rld(v, l); }
+__device__ __forceinline__ float readlane(float v, int l) { return rlf(v, l); }
 
 // Sequential dot over f = 0..k-1 where lane l holds element l + 64c in prod[c]:
 // acc = ((0 + x0) + x1) + ... exactly as F2jBLAS.ddot / Scala's foldLeft sum.
@@ -49,10 +47,6 @@ __device__ __forceinline__ T seq_dot(const T (&prod)[KPL], int k) {
   }
   return acc;
 }
-
-#include "online_f32.hpp"
-#include "seq_fold.hpp"
-#include "ticket_wait.hpp"
 
 // SGDUpdater.nextFactors of one rating in f32 with online_f32.hpp's arithmetic and k_online_f32's
 // row layout (kernels_online_sweep.hip), so the level replay equals the one-launch sweep bit for
@@ -199,7 +193,7 @@ __global__ __launch_bounds__(64) void k_online_sweep(const int64_t* __restrict__
       for (int c = 0; c < KPL; ++c) pv[c] = FULL || lane + 64 * c < k ? slot[c] : T(0);
     } else {
       if (has_pend) {  // publish the held-back ticket before any wait
-        __builtin_amdgcn_s_waitcnt(0x0F70);
+        wait_vmcnt<0>();
         if (lane == 0) __hip_atomic_store(ticket + pend_u, pend_q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         has_pend = false;
       }
@@ -265,18 +259,14 @@ __global__ __launch_bounds__(64) void k_online_sweep(const int64_t* __restrict__
     if (g2) ld_row(U + static_cast<size_t>(u2) * k, slot);
     // vmcnt(n): every operation older than the n just issued has landed (vector memory
     // operations complete in issue order)
-    constexpr int kW1 = 0x0F70 | ((1 * KPL) & 15) | (((1 * KPL) >> 4) << 14);
-    constexpr int kW2 = 0x0F70 | ((2 * KPL) & 15) | (((2 * KPL) >> 4) << 14);
-    constexpr int kW3 = 0x0F70 | ((3 * KPL) & 15) | (((3 * KPL) >> 4) << 14);
-    constexpr int kW4 = 0x0F70 | ((4 * KPL) & 15) | (((4 * KPL) >> 4) << 14);
     if (defer) {
       // n = this update's stores (its user row, its item row when written back) and the loads
       // ahead: the previous update's stores have landed, so its ticket goes out now
       const int m = (istore ? 2 : 1) + (g1 ? 1 : 0) + (g2 ? 1 : 0);
-      if (m == 1) __builtin_amdgcn_s_waitcnt(kW1);
-      else if (m == 2) __builtin_amdgcn_s_waitcnt(kW2);
-      else if (m == 3) __builtin_amdgcn_s_waitcnt(kW3);
-      else __builtin_amdgcn_s_waitcnt(kW4);
+      if (m == 1) wait_vmcnt<1 * KPL>();
+      else if (m == 2) wait_vmcnt<2 * KPL>();
+      else if (m == 3) wait_vmcnt<3 * KPL>();
+      else wait_vmcnt<4 * KPL>();
       if (has_pend && lane == 0)
         __hip_atomic_store(ticket + pend_u, pend_q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       pend_u = ur;
@@ -284,9 +274,9 @@ __global__ __launch_bounds__(64) void k_online_sweep(const int64_t* __restrict__
       has_pend = true;
     } else {
       // n = the loads just issued: this update's stores have landed
-      if (g1 && g2) __builtin_amdgcn_s_waitcnt(kW2);
-      else if (g1 || g2) __builtin_amdgcn_s_waitcnt(kW1);
-      else __builtin_amdgcn_s_waitcnt(0x0F70);
+      if (g1 && g2) wait_vmcnt<2 * KPL>();
+      else if (g1 || g2) wait_vmcnt<1 * KPL>();
+      else wait_vmcnt<0>();
       if (lane == 0) __hip_atomic_store(ticket + ur, q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   };
@@ -299,7 +289,7 @@ __global__ __launch_bounds__(64) void k_online_sweep(const int64_t* __restrict__
   }
   if (jp < j1) step(jp, sa, ha, sb, hb);
   if (has_pend) {
-    __builtin_amdgcn_s_waitcnt(0x0F70);
+    wait_vmcnt<0>();
     if (lane == 0) __hip_atomic_store(ticket + pend_u, pend_q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }

@@ -25,26 +25,16 @@
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
-
 #include "kernels.hpp"
+#include "seq_fold.hpp"
+#include "ticket_wait.hpp"
+#include "wave_device.hpp"
 
 namespace mfhip {
 namespace {
-
-__device__ __forceinline__ uint32_t rl(uint32_t v, int l) {
-  return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(v), l));
-}
-__device__ __forceinline__ double rld(double v, int l) {
-  const unsigned long long b = static_cast<unsigned long long>(__double_as_longlong(v));
-  const unsigned lo = static_cast<unsigned>(__builtin_amdgcn_readlane(static_cast<int>(b & 0xffffffffu), l));
-  const unsigned hi = static_cast<unsigned>(__builtin_amdgcn_readlane(static_cast<int>(b >> 32), l));
-  return __longlong_as_double(static_cast<long long>((static_cast<unsigned long long>(hi) << 32) | lo));
-}
+using namespace dev;
 
 __device__ __forceinline__ double uniform(double v) { return rld(v, 0); }
-
-#include "seq_fold.hpp"
-#include "ticket_wait.hpp"
 
 // Entry fields of a wave's entry list, 64 per lane-register chunk (the host pads every entry
 // array by 64, so a chunk load never needs a bounds branch).
@@ -57,16 +47,11 @@ __device__ __forceinline__ DetChunk det_chunk(const uint32_t* eu, const uint32_t
   return DetChunk{eu[x], ei[x], eq[x], er[x]};
 }
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t raw_rsrc(const void* base, uint64_t bytes) {
-  const uint32_t n = bytes > 0xFFFFF000ull ? 0xFFFFF000u : static_cast<uint32_t>(bytes);
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, n, 0x00020000);
-}
-constexpr int kSC1 = 16;                   // buffer cache policy: sc1 (L1 bypass, write-through)
-constexpr uint32_t kOOB = 0xFFFFF000u;     // a row offset past the slab: the load returns 0, no store
-
+// The ticket hand-off of this sweep, publish / poll_issue (kernels_online_sweep.hip has the same
+// pair on plain pointers; the rare blocking wait of both is poll_until, ticket_wait.hpp).
 // Ticket words and lambda / omega through raw buffers with the word's byte offset in an SGPR: one
 // scalar shift per access instead of a 64-bit address and a select, and "none" is the out-of-range
-// offset kOOB (the load returns 0, the store is dropped) instead of a per-wave dummy word.  Every
+// offset kOffOOB (the load returns 0, the store is dropped) instead of a per-wave dummy word.  Every
 // lane touches the same word (same value): no exec mask around a publish.  sc1 loads and stores,
 // the agent-scope relaxed atomics of the hand-off (MI355X_MICROARCH.md, valid forms: buffer_load_dword
 // sc1 poll).
@@ -104,20 +89,12 @@ __device__ __forceinline__ DRow<KPL> ldrow(__amdgpu_buffer_rsrc_t rs, const uint
 template <int KPL>
 __device__ __forceinline__ void strow(__amdgpu_buffer_rsrc_t rs, const uint32_t (&voff)[KPL], uint32_t off,
                                       const double (&v)[KPL]) {
-  using u2 = uint32_t __attribute__((ext_vector_type(2)));
 #pragma unroll
   for (int c = 0; c < KPL; ++c) {
     const uint64_t b = static_cast<uint64_t>(__double_as_longlong(v[c]));
-    __builtin_amdgcn_raw_buffer_store_b64(u2{static_cast<uint32_t>(b), static_cast<uint32_t>(b >> 32)}, rs, voff[c],
+    __builtin_amdgcn_raw_buffer_store_b64(u2v{static_cast<uint32_t>(b), static_cast<uint32_t>(b >> 32)}, rs, voff[c],
                                           off, kSC1);
   }
-}
-
-// vmcnt(N) in the gfx9 encoding (expcnt 7, lgkmcnt 15 left unconstrained).
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  static_assert(N >= 0 && N < 64, "vmcnt range");
-  __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | 0x0F70 & ~0xF);
 }
 
 // k_det_sweep2: per wave, the entries of its items in shuffled order, with a two-deep pipeline for
@@ -148,7 +125,7 @@ constexpr int kDetChunk = 16;
 constexpr int kArDsgd = 0, kArNext = 1;
 template <int AR>
 constexpr uint64_t reg_bytes() {
-  return AR == kArDsgd ? 0xFFFFF000ull : 0ull;
+  return AR == kArDsgd ? kSlabLimit : 0ull;
 }
 // (p', q') from the rows before the update, e = r - p.q
 template <int AR>
@@ -163,7 +140,6 @@ __device__ __forceinline__ void update_pair(double p, double q, double e, double
     qn = q + le * p;
   }
 }
-
 
 // One wave's entries.  SINGLE (DetWave::flags & kDetWaveSingleItem): every entry updates the same
 // item, so its row and lambda / omega are loaded once and stored once at the end, and an entry moves
@@ -181,10 +157,9 @@ __device__ __forceinline__ void det_wave(const DetWave d, const uint32_t* __rest
                                          int32_t* dummy_ticket, int32_t* err, double* lds, int lane) {
   constexpr int CH = kDetChunk;
   constexpr int NW = SINGLE ? 3 * KPL + 5 : 6 * KPL + 7;
-  static_assert(NW < 64, "vmcnt range");
   const int32_t cnt = d.count;  // 32-bit: the entry tests are scalar compares, not 64-bit VALU ones
   const __amdgpu_buffer_rsrc_t urs = raw_rsrc(U, u_bytes), irs = raw_rsrc(I, i_bytes);
-  const __amdgpu_buffer_rsrc_t trs = raw_rsrc(ticket, 0xFFFFF000ull);  // offsets are user rows * 4
+  const __amdgpu_buffer_rsrc_t trs = raw_rsrc(ticket, kSlabLimit);  // offsets are user rows * 4
   const __amdgpu_buffer_rsrc_t rus = raw_rsrc(regU, reg_bytes<AR>()), ris = raw_rsrc(regI, reg_bytes<AR>());
   uint32_t voff[KPL];
 #pragma unroll
@@ -209,19 +184,19 @@ __device__ __forceinline__ void det_wave(const DetWave d, const uint32_t* __rest
     const bool live = x < cnt;
     const uint32_t u = fu(x), i = fi(x), q = fq(x);
     okP[x] = !live || poll(trs, u * 4u) == static_cast<int32_t>(q & kDetUseqMask);
-    P[x] = ldrow<KPL>(urs, voff, live && okP[x] ? u * rowb : kOOB);
+    P[x] = ldrow<KPL>(urs, voff, live && okP[x] ? u * rowb : kOffOOB);
     RU[x] = ld_reg(rus, live ? u : 0u);
     if (!SINGLE || x == 0) {
-      Q[x] = ldrow<KPL>(irs, voff, live && !(x > 0 && i == fi(x - 1)) ? i * rowb : kOOB);
+      Q[x] = ldrow<KPL>(irs, voff, live && !(x > 0 && i == fi(x - 1)) ? i * rowb : kOffOOB);
       RI[x] = ld_reg(ris, live ? i : 0u);
     }
   }
 #pragma unroll
-  for (int x = 0; x < 2; ++x) tk[x] = poll_issue(trs, x + 2 < cnt ? fu(x + 2) * 4u : kOOB);
-  __builtin_amdgcn_s_waitcnt(0x0F70);
-  uint32_t pend0 = kOOB;  // entry j-2's ticket word (byte offset; kOOB: none) and value
+  for (int x = 0; x < 2; ++x) tk[x] = poll_issue(trs, x + 2 < cnt ? fu(x + 2) * 4u : kOffOOB);
+  wait_vmcnt<0>();
+  uint32_t pend0 = kOffOOB;  // entry j-2's ticket word (byte offset; kOffOOB: none) and value
   int32_t pv0 = 0;
-  uint32_t pend1 = kOOB;  // entry j-1's
+  uint32_t pend1 = kOffOOB;  // entry j-1's
   int32_t pv1 = 0;
   double q[KPL];
 #pragma unroll
@@ -252,13 +227,13 @@ __device__ __forceinline__ void det_wave(const DetWave d, const uint32_t* __rest
     // 1. the user row, when its ticket was not ready at prefetch time (rare): publish every
     //    pending ticket (after its stores), wait for ours, load now
     if (!okP[slot]) {
-      __builtin_amdgcn_s_waitcnt(0x0F70);
+      wait_vmcnt<0>();
       publish(trs, pend0, pv0);
       publish(trs, pend1, pv1);
-      pend0 = pend1 = kOOB;
+      pend0 = pend1 = kOffOOB;
       wait_ticket_or_fail(ticket + u, useq, err, lane);  // no early return (ticket_wait.hpp)
       P[slot] = ldrow<KPL>(urs, voff, u * rowb);
-      __builtin_amdgcn_s_waitcnt(0x0F70);
+      wait_vmcnt<0>();
     }
     // 2. compute entry j (DSGDforMF.scala:405-410, the reference's rounding, no FMA)
     if (!SINGLE && !keepq) {
@@ -286,21 +261,21 @@ __device__ __forceinline__ void det_wave(const DetWave d, const uint32_t* __rest
     pv1 = useq + 1;
     // 4. entry j's stores
     strow<KPL>(urs, voff, u * rowb, pn);
-    if (!SINGLE) strow<KPL>(irs, voff, deferq ? kOOB : i * rowb, q);
+    if (!SINGLE) strow<KPL>(irs, voff, deferq ? kOffOOB : i * rowb, q);
     stamp(2);
     // 5. prefetch entry j+2 into this slot (after the stores: a reload of an item row this wave
     //    just stored sees it); its user row only if its ticket (polled at entry j-2) was ready
     const bool live2 = j + 2 < cnt;
     const int32_t okN = !live2 || __builtin_amdgcn_readfirstlane(tk[slot]) == static_cast<int32_t>(q2 & kDetUseqMask);
-    P[slot] = ldrow<KPL>(urs, voff, live2 && okN ? u2 * rowb : kOOB);
+    P[slot] = ldrow<KPL>(urs, voff, live2 && okN ? u2 * rowb : kOffOOB);
     RU[slot] = ld_reg(rus, live2 ? u2 : 0u);
     if (!SINGLE) {
-      Q[slot] = ldrow<KPL>(irs, voff, live2 && !(i2 == fi(s + 1)) ? i2 * rowb : kOOB);
+      Q[slot] = ldrow<KPL>(irs, voff, live2 && !(i2 == fi(s + 1)) ? i2 * rowb : kOffOOB);
       RI[slot] = ld_reg(ris, live2 ? i2 : 0u);
     }
     okP[slot] = okN;
     // 6. poll entry j+4's ticket (read at entry j+2)
-    tk[slot] = poll_issue(trs, j + 4 < cnt ? u4 * 4u : kOOB);
+    tk[slot] = poll_issue(trs, j + 4 < cnt ? u4 * 4u : kOffOOB);
     prev_i = i;
     stamp(3);
   };
@@ -325,7 +300,7 @@ __device__ __forceinline__ void det_wave(const DetWave d, const uint32_t* __rest
   }
 done:
   if (SINGLE) strow<KPL>(irs, voff, item0 * rowb, q);  // the item row, once
-  __builtin_amdgcn_s_waitcnt(0x0F70);
+  wait_vmcnt<0>();
   publish(trs, pend0, pv0);
   publish(trs, pend1, pv1);
 #if defined(MFHIP_EXPERIMENTS) && defined(MFHIP_DET_PROBE)
@@ -424,7 +399,7 @@ __device__ __forceinline__ void link_wait(F v, int32_t want, int32_t* err, int l
     __builtin_amdgcn_s_sleep(1);
     if (__builtin_amdgcn_s_memrealtime() - t0 > 400000000ull) {
       if (lane == 0) __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __builtin_amdgcn_s_waitcnt(0x0F70);  // the flag store is not a row store a ticket publishes
+      wait_vmcnt<0>();  // the flag store is not a row store a ticket publishes
       break;
     }
   }
@@ -523,10 +498,9 @@ __device__ __forceinline__ void det_helper(const DetWave d, const uint32_t* __re
   // NW = the operations issued after entry j-2's stores up to entry j's publish: entry j-2's loads
   // and poll, all of entry j-1's: (KPL + 2) + (2 KPL + 3).
   constexpr int NW = 3 * KPL + 5;
-  static_assert(NW < 64, "vmcnt range");
   const int32_t cnt = d.count;
   const __amdgpu_buffer_rsrc_t urs = raw_rsrc(U, u_bytes), irs = raw_rsrc(I, i_bytes);
-  const __amdgpu_buffer_rsrc_t trs = raw_rsrc(ticket, 0xFFFFF000ull);
+  const __amdgpu_buffer_rsrc_t trs = raw_rsrc(ticket, kSlabLimit);
   const __amdgpu_buffer_rsrc_t rus = raw_rsrc(regU, reg_bytes<AR>()), ris = raw_rsrc(regI, reg_bytes<AR>());
   uint32_t voff[KPL];
 #pragma unroll
@@ -563,9 +537,9 @@ __device__ __forceinline__ void det_helper(const DetWave d, const uint32_t* __re
     const bool live = x < cnt;
     const uint32_t u = fu(x);
     const bool ok = live && poll(trs, u * 4u) == static_cast<int32_t>(fq(x) & kDetUseqMask);
-    const DRow<KPL> p = ldrow<KPL>(urs, voff, ok ? u * rowb : kOOB);
+    const DRow<KPL> p = ldrow<KPL>(urs, voff, ok ? u * rowb : kOffOOB);
     const double ru = ld_reg(rus, live ? u : 0u);
-    __builtin_amdgcn_s_waitcnt(0x0F70);
+    wait_vmcnt<0>();
     if (x < R) {
       if (ok) put(x, p.v, fr(x), ru);
       else if (live) later |= 1u << (x % R);
@@ -577,9 +551,9 @@ __device__ __forceinline__ void det_helper(const DetWave d, const uint32_t* __re
     }
   }
 #pragma unroll
-  for (int x = 0; x < 2; ++x) tk[x] = poll_issue(trs, D + x < cnt ? fu(D + x) * 4u : kOOB);
-  __builtin_amdgcn_s_waitcnt(0x0F70);
-  uint32_t pend0 = kOOB, pend1 = kOOB;  // entries j-2 / j-1: ticket word byte offsets (kOOB: none)
+  for (int x = 0; x < 2; ++x) tk[x] = poll_issue(trs, D + x < cnt ? fu(D + x) * 4u : kOffOOB);
+  wait_vmcnt<0>();
+  uint32_t pend0 = kOffOOB, pend1 = kOffOOB;  // entries j-2 / j-1: ticket word byte offsets (kOffOOB: none)
   int32_t pv0 = 0, pv1 = 0;
   auto entry = [&](const int s, const int32_t j) {
     const uint32_t u = fu(s), qf = fq(s);
@@ -587,14 +561,14 @@ __device__ __forceinline__ void det_helper(const DetWave d, const uint32_t* __re
     // a. entry j's row when its ticket was not ready in time: publish every pending ticket
     //    (after its stores), wait for ours, hand the row over now
     if (later & (1u << (j % R))) {
-      __builtin_amdgcn_s_waitcnt(0x0F70);
+      wait_vmcnt<0>();
       publish(trs, pend0, pv0);
       publish(trs, pend1, pv1);
-      pend0 = pend1 = kOOB;
+      pend0 = pend1 = kOffOOB;
       wait_ticket_or_fail(ticket + u, useq, err, lane);
       const DRow<KPL> p = ldrow<KPL>(urs, voff, u * rowb);
       const double ru = ld_reg(rus, u);
-      __builtin_amdgcn_s_waitcnt(0x0F70);
+      wait_vmcnt<0>();
       put(j, p.v, fr(s), ru);
       later &= ~(1u << (j % R));
     }
@@ -627,13 +601,13 @@ __device__ __forceinline__ void det_helper(const DetWave d, const uint32_t* __re
     const int32_t m2 = j + D;
     const bool ok2 = m2 < cnt && __builtin_amdgcn_readfirstlane(tk[j & 1]) == static_cast<int32_t>(fq(s + D) & kDetUseqMask);
     const uint32_t u2 = fu(s + D);
-    const DRow<KPL> p2 = ldrow<KPL>(urs, voff, ok2 ? u2 * rowb : kOOB);
+    const DRow<KPL> p2 = ldrow<KPL>(urs, voff, ok2 ? u2 * rowb : kOffOOB);
 #pragma unroll
     for (int c = 0; c < KPL; ++c) PR[m2 % RING][c] = p2.v[c];
     RU[m2 % RING] = ld_reg(rus, m2 < cnt ? u2 : 0u);
     okR = ok2 ? (okR | (1u << (m2 % RING))) : (okR & ~(1u << (m2 % RING)));
     // g. poll entry j + D + 2's ticket
-    tk[j & 1] = poll_issue(trs, m2 + 2 < cnt ? fu(s + D + 2) * 4u : kOOB);
+    tk[j & 1] = poll_issue(trs, m2 + 2 < cnt ? fu(s + D + 2) * 4u : kOffOOB);
   };
   for (int32_t c0 = 0;; c0 += CH) {
     if (c0 + CH <= cnt) {
@@ -661,7 +635,7 @@ done:
   }
   asm volatile("" ::"v"(tk[0]), "v"(tk[1]));
   strow<KPL>(irs, voff, item * rowb, q);  // the item row, once
-  __builtin_amdgcn_s_waitcnt(0x0F70);
+  wait_vmcnt<0>();
   publish(trs, pend0, pv0);
   publish(trs, pend1, pv1);
 }
@@ -705,7 +679,7 @@ __global__ __launch_bounds__(64) void k_det_sweep2(const DetWave* __restrict__ w
                                                    const double* __restrict__ regI, int k, double eta,
                                                    int32_t* ticket, int32_t* dummy_ticket, int32_t* err) {
   __shared__ __attribute__((aligned(16))) double lds[64 * KPL];
-  (void)dummy_ticket;  // "no ticket" is the out-of-range offset kOOB now
+  (void)dummy_ticket;  // "no ticket" is the out-of-range offset kOffOOB now
   const DetWave d = waves[blockIdx.x];
   if (d.count == 0) return;
   if (d.flags & kDetWaveSingleItem)

@@ -32,22 +32,13 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels.hpp"
+#include "wave_device.hpp"
 
 namespace mfhip {
 namespace {
+using namespace dev;
 
 constexpr uint32_t kNone = 0xffffffffu;
-constexpr uint32_t kPad = kPadBit;
-
-__device__ __forceinline__ uint32_t rl(uint32_t v, int l) {
-  return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(v), l));
-}
-__device__ __forceinline__ float rlf(uint32_t v, int l) { return __uint_as_float(rl(v, l)); }
-
-template <int CTRL>
-__device__ __forceinline__ float dpp(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, false));
-}
 
 // ---- row I/O ------------------------------------------------------------------------------
 // A lane holds elements [lane*KPL, lane*KPL + KPL) of a row.  FULL: k == 64*KPL (vector I/O);
@@ -58,11 +49,6 @@ template <int KPL>
 struct Row {
   float v[KPL];
 };
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, uint64_t bytes) {
-  const uint32_t n = bytes > 0xffffffffull ? 0xffffffffu : static_cast<uint32_t>(bytes);
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, n, 0x00020000);
-}
 
 // `off` is the row's byte offset in the slab (scalar, passed as soffset); the per-lane part of
 // the address is a constant VGPR.
@@ -109,19 +95,13 @@ __device__ __forceinline__ void store_row(__amdgpu_buffer_rsrc_t rs, uint32_t of
     if constexpr (KPL == 1) {
       __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(r.v[0]), rs, vo, off, AUX);
     } else if constexpr (KPL == 2) {
-      using u2 = uint32_t __attribute__((ext_vector_type(2)));
-      u2 x = {__float_as_uint(r.v[0]), __float_as_uint(r.v[1])};
-      __builtin_amdgcn_raw_buffer_store_b64(x, rs, vo, off, AUX);
+      __builtin_amdgcn_raw_buffer_store_b64(u2v{__float_as_uint(r.v[0]), __float_as_uint(r.v[1])}, rs, vo, off, AUX);
     } else {
-      using u4 = uint32_t __attribute__((ext_vector_type(4)));
 #pragma unroll
-      for (int c = 0; c < KPL; c += 4) {
-        u4 x = {__float_as_uint(r.v[c]), __float_as_uint(r.v[c + 1]), __float_as_uint(r.v[c + 2]),
-                __float_as_uint(r.v[c + 3])};
-        __builtin_amdgcn_raw_buffer_store_b128(x, rs, vo + c * 4u, off, AUX);
-        // two wait states before the data VGPRs may be rewritten (gfx950 store-data hazard, pair_device.hpp)
-        asm volatile("s_nop 1" ::"v"(x[0]), "v"(x[1]), "v"(x[2]), "v"(x[3]));
-      }
+      for (int c = 0; c < KPL; c += 4)
+        store_b128(u4v{__float_as_uint(r.v[c]), __float_as_uint(r.v[c + 1]), __float_as_uint(r.v[c + 2]),
+                       __float_as_uint(r.v[c + 3])},
+                   rs, vo + c * 4u, off, AUX);
     }
   } else {
 #pragma unroll
@@ -132,7 +112,7 @@ __device__ __forceinline__ void store_row(__amdgpu_buffer_rsrc_t rs, uint32_t of
   }
 }
 
-// Bounded wait until *flag >= want (sc1 polls).  Returns false on timeout (sets *err).
+// The persistent driver's progress wait: bounded, until *flag >= want (sc1 polls); false on timeout (sets *err).
 __device__ __forceinline__ bool wait_flag(const int32_t* flag, int32_t want, int32_t* err) {
   if (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= want) return true;
   const uint64_t t0 = __builtin_amdgcn_s_memrealtime();  // 100 MHz
@@ -185,7 +165,7 @@ __device__ __forceinline__ float wave_sum(float v) {
   asm("s_nop 1\n\tv_add_f32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
       "s_nop 1\n\tv_add_f32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf"
       : "+v"(v));
-  return rlf(__float_as_uint(v), 63);
+  return rlf(v, 63);
 }
 
 // Sequential sweep of one cell: `len` records starting at record `beg`.  Per step the wave
@@ -243,8 +223,8 @@ __device__ __forceinline__ void sweep_cell(int64_t beg, int len, const uint32_t*
     _Pragma("unroll") for (int e = 0; e < KPL; ++e) q.v[e] = nr_ ? ql_.v[e] : q.v[e];       \
     float part_ = 0.f;                                                                      \
     _Pragma("unroll") for (int e = 0; e < KPL; ++e) part_ = fmaf(p_.v[e], q.v[e], part_);   \
-    const float w_ = fmaf(-eta, wave_sum(part_), rlf(__float_as_uint(X.er), (y)));          \
-    const float a_ = rlf(__float_as_uint(X.a), (y)), b_ = rlf(__float_as_uint(X.b), (y));   \
+    const float w_ = fmaf(-eta, wave_sum(part_), rlf(X.er, (y)));                           \
+    const float a_ = rlf(X.a, (y)), b_ = rlf(X.b, (y));                                     \
     Row<KPL> pn_;                                                                           \
     _Pragma("unroll") for (int e = 0; e < KPL; ++e) {                                       \
       pn_.v[e] = fmaf(w_, q.v[e], b_ * p_.v[e]);                                            \
@@ -313,8 +293,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 4))) void
   if (len <= 0) return;
   // the longest cells set the sub-step's length: give their waves issue priority on the SIMD
   if (len >= prio_len) __builtin_amdgcn_s_setprio(3);
-  sweep_cell<KPL, FULL, D, 0>(beg, len, recw, make_rsrc(U, u_bytes), make_rsrc(I, i_bytes), k, eta, lane,
-                              dummy_u_off, dummy_i_off);
+  sweep_cell<KPL, FULL, D, 0>(beg, len, recw, raw_rsrc(U, u_bytes, kWholeRange), raw_rsrc(I, i_bytes, kWholeRange), k,
+                              eta, lane, dummy_u_off, dummy_i_off);
 }
 
 // ---- one persistent launch per superstep (systolic rotation) --------------------------------
@@ -334,7 +314,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 4))) void
   int32_t* prog = progress + static_cast<int64_t>(slot) * G * kProgStride;
   const int32_t* off = cell_off + d.cell_base;
   const int32_t* next_prog = prog + static_cast<int64_t>(g + 1 == G ? 0 : g + 1) * kProgStride;
-  const __amdgpu_buffer_rsrc_t urs = make_rsrc(U, u_bytes), irs = make_rsrc(I, i_bytes);
+  const __amdgpu_buffer_rsrc_t urs = raw_rsrc(U, u_bytes, kWholeRange), irs = raw_rsrc(I, i_bytes, kWholeRange);
   for (int t = 0; t < G; ++t) {
     const int64_t cb = static_cast<int64_t>(t) * G + g;
     const int64_t beg = d.rec_base + off[cb];

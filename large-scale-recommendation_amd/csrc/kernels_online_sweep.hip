@@ -39,16 +39,15 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels.hpp"
+#include "online_f32.hpp"
+#include "ticket_wait.hpp"
+#include "wave_device.hpp"
 
 namespace mfhip {
 namespace {
+using namespace dev;
 
-#include "online_f32.hpp"
-#include "ticket_wait.hpp"
-
-constexpr int kSC1 = 16;                // buffer cache policy: sc1 (L1 bypass, write-through)
-constexpr uint32_t kOOB = 0xFFFFF000u;  // a row offset past the slab: the load returns 0, no store
-constexpr int kOnChunk = 16;            // updates per register chunk
+constexpr int kOnChunk = 16;  // updates per register chunk
 // The general path publishes a ticket two updates late, the single-item path kSingle late, and
 // prefetches its user rows and reads its ticket polls kSingle updates on (tools/isa_check.py checks
 // the built code against both).  Measured on NFLX 1M batches (gpurun_out/r6f, r6g): every wave at
@@ -57,13 +56,6 @@ constexpr int kOnChunk = 16;            // updates per register chunk
 // general waves).
 constexpr int kSingle = 4;
 
-__device__ __forceinline__ uint32_t rl(uint32_t v, int l) {
-  return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(v), l));
-}
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t raw_rsrc(const void* base, uint64_t bytes) {
-  const uint32_t n = bytes > 0xFFFFF000ull ? 0xFFFFF000u : static_cast<uint32_t>(bytes);
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, n, 0x00020000);
-}
 // One row of k floats as this lane's KPL elements (online_f32.hpp layout).  FULL: one access of
 // 4 KPL bytes.  Else KPL 4-B accesses; a lane's element past k reads a clamped in-row address and
 // is zeroed, and its store is masked off (a voffset past the slab would not do: with an
@@ -108,14 +100,10 @@ struct Rows {
     if constexpr (FULL && KPL == 1) {
       __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[0]), rs, voff[0], off, kSC1);
     } else if constexpr (FULL && KPL == 2) {
-      using u2 = uint32_t __attribute__((ext_vector_type(2)));
-      __builtin_amdgcn_raw_buffer_store_b64(u2{__float_as_uint(v[0]), __float_as_uint(v[1])}, rs, voff[0], off, kSC1);
+      __builtin_amdgcn_raw_buffer_store_b64(u2v{__float_as_uint(v[0]), __float_as_uint(v[1])}, rs, voff[0], off, kSC1);
     } else if constexpr (FULL && KPL == 4) {
-      using u4 = uint32_t __attribute__((ext_vector_type(4)));
-      const u4 d = {__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])};
-      __builtin_amdgcn_raw_buffer_store_b128(d, rs, voff[0], off, kSC1);
-      // two wait states before the data VGPRs may be rewritten (gfx950 store-data hazard, pair_device.hpp)
-      asm volatile("s_nop 1" ::"v"(d[0]), "v"(d[1]), "v"(d[2]), "v"(d[3]));
+      store_b128(u4v{__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])}, rs,
+                 voff[0], off, kSC1);
     } else {
       // lane 0 is valid for every c (KPL = ceil(k / 64)), so every store issues
 #pragma unroll
@@ -132,17 +120,13 @@ struct OnChunk {
   float r;
 };
 
+// The ticket hand-off, publish / poll_issue, on plain pointers ("none" is the wave's dummy word;
+// kernels_detsweep.hip's pair uses raw buffers); the rare blocking wait is poll_until (ticket_wait.hpp).
 __device__ __forceinline__ void publish(int32_t* t, int32_t v, int lane) {
   if (lane == 0) __hip_atomic_store(t, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 __device__ __forceinline__ int32_t poll_issue(const int32_t* t) {
   return __hip_atomic_load(t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  static_assert(N >= 0 && N < 64, "vmcnt range");
-  __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | 0x0F70 & ~0xF);
 }
 
 // One wave's updates.  UD: user rows prefetched UD updates ahead (guarded by the user's ticket);
@@ -165,7 +149,6 @@ __device__ __forceinline__ void online_wave(const int64_t jb, const int32_t cnt,
   // then PD-1 whole updates (publish, stores, loads, poll); SINGLE moves no item row per update
   constexpr int IO = SINGLE ? 0 : R::OPS;  // item-row operations per update (load, store)
   constexpr int NW = (R::OPS + IO + 1) + (PD - 1) * (1 + R::OPS + IO + R::OPS + IO + 1);
-  static_assert(NW < 64, "vmcnt range");
   const int lane = threadIdx.x;
   const R rows(lane, k);
   const __amdgpu_buffer_rsrc_t urs = raw_rsrc(U, u_bytes), irs = raw_rsrc(I, i_bytes);
@@ -182,7 +165,7 @@ __device__ __forceinline__ void online_wave(const int64_t jb, const int32_t cnt,
   auto fu = [&](int s) { return s < CH ? rl(C0.u, s) : rl(C1.u, s - CH); };
   auto fi = [&](int s) { return s < CH ? rl(C0.i, s) : rl(C1.i, s - CH); };
   auto fq = [&](int s) { return s < CH ? rl(C0.q, s) : rl(C1.q, s - CH); };
-  auto fr = [&](int s) { return __uint_as_float(s < CH ? rl(__float_as_uint(C0.r), s) : rl(__float_as_uint(C1.r), s - CH)); };
+  auto fr = [&](int s) { return s < CH ? rlf(C0.r, s) : rlf(C1.r, s - CH); };
 
   float P[UD][KPL], Q[2][KPL];
   int32_t okP[UD];  // the slot's user row was prefetched (its ticket was due)
@@ -194,17 +177,17 @@ __device__ __forceinline__ void online_wave(const int64_t jb, const int32_t cnt,
     const bool live = x < cnt;
     const uint32_t u = fu(x);
     okP[x] = !live || __builtin_amdgcn_readfirstlane(poll_issue(ticket + u)) == static_cast<int32_t>(fq(x));
-    rows.load(urs, live && okP[x] ? u * rowb : kOOB, P[x]);
+    rows.load(urs, live && okP[x] ? u * rowb : kOffOOB, P[x]);
   }
   if constexpr (SINGLE) {
     rows.load(irs, fi(0) * rowb, Q[0]);  // (every entry of the wave has this item)
   } else {
 #pragma unroll
-    for (int x = 0; x < 2; ++x) rows.load(irs, x < cnt && (x == 0 || fi(1) != fi(0)) ? fi(x) * rowb : kOOB, Q[x]);
+    for (int x = 0; x < 2; ++x) rows.load(irs, x < cnt && (x == 0 || fi(1) != fi(0)) ? fi(x) * rowb : kOffOOB, Q[x]);
   }
 #pragma unroll
   for (int x = 0; x < TD; ++x) tk[x] = poll_issue(x + UD < cnt ? ticket + fu(x + UD) : dummy_ticket);
-  __builtin_amdgcn_s_waitcnt(0x0F70);
+  wait_vmcnt<0>();
   int32_t* pend[PD];  // the tickets of updates j-PD .. j-1 (word, value), published PD updates late
   int32_t pv[PD];
 #pragma unroll
@@ -235,11 +218,11 @@ __device__ __forceinline__ void online_wave(const int64_t jb, const int32_t cnt,
     // 1. the user row, when its ticket was not due at prefetch time: publish the pending tickets
     //    (after their stores), wait for ours, load now
     if (!okP[us]) {
-      __builtin_amdgcn_s_waitcnt(0x0F70);
+      wait_vmcnt<0>();
       publish_all();
       wait_ticket_or_fail(ticket + u, qseq, err, lane);  // no early return (ticket_wait.hpp)
       rows.load(urs, u * rowb, P[us]);
-      __builtin_amdgcn_s_waitcnt(0x0F70);
+      wait_vmcnt<0>();
     }
     // 2. the item row: prefetched when the item changed, else the one in registers
     if constexpr (!SINGLE) {
@@ -270,16 +253,16 @@ __device__ __forceinline__ void online_wave(const int64_t jb, const int32_t cnt,
     rows.store(urs, u * rowb, p);
     if constexpr (!SINGLE) {
       const uint32_t i1 = fi(s + 1);
-      rows.store(irs, !live1 || i1 != i ? i * rowb : kOOB, q);
+      rows.store(irs, !live1 || i1 != i ? i * rowb : kOffOOB, q);
     }
     // 6. prefetch: update j+UD's user row into this user slot if its ticket (polled TD updates ago) is
     //    due -- every earlier update of that user, this wave's included, has landed -- and update
     //    j+2's item row if it starts another item's run
     const int32_t okN = !liveD || __builtin_amdgcn_readfirstlane(tk[ts]) == static_cast<int32_t>(qD);
-    rows.load(urs, liveD && okN ? uD * rowb : kOOB, P[us]);
+    rows.load(urs, liveD && okN ? uD * rowb : kOffOOB, P[us]);
     if constexpr (!SINGLE) {
       const uint32_t i1 = fi(s + 1), i2 = fi(s + 2);
-      rows.load(irs, live2 && i2 != i1 ? i2 * rowb : kOOB, Q[slot]);
+      rows.load(irs, live2 && i2 != i1 ? i2 * rowb : kOffOOB, Q[slot]);
     }
     okP[us] = okN;
     // 7. poll update j+UD+TD's ticket (read at j+TD)
@@ -302,7 +285,7 @@ __device__ __forceinline__ void online_wave(const int64_t jb, const int32_t cnt,
   }
 done:
   if constexpr (SINGLE) rows.store(irs, single_off, q);
-  __builtin_amdgcn_s_waitcnt(0x0F70);
+  wait_vmcnt<0>();
   publish_all();
 }
 

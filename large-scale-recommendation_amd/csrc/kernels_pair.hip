@@ -30,14 +30,12 @@
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
-#include <utility>
-
 #include "kernels.hpp"
+#include "pair_device.hpp"
 
 namespace mfhip {
 namespace {
-
-#include "pair_device.hpp"
+using namespace dev;
 
 // experiment: explicit agent-scope acquire / release around a launch (L2 invalidate / write-back)
 #ifdef MFHIP_EXP_FENCES
@@ -53,6 +51,17 @@ constexpr int kItemPolicy = kSC1;
 #else
 constexpr int kItemPolicy = 0;
 #endif
+
+// The wait after a cell's ring prefill.  Round 4 drained the prefill (vmcnt(0)): otherwise the loop
+// header inherited the preheader's "just loaded" ring rows and the compiler drained the ring at
+// every chunk boundary.  With the exit-free chunk loop (sweep_chunks) the header waits are the same
+// with or without it at KPL <= 2 (tools/isa_waits.py), so those cells start on their first pair's
+// rows instead of waiting for the whole ring (~56 loads issued back to back, ~0.25 us per cell);
+// KPL = 4 keeps it (without it its header waits turn conservative).
+template <int KPL>
+__device__ __forceinline__ void prefill_wait() {
+  if constexpr (KPL >= 4) wait_vmcnt<0>();
+}
 
 // A cell that is one item run (build_pair_plan): the item row stays in registers from the first
 // pair to the last, so a pair moves no item row, only user rows (4 VMEM operations).  B's user row
@@ -78,7 +87,7 @@ __device__ __forceinline__ void single_run_cell(Chunk C0, __amdgpu_buffer_rsrc_t
     RA[s] = ld<KPL, UP>(urs, voff, rl(C0.ua, s));
     RB[s] = ld<KPL, UP>(urs, voff, rl(C0.ub, s));
   }
-  if constexpr (KPL >= 4) drain_vmem();  // prefill_wait (pair_device.hpp)
+  prefill_wait<KPL>();
   const float neta = vgpr_of(-eta);
   ChunkRaw N{};  // the next chunk (sweep_chunks loads it when the current one starts)
   auto pair = [&](auto S) __attribute__((always_inline)) {
@@ -87,7 +96,7 @@ __device__ __forceinline__ void single_run_cell(Chunk C0, __amdgpu_buffer_rsrc_t
 #if defined(MFHIP_EXPERIMENTS) && defined(MFHIP_WAITPROBE)
     {  // experiment build: shader cycles spent waiting for this pair's prefetched user rows
       const uint64_t a = __builtin_amdgcn_s_memtime();
-      __builtin_amdgcn_s_waitcnt((4 * (DS - 1)) & 15 | (((4 * (DS - 1)) >> 4) << 14) | 0x0F70 & ~0xF);
+      wait_vmcnt<4 * (DS - 1)>();
       wait_clk += __builtin_amdgcn_s_memtime() - a;
     }
 #endif
@@ -169,7 +178,7 @@ __device__ __forceinline__ void single_run_cell_k1(Chunk C0, __amdgpu_buffer_rsr
     RA[s] = ld1<UP>(urs, voff, rl(C0.ua, s));
     RB[s] = ld1<UP>(urs, voff, rl(C0.ub, s));
   }
-  // no drain after the prefill (pair_device.hpp drain_vmem)
+  // KPL = 1: no wait after the prefill (prefill_wait)
   const float neta = vgpr_of(-eta);
   ChunkRaw N{};  // the next chunk (sweep_chunks loads it when the current one starts)
   auto pair = [&](auto S) __attribute__((always_inline)) {
@@ -225,7 +234,7 @@ __device__ __forceinline__ void generic_cell_k1(Chunk C0, __amdgpu_buffer_rsrc_t
     QA[s] = ld1<IP>(irs, voff, rl(C0.ia, s));
     QB[s] = ld1<IP>(irs, voff, rl(C0.ib, s));
   }
-  // no drain after the prefill (pair_device.hpp drain_vmem)
+  // KPL = 1: no wait after the prefill (prefill_wait)
   const float neta = vgpr_of(-eta);
   float q = 0.f;
   ChunkRaw N{};  // the next chunk (sweep_chunks loads it when the current one starts)
@@ -322,7 +331,7 @@ __device__ __forceinline__ void pair_cell(const WaveDesc d, const ChunkRaw& L0,
     } while (0)
 #pragma unroll
     for (int s = 0; s < D; ++s) MF_PREFETCH(s, C0.ua, C0.ub, C0.ia, C0.ib, s);
-    if constexpr (KPL >= 4) drain_vmem();  // prefill_wait (pair_device.hpp)
+    prefill_wait<KPL>();
     const float neta = vgpr_of(-eta);
     Row<KPL> q;
 #pragma unroll
@@ -335,7 +344,7 @@ __device__ __forceinline__ void pair_cell(const WaveDesc d, const ChunkRaw& L0,
 #if defined(MFHIP_EXPERIMENTS) && defined(MFHIP_WAITPROBE)
       {  // experiment build: shader cycles spent waiting for this pair's prefetched rows
         const uint64_t a = __builtin_amdgcn_s_memtime();
-        __builtin_amdgcn_s_waitcnt((8 * (D - 1)) & 15 | (((8 * (D - 1)) >> 4) << 14) | 0x0F70 & ~0xF);
+        wait_vmcnt<8 * (D - 1)>();
         wait_clk += __builtin_amdgcn_s_memtime() - a;
       }
 #endif
@@ -474,6 +483,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void
   uint32_t seen = base;  // the neighbour's progress as last read
   for (int t = 0; t < w.G; ++t) {
     const WaveDesc dn = my[t + 1 < w.G ? t + 1 : t];  // scalar load, used after this cell
+    // The systolic wait: the neighbour's progress word, monotonic across launches (compared modulo
+    // 2^32), skipped when `seen` already has it.  Not wait_flag (kernels_fast.hip: a per-launch
+    // word) nor the ticket waits (publish / poll_issue of the det and online sweeps, poll_until).
     if (t > 0 && w.G > 1 && static_cast<int32_t>(seen - (base + static_cast<uint32_t>(t))) < 0) {
       const uint32_t want = base + static_cast<uint32_t>(t);
       const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
@@ -502,9 +514,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void
     if (EARLY && t + 1 < w.G) early = __hip_atomic_load(nb_prog, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (PRE) {
       first_chunks(dn, L0);
-      __builtin_amdgcn_s_waitcnt(0x0F74);  // vmcnt(4): the 4 loads above may fly, every older store has landed
+      wait_vmcnt<4>();  // the 4 loads above may fly, every older store has landed
     } else {
-      __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): every user-row store of this wave has landed
+      wait_vmcnt<0>();  // every user-row store of this wave has landed
     }
     if (EARLY && t + 1 < w.G) seen = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(early)));
     if (lane == 0)

@@ -203,7 +203,7 @@ void choose_online_path(OnlineBatch& b) {
   const int k = b.k;
   if (b.n > 0 && !b.outs() && test_knob("online_kernel") != "level") {
     DeviceGuard g(b.s.device);
-    double limit = 4294963200.0;  // raw_rsrc's clamp (pair_device.hpp)
+    double limit = kSlabLimit;  // raw_rsrc's clamp
     if (const std::string v = test_knob("offset_limit"); !v.empty()) limit = std::stod(v);
     const auto fits = [&](int64_t rows, int eb) { return static_cast<double>(rows + b.n) * k * eb <= limit; };
     const bool det_online = ctx->f64 && test_knob("online_kernel") != "ticket" && online_det_capacity(k) > 0 &&
@@ -698,7 +698,7 @@ void block_update(mf_ctx* ctx, const double* r, const int32_t* uidx, const int32
     MF_HIP(hipStreamSynchronize(s.stream));  // ru / ri are released here
   }
   const int cap = det_split_capacity(k);
-  const bool sweep = cap >= 2 && test_knob("det_kernel") != "level" && ub < 0xFFFFF000ull && ib < 0xFFFFF000ull;
+  const bool sweep = cap >= 2 && test_knob("det_kernel") != "level" && ub < kSlabLimit && ib < kSlabLimit;
   int64_t levels = 0;
   if (!sweep) {
     block_update_levels(s, order, r, uidx, iidx, len, du, di, dru, dri, nu, ni, k, eta, levels);

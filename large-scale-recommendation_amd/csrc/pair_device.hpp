@@ -1,21 +1,17 @@
 // pair_device.hpp -- device helpers of the pair sweep (kernels_pair.hip):
 // wave reductions, raw-buffer row access, and the 64-B pair record chunks (plan.hpp PairRec).
-// Included inside namespace mfhip { namespace { ... } } of each kernel file.
 #pragma once
 
+#include <cstdint>
+#include <utility>
+
+#include "plan.hpp"
+#include "wave_device.hpp"
+
+namespace mfhip::dev {
+
 typedef float f2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u4v __attribute__((ext_vector_type(4)));
 typedef uint32_t u3v __attribute__((ext_vector_type(3)));
-
-__device__ __forceinline__ uint32_t rl(uint32_t v, int l) {
-  return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(v), l));
-}
-__device__ __forceinline__ float rlf(float v, int l) { return __uint_as_float(rl(__float_as_uint(v), l)); }
-
-template <int CTRL>
-__device__ __forceinline__ float dpp(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, false));
-}
 
 __device__ __forceinline__ float u2f(uint32_t v) { return __uint_as_float(v); }
 __device__ __forceinline__ uint32_t f2u(float v) { return __float_as_uint(v); }
@@ -40,11 +36,6 @@ __device__ __forceinline__ void wave_sum3(float& x, float& y, float& z) {
   y = rlf(s, 32);
 }
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t raw_rsrc(const void* base, uint64_t bytes) {
-  const uint32_t n = bytes > 0xFFFFF000ull ? 0xFFFFF000u : static_cast<uint32_t>(bytes);
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, n, 0x00020000);
-}
-
 // A lane holds floats [lane*KPL, (lane+1)*KPL) of a row, as NV float pairs.
 template <int KPL>
 struct Row {
@@ -52,11 +43,7 @@ struct Row {
   f2 v[NV];
 };
 
-// Cache policy of a row access: 0 = plain; kSC1 = sc1 (L1 bypass on loads, write-through and
-// dropped from the XCD's L2 on stores), used for user rows handed between waves of the
-// systolic sweep (MI355X_MICROARCH.md, inter-workgroup visibility, valid forms).
-constexpr int kSC1 = 16;
-
+// POL: the access's cache policy, 0 or kSC1 (user rows handed between waves of the systolic sweep)
 template <int KPL, int POL = 0>
 __device__ __forceinline__ Row<KPL> ld(__amdgpu_buffer_rsrc_t rs, uint32_t voff, uint32_t off) {
   Row<KPL> r;
@@ -76,36 +63,19 @@ __device__ __forceinline__ Row<KPL> ld(__amdgpu_buffer_rsrc_t rs, uint32_t voff,
   return r;
 }
 
-// A 16-B buffer store, then two wait states before its data VGPRs can be rewritten.  gfx950
-// reads a store's data after issuing it: a VALU that overwrites the data VGPRs right behind a
-// buffer_store_dwordx4 corrupts the stored row under load -- 1.2% of 16-B records with the offset
-// in an SGPR and no wait state, 1.5% with soffset 0 and one wait state, none with two
-// (tools/micro/store_data_hazard.hip, profiles/r05_store_data_hazard.txt).  LLVM pads one wait
-// state, and none at all when soffset is an SGPR (the table's exemption), so the round-4 k = 256
-// lean sweep, whose compiler reused the data VGPRs one or two instructions after the store, wrote
-// torn user rows: it did not repeat itself and biased RMSE by 0.27%.  The s_nop below takes the
-// data as operands, so no instruction can rewrite those VGPRs before it, and it is ordered after
-// the store (both have side effects).  tests/test_isa.py checks every wide store of the library.
-__device__ __forceinline__ void store_b128(u4v d, __amdgpu_buffer_rsrc_t rs, uint32_t voff, uint32_t off, int pol_sc1) {
-  if (pol_sc1) __builtin_amdgcn_raw_buffer_store_b128(d, rs, voff, off, 16);
-  else __builtin_amdgcn_raw_buffer_store_b128(d, rs, voff, off, 0);
-  asm volatile("s_nop 1" ::"v"(d[0]), "v"(d[1]), "v"(d[2]), "v"(d[3]));
-}
-
 template <int KPL, int POL = 0>
 __device__ __forceinline__ void st(__amdgpu_buffer_rsrc_t rs, uint32_t voff, uint32_t off, const Row<KPL>& r) {
   if constexpr (KPL == 1) {
     __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(r.v[0].x), rs, voff, off, POL);
   } else if constexpr (KPL == 2) {
-    using u2 = uint32_t __attribute__((ext_vector_type(2)));
-    __builtin_amdgcn_raw_buffer_store_b64(u2{__float_as_uint(r.v[0].x), __float_as_uint(r.v[0].y)}, rs, voff, off, POL);
+    __builtin_amdgcn_raw_buffer_store_b64(u2v{__float_as_uint(r.v[0].x), __float_as_uint(r.v[0].y)}, rs, voff, off, POL);
   } else {
-    static_assert(POL == 0 || POL == 16, "store policy");
+    static_assert(POL == 0 || POL == kSC1, "store policy");
 #pragma unroll
     for (int c = 0; c < KPL / 4; ++c)
       store_b128(u4v{__float_as_uint(r.v[2 * c].x), __float_as_uint(r.v[2 * c].y), __float_as_uint(r.v[2 * c + 1].x),
                      __float_as_uint(r.v[2 * c + 1].y)},
-                 rs, voff + 16u * c, off, POL == 16);
+                 rs, voff + 16u * c, off, POL);
   }
 }
 
@@ -135,15 +105,6 @@ struct Chunk {
 // chunk ahead and only converted (eta folded in) when it becomes current, so nothing reads a
 // just-loaded register at the chunk boundary and the factor-row ring keeps running across it
 // (converting at load time made every chunk boundary wait for its own record loads).
-// s_waitcnt vmcnt(0) the compiler can see (gfx9 encoding: expcnt 7, lgkmcnt 15).  Round 4 issued
-// it after a cell's ring prefill: otherwise the loop header inherited the preheader's "just loaded"
-// ring rows and the compiler drained the ring at every chunk boundary.  With the exit-free chunk
-// loop (sweep_chunks) the header waits are the same with or without it at KPL <= 2
-// (tools/isa_waits.py), so those cells start on their first pair's rows instead of waiting for the
-// whole ring (~56 loads issued back to back, ~0.25 us per cell); KPL = 4 keeps it (without it
-// its header waits turn conservative).
-__device__ __forceinline__ void drain_vmem() { __builtin_amdgcn_s_waitcnt(0x0F70); }
-
 struct ChunkRaw {
   u4v w0, w1, w2;
   u3v w3;  // the fourth word group's last word is unused: a 12-B load (no dead VGPR a load still writes)
@@ -250,3 +211,5 @@ __device__ __forceinline__ float vgpr_of(float x) {
   asm volatile("v_mov_b32 %0, %1" : "=v"(v) : "s"(x));
   return v;
 }
+
+}  // namespace mfhip::dev

@@ -242,7 +242,9 @@ struct FastPlan {
 
 // ---------------------------------------------------------------------------------------
 // Per-cell sweep launch table (kernels_pair.hip): one wave per cell.
-constexpr uint32_t kOffOOB = 0xFFFFF000u;  // a row byte offset past any slab: load 0 / no store
+// raw_rsrc's clamp (wave_device.hpp): a slab that does not fit takes a path with 64-bit addressing
+constexpr uint32_t kSlabLimit = 0xFFFFF000u;
+constexpr uint32_t kOffOOB = kSlabLimit;  // a row byte offset past any slab: load 0 / no store
 struct WaveDesc {
   int64_t base;   // first record
   int32_t steps;  // records

@@ -1,5 +1,5 @@
 // seq_fold.hpp -- the reference's sequential dot product (kernels_detsweep.hip,
-// k_online_sweep in kernels_det.hip).  Included inside namespace mfhip { namespace { ... } }.
+// k_online_sweep in kernels_det.hip).
 //
 // acc = ((0 + x0) + x1) + ... + x_{k-1} exactly as netlib F2jBLAS.ddot / Scala's foldLeft sum
 // (DSGDforMF.scala:405, core/FactorUpdater.scala:39), where lane l holds x_{l + 64c} in prod[c].
@@ -19,16 +19,14 @@
 // only keep the compiler from moving them.
 #pragma once
 
+#include "wave_device.hpp"
+
+namespace mfhip::dev {
+
 template <typename T>
 __device__ __forceinline__ T lane0_value(T v) {
-  if constexpr (sizeof(T) == 8) {
-    const unsigned long long b = static_cast<unsigned long long>(__double_as_longlong(v));
-    const unsigned lo = static_cast<unsigned>(__builtin_amdgcn_readlane(static_cast<int>(b & 0xffffffffu), 0));
-    const unsigned hi = static_cast<unsigned>(__builtin_amdgcn_readlane(static_cast<int>(b >> 32), 0));
-    return __longlong_as_double(static_cast<long long>((static_cast<unsigned long long>(hi) << 32) | lo));
-  } else {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0));
-  }
+  if constexpr (sizeof(T) == 8) return rld(v, 0);
+  else return rlf(v, 0);
 }
 
 // The same fold with no LDS round trip, for k == 64 * KPL.  A single wave issues at most one LDS
@@ -141,3 +139,5 @@ __device__ __forceinline__ T seq_fold(const T (&prod)[KPL], int k, T* lds, int l
   __builtin_amdgcn_wave_barrier();
   return LANE0 ? lane0_value(acc) : acc;
 }
+
+}  // namespace mfhip::dev

@@ -1,6 +1,7 @@
 // ticket_wait.hpp -- the rare blocking wait of the persistent ticket sweeps (k_det_sweep2 in
-// kernels_detsweep.hip, k_online_sweep in kernels_det.hip).  Included inside
-// namespace mfhip { namespace { ... } }.
+// kernels_detsweep.hip, k_online_sweep in kernels_det.hip, k_online_f32 in kernels_online_sweep.hip).
+// (Their usual hand-off is publish / poll_issue in their own files: a poll issued ahead and looked
+// at later, never blocking.  poll_until is what a wave falls back to when that poll missed.)
 //
 // The polling loop is one inline-asm block.  Written as a C++ loop (or as an out-of-line call), or
 // left with an early return on failure, it made the compiler's wait counts of EVERY step of the
@@ -9,6 +10,12 @@
 // callers therefore never return early: a wave that times out sets err and carries on, and every
 // later wait then sees err at once (the host refuses the context when err is set).
 #pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace mfhip::dev {
 
 // Poll *t until it equals want (returns 0), *err becomes non-zero (1) or ~2^20 polls pass (2,
 // ~1-2 s: a producer never ran).  Agent-scope relaxed loads (sc1); ends with vmcnt(0), so every
@@ -48,3 +55,5 @@ __device__ __forceinline__ void wait_ticket_or_fail(const int32_t* t, int32_t wa
   if (poll_until(t, want, err) == 2 && lane == 0)
     __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
+
+}  // namespace mfhip::dev

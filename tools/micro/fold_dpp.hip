@@ -11,12 +11,8 @@
 #include <random>
 #include <vector>
 
-namespace mfhip {
-namespace {
 #include "seq_fold.hpp"
-}  // namespace
-}  // namespace mfhip
-using namespace mfhip;
+using namespace mfhip::dev;
 
 template <typename T, int KPL, bool DPP>
 __global__ __launch_bounds__(64) void k_check(const T* x, T* out, int n) {
