@@ -40,6 +40,21 @@ int mf_debug_fast_split(const int32_t* users, const int32_t* items, int64_t n, i
    (DSGDforMF.scala:611-619) over ranks. */
 int mf_debug_ring_schedule(int32_t rank, int32_t world, int32_t n_blocks, int64_t superstep, int32_t* out_blk,
                            int32_t* in_blk, int32_t* dst, int32_t* src);
+/* mf_debug_det_slot_table: the split deterministic sweep's slot table (det_slot_table) for nw waves
+   {begin, count, flags} (flags bit 0: every entry of the wave updates one item), at most max_blocks
+   co-resident blocks of two slots, `alone` != 0: the longest single-item chains on CUs of their own,
+   blocks b and b + period sharing a CU.  The *_out arrays have room for 4 * nw + 4 slots;
+   *nslots_out = the slots written.  MF_ERR_INVALID when the work needs more than max_blocks blocks. */
+int mf_debug_det_slot_table(const int64_t* begin, const int32_t* count, const int32_t* flags, int64_t nw,
+                            int64_t max_blocks, int32_t alone, int64_t period, int64_t* begin_out, int32_t* count_out,
+                            int32_t* flags_out, int64_t* nslots_out);
+/* mf_debug_sys_placement: the block -> wave map of one systolic fast-sweep launch of nw waves with
+   modelled times load[0 .. nw), when `cap` blocks can be resident at once and the `iso` (0..8)
+   heaviest waves of every XCD are to be alone on their CUs: *pad_out = the empty blocks per XCD
+   (sys_iso_pad; 0 for iso = 0), place_out[b] = the wave of block b or -1 for an empty block, nw +
+   8 * *pad_out entries (room for nw + 24 * iso), checked to hold every wave exactly once. */
+int mf_debug_sys_placement(const double* load, int64_t nw, int64_t cap, int32_t iso, int32_t* pad_out,
+                           int32_t* place_out);
 /* mf_debug_plan_digest: after mf_dsgd_prepare of a fast-mode fit on one shard, an FNV-1a digest
    of the device schedule -- the pair records, the wave table and (systolic) the per-wave cell
    tables -- and the pair-record count: out[0] = digest, out[1] = records.  Compares the device-

@@ -1,6 +1,7 @@
 // abi.cpp -- the C ABI of libmfhip.so: every entry point of include/mfhip.h and
 // include/mfhip_testing.h, as a thin wrapper that checks its arguments and calls the feature's
-// function (mfhip.cpp, online.cpp, eval.cpp, als.cpp; declared in context.hpp) under `guarded`.
+// function (mfhip.cpp, dsgd_det.cpp, dsgd_fast.cpp, ring.cpp, online.cpp, eval.cpp, als.cpp, declared
+// in context.hpp; placement.cpp, declared in plan.hpp) under `guarded`.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -464,6 +465,41 @@ int mf_debug_ring_schedule(int32_t rank, int32_t world, int32_t n_blocks, int64_
     *in_blk = rs.in_blk;
     *dst = rs.dst;
     *src = rs.src;
+  });
+}
+
+int mf_debug_det_slot_table(const int64_t* begin, const int32_t* count, const int32_t* flags, int64_t nw,
+                            int64_t max_blocks, int32_t alone, int64_t period, int64_t* begin_out, int32_t* count_out,
+                            int32_t* flags_out, int64_t* nslots_out) {
+  return guarded([&] {
+    MF_REQUIRE(begin_out && count_out && flags_out && nslots_out && (nw == 0 || (begin && count && flags)),
+               "null argument");
+    MF_REQUIRE(nw >= 0 && nw <= (1 << 24) && max_blocks >= 1 && period >= 1, "bad slot table arguments");
+    std::vector<DetWave> waves(static_cast<size_t>(det_slot_room(nw)));
+    for (int64_t w = 0; w < nw; ++w) {
+      MF_REQUIRE(count[w] >= 0, "negative wave count");
+      waves[w] = DetWave{begin[w], count[w], flags[w]};
+    }
+    const int64_t n = det_slot_table(waves.data(), nw, max_blocks, alone != 0, period);
+    for (int64_t x = 0; x < n; ++x) {
+      begin_out[x] = waves[x].begin;
+      count_out[x] = waves[x].count;
+      flags_out[x] = waves[x].flags;
+    }
+    *nslots_out = n;
+  });
+}
+
+int mf_debug_sys_placement(const double* load, int64_t nw, int64_t cap, int32_t iso, int32_t* pad_out,
+                           int32_t* place_out) {
+  return guarded([&] {
+    MF_REQUIRE(load && pad_out && place_out, "null argument");
+    MF_REQUIRE(nw >= 1 && nw <= cap && cap <= (1 << 24) && iso >= 0 && iso <= 8,
+               "bad placement arguments (1 <= nw <= cap, iso in [0, 8])");
+    const int32_t pad = iso ? sys_iso_pad(nw, cap, iso) : 0;
+    place_by_load(load, nw, pad, place_out);
+    check_placement(place_out, nw + 8 * pad, nw);
+    *pad_out = pad;
   });
 }
 

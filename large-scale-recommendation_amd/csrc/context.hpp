@@ -1,6 +1,7 @@
 // context.hpp -- the context (mf_ctx), its shards, and the helpers more than one host translation
-// unit uses.  Private to the host side: included by the .cpp files only (mfhip.cpp, abi.cpp,
-// online.cpp, eval.cpp, als.cpp), never by a .hip file or by kernels.hpp / plan.hpp.
+// unit uses.  Private to the host side: included by the .cpp files only (mfhip.cpp, dsgd_det.cpp,
+// dsgd_fast.cpp, ring.cpp, abi.cpp, online.cpp, eval.cpp, als.cpp), never by a .hip file or by
+// kernels.hpp / plan.hpp; placement.cpp, which knows no context, does without it.
 #pragma once
 
 #include <array>
@@ -216,6 +217,13 @@ enum class FastKernel { kPair, kCell, kPersistent };
 
 inline SideLayout& side_of(mf_ctx* ctx, int side) { return side == kSideU ? ctx->U : ctx->I; }
 
+// The rating block that user block j of a shard runs in the supersteps with (s - 1) mod n == sm:
+// (p, (p + sm) mod n) as a rating block id (toRatingBlockId, DSGDforMF.scala:597-601).
+inline int64_t rating_block_of(const mf_ctx* ctx, int shard_index, int64_t sm, int32_t j) {
+  const int32_t p = shard_index * ctx->c + j;
+  return static_cast<int64_t>(p) * ctx->nb + (p + sm) % ctx->nb;
+}
+
 // ---------------------------------------------------------------------------------------
 // profiling: a pair of HIP events around every sweep-kernel launch on the shard's stream.
 // ext = true: the launch records the pair itself (hipExtLaunchKernel start/stop events, part
@@ -269,13 +277,10 @@ struct EvalOut {
   double sse = 0, cnt = 0, risk = 0;
 };
 
-// mfhip.cpp: context lifetime, slabs, health, the DSGD driver
+// mfhip.cpp: context lifetime, slabs, health, model construction, the top of the DSGD driver
 mf_ctx* create_ctx(const mf_params* p, const int* device_ids, int n_devices);
 mf_ctx* create_rank_ctx(const mf_params* p, int device_id, int nranks, int rank, const uint8_t* uid);
 void destroy_ctx(mf_ctx* ctx);
-bool want_pair_sys();
-FastKernel choose_fast_kernel(int k);
-int32_t plan_window(int32_t k);
 double bytes_per_update(const mf_ctx* ctx);
 void ensure_rows(mf_ctx* ctx, Shard& s, int side, int64_t rows);
 void upload_rows(mf_ctx* ctx, Shard& s, int side, int64_t row0, const double* src, int64_t n);
@@ -283,24 +288,38 @@ void upload_regs(mf_ctx* ctx, Shard& s, int side, int64_t row0, const double* sr
 void download_rows(mf_ctx* ctx, Shard& s, int side, int64_t row0, int64_t n, double* out);
 void init_vectors(const int32_t* ids, int64_t n, int k, bool xor_seed, int64_t seed, std::vector<double>& out);
 void init_factors(mf_ctx* ctx);
-void det_spec_wait(mf_ctx* ctx, bool invalidate);
 void sync_all(mf_ctx* ctx);
 void require_healthy(const mf_ctx* ctx);
 void ensure_order(mf_ctx* ctx);
-void consolidate(mf_ctx* ctx, Shard& dst);
 int32_t online_row(mf_ctx* ctx, SideLayout& S, int32_t id, std::vector<int32_t>& fresh);
-int64_t device_cu_count(int dev);
-int64_t det_slot_room(int64_t nw);
-int64_t det_slot_table(DetWave* waves, int64_t nw, int64_t max_blocks, bool alone, int64_t period);
-RingStep ring_step(int32_t g, int32_t G, int32_t c, int32_t n, int64_t superstep);
-void reset_item_loc(mf_ctx* ctx);
 void prepare(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n);
 void run_supersteps(mf_ctx* ctx, int64_t count);
 void debug_levels(const uint32_t* urow, const uint32_t* irow, const int32_t* order, int64_t n, int32_t* level_out);
+
+// dsgd_det.cpp: deterministic supersteps (level launches; the persistent sweep and its builds)
+void prepare_det_sweep(mf_ctx* ctx);
+void det_superstep(mf_ctx* ctx, Shard& s, int64_t superstep, double eta);
+void det_run(mf_ctx* ctx, int64_t count);
+void det_spec_wait(mf_ctx* ctx, bool invalidate);
+int64_t device_cu_count(int dev);
+
+// dsgd_fast.cpp: fast supersteps (the four launch shapes, their schedules and device tables)
+bool want_pair_sys();
+FastKernel choose_fast_kernel(int k);
+int32_t plan_window(int32_t k);
+void prepare_fast(mf_ctx* ctx, DevRatingBlocks& dev_rb, PhaseClock& clk, int32_t lo, int32_t hi);
+void fast_superstep(mf_ctx* ctx, Shard& s, int64_t superstep, double eta);
+void dump_wave_trace(mf_ctx* ctx);
 int debug_fast_plan(const int32_t* u, const int32_t* i, int64_t n, int32_t n_blocks, int64_t seed, int32_t groups,
                     int32_t blocking, int32_t window, int32_t k, int32_t item_split, int32_t* block_out, int32_t* substep_out, int32_t* group_out, int64_t* pos_out,
                     int32_t* replica_out);
 void plan_digest(mf_ctx* ctx, uint64_t out[2]);
+
+// ring.cpp: the item-block ring between shards
+RingStep ring_step(int32_t g, int32_t G, int32_t c, int32_t n, int64_t superstep);
+void ring_shift(mf_ctx* ctx, int64_t superstep);
+void reset_item_loc(mf_ctx* ctx);
+void consolidate(mf_ctx* ctx, Shard& dst);
 
 // online.cpp
 void online_update(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n, int flavour,

@@ -182,8 +182,8 @@ void launch_sweep_pair(hipStream_t st, const WaveDesc* waves, int nwaves, const 
 // [2*(cell index in sys)].
 int sweep_pair_sys_capacity(int k);
 // lbase: index of sw[0] among the superstep's waves (a superstep may be split over two launches,
-// see mfhip.cpp ring overlap); prog and SysWave::nbr count from the superstep's first wave.
-// place (may be null): block b of the launch sweeps wave sw[place[b]] (sys_placement, mfhip.cpp);
+// see dsgd_fast.cpp ring overlap); prog and SysWave::nbr count from the superstep's first wave.
+// place (may be null): block b of the launch sweeps wave sw[place[b]] (sys_placement, placement.cpp);
 // null: the XCD-contiguous map.
 void launch_sweep_pair_sys(hipStream_t st, const SysWave* sw, const WaveDesc* sys, int nw, int lbase,
                            const PairRec* recs, float* U, float* I, uint64_t u_bytes, uint64_t i_bytes, int k, float eta,

@@ -5,7 +5,7 @@
 // (g+t) mod G).  Cells of one sub-step share no user or item row (conflict-free batching).
 //
 // This file sweeps every rank the pair kernels (kernels_pair.hip: k = 64, 128, 256) do not take,
-// and those three with MFHIP_TEST fast_kernel=cell (mfhip.cpp choose_fast_kernel).
+// and those three with MFHIP_TEST fast_kernel=cell (dsgd_fast.cpp choose_fast_kernel).
 //
 // Two drivers of the same schedule (identical results, bit for bit:
 // tests/test_gpu_fast_cell.py test_persistent_driver_equals_cell):

@@ -345,7 +345,7 @@ struct PairPlan {
   std::vector<double> sm_bytes;  // per superstep index: bytes the sweep requests (records + in-range rows)
 };
 // The plan window must be >= 2 * pair_ring(pair_kpl(k)) records (pair_window(k) is; the knob
-// MFHIP_TEST pair_window=N is clamped to it, mfhip.cpp plan_window).  substep_waves: order the cells (and
+// MFHIP_TEST pair_window=N is clamped to it, dsgd_fast.cpp plan_window).  substep_waves: order the cells (and
 // pp.waves / sub_off) per sub-step (sm, t), longest first, for the per-sub-step launches (needs a
 // uniform G); otherwise per superstep, and only the systolic tables are meaningful.
 // cell_pairs (tables only): the pair count of every cell, indexed like fp.cell_off; the records
@@ -400,5 +400,21 @@ std::vector<int32_t> choose_block_groups(const RatingBlocks& rb, const SideLayou
 std::vector<int32_t> choose_block_groups(const std::vector<int64_t>& size, const std::vector<int64_t>& top, int32_t nb,
                                          int32_t c, int32_t shard, int32_t waves, double cell_ns = kSysCellNs,
                                          double run_ns = kSysRunPairNs);
+
+// ---------------------------------------------------------------------------------------
+// placement.cpp: the persistent sweeps' launch tables, pure host functions (no device, no context).
+// The split deterministic sweep's slot table, in place over waves[0 .. nw) (room for
+// det_slot_room(nw) slots); returns the slot count.
+int64_t det_slot_room(int64_t nw);
+int64_t det_slot_table(DetWave* waves, int64_t nw, int64_t max_blocks, bool alone, int64_t period);
+// The systolic fast sweep's block -> wave maps: the load model, one launch's map from its waves'
+// loads (nw + 8 pad entries, -1 = an empty block), the empty blocks per XCD that isolate each XCD's
+// `iso` heaviest waves, the permutation check of one launch's map, and the whole table of a shard.
+double sys_wave_load(const PairPlan& pp, int64_t w);
+void place_by_load(const double* load, int64_t nw, int32_t pad, int32_t* place);
+int32_t sys_iso_pad(int64_t nw, int64_t cap, int32_t iso);
+void check_placement(const int32_t* place, int64_t len, int64_t waves);
+void sys_placement(const PairPlan& pp, int32_t nb, int32_t c, bool ring_overlap, int32_t iso, int64_t sys_cap,
+                   std::vector<int32_t>& place, std::vector<int64_t>& off, std::vector<int32_t>& pad);
 
 }  // namespace mfhip

@@ -106,6 +106,7 @@ TESTING_EXPORTS = [
     "mf_debug_levels", "mf_debug_fast_schedule", "mf_debug_fast_split", "mf_debug_ring_schedule",
     "mf_debug_plan_digest", "mf_fast_plan_window", "mf_fast_kernel_name", "mf_debug_build_flags",
     "mf_debug_device_bytes", "mf_debug_als_normal_eq", "mf_debug_als_gram", "mf_debug_als_normal_eq_implicit",
+    "mf_debug_det_slot_table", "mf_debug_sys_placement",
 ]
 
 _i32p = C.POINTER(C.c_int32)
@@ -187,6 +188,9 @@ def lib() -> C.CDLL:
         "mf_debug_als_normal_eq_implicit": (C.c_int, [_ctxp, C.c_int, C.c_int32, C.c_double, C.c_int32, C.c_double,
                                                       _f64p, _f64p]),
         "mf_debug_ring_schedule": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, _i32p, _i32p, _i32p, _i32p]),
+        "mf_debug_det_slot_table": (C.c_int, [_i64p, _i32p, _i32p, C.c_int64, C.c_int64, C.c_int32, C.c_int64, _i64p,
+                                              _i32p, _i32p, _i64p]),
+        "mf_debug_sys_placement": (C.c_int, [_f64p, C.c_int64, C.c_int64, C.c_int32, _i32p, _i32p]),
         "mf_debug_plan_digest": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
         "mf_debug_build_flags": (C.c_int32, []),
         "mf_debug_device_bytes": (C.c_int, [_i64p]),

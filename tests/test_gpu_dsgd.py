@@ -146,7 +146,7 @@ def test_staged_run_and_resume_equal_one_shot():
 
 
 def test_staged_runs_take_over_prebuilt_supersteps():
-    """A deterministic run builds the next run's first supersteps ahead (mfhip.cpp det_run): staged runs of
+    """A deterministic run builds the next run's first supersteps ahead (dsgd_det.cpp det_run): staged runs of
     1-3 supersteps each take them over, a restart or a factor upload drops them, and every path equals the
     oracle's one-shot fit bit for bit."""
     d = synth.generate(300, 150, 8000, seed=2)

@@ -1,6 +1,6 @@
 """Item-block rotation between ranks, checked on CPU with gloo.
 
-mfhip's rank mode (csrc/mfhip.cpp ring_shift) moves item blocks with RCCL send/recv after every
+mfhip's rank mode (csrc/ring.cpp ring_shift) moves item blocks with RCCL send/recv after every
 superstep: rank g owns user blocks g*c .. g*c+c-1 (n = c * world), sends item block
 (g*c + s - 1) mod n to rank g-1 and receives ((g+1)*c + s - 1) mod n from rank g+1 -- the
 reference's nextRatingBlock (DSGDforMF.scala:611-619).  RCCL cannot run two ranks on the one
