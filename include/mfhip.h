@@ -206,6 +206,61 @@ int mf_recommend(mf_ctx* ctx, int query_side, const int32_t* queries, int64_t n_
                  const int32_t* excl_query, const int32_t* excl_cand, int64_t n_excl,
                  int32_t* ids_out, double* scores_out, int32_t* counts_out);
 
+/* RankingMetrics (precisionAt, meanAveragePrecision, ndcgAt) of MLlib, for the models ALS.train builds
+   (sp/OnlineSpark.scala:125-131), plus recall, reciprocal rank and hit rate: held-out (query,
+   candidate) pairs against the model's top-N lists, on the device.  The pair tables are built, the
+   lists scored and selected, the per-query metrics taken and summed there; only the metrics cross to
+   the host.
+   Evaluated queries.  The distinct ids of gt_query[] the model holds on query_side.  Each has its
+   ground-truth set G = the distinct gt_cand ids paired with it, g = |G| >= 1.  A ground-truth
+   candidate the model does not hold still counts in G (it can never be hit); duplicate pairs count
+   once.  Distinct unknown query ids are counted in unknown_queries and take no part in the means.
+   Lists.  The list L of a query is exactly what mf_recommend(ctx, query_side, that id, top_n,
+   excl_query, excl_cand, n_excl, ...) returns: the same scores, the same order (score descending,
+   ties by id ascending, NaN last), the same exclusion rules, count c <= N = top_n.  A pair that is
+   both excluded and in G stays in G and is never hit.
+   Per query, with h_i = [L_i in G] for i = 0 .. c-1, in f64, every sum taken sequentially over
+   ascending i:
+     hits      = sum h_i
+     precision = hits / N            (N even when c < N, as MLlib's precisionAt)
+     recall    = hits / g
+     ap        = (sum over hit positions i of cnt_i / (i + 1)) / g, cnt_i = hits up to and including i
+                 (MLlib 2.2's meanAveragePrecision applied to the N-list)
+     ndcg      = dcg / idcg, gain_i = 1 / log(i + 2) (natural log), dcg = sum_{h_i} gain_i,
+                 idcg = sum_{i < min(g, N)} gain_i  (MLlib's ndcgAt reduces to this)
+     rr        = 1 / (position of the first hit + 1), 0 with no hit
+     hit       = 1.0 if hits > 0 else 0.0
+   The 128 gains and their 129 prefix sums are computed once on the host with libm's log and uploaded;
+   no device log is called, so a host replay with the same libm matches bit for bit.
+   Aggregates.  Each mean is (sum over the evaluated queries) / queries; queries == 0 gives all zeros,
+   not NaN.  The sums are taken in a fixed order: the per-query values in ascending factor-row order of
+   the queries, in slices of 1024 with a fixed pairwise tree inside a slice, the slices added in
+   ascending order; no floating-point atomics.  Results are bitwise reproducible from run to run and do
+   not depend on how the queries are batched or the candidates split.
+   Per-query outputs (optional: all three pointers NULL, or all given, with room for cap rows): rows in
+   ascending query id; q_ids_out[cap], q_counts_out[cap][2] = (hits, g),
+   q_metrics_out[cap][MF_RANK_NMETRICS] = precision, recall, ap, ndcg, rr, hit.  cap < queries returns
+   MF_ERR_CAPACITY with the needed count in out->queries and in the message.
+   Errors.  MF_ERR_INVALID: NULL ctx or out, a bad side, top_n outside 1 .. MF_RECOMMEND_MAX_TOP, a
+   negative count, a NULL array with a positive count, some but not all per-query pointers.
+   MF_ERR_NOT_FITTED before a model exists; MF_ERR_STATE on a rank-mode context, as mf_recommend.
+   n_gt == 0 is valid and gives all zeros.  A context on several devices evaluates on its first. */
+typedef struct mf_rank_metrics {
+  int64_t queries;          /* evaluated queries */
+  int64_t unknown_queries;  /* distinct ground-truth query ids the model does not hold */
+  int64_t gt_pairs;         /* distinct ground-truth pairs of the evaluated queries */
+  int64_t hits;             /* ground-truth candidates found in the top-N lists */
+  double precision, recall, map, ndcg, mrr, hit_rate;   /* means over `queries` */
+  double reserved[6];
+} mf_rank_metrics;
+#define MF_RANK_NMETRICS 6   /* precision, recall, ap, ndcg, rr, hit -- per-query row layout */
+int mf_rank_eval(mf_ctx* ctx, int query_side,
+                 const int32_t* gt_query, const int32_t* gt_cand, int64_t n_gt,
+                 int32_t top_n,
+                 const int32_t* excl_query, const int32_t* excl_cand, int64_t n_excl,
+                 mf_rank_metrics* out,
+                 int32_t* q_ids_out, int32_t* q_counts_out, double* q_metrics_out, int64_t cap);
+
 /* ALS.train(ratings, rank = params.num_factors, iterations, lambda), the "ALS" branch of
    OnlineSpark.buildModelCombineOffline (sp/OnlineSpark.scala:125-131), as alternating least squares
    on the device.  mf_als_prepare keeps the ratings on the device as one CSR per side (the ratings of

@@ -87,6 +87,17 @@ int mf_debug_als_normal_eq(mf_ctx* ctx, int side, int32_t id, double lambda, int
 int mf_debug_als_gram(mf_ctx* ctx, int side, double* G_out);
 int mf_debug_als_normal_eq_implicit(mf_ctx* ctx, int side, int32_t id, double lambda, int32_t reg, double alpha,
                                     double* A_out, double* b_out);
+/* mf_debug_rank_csr: the pair table mf_rank_eval builds on the device for one pair list, copied back.
+   The evaluated queries are the distinct ids of query[] the model holds on query_side, in ascending
+   factor-row order: q_ids_out[*nq_out].  off_out[*nq_out + 1] and entries_out[*ne_out] are the table:
+   per query its distinct entries, ascending.  ground_truth = 0, the exclusion table: an entry is the
+   candidate's factor row (what the selection kernels read), pairs with an unknown candidate are
+   dropped.  ground_truth = 1: an entry is the candidate id, unknown candidates kept.  *nq_out and
+   *ne_out are always set; MF_ERR_CAPACITY when cap_q < *nq_out or cap_e < *ne_out (nothing else is
+   written then). */
+int mf_debug_rank_csr(mf_ctx* ctx, int query_side, int ground_truth, const int32_t* query, const int32_t* cand,
+                      int64_t n, int32_t* q_ids_out, int64_t* off_out, int32_t* entries_out, int64_t cap_q,
+                      int64_t cap_e, int64_t* nq_out, int64_t* ne_out);
 
 #ifdef __cplusplus
 }

@@ -54,6 +54,11 @@ public final class MfHip {
   public static native void recommend(long ctx, int querySide, int[] queries, int topN,
                                       int[] exclQuery, int[] exclCand,
                                       int[] idsOut, double[] scoresOut, int[] countsOut);
+  // RankingMetrics of held-out (query, candidate) pairs against the model's topN lists (mf_rank_eval),
+  // taken on the device.  metricsOut (length >= 8) receives queries, hits, precision, recall, MAP, NDCG,
+  // MRR, hit rate; exclQuery / exclCand as for recommend
+  public static native void rankEval(long ctx, int querySide, int[] gtQuery, int[] gtCand, int topN,
+                                     int[] exclQuery, int[] exclCand, double[] metricsOut);
   public static native void blockUpdate(long ctx, double[] r, int[] uidx, int[] iidx,
                                         double[] users, int[] uomega, double[] items, int[] iomega,
                                         int k, int iteration, int ratingBlockId, long seed,

@@ -311,6 +311,47 @@ JNIEXPORT void JNICALL JFN(recommend)(JNIEnv* env, jclass c, jlong h, jint side,
   check(env, st);
 }
 
+JNIEXPORT void JNICALL JFN(rankEval)(JNIEnv* env, jclass c, jlong h, jint side, jintArray gq, jintArray gc, jint top,
+                                     jintArray xq, jintArray xc, jdoubleArray metrics) {
+  if (require(env, gq && gc && len(env, gq) == len(env, gc), "gtQuery and gtCand must match in length")) return;
+  if (require(env, metrics && len(env, metrics) >= 8, "metricsOut must hold 8 entries")) return;
+  if (require(env, top >= 1 && top <= MF_RECOMMEND_MAX_TOP, "topN out of range")) return;
+  if (require(env, (!xq && !xc) || (xq && xc && len(env, xq) == len(env, xc)),
+              "exclQuery and exclCand must both be null or match in length"))
+    return;
+  const jsize ng = len(env, gq), ne = xq ? len(env, xq) : 0;
+  Elems eq = {0}, ec = {0}, exq = {0}, exc = {0}, em = {0};
+  if (acquire(env, &eq, gq, kInt) || acquire(env, &ec, gc, kInt) || acquire(env, &exq, xq, kInt) ||
+      acquire(env, &exc, xc, kInt) || acquire(env, &em, metrics, kDouble)) {
+    release(env, &exc, JNI_ABORT);
+    release(env, &exq, JNI_ABORT);
+    release(env, &ec, JNI_ABORT);
+    release(env, &eq, JNI_ABORT);
+    return;
+  }
+  mf_rank_metrics m;
+  int st = mf_rank_eval(CTX(h), side, ng ? (const int32_t*)eq.p : NULL, ng ? (const int32_t*)ec.p : NULL, ng, top,
+                        ne ? (const int32_t*)exq.p : NULL, ne ? (const int32_t*)exc.p : NULL, ne, &m, NULL, NULL, NULL,
+                        0);
+  if (st == MF_OK) {
+    double* o = (double*)em.p;
+    o[0] = (double)m.queries;
+    o[1] = (double)m.hits;
+    o[2] = m.precision;
+    o[3] = m.recall;
+    o[4] = m.map;
+    o[5] = m.ndcg;
+    o[6] = m.mrr;
+    o[7] = m.hit_rate;
+  }
+  release(env, &em, st == MF_OK ? 0 : JNI_ABORT);
+  release(env, &exc, JNI_ABORT);
+  release(env, &exq, JNI_ABORT);
+  release(env, &ec, JNI_ABORT);
+  release(env, &eq, JNI_ABORT);
+  check(env, st);
+}
+
 typedef int (*eval_fn)(JNIEnv*, jlong, const int32_t*, const int32_t*, const double*, jsize, jdouble, double*);
 
 static int call_rmse(JNIEnv* env, jlong h, const int32_t* u, const int32_t* i, const double* r, jsize n, jdouble unused,

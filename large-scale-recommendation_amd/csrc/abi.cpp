@@ -1,7 +1,7 @@
 // abi.cpp -- the C ABI of libmfhip.so: every entry point of include/mfhip.h and
 // include/mfhip_testing.h, as a thin wrapper that checks its arguments and calls the feature's
-// function (mfhip.cpp, dsgd_det.cpp, dsgd_fast.cpp, ring.cpp, online.cpp, eval.cpp, als.cpp, declared
-// in context.hpp; placement.cpp, declared in plan.hpp) under `guarded`.
+// function (mfhip.cpp, dsgd_det.cpp, dsgd_fast.cpp, ring.cpp, online.cpp, eval.cpp, rank_eval.cpp, als.cpp,
+// declared in context.hpp; placement.cpp, declared in plan.hpp) under `guarded`.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -239,6 +239,56 @@ int mf_recommend(mf_ctx* ctx, int query_side, const int32_t* queries, int64_t n_
     MF_REQUIRE(queries && ids_out && counts_out, "null argument");
     recommend(ctx, query_side, queries, n_queries, top_n, excl_query, excl_cand, n_excl, ids_out, scores_out,
               counts_out);
+  });
+}
+
+namespace {
+// the checks mf_rank_eval and its testing hook share with mf_recommend
+void rank_check(mf_ctx* ctx, int query_side, const char* who) {
+  MF_REQUIRE(ctx, "null context");
+  MF_REQUIRE(query_side == MF_SIDE_USER || query_side == MF_SIDE_ITEM, "bad side");
+  if (ctx->rank_mode)
+    fail(MF_ERR_STATE, std::string(who) + " runs on a single-process context; a rank-mode context (mf_create_rank) "
+                                          "holds only its own users' rows");
+  if (!ctx->have_model)
+    fail(MF_ERR_NOT_FITTED, "The MatrixFactorization model has not been fitted to data. "
+                            "Prior to predicting values, it has to be trained on data.");
+  require_healthy(ctx);
+}
+}  // namespace
+
+int mf_rank_eval(mf_ctx* ctx, int query_side, const int32_t* gt_query, const int32_t* gt_cand, int64_t n_gt,
+                 int32_t top_n, const int32_t* excl_query, const int32_t* excl_cand, int64_t n_excl,
+                 mf_rank_metrics* out, int32_t* q_ids_out, int32_t* q_counts_out, double* q_metrics_out, int64_t cap) {
+  return guarded([&] {
+    MF_REQUIRE(ctx, "null context");
+    MF_REQUIRE(out, "out is null");
+    MF_REQUIRE(query_side == MF_SIDE_USER || query_side == MF_SIDE_ITEM, "bad side");
+    MF_REQUIRE(top_n >= 1 && top_n <= MF_RECOMMEND_MAX_TOP,
+               "top_n must be in [1, " + std::to_string(MF_RECOMMEND_MAX_TOP) + "]");
+    MF_REQUIRE(n_gt >= 0 && n_excl >= 0, "negative count");
+    MF_REQUIRE(n_gt == 0 || (gt_query && gt_cand), "null ground-truth list");
+    MF_REQUIRE(n_excl == 0 || (excl_query && excl_cand), "null exclusion list");
+    const int given = (q_ids_out != nullptr) + (q_counts_out != nullptr) + (q_metrics_out != nullptr);
+    MF_REQUIRE(given == 0 || given == 3, "per-query outputs: give all three arrays or none");
+    MF_REQUIRE(given == 0 || cap >= 0, "negative count");
+    rank_check(ctx, query_side, "mf_rank_eval");
+    rank_eval(ctx, query_side, gt_query, gt_cand, n_gt, top_n, excl_query, excl_cand, n_excl, out, q_ids_out,
+              q_counts_out, q_metrics_out, cap);
+  });
+}
+
+int mf_debug_rank_csr(mf_ctx* ctx, int query_side, int ground_truth, const int32_t* query, const int32_t* cand,
+                      int64_t n, int32_t* q_ids_out, int64_t* off_out, int32_t* entries_out, int64_t cap_q,
+                      int64_t cap_e, int64_t* nq_out, int64_t* ne_out) {
+  return guarded([&] {
+    MF_REQUIRE(ctx, "null context");
+    MF_REQUIRE(nq_out && ne_out && q_ids_out && off_out && entries_out, "null argument");
+    MF_REQUIRE(n >= 0 && cap_q >= 0 && cap_e >= 0, "negative count");
+    MF_REQUIRE(n == 0 || (query && cand), "null pair list");
+    rank_check(ctx, query_side, "mf_debug_rank_csr");
+    debug_rank_csr(ctx, query_side, ground_truth != 0, query, cand, n, q_ids_out, off_out, entries_out, cap_q, cap_e,
+                   nq_out, ne_out);
   });
 }
 

@@ -151,6 +151,13 @@ struct DetBuildScratch {
   size_t tmp_bytes = 0, tmp2_bytes = 0;
 };
 
+// Device scratch of the pair tables of mf_rank_eval (kernels_rank.hip): per query-side row its flag
+// and position among the evaluated queries (kept from rank_query_set for the rank_pair_csr calls that
+// follow it), and one pair list's keys, run heads and write positions.
+struct RankScratch {
+  DevBuf flag, pos, key, key2, head, wp, tmp;
+};
+
 // Pinned host staging buffer.
 class PinnedBuf {
  public:
@@ -177,7 +184,7 @@ class PinnedBuf {
 
 // Runtime switches.  The library reads five environment variables:
 //   MFHIP_THREADS / OMP_NUM_THREADS  host workers (below);
-//   MFHIP_TIMING                     prepare's phase timings on stderr;
+//   MFHIP_TIMING                     prepare's and mf_rank_eval's phase timings on stderr;
 //   MFHIP_DEBUG_PLAN                 planner diagnostics and the sweeps' error words on stderr;
 //   MFHIP_DEVICE_SHARERS             rank mode: ranks sharing one device (the one-GPU ring rehearsal);
 //   MFHIP_TEST                       "key=value,..." overrides the test suite uses to force the

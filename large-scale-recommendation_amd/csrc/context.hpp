@@ -1,6 +1,6 @@
 // context.hpp -- the context (mf_ctx), its shards, and the helpers more than one host translation
 // unit uses.  Private to the host side: included by the .cpp files only (mfhip.cpp, dsgd_det.cpp,
-// dsgd_fast.cpp, ring.cpp, abi.cpp, online.cpp, eval.cpp, als.cpp), never by a .hip file or by
+// dsgd_fast.cpp, ring.cpp, abi.cpp, online.cpp, eval.cpp, rank_eval.cpp, als.cpp), never by a .hip file or by
 // kernels.hpp / plan.hpp; placement.cpp, which knows no context, does without it.
 #pragma once
 
@@ -128,6 +128,11 @@ struct Shard {
   DevBuf rec_id[2];
   uint64_t rec_id_gen[2] = {0, 0};
   DevBuf rec_q, rec_eoff, rec_erows, rec_part, rec_ids, rec_scores, rec_counts;
+  // ranking metrics (mf_rank_eval, which also uses the rec_* buffers): the table build's scratch, a pair
+  // list as uploaded (query rows, then candidate rows or ids), the ground-truth CSR, the per-query
+  // metrics and (hits, g), the slice sums, the gain table and the call's totals
+  RankScratch rank_sc;
+  DevBuf rk_in, rk_goff, rk_gent, rk_met, rk_cnt, rk_part, rk_tab, rk_res;
   // ALS (mf_als_prepare): per solved side [user, item] the CSR (counterpart rows, ratings) and the
   // work lists; the long rows' partial systems of one launch; the testing hook's output
   DevBuf als_cols[2], als_vals[2], als_items[2], als_splits[2], als_part, als_dump;
@@ -338,6 +343,14 @@ void recommend(mf_ctx* ctx, int qside, const int32_t* queries, int64_t nq, int32
                const int32_t* ec, int64_t ne, int32_t* ids_out, double* scores_out, int32_t* counts_out);
 void get_factors(mf_ctx* ctx, int side, int32_t* ids, double* vecs, int64_t cap, int64_t* written);
 void lookup_factors(mf_ctx* ctx, int side, const int32_t* ids, int64_t n, double* vecs_out, uint8_t* found);
+
+// rank_eval.cpp
+void rank_eval(mf_ctx* ctx, int qside, const int32_t* gq, const int32_t* gc, int64_t ng, int32_t top_n,
+               const int32_t* eq, const int32_t* ec, int64_t ne, mf_rank_metrics* out, int32_t* q_ids_out,
+               int32_t* q_counts_out, double* q_metrics_out, int64_t cap);
+void debug_rank_csr(mf_ctx* ctx, int qside, bool gt, const int32_t* q, const int32_t* c, int64_t n, int32_t* q_ids_out,
+                    int64_t* off_out, int32_t* entries_out, int64_t cap_q, int64_t cap_e, int64_t* nq_out,
+                    int64_t* ne_out);
 
 // als.cpp
 void als_check(const mf_ctx* ctx);

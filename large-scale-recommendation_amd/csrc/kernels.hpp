@@ -237,12 +237,40 @@ void device_fast_schedule(hipStream_t st, const DevRatingBlocks& dr, const Ratin
 // the fmaf chain over f = 0..k-1 on the f32-input MFMA.  cand_id: row -> id of the candidate side.
 // excl_off (nq + 1) / excl_rows: per query the sorted candidate rows never returned.  The candidate
 // rows are walked in S <= 64 splits; part: nq * S * top_n keys of recommend_key_bytes(f64) scratch.
-// recommend_query_tile: the queries one workgroup owns (the host sizes S by it).
+// recommend_query_tile: the queries one workgroup owns (the host sizes S by it).  scores may be null
+// (mf_rank_eval reads only ids and counts).
 size_t recommend_key_bytes(bool f64);
 int recommend_query_tile(int top_n, bool f64);
 void launch_recommend(hipStream_t st, const void* Q, const void* Cf, const int32_t* qrows, int nq, int32_t C, int S,
                       int k, int top_n, bool f64, const int32_t* cand_id, const int64_t* excl_off,
                       const int32_t* excl_rows, void* part, int32_t* ids, double* scores, int32_t* counts);
+
+// ---- kernels_rank.hip: ranking metrics ----------------------------------------------------------
+// The pair tables of mf_rank_eval on the device.  qrow[n]: the query-side row of every pair
+// (0xFFFFFFFF: unknown id), rows: the rows of that side.
+// rank_query_set: the distinct known rows, ascending, into qrows (the list launch_recommend takes);
+// returns their count nq (one small read-back) and leaves every row's flag / position in sc.
+// rank_pair_csr (after rank_query_set on the same scratch; the pairs may be another list): per
+// evaluated query its distinct entries, sorted: off (int64, nq + 1) and ent (room for n).  gt = false:
+// cand[] holds candidate rows, pairs with 0xFFFFFFFF are dropped, ent = rows ascending (launch_recommend's
+// excl_off / excl_rows).  gt = true: cand[] holds candidate ids, all kept, ent = ids ascending.
+// Pairs whose query is unknown or not in the query set are dropped.
+struct RankScratch;
+int64_t rank_query_set(hipStream_t st, RankScratch& sc, const uint32_t* qrow, int64_t n, uint32_t rows, DevBuf& qrows);
+void rank_pair_csr(hipStream_t st, RankScratch& sc, const uint32_t* qrow, const uint32_t* cand, int64_t n, uint32_t rows,
+                   int64_t nq, bool gt, DevBuf& off, DevBuf& ent);
+// Per-query metrics of a batch of nb lists (ids [nb][top_n] / counts [nb] as launch_recommend wrote
+// them) against the ground-truth rows gt_off[0 .. nb] / gt_ent: met[q][MF_RANK_NMETRICS] and cnt[q][2] =
+// (hits, g).  gt_off / met / cnt point at the batch's first query.  tab: 128 gains 1 / log(i + 2), then
+// their 129 prefix sums (host libm).
+void launch_rank_metrics(hipStream_t st, const int32_t* ids, const int32_t* counts, int nb, int top_n,
+                         const int64_t* gt_off, const int32_t* gt_ent, const double* tab, double* met, int64_t* cnt);
+// Sums over all nq queries in a fixed order: slices of 1024 queries (a fixed tree inside a slice) into
+// part [slices][MF_RANK_NMETRICS] / ipart [slices][2], then the slices in ascending order into sums[6] /
+// isums[2].
+int64_t rank_reduce_slices(int64_t nq);
+void launch_rank_reduce(hipStream_t st, const double* met, const int64_t* cnt, int64_t nq, double* part, int64_t* ipart,
+                        double* sums, int64_t* isums);
 
 // ---- kernels_als.hip: ALS half-sweeps -----------------------------------------------------------
 // ALS half-sweep (kernels_als.hip).  A work item is a whole row of the side being solved (slot < 0:

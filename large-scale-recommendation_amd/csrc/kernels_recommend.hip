@@ -359,7 +359,7 @@ __global__ __launch_bounds__(256) void k_rec_f64(const double* __restrict__ Qf, 
 
 // ---- merge ------------------------------------------------------------------------------------
 // One wave per query: lane l < S holds the head of partial list l (each sorted descending); N
-// rounds of a wave-wide maximum.  Slots past the count hold id 0 / score 0.0.
+// rounds of a wave-wide maximum.  Slots past the count hold id 0 / score 0.0.  scores may be null.
 template <typename K>
 __global__ __launch_bounds__(256) void k_rec_merge(const K* __restrict__ part, int nq, int S, int N,
                                                    int32_t* __restrict__ ids, double* __restrict__ scores,
@@ -383,7 +383,7 @@ __global__ __launch_bounds__(256) void k_rec_merge(const K* __restrict__ part, i
     if (live && lane < S && pos < N && !key_gt(best, head) && !key_gt(head, best)) ++pos;
     if (lane == 0) {
       ids[static_cast<int64_t>(q) * N + o] = live ? key_id(best) : 0;
-      scores[static_cast<int64_t>(q) * N + o] = live ? key_score(best) : 0.0;
+      if (scores) scores[static_cast<int64_t>(q) * N + o] = live ? key_score(best) : 0.0;
     }
     cnt += live ? 1 : 0;
   }

@@ -40,6 +40,7 @@ RECOMMEND_MAX_TOP = 128
 ALS_REG_WEIGHTED = 0
 ALS_REG_PLAIN = 1
 ALS_MAX_RANK = 128
+RANK_NMETRICS = 6  # precision, recall, ap, ndcg, rr, hit: a per-query row of mf_rank_eval
 
 
 class MFError(RuntimeError):
@@ -89,6 +90,22 @@ class mf_stats(C.Structure):
     ]
 
 
+class mf_rank_metrics(C.Structure):
+    _fields_ = [
+        ("queries", C.c_int64),
+        ("unknown_queries", C.c_int64),
+        ("gt_pairs", C.c_int64),
+        ("hits", C.c_int64),
+        ("precision", C.c_double),
+        ("recall", C.c_double),
+        ("map", C.c_double),
+        ("ndcg", C.c_double),
+        ("mrr", C.c_double),
+        ("hit_rate", C.c_double),
+        ("reserved", C.c_double * 6),
+    ]
+
+
 # Every symbol include/mfhip.h declares (tests check the library exports all of them).
 EXPORTS = [
     "mf_params_init", "mf_last_error", "mf_version", "mf_device_count", "mf_create",
@@ -99,14 +116,14 @@ EXPORTS = [
     "mf_reset_stats", "mf_jvm_shuffle", "mf_jvm_block_of", "mf_jvm_random_factors",
     "mf_learning_rate", "mf_get_params", "mf_read_ratings", "mf_save_model", "mf_load_model",
     "mf_dsgd_restart", "mf_online_update_out", "mf_recommend", "mf_als_fit", "mf_als_prepare",
-    "mf_als_run", "mf_als_run_implicit", "mf_als_fit_implicit",
+    "mf_als_run", "mf_als_run_implicit", "mf_als_fit_implicit", "mf_rank_eval",
 ]
 # The test hooks include/mfhip_testing.h declares (not product surface; same library).
 TESTING_EXPORTS = [
     "mf_debug_levels", "mf_debug_fast_schedule", "mf_debug_fast_split", "mf_debug_ring_schedule",
     "mf_debug_plan_digest", "mf_fast_plan_window", "mf_fast_kernel_name", "mf_debug_build_flags",
     "mf_debug_device_bytes", "mf_debug_als_normal_eq", "mf_debug_als_gram", "mf_debug_als_normal_eq_implicit",
-    "mf_debug_det_slot_table", "mf_debug_sys_placement",
+    "mf_debug_det_slot_table", "mf_debug_sys_placement", "mf_debug_rank_csr",
 ]
 
 _i32p = C.POINTER(C.c_int32)
@@ -177,6 +194,10 @@ def lib() -> C.CDLL:
                                            _f64p, _f64p]),
         "mf_recommend": (C.c_int, [_ctxp, C.c_int, _i32p, C.c_int64, C.c_int32, _i32p, _i32p, C.c_int64, _i32p, _f64p,
                                    _i32p]),
+        "mf_rank_eval": (C.c_int, [_ctxp, C.c_int, _i32p, _i32p, C.c_int64, C.c_int32, _i32p, _i32p, C.c_int64,
+                                   C.POINTER(mf_rank_metrics), _i32p, _i32p, _f64p, C.c_int64]),
+        "mf_debug_rank_csr": (C.c_int, [_ctxp, C.c_int, C.c_int, _i32p, _i32p, C.c_int64, _i32p, _i64p, _i32p,
+                                        C.c_int64, C.c_int64, _i64p, _i64p]),
         "mf_als_fit": (C.c_int, [_ctxp, _i32p, _i32p, _f64p, C.c_int64, C.c_int32, C.c_double, C.c_int32]),
         "mf_als_prepare": (C.c_int, [_ctxp, _i32p, _i32p, _f64p, C.c_int64]),
         "mf_als_run": (C.c_int, [_ctxp, C.c_int64, C.c_double, C.c_int32]),

@@ -21,6 +21,7 @@ import numpy as np
 from . import _lib as L
 from .context import Context
 from .dsgd import _columns, _pairs
+from .ranking import RankingMetrics
 
 
 class MatrixFactorizationModel:
@@ -73,6 +74,12 @@ class MatrixFactorizationModel:
         ids, sc, cnt = self._ctx.recommend(users, num, side=L.SIDE_USER, exclude=exclude)
         return {int(u): [(int(u), int(ids[j, x]), float(sc[j, x])) for x in range(int(cnt[j]))]
                 for j, u in enumerate(users)}
+
+    def rankingMetrics(self, heldout_pairs, exclude=None) -> RankingMetrics:
+        """RankingMetrics of the model's top-k product lists against held-out (user, product) pairs (tuples
+        or two arrays); exclude: (user ids, item ids) pairs never recommended, e.g. the training pairs."""
+        u, i = _pairs(heldout_pairs)
+        return RankingMetrics(self._ctx, u, i, exclude=exclude, side=L.SIDE_USER)
 
 
 class ALS:

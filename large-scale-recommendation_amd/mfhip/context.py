@@ -2,12 +2,32 @@
 from __future__ import annotations
 
 import ctypes as C
+from dataclasses import dataclass
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
 
 from . import _lib as L
 from ._lib import as_f64, as_i32, check, ptr, same_length
+
+
+@dataclass
+class RankMetrics:
+    """What mf_rank_eval returns (include/mfhip.h): counts, the six means over `queries`, and with
+    per_query=True the evaluated queries' ids, (hits, g) and six values, rows in ascending id."""
+    queries: int
+    unknown_queries: int
+    gt_pairs: int
+    hits: int
+    precision: float
+    recall: float
+    map: float
+    ndcg: float
+    mrr: float
+    hit_rate: float
+    ids: Optional[np.ndarray] = None
+    counts: Optional[np.ndarray] = None
+    values: Optional[np.ndarray] = None
 
 
 class Context:
@@ -217,6 +237,53 @@ class Context:
                                    ptr(counts, C.c_int32)))
         shape = (n, max(top_n, 1))
         return (ids[:n * shape[1]].reshape(shape), sc[:n * shape[1]].reshape(shape) if scores else None, counts[:n])
+
+    def rank_eval(self, gt_queries, gt_cands, top_n: int, side: int = L.SIDE_USER, exclude=None,
+                  per_query: bool = False) -> "RankMetrics":
+        """mf_rank_eval: ranking metrics of the held-out pairs (gt_queries[j], gt_cands[j]) against the
+        top_n lists recommend(..., exclude=exclude) would return, taken and summed on the device.
+        per_query=True: also ids [n] (ascending), counts [n, 2] = (hits, g) and values [n, 6] =
+        precision, recall, ap, ndcg, rr, hit of every evaluated query."""
+        gq, gc = as_i32(gt_queries), as_i32(gt_cands)
+        ng = same_length(gq, gc)
+        eq = ec = None
+        ne = 0
+        if exclude is not None:
+            eq, ec = as_i32(exclude[0]), as_i32(exclude[1])
+            ne = same_length(eq, ec)
+        out = L.mf_rank_metrics()
+        cap = int(np.unique(gq).size) if per_query else 0
+        ids = np.zeros(max(cap, 1), np.int32)
+        counts = np.zeros((max(cap, 1), 2), np.int32)
+        values = np.zeros((max(cap, 1), L.RANK_NMETRICS), np.float64)
+        check(L.lib().mf_rank_eval(self._h, int(side), ptr(gq, C.c_int32) if ng else None,
+                                   ptr(gc, C.c_int32) if ng else None, ng, int(top_n),
+                                   ptr(eq, C.c_int32) if ne else None, ptr(ec, C.c_int32) if ne else None, ne,
+                                   C.byref(out), ptr(ids, C.c_int32) if per_query else None,
+                                   ptr(counts, C.c_int32) if per_query else None,
+                                   ptr(values, C.c_double) if per_query else None, cap))
+        m = RankMetrics(queries=out.queries, unknown_queries=out.unknown_queries, gt_pairs=out.gt_pairs, hits=out.hits,
+                        precision=out.precision, recall=out.recall, map=out.map, ndcg=out.ndcg, mrr=out.mrr,
+                        hit_rate=out.hit_rate)
+        if per_query:
+            n = int(out.queries)
+            m.ids, m.counts, m.values = ids[:n], counts[:n], values[:n]
+        return m
+
+    def rank_csr(self, queries, cands, side: int = L.SIDE_USER, ground_truth: bool = True):
+        """mf_debug_rank_csr: the pair table rank_eval builds on the device for one pair list, as (query
+        ids in factor-row order, offsets [n + 1], entries): candidate ids (ground_truth) or candidate
+        factor rows (the exclusion table)."""
+        q, c = as_i32(queries), as_i32(cands)
+        n = same_length(q, c)
+        qids = np.zeros(max(n, 1), np.int32)
+        off = np.zeros(max(n, 1) + 1, np.int64)
+        ent = np.zeros(max(n, 1), np.int32)
+        nq, ne = C.c_int64(0), C.c_int64(0)
+        check(L.lib().mf_debug_rank_csr(self._h, int(side), 1 if ground_truth else 0, ptr(q, C.c_int32) if n else None,
+                                        ptr(c, C.c_int32) if n else None, n, ptr(qids, C.c_int32), ptr(off, C.c_int64),
+                                        ptr(ent, C.c_int32), max(n, 1), max(n, 1), C.byref(nq), C.byref(ne)))
+        return qids[:nq.value], off[:nq.value + 1], ent[:ne.value]
 
     # -- online ----------------------------------------------------------------
     def online_update(self, u, i, r, flavour: int = L.ONLINE_NEXT_FACTORS, num_partitions: int = 0):
