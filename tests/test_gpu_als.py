@@ -126,14 +126,18 @@ def test_normal_equations_exact(monkeypatch, mode, k):
 # 2. the solve, within the backward-error bound of a Cholesky solve
 
 @pytest.mark.parametrize("mode", MODES)
-@pytest.mark.parametrize("k,rows,lo,hi", [(3, 40, 33, 33), (10, 70, 5, 60), (64, 40, 100, 100), (128, 20, 200, 200)])
+@pytest.mark.parametrize("k,rows,lo,hi", [(3, 40, 33, 33), (10, 70, 5, 60), (64, 40, 100, 100), (128, 20, 200, 200),
+                                          (33, 40, 40, 40), (80, 30, 120, 120), (100, 20, 150, 150)])
 def test_solve_within_backward_error_bound(mode, k, rows, lo, hi):
     """One half-sweep (items from users).  Per solved row, with A = Q^T Q + lambda' I and b = Q^T r in
     numpy f64: ||b - A x|| <= 2 u c (||A|| ||x|| + || |Q|^T |r| ||), c = k (n + 2) + 4 k (3 k + 1) + 2:
     accumulation over n terms, Higham's bound for a Cholesky solve, the final rounding of x; the factor
     2 covers second-order terms.  Measured on an MI355X, the largest residual / bound over the rows
     of a case: k = 3: 4.3e-3 (f64) / 2.7e-3 (f32), k = 10: 2.9e-4 / 2.8e-4, k = 64: 7.5e-6 / 8.3e-6,
-    k = 128: 1.8e-6 / 2.0e-6."""
+    k = 128: 1.8e-6 / 2.0e-6; at the other rank buckets (real-valued data where tests/test_gpu_als_ranks.py
+    has the exact systems) k = 33: 2.5e-5 / 2.9e-5, k = 80: 4.2e-6 / 5.2e-6, k = 100: 3.2e-6 / 3.2e-6
+    (DESIGN.md section 4.7).  The bound is sound, not sharp: in f32 at k = 128 it admits a solve with
+    a trailing update of the factorisation left out; the exact systems are the sharp check."""
     rng = np.random.default_rng(7 * k + rows)
     f32 = mode == L.MODE_FAST_F32
     u_round = 2.0 ** -24 if f32 else 2.0 ** -53

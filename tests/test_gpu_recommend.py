@@ -74,9 +74,11 @@ def fill(ctx, rng, nq, nc, k, draw):
 
 
 # every value of each axis: k {1,3,10,64,100,130,256}, candidates {1,31,33,1000}, queries {1,33,70},
-# top_n {1,10,128} (top_n above the candidate count included)
+# top_n {1,10,128} (top_n above the candidate count included); then k_rec_f32<2, false> (top_n in
+# 17..48, k no multiple of 4) with 70 queries over its 64-query tile, and the NW = 4 instance with 130
+# queries, a second query block
 INT_CASES = [(1, 1, 1, 1), (3, 31, 33, 10), (10, 33, 70, 128), (64, 1000, 70, 10), (100, 1000, 33, 128),
-             (130, 33, 1, 10), (256, 1000, 70, 1), (64, 31, 1, 128)]
+             (130, 33, 1, 10), (256, 1000, 70, 1), (64, 31, 1, 128), (10, 200, 70, 32), (3, 40, 130, 10)]
 
 
 @pytest.mark.parametrize("mode", MODES)
