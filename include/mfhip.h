@@ -261,6 +261,73 @@ int mf_rank_eval(mf_ctx* ctx, int query_side,
                  mf_rank_metrics* out,
                  int32_t* q_ids_out, int32_t* q_counts_out, double* q_metrics_out, int64_t cap);
 
+/* The position of given (query, candidate) pairs in the query's complete ranked list, computed on the
+   device without building the list (a fused score-and-count): what prequential evaluation, the expected
+   percentile rank of the implicit-feedback literature and a check of mf_recommend past its first 128
+   positions need.
+   For pair j, rank_out[j] is the 0-based position cands[j] takes in the complete list of queries[j]:
+   every candidate row the model holds on the other side, minus the exclusions of that query, ordered
+   exactly as mf_recommend orders (score descending, ties by candidate id ascending (signed), NaN below
+   every number, -0 tied with +0).  Put differently: the number of non-excluded candidates other than
+   cands[j] whose key beats the pair's key.  score_out[j] (may be NULL) is the score mf_recommend reports
+   for the pair: MF_MODE_DETERMINISTIC_F64 mf_predict's value, MF_MODE_FAST_F32 the f32 fmaf chain over
+   f = 0..k-1 from 0, widened (in both, as there, a NaN is the canonical quiet NaN and -0 reads +0).  So for
+   every N <= MF_RECOMMEND_MAX_TOP, rank_out[j] < N holds exactly when cands[j] is entry rank_out[j] of
+   mf_recommend(queries[j], N, the same exclusions), and score_out[j] is that entry's score bit for bit.
+   valid_out[j] (may be NULL) is the length of that complete list: the candidate rows minus the distinct
+   excluded candidates of the query that the model holds; >= 1 for a ranked pair.
+   A pair whose query id or candidate id the model does not hold gets MF_PAIR_RANK_COLD, a pair that is
+   itself in the exclusion list MF_PAIR_RANK_EXCLUDED; both with valid_out 0 and score_out 0.0.
+   Exclusion pairs follow mf_recommend's rules: unknown ids ignored, duplicates allowed, pairs naming a
+   query not in queries[] ignored.  Every pair is ranked independently: duplicates in queries / cands are
+   allowed, output order is input order.  Results do not depend on how the pairs are batched or the
+   candidates split and are reproducible bit for bit (counts are integers).
+   Errors and state rules are mf_recommend's: MF_ERR_INVALID (NULL ctx, a bad side, a negative count, a
+   NULL array with a positive count), MF_ERR_NOT_FITTED, MF_ERR_STATE on a rank-mode context.  A context
+   on several devices evaluates on its first.  n == 0 is valid. */
+#define MF_PAIR_RANK_COLD     (-1)  /* the model does not hold the query id or the candidate id */
+#define MF_PAIR_RANK_EXCLUDED (-2)  /* the pair itself is in the exclusion list */
+int mf_pair_ranks(mf_ctx* ctx, int query_side,
+                  const int32_t* queries, const int32_t* cands, int64_t n,
+                  const int32_t* excl_query, const int32_t* excl_cand, int64_t n_excl,
+                  int32_t* rank_out,      /* [n] */
+                  int32_t* valid_out,     /* [n] or NULL */
+                  double*  score_out);    /* [n] or NULL */
+
+/* Prequential (test-then-train) evaluation of the online path, the "online DCG" online recommenders are
+   judged by: every event of a micro-batch is ranked with the model as it stands, then the model learns
+   the batch.
+   Step 1 ranks all n events with mf_pair_ranks(ctx, MF_SIDE_USER, users, items, n, excl_user, excl_item,
+   n_excl, ...) against the model as it stands on entry (micro-batch prequential: no event of the batch
+   sees another event of the batch; n = 1 gives strict test-then-train).  rank_out (may be NULL) receives
+   those ranks and codes.  A context that holds no model yet is not an error: every event is cold.
+   Step 2 performs exactly mf_online_update(ctx, users, items, ratings, n, flavour, num_partitions,
+   touched_users, touched_items): the model afterwards is bitwise what mf_online_update alone leaves.
+   Per evaluated event with rank r and list length V, N = top_n in 1 .. MF_RECOMMEND_MAX_TOP, in f64:
+     ndcg = gain[r] / idcg[1] for r < N, else 0: mf_rank_eval's table, so bitwise mf_rank_eval's per-query
+            ndcg of a query whose ground truth is this one item (mathematically 1 / log2(r + 2))
+     rr   = 1 / (r + 1) for r < N, else 0
+     hit  = [r < N]
+     pr   = r / (V - 1), 0 when V = 1: the expected percentile rank (Hu, Koren, Volinsky); not cut at N
+   Cold and excluded events contribute 0.0.  The three sums are taken over the events in ascending j, in
+   slices of 1024 with a fixed pairwise tree inside a slice, the slices added in ascending order
+   (mf_rank_eval's order); no floating-point atomics.  The sums are returned beside the means so that a
+   caller adds batches exactly.
+   Errors: mf_online_update's own; top_n out of range; a NULL out; a NULL array with a positive count;
+   MF_ERR_STATE on a rank-mode context.  Validation runs before anything is updated: a failing call
+   leaves the model untouched. */
+typedef struct mf_prequential {
+  int64_t events, evaluated, cold, excluded, hits;   /* events = n = evaluated + cold + excluded */
+  double sum_ndcg, sum_rr, sum_pr;                   /* sums over the evaluated events */
+  double ndcg, mrr, hit_rate, mpr;                   /* sums / evaluated; 0 when evaluated == 0 */
+  double reserved[6];
+} mf_prequential;
+int mf_online_prequential(mf_ctx* ctx, const int32_t* users, const int32_t* items, const double* ratings,
+                          int64_t n, int flavour, int num_partitions, int32_t top_n,
+                          const int32_t* excl_user, const int32_t* excl_item, int64_t n_excl,
+                          mf_prequential* out, int32_t* rank_out /* [n] or NULL */,
+                          int64_t* touched_users, int64_t* touched_items);
+
 /* ALS.train(ratings, rank = params.num_factors, iterations, lambda), the "ALS" branch of
    OnlineSpark.buildModelCombineOffline (sp/OnlineSpark.scala:125-131), as alternating least squares
    on the device.  mf_als_prepare keeps the ratings on the device as one CSR per side (the ratings of

@@ -59,6 +59,19 @@ public final class MfHip {
   // MRR, hit rate; exclQuery / exclCand as for recommend
   public static native void rankEval(long ctx, int querySide, int[] gtQuery, int[] gtCand, int topN,
                                      int[] exclQuery, int[] exclCand, double[] metricsOut);
+  // the 0-based position of every (queries[j], cands[j]) in the query's complete ranked list (mf_pair_ranks):
+  // ranksOut[j] = -1 for an id the model does not hold, -2 for a pair in the exclusion list; validOut
+  // (may be null) the length of the list, scoresOut (may be null) the pair's score as recommend reports it
+  public static native void pairRanks(long ctx, int querySide, int[] queries, int[] cands,
+                                      int[] exclQuery, int[] exclCand, int[] ranksOut, int[] validOut,
+                                      double[] scoresOut);
+  // prequential evaluation of one micro-batch (mf_online_prequential): every event is ranked against the
+  // model as it stands, then onlineUpdate(users, items, r, flavour, numPartitions) runs.  metricsOut
+  // (length >= 12) receives events, evaluated, cold, excluded, hits, the sums of NDCG, RR and percentile
+  // rank, then NDCG, MRR, hit rate and mean percentile rank; ranksOut (may be null) every event's rank
+  public static native void onlinePrequential(long ctx, int[] users, int[] items, double[] r,
+                                              int flavour, int numPartitions, int topN,
+                                              int[] exclUser, int[] exclItem, double[] metricsOut, int[] ranksOut);
   public static native void blockUpdate(long ctx, double[] r, int[] uidx, int[] iidx,
                                         double[] users, int[] uomega, double[] items, int[] iomega,
                                         int k, int iteration, int ratingBlockId, long seed,

@@ -352,6 +352,82 @@ JNIEXPORT void JNICALL JFN(rankEval)(JNIEnv* env, jclass c, jlong h, jint side, 
   check(env, st);
 }
 
+/* Elements of up to 8 arrays, acquired in order; on failure the ones already held are discarded. */
+static int acquire_all(JNIEnv* env, Elems* e, const jarray* a, const int* kind, int n) {
+  for (int x = 0; x < n; ++x) {
+    if (acquire(env, &e[x], a[x], kind[x])) {
+      while (x-- > 0) release(env, &e[x], JNI_ABORT);
+      return -1;
+    }
+  }
+  return 0;
+}
+
+JNIEXPORT void JNICALL JFN(pairRanks)(JNIEnv* env, jclass c, jlong h, jint side, jintArray q, jintArray cd,
+                                      jintArray xq, jintArray xc, jintArray ranks, jintArray valid,
+                                      jdoubleArray scores) {
+  if (require(env, q && cd && len(env, q) == len(env, cd), "queries and cands must match in length")) return;
+  const jsize n = len(env, q), ne = xq ? len(env, xq) : 0;
+  if (require(env, ranks && len(env, ranks) >= n, "ranksOut must hold one entry per pair")) return;
+  if (require(env, (!valid || len(env, valid) >= n) && (!scores || len(env, scores) >= n),
+              "validOut / scoresOut must be null or hold one entry per pair"))
+    return;
+  if (require(env, (!xq && !xc) || (xq && xc && len(env, xq) == len(env, xc)),
+              "exclQuery and exclCand must both be null or match in length"))
+    return;
+  Elems e[7];
+  const jarray arr[7] = {q, cd, xq, xc, ranks, valid, scores};
+  const int kind[7] = {kInt, kInt, kInt, kInt, kInt, kInt, kDouble};
+  if (acquire_all(env, e, arr, kind, 7)) return;
+  int st = mf_pair_ranks(CTX(h), side, n ? (const int32_t*)e[0].p : NULL, n ? (const int32_t*)e[1].p : NULL, n,
+                         ne ? (const int32_t*)e[2].p : NULL, ne ? (const int32_t*)e[3].p : NULL, ne, (int32_t*)e[4].p,
+                         (int32_t*)e[5].p, (double*)e[6].p);
+  for (int x = 6; x >= 4; --x) release(env, &e[x], st == MF_OK ? 0 : JNI_ABORT);
+  for (int x = 3; x >= 0; --x) release(env, &e[x], JNI_ABORT);
+  check(env, st);
+}
+
+JNIEXPORT void JNICALL JFN(onlinePrequential)(JNIEnv* env, jclass c, jlong h, jintArray u, jintArray i, jdoubleArray r,
+                                              jint flavour, jint parts, jint top, jintArray xu, jintArray xi,
+                                              jdoubleArray metrics, jintArray ranks) {
+  if (require(env, u && i && r && len(env, u) == len(env, i) && len(env, u) == len(env, r),
+              "users, items and ratings must match in length"))
+    return;
+  const jsize n = len(env, u), ne = xu ? len(env, xu) : 0;
+  if (require(env, metrics && len(env, metrics) >= 12, "metricsOut must hold 12 entries")) return;
+  if (require(env, !ranks || len(env, ranks) >= n, "ranksOut must be null or hold one entry per event")) return;
+  if (require(env, (!xu && !xi) || (xu && xi && len(env, xu) == len(env, xi)),
+              "exclUser and exclItem must both be null or match in length"))
+    return;
+  Elems e[7];
+  const jarray arr[7] = {u, i, r, xu, xi, metrics, ranks};
+  const int kind[7] = {kInt, kInt, kDouble, kInt, kInt, kDouble, kInt};
+  if (acquire_all(env, e, arr, kind, 7)) return;
+  mf_prequential m;
+  int st = mf_online_prequential(CTX(h), n ? (const int32_t*)e[0].p : NULL, n ? (const int32_t*)e[1].p : NULL,
+                                 n ? (const double*)e[2].p : NULL, n, flavour, parts, top,
+                                 ne ? (const int32_t*)e[3].p : NULL, ne ? (const int32_t*)e[4].p : NULL, ne, &m,
+                                 (int32_t*)e[6].p, NULL, NULL);
+  if (st == MF_OK) {
+    double* o = (double*)e[5].p;
+    o[0] = (double)m.events;
+    o[1] = (double)m.evaluated;
+    o[2] = (double)m.cold;
+    o[3] = (double)m.excluded;
+    o[4] = (double)m.hits;
+    o[5] = m.sum_ndcg;
+    o[6] = m.sum_rr;
+    o[7] = m.sum_pr;
+    o[8] = m.ndcg;
+    o[9] = m.mrr;
+    o[10] = m.hit_rate;
+    o[11] = m.mpr;
+  }
+  for (int x = 6; x >= 5; --x) release(env, &e[x], st == MF_OK ? 0 : JNI_ABORT);
+  for (int x = 4; x >= 0; --x) release(env, &e[x], JNI_ABORT);
+  check(env, st);
+}
+
 typedef int (*eval_fn)(JNIEnv*, jlong, const int32_t*, const int32_t*, const double*, jsize, jdouble, double*);
 
 static int call_rmse(JNIEnv* env, jlong h, const int32_t* u, const int32_t* i, const double* r, jsize n, jdouble unused,

@@ -1,7 +1,7 @@
 // abi.cpp -- the C ABI of libmfhip.so: every entry point of include/mfhip.h and
 // include/mfhip_testing.h, as a thin wrapper that checks its arguments and calls the feature's
-// function (mfhip.cpp, dsgd_det.cpp, dsgd_fast.cpp, ring.cpp, online.cpp, eval.cpp, rank_eval.cpp, als.cpp,
-// declared in context.hpp; placement.cpp, declared in plan.hpp) under `guarded`.
+// function (mfhip.cpp, dsgd_det.cpp, dsgd_fast.cpp, ring.cpp, online.cpp, eval.cpp, rank_eval.cpp,
+// pair_rank.cpp, als.cpp, declared in context.hpp; placement.cpp, declared in plan.hpp) under `guarded`.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -275,6 +275,50 @@ int mf_rank_eval(mf_ctx* ctx, int query_side, const int32_t* gt_query, const int
     rank_check(ctx, query_side, "mf_rank_eval");
     rank_eval(ctx, query_side, gt_query, gt_cand, n_gt, top_n, excl_query, excl_cand, n_excl, out, q_ids_out,
               q_counts_out, q_metrics_out, cap);
+  });
+}
+
+int mf_pair_ranks(mf_ctx* ctx, int query_side, const int32_t* queries, const int32_t* cands, int64_t n,
+                  const int32_t* excl_query, const int32_t* excl_cand, int64_t n_excl, int32_t* rank_out,
+                  int32_t* valid_out, double* score_out) {
+  return guarded([&] {
+    MF_REQUIRE(ctx, "null context");
+    MF_REQUIRE(query_side == MF_SIDE_USER || query_side == MF_SIDE_ITEM, "bad side");
+    MF_REQUIRE(n >= 0 && n_excl >= 0, "negative count");
+    MF_REQUIRE(n == 0 || (queries && cands && rank_out), "null argument");
+    MF_REQUIRE(n_excl == 0 || (excl_query && excl_cand), "null exclusion list");
+    rank_check(ctx, query_side, "mf_pair_ranks");
+    pair_ranks(ctx, query_side, queries, cands, n, excl_query, excl_cand, n_excl, rank_out, valid_out, score_out);
+  });
+}
+
+int mf_online_prequential(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n, int flavour,
+                          int num_partitions, int32_t top_n, const int32_t* excl_user, const int32_t* excl_item,
+                          int64_t n_excl, mf_prequential* out, int32_t* rank_out, int64_t* touched_users,
+                          int64_t* touched_items) {
+  return guarded([&] {
+    // everything mf_online_update would refuse is refused here, before the model is touched
+    MF_REQUIRE(ctx, "null context");
+    MF_REQUIRE(out, "out is null");
+    MF_REQUIRE(top_n >= 1 && top_n <= MF_RECOMMEND_MAX_TOP,
+               "top_n must be in [1, " + std::to_string(MF_RECOMMEND_MAX_TOP) + "]");
+    MF_REQUIRE(n >= 0 && n_excl >= 0, "negative count");
+    MF_REQUIRE(n == 0 || (u && i && r), "bad rating arrays");
+    MF_REQUIRE(n_excl == 0 || (excl_user && excl_item), "null exclusion list");
+    if (ctx->rank_mode)
+      fail(MF_ERR_STATE, "mf_online_prequential runs on a single-process context; a rank-mode context "
+                         "(mf_create_rank) holds only its own users' rows");
+    MF_REQUIRE(ctx->shards.size() == 1, "online updates run on a single-device context");
+    MF_REQUIRE(flavour >= MF_ONLINE_NEXT_FACTORS && flavour <= MF_ONLINE_SPARK_SWEEP, "unknown online flavour");
+    if (flavour == MF_ONLINE_SPARK_SWEEP && n > 0) {
+      MF_REQUIRE(num_partitions >= 1, "num_partitions must be >= 1 for MF_ONLINE_SPARK_SWEEP");
+      for (int64_t j = 0; j < n; ++j)
+        MF_REQUIRE(u[j] >= 0 && i[j] != INT32_MIN, "Spark sweep needs non-negative user ids");
+    }
+    require_healthy(ctx);
+    det_spec_wait(ctx, true);  // new ids change the layouts the builds read
+    online_prequential(ctx, u, i, r, n, flavour, num_partitions, top_n, excl_user, excl_item, n_excl, out, rank_out,
+                       touched_users, touched_items);
   });
 }
 

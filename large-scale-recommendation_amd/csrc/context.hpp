@@ -1,6 +1,6 @@
 // context.hpp -- the context (mf_ctx), its shards, and the helpers more than one host translation
 // unit uses.  Private to the host side: included by the .cpp files only (mfhip.cpp, dsgd_det.cpp,
-// dsgd_fast.cpp, ring.cpp, abi.cpp, online.cpp, eval.cpp, rank_eval.cpp, als.cpp), never by a .hip file or by
+// dsgd_fast.cpp, ring.cpp, abi.cpp, online.cpp, eval.cpp, rank_eval.cpp, pair_rank.cpp, als.cpp), never by a .hip file or by
 // kernels.hpp / plan.hpp; placement.cpp, which knows no context, does without it.
 #pragma once
 
@@ -133,6 +133,10 @@ struct Shard {
   // metrics and (hits, g), the slice sums, the gain table and the call's totals
   RankScratch rank_sc;
   DevBuf rk_in, rk_goff, rk_gent, rk_met, rk_cnt, rk_part, rk_tab, rk_res;
+  // pair ranks (mf_pair_ranks / mf_online_prequential, which also use the rec_* exclusion table and the
+  // rk_* sums): the pairs' factor rows (query rows, then candidate rows), the two parts of their keys,
+  // and the per-pair rank / list length / score
+  DevBuf pr_in, pr_ord, pr_tid, pr_rank, pr_valid, pr_score;
   // ALS (mf_als_prepare): per solved side [user, item] the CSR (counterpart rows, ratings) and the
   // work lists; the long rows' partial systems of one launch; the testing hook's output
   DevBuf als_cols[2], als_vals[2], als_items[2], als_splits[2], als_part, als_dump;
@@ -345,12 +349,22 @@ void get_factors(mf_ctx* ctx, int side, int32_t* ids, double* vecs, int64_t cap,
 void lookup_factors(mf_ctx* ctx, int side, const int32_t* ids, int64_t n, double* vecs_out, uint8_t* found);
 
 // rank_eval.cpp
+const std::vector<double>& gain_table();  // 128 gains 1 / log(i + 2), then their 129 prefix sums
 void rank_eval(mf_ctx* ctx, int qside, const int32_t* gq, const int32_t* gc, int64_t ng, int32_t top_n,
                const int32_t* eq, const int32_t* ec, int64_t ne, mf_rank_metrics* out, int32_t* q_ids_out,
                int32_t* q_counts_out, double* q_metrics_out, int64_t cap);
 void debug_rank_csr(mf_ctx* ctx, int qside, bool gt, const int32_t* q, const int32_t* c, int64_t n, int32_t* q_ids_out,
                     int64_t* off_out, int32_t* entries_out, int64_t cap_q, int64_t cap_e, int64_t* nq_out,
                     int64_t* ne_out);
+
+// pair_rank.cpp
+// The ranks of n pairs, left on the device in the shard's pr_rank / pr_valid / pr_score and copied to the
+// non-null outputs; returns the number of cold pairs.
+int64_t pair_ranks(mf_ctx* ctx, int qside, const int32_t* q, const int32_t* c, int64_t n, const int32_t* eq,
+                   const int32_t* ec, int64_t ne, int32_t* rank_out, int32_t* valid_out, double* score_out);
+void online_prequential(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n, int flavour,
+                        int num_partitions, int32_t top_n, const int32_t* eu, const int32_t* ei, int64_t ne,
+                        mf_prequential* out, int32_t* rank_out, int64_t* tu, int64_t* ti);
 
 // als.cpp
 void als_check(const mf_ctx* ctx);

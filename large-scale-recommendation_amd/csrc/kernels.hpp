@@ -272,6 +272,33 @@ int64_t rank_reduce_slices(int64_t nq);
 void launch_rank_reduce(hipStream_t st, const double* met, const int64_t* cnt, int64_t nq, double* part, int64_t* ipart,
                         double* sums, int64_t* isums);
 
+// ---- kernels_pairrank.hip: ranks of given pairs -------------------------------------------------
+// The position of pairs (query row, candidate row) in the query's complete ranked list (mf_pair_ranks,
+// mf_online_prequential): rank = the candidates whose key (mf_recommend's order) beats the pair's.
+// qrow / crow: the factor rows of the n pairs (0xFFFFFFFF: unknown id).  qpos: per query-side row its
+// position in the exclusion CSR excl_off / excl_rows (rank_query_set's positions, rank_pair_csr's
+// table).  Per pair: tord (pair_rank_ord_bytes(f64) each; 0 = not ranked) and tid, the two parts of its
+// key; rank (the count, or MF_PAIR_RANK_COLD / MF_PAIR_RANK_EXCLUDED), valid (the list's length) and
+// score (the value mf_recommend reports for the pair; 0.0 where not ranked).
+// launch_pair_targets fills all five for every pair; launch_pair_count then adds, for pairs [0, n) of
+// one batch (the pointers at the batch's first pair), every candidate row of [0, C) that beats the
+// target (S splits of the rows, combined with integer atomics) and, with have_excl, takes the query's
+// excluded rows that beat it off again.  nw (1, 2, 4): waves per workgroup of the f32 walk;
+// pair_rank_tile: the pairs one workgroup owns.
+size_t pair_rank_ord_bytes(bool f64);
+int pair_rank_tile(bool f64, int nw);
+void launch_pair_targets(hipStream_t st, const void* Q, const void* Cf, const uint32_t* qrow, const uint32_t* crow,
+                         int64_t n, int32_t C, int k, bool f64, const int32_t* cand_id, const int32_t* qpos,
+                         const int64_t* excl_off, const int32_t* excl_rows, void* tord, uint32_t* tid, int32_t* rank,
+                         int32_t* valid, double* score);
+void launch_pair_count(hipStream_t st, const void* Q, const void* Cf, const uint32_t* qrow, int n, int32_t C, int S,
+                       int k, bool f64, int nw, const int32_t* cand_id, const int32_t* qpos, const int64_t* excl_off,
+                       const int32_t* excl_rows, bool have_excl, const void* tord, const uint32_t* tid, int32_t* rank);
+// Per pair ndcg / rr / pr (columns 0 .. 2 of a met row of MF_RANK_NMETRICS, the rest 0) and cnt[j][2] =
+// (hit, evaluated), the rows launch_rank_reduce sums; tab as launch_rank_metrics takes it.
+void launch_pair_metrics(hipStream_t st, const int32_t* rank, const int32_t* valid, int64_t n, int top_n,
+                         const double* tab, double* met, int64_t* cnt);
+
 // ---- kernels_als.hip: ALS half-sweeps -----------------------------------------------------------
 // ALS half-sweep (kernels_als.hip).  A work item is a whole row of the side being solved (slot < 0:
 // its system is solved in the kernel and x stored to X[row]) or one chunk of a long row (slot >= 0:

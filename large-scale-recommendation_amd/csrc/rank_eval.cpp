@@ -58,6 +58,8 @@ void build_exclusions(Shard& s, const SideLayout& QS, const SideLayout& CS, cons
                 s.rec_erows);
 }
 
+}  // namespace
+
 // 128 gains 1 / log(i + 2), then idcg[m] = gain_0 + ... + gain_{m-1} summed in that order, m = 0 .. 128
 const std::vector<double>& gain_table() {
   static const std::vector<double> tab = [] {
@@ -69,8 +71,6 @@ const std::vector<double>& gain_table() {
   }();
   return tab;
 }
-
-}  // namespace
 
 void rank_eval(mf_ctx* ctx, int qside, const int32_t* gq, const int32_t* gc, int64_t ng, int32_t top_n,
                const int32_t* eq, const int32_t* ec, int64_t ne, mf_rank_metrics* out, int32_t* q_ids_out,

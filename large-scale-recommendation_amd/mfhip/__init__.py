@@ -6,13 +6,14 @@ this package is the Python equivalent of the Scala entry points that bind it.
 from . import _lib, jvm, synth
 from ._lib import MFError, MFNoDeviceError, device_count, version
 from .als import ALS, MatrixFactorizationModel
-from .context import Context, RankMetrics, block_update
+from .context import Context, Prequential, RankMetrics, block_update
 from .core import (FactorInitializer, FactorInitializerDescriptor, Factors, FactorUpdater, FactorVector,
                    ItemUpdate, MockFactorUpdater, PseudoRandomFactorInitializer,
                    PseudoRandomFactorInitializerDescriptor, RandomFactorInitializer,
                    RandomFactorInitializerDescriptor, Rating, SGDUpdater, UserUpdate)
 from .dsgd import DSGDforMF, LearningRateMethod
 from .online import OnlineMF
+from .prequential import PrequentialEvaluator, host_prequential
 from .ranking import RankingMetrics
 from .ratings_io import read_ratings
 
@@ -22,5 +23,5 @@ __all__ = [
     "MockFactorUpdater", "FactorInitializer", "FactorInitializerDescriptor", "PseudoRandomFactorInitializer",
     "PseudoRandomFactorInitializerDescriptor", "RandomFactorInitializer", "RandomFactorInitializerDescriptor",
     "UserUpdate", "ItemUpdate", "read_ratings", "ALS", "MatrixFactorizationModel",
-    "RankMetrics", "RankingMetrics",
+    "RankMetrics", "RankingMetrics", "Prequential", "PrequentialEvaluator", "host_prequential",
 ]

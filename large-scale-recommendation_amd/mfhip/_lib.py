@@ -41,6 +41,8 @@ ALS_REG_WEIGHTED = 0
 ALS_REG_PLAIN = 1
 ALS_MAX_RANK = 128
 RANK_NMETRICS = 6  # precision, recall, ap, ndcg, rr, hit: a per-query row of mf_rank_eval
+PAIR_RANK_COLD = -1      # mf_pair_ranks: the model does not hold the query id or the candidate id
+PAIR_RANK_EXCLUDED = -2  # ... the pair itself is in the exclusion list
 
 
 class MFError(RuntimeError):
@@ -106,6 +108,24 @@ class mf_rank_metrics(C.Structure):
     ]
 
 
+class mf_prequential(C.Structure):
+    _fields_ = [
+        ("events", C.c_int64),
+        ("evaluated", C.c_int64),
+        ("cold", C.c_int64),
+        ("excluded", C.c_int64),
+        ("hits", C.c_int64),
+        ("sum_ndcg", C.c_double),
+        ("sum_rr", C.c_double),
+        ("sum_pr", C.c_double),
+        ("ndcg", C.c_double),
+        ("mrr", C.c_double),
+        ("hit_rate", C.c_double),
+        ("mpr", C.c_double),
+        ("reserved", C.c_double * 6),
+    ]
+
+
 # Every symbol include/mfhip.h declares (tests check the library exports all of them).
 EXPORTS = [
     "mf_params_init", "mf_last_error", "mf_version", "mf_device_count", "mf_create",
@@ -116,7 +136,8 @@ EXPORTS = [
     "mf_reset_stats", "mf_jvm_shuffle", "mf_jvm_block_of", "mf_jvm_random_factors",
     "mf_learning_rate", "mf_get_params", "mf_read_ratings", "mf_save_model", "mf_load_model",
     "mf_dsgd_restart", "mf_online_update_out", "mf_recommend", "mf_als_fit", "mf_als_prepare",
-    "mf_als_run", "mf_als_run_implicit", "mf_als_fit_implicit", "mf_rank_eval",
+    "mf_als_run", "mf_als_run_implicit", "mf_als_fit_implicit", "mf_rank_eval", "mf_pair_ranks",
+    "mf_online_prequential",
 ]
 # The test hooks include/mfhip_testing.h declares (not product surface; same library).
 TESTING_EXPORTS = [
@@ -196,6 +217,10 @@ def lib() -> C.CDLL:
                                    _i32p]),
         "mf_rank_eval": (C.c_int, [_ctxp, C.c_int, _i32p, _i32p, C.c_int64, C.c_int32, _i32p, _i32p, C.c_int64,
                                    C.POINTER(mf_rank_metrics), _i32p, _i32p, _f64p, C.c_int64]),
+        "mf_pair_ranks": (C.c_int, [_ctxp, C.c_int, _i32p, _i32p, C.c_int64, _i32p, _i32p, C.c_int64, _i32p, _i32p,
+                                    _f64p]),
+        "mf_online_prequential": (C.c_int, [_ctxp, _i32p, _i32p, _f64p, C.c_int64, C.c_int, C.c_int, C.c_int32, _i32p,
+                                            _i32p, C.c_int64, C.POINTER(mf_prequential), _i32p, _i64p, _i64p]),
         "mf_debug_rank_csr": (C.c_int, [_ctxp, C.c_int, C.c_int, _i32p, _i32p, C.c_int64, _i32p, _i64p, _i32p,
                                         C.c_int64, C.c_int64, _i64p, _i64p]),
         "mf_als_fit": (C.c_int, [_ctxp, _i32p, _i32p, _f64p, C.c_int64, C.c_int32, C.c_double, C.c_int32]),

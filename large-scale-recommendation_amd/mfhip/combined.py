@@ -12,6 +12,11 @@ factors: every micro-batch either
 The counters follow the reference (decrement, fire at <= 0, reset).  Every `checkpoint_every`-th
 batch the model is written as an mf_save_model snapshot when `snapshot_dir` is given: the
 localCheckpoint of the reference (:93-99) cuts RDD lineage; here it is a restartable file.
+
+With eval_top_n=N both classes judge the stream prequentially (mf_online_prequential): every batch is
+ranked against the model as it stands before the model learns it, and `metrics` (a
+PrequentialEvaluator) keeps one record per batch.  A batch that triggers an offline refit is ranked
+against the pre-refit model, then the refit runs.  Unset, nothing changes.
 """
 from __future__ import annotations
 
@@ -22,13 +27,15 @@ import numpy as np
 
 from . import _lib as L
 from .context import Context
+from .prequential import PrequentialEvaluator, evaluate_only
 
 
 class OnlineOfflineSpark:
     def __init__(self, num_factors: int, learning_rate: float = 0.01, num_partitions: int = 4,
                  offline_every: int = 10, checkpoint_every: int = 10, iterations: int = 10,
                  init: str = "pseudo_random", seed: int = 0, mode: str = "deterministic",
-                 snapshot_dir: Optional[str] = None, offline_algorithm: str = "DSGD"):
+                 snapshot_dir: Optional[str] = None, offline_algorithm: str = "DSGD",
+                 eval_top_n: Optional[int] = None):
         if offline_algorithm not in ("DSGD", "ALS"):
             raise ValueError(f'offline_algorithm must be "DSGD" or "ALS", got {offline_algorithm!r}')
         self.offline_algorithm = offline_algorithm
@@ -50,6 +57,9 @@ class OnlineOfflineSpark:
         self._params = p
         self.ctx = Context(p)
         self._hist = ([], [], [])  # ratings history (OnlineSpark.scala:71), as array chunks
+        self.eval_top_n = eval_top_n
+        self.metrics = (PrequentialEvaluator(self.ctx, eval_top_n, L.ONLINE_SPARK_SWEEP, num_partitions)
+                        if eval_top_n is not None else None)
 
     def close(self) -> None:
         self.ctx.close()
@@ -71,9 +81,14 @@ class OnlineOfflineSpark:
         for dst, src in zip(self._hist, (u, i, r)):
             dst.append(src)
         if not offline:
-            self.ctx.online_update(u, i, r, L.ONLINE_SPARK_SWEEP, self.P)
+            if self.metrics is not None:
+                self.metrics.process(u, i, r)
+            else:
+                self.ctx.online_update(u, i, r, L.ONLINE_SPARK_SWEEP, self.P)
             users, items = np.unique(u), np.unique(i)
         else:
+            if self.metrics is not None:
+                self.metrics.add(evaluate_only(self.ctx, u, i, self.eval_top_n))
             hu, hi, hr = (np.concatenate(x) for x in self._hist)
             fresh = Context(self._params)
             if self.offline_algorithm == "ALS":
@@ -83,6 +98,8 @@ class OnlineOfflineSpark:
                     fresh.online_update(hu, hi, hr, L.ONLINE_SPARK_SWEEP, self.P)
             self.ctx.close()
             self.ctx = fresh
+            if self.metrics is not None:
+                self.metrics.ctx = fresh
             users, items = np.unique(hu), np.unique(hi)
         uv, _ = self.ctx.lookup(L.SIDE_USER, users)
         iv, _ = self.ctx.lookup(L.SIDE_ITEM, items)
@@ -114,7 +131,7 @@ class PSOfflineOnlineMF:
 
     def __init__(self, num_factors: int, learning_rate: float = 0.01, iterations: int = 10,
                  init: str = "pseudo_random", seed: int = 0, mode: str = "deterministic",
-                 emit_outputs: bool = False):
+                 emit_outputs: bool = False, eval_top_n: Optional[int] = None):
         self.k = num_factors
         self.iterations = iterations
         self.emit_outputs = emit_outputs
@@ -128,6 +145,9 @@ class PSOfflineOnlineMF:
         self._params = p
         self.ctx = Context(p)
         self._hist = ([], [], [])  # rs (:54)
+        self.eval_top_n = eval_top_n
+        self.metrics = (PrequentialEvaluator(self.ctx, eval_top_n, L.ONLINE_DELTA)
+                        if eval_top_n is not None else None)
 
     def close(self) -> None:
         self.ctx.close()
@@ -144,7 +164,12 @@ class PSOfflineOnlineMF:
         r = np.ascontiguousarray(r, np.float64)
         for dst, src in zip(self._hist, (u, i, r)):
             dst.append(src)
-        self._apply(self.ctx, [(u, i, r)])
+        if self.metrics is not None and not self.emit_outputs:
+            self.metrics.process(u, i, r)
+        else:
+            if self.metrics is not None:  # the per-rating records need mf_online_update_out: rank first
+                self.metrics.add(evaluate_only(self.ctx, u, i, self.eval_top_n))
+            self._apply(self.ctx, [(u, i, r)])
         return self._vectors(np.unique(u), np.unique(i))
 
     def _apply(self, ctx: Context, passes) -> None:
@@ -171,4 +196,6 @@ class PSOfflineOnlineMF:
         self._apply(fresh, [(hu, hi, hr)] * self.iterations)
         self.ctx.close()
         self.ctx = fresh
+        if self.metrics is not None:
+            self.metrics.ctx = fresh
         return self._vectors(np.unique(hu), np.unique(hi))

@@ -30,6 +30,28 @@ class RankMetrics:
     values: Optional[np.ndarray] = None
 
 
+@dataclass
+class Prequential:
+    """What mf_online_prequential returns (include/mfhip.h) for one micro-batch: the counts (events =
+    evaluated + cold + excluded), the three sums over the evaluated events, their means, and with
+    ranks=True every event's rank or negative code."""
+    events: int
+    evaluated: int
+    cold: int
+    excluded: int
+    hits: int
+    sum_ndcg: float
+    sum_rr: float
+    sum_pr: float
+    ndcg: float
+    mrr: float
+    hit_rate: float
+    mpr: float
+    touched_users: int = 0
+    touched_items: int = 0
+    ranks: Optional[np.ndarray] = None
+
+
 class Context:
     """Owns an mf_ctx.  mode: "deterministic" (bit-exact f64 replay) or "fast" (f32)."""
 
@@ -270,6 +292,29 @@ class Context:
             m.ids, m.counts, m.values = ids[:n], counts[:n], values[:n]
         return m
 
+    def pair_ranks(self, queries, cands, side: int = L.SIDE_USER, exclude=None, scores: bool = False):
+        """mf_pair_ranks: for every pair (queries[j], cands[j]) the 0-based position of the candidate in the
+        query's complete list -- every row of the other side minus the query's exclusions, in recommend()'s
+        order -- counted on the device without building the list.  Returns (ranks [n], valid [n], scores
+        [n] or None): ranks[j] is PAIR_RANK_COLD for an id the model does not hold and PAIR_RANK_EXCLUDED for
+        a pair in `exclude` (valid 0, score 0.0); valid[j] is the length of the list."""
+        q, c = as_i32(queries), as_i32(cands)
+        n = same_length(q, c)
+        eq = ec = None
+        ne = 0
+        if exclude is not None:
+            eq, ec = as_i32(exclude[0]), as_i32(exclude[1])
+            ne = same_length(eq, ec)
+        ranks = np.zeros(max(n, 1), np.int32)
+        valid = np.zeros(max(n, 1), np.int32)
+        sc = np.zeros(max(n, 1), np.float64) if scores else None
+        check(L.lib().mf_pair_ranks(self._h, int(side), ptr(q, C.c_int32) if n else None,
+                                    ptr(c, C.c_int32) if n else None, n,
+                                    ptr(eq, C.c_int32) if ne else None, ptr(ec, C.c_int32) if ne else None, ne,
+                                    ptr(ranks, C.c_int32), ptr(valid, C.c_int32),
+                                    ptr(sc, C.c_double) if scores else None))
+        return ranks[:n], valid[:n], (sc[:n] if scores else None)
+
     def rank_csr(self, queries, cands, side: int = L.SIDE_USER, ground_truth: bool = True):
         """mf_debug_rank_csr: the pair table rank_eval builds on the device for one pair list, as (query
         ids in factor-row order, offsets [n + 1], entries): candidate ids (ground_truth) or candidate
@@ -293,6 +338,32 @@ class Context:
         check(L.lib().mf_online_update(self._h, ptr(u, C.c_int32), ptr(i, C.c_int32), ptr(r, C.c_double), len(u),
                                        flavour, num_partitions, C.byref(tu), C.byref(ti)))
         return tu.value, ti.value
+
+    def online_prequential(self, u, i, r, top_n: int, flavour: int = L.ONLINE_NEXT_FACTORS, num_partitions: int = 0,
+                           exclude=None, ranks: bool = False) -> "Prequential":
+        """mf_online_prequential: test-then-train on one micro-batch.  Every event (u[j], i[j]) is ranked
+        among all items for its user with the model as it stands (pair_ranks; exclude = (user ids, item
+        ids) never ranked above it), its ndcg / rr / hit at top_n and its percentile rank summed on the
+        device in a fixed order, and only then online_update(u, i, r, flavour, num_partitions) runs."""
+        u, i, r = as_i32(u), as_i32(i), as_f64(r)
+        n = same_length(u, i, r)
+        eq = ec = None
+        ne = 0
+        if exclude is not None:
+            eq, ec = as_i32(exclude[0]), as_i32(exclude[1])
+            ne = same_length(eq, ec)
+        out = L.mf_prequential()
+        rk = np.zeros(max(n, 1), np.int32) if ranks else None
+        tu, ti = C.c_int64(0), C.c_int64(0)
+        check(L.lib().mf_online_prequential(self._h, ptr(u, C.c_int32), ptr(i, C.c_int32), ptr(r, C.c_double), n,
+                                            int(flavour), int(num_partitions), int(top_n),
+                                            ptr(eq, C.c_int32) if ne else None, ptr(ec, C.c_int32) if ne else None, ne,
+                                            C.byref(out), ptr(rk, C.c_int32) if ranks else None,
+                                            C.byref(tu), C.byref(ti)))
+        return Prequential(events=out.events, evaluated=out.evaluated, cold=out.cold, excluded=out.excluded,
+                           hits=out.hits, sum_ndcg=out.sum_ndcg, sum_rr=out.sum_rr, sum_pr=out.sum_pr, ndcg=out.ndcg,
+                           mrr=out.mrr, hit_rate=out.hit_rate, mpr=out.mpr, touched_users=tu.value,
+                           touched_items=ti.value, ranks=rk[:n] if ranks else None)
 
     def online_update_out(self, u, i, r, flavour: int = L.ONLINE_NEXT_FACTORS, items: bool = True):
         """online_update plus the per-rating records the operators emit (mf_online_update_out):
