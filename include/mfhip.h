@@ -421,6 +421,51 @@ int mf_online_update_out(mf_ctx* ctx, const int32_t* users, const int32_t* items
                          const double* ratings, int64_t n, int flavour, int num_partitions,
                          int64_t* touched_users, int64_t* touched_items, double* user_out,
                          double* item_out);
+/* Online updates on implicit feedback: every event is followed by `negatives` sampled updates
+   (users[j], another item, negative_rating), drawn and expanded on the device.
+   Meaning.  The call is mf_online_update(flavour, arrival order) on the expanded batch, bit for bit: N =
+   n * (1 + negatives) records, for each event j its own (users[j], items[j], ratings[j]) followed by
+   (users[j], id of row_{j,s}, negative_rating) for s = 0 .. negatives-1.  Only the events bring new ids;
+   they get rows and first-touch values exactly as mf_online_update gives them, before anything is drawn.
+   touched_* and mf_stats.updates count the expanded batch.
+   The draw.  Event j of the call is event t = first_event + j of the stream.  With pool = the item rows
+   the model holds once this batch's new ids have theirs and pos_row = the factor row of items[j]:
+       z = (uint64)seed + 0x9E3779B97F4A7C15 * (t * 64 + s + 1)     (mod 2^64: SplitMix64)
+       z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  z ^= z >> 31
+       c = ((z >> 32) * (pool - 1)) >> 32;        row = c + (c >= pos_row)
+   uniform over the other pool - 1 rows, never the event's own item; no rejection, duplicates among one
+   event's negatives allowed.  A batch that leaves the model with one item (pool == 1) has nothing to
+   draw from: the call is then mf_online_update on the events alone and sampled_items_out is not written.
+   The pool is indexed by factor row (rows are given in first-touch order), so the draws of a given (seed,
+   first_event) depend on the model's row layout: they are reproducible for the same sequence of calls on
+   the same model, not across models built in another order.  The library keeps no counter: the caller
+   passes first_event and advances it by n, so a checkpointed stream resumes exactly.
+   sampled_items_out (may be NULL) receives the n * negatives drawn item ids, event-major; they are mapped
+   from rows on the host only when asked for.  mf_negative_draws is the draw itself (rows, no GPU needed).
+   Errors: mf_online_update's own; MF_ERR_INVALID for negatives outside 0 .. MF_NEG_MAX, a negative_rating
+   that is not finite, first_event < 0, N >= 2^31, or flavour == MF_ONLINE_SPARK_SWEEP (its sequence is not
+   the arrival order).  negatives == 0 is exactly mf_online_update; n == 0 is valid.  Validation runs
+   before anything is inserted or updated. */
+#define MF_NEG_MAX 64
+int mf_online_update_sampled(mf_ctx* ctx, const int32_t* users, const int32_t* items, const double* ratings,
+                             int64_t n, int flavour, int32_t negatives, double negative_rating,
+                             int64_t seed, int64_t first_event,
+                             int32_t* sampled_items_out /* [n * negatives] item ids, or NULL */,
+                             int64_t* touched_users, int64_t* touched_items);
+/* rows_out[j * negatives + s] = the draw above for event first_event + j with pos_row[j] < pool.
+   MF_ERR_INVALID: n < 0, negatives outside 0 .. MF_NEG_MAX, first_event < 0, pool outside 1 .. 2^31, a
+   pos_row outside the pool, or pool == 1 with something to draw. */
+int mf_negative_draws(int64_t seed, int64_t first_event, int64_t n, int32_t negatives, int64_t pool,
+                      const int32_t* pos_row /* [n] */, int32_t* rows_out /* [n * negatives] */);
+/* mf_online_prequential with mf_online_update_sampled as its step 2.  Step 1 is unchanged: it ranks the n
+   events against the model on entry.  Errors: mf_online_prequential's and mf_online_update_sampled's. */
+int mf_online_prequential_sampled(mf_ctx* ctx, const int32_t* users, const int32_t* items, const double* ratings,
+                                  int64_t n, int flavour, int32_t top_n,
+                                  const int32_t* excl_user, const int32_t* excl_item, int64_t n_excl,
+                                  mf_prequential* out, int32_t* rank_out /* [n] or NULL */,
+                                  int64_t* touched_users, int64_t* touched_items,
+                                  int32_t negatives, double negative_rating, int64_t seed, int64_t first_event,
+                                  int32_t* sampled_items_out /* [n * negatives] or NULL */);
 /* Vectors for specific ids (found[j] = 0 for unknown ids). */
 int mf_lookup(mf_ctx* ctx, int side, const int32_t* ids, int64_t n, double* vecs_out,
               uint8_t* found);

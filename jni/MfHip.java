@@ -72,6 +72,18 @@ public final class MfHip {
   public static native void onlinePrequential(long ctx, int[] users, int[] items, double[] r,
                                               int flavour, int numPartitions, int topN,
                                               int[] exclUser, int[] exclItem, double[] metricsOut, int[] ranksOut);
+  // implicit feedback (mf_online_update_sampled / mf_online_prequential_sampled): every event is followed
+  // by `negatives` (0 .. 64) updates (user, another item drawn on the device, negRating).  firstEvent: the
+  // events of the stream before this batch -- the caller adds users.length after every call.  sampledOut
+  // (may be null, length >= users.length * negatives) receives the drawn item ids, event-major.
+  public static native void onlineUpdateSampled(long ctx, int[] users, int[] items, double[] r, int flavour,
+                                                int negatives, double negRating, long seed, long firstEvent,
+                                                int[] sampledOut);
+  public static native void onlinePrequentialSampled(long ctx, int[] users, int[] items, double[] r,
+                                                     int flavour, int topN, int[] exclUser, int[] exclItem,
+                                                     double[] metricsOut, int[] ranksOut, int negatives,
+                                                     double negRating, long seed, long firstEvent,
+                                                     int[] sampledOut);
   public static native void blockUpdate(long ctx, double[] r, int[] uidx, int[] iidx,
                                         double[] users, int[] uomega, double[] items, int[] iomega,
                                         int k, int iteration, int ratingBlockId, long seed,

@@ -428,6 +428,77 @@ JNIEXPORT void JNICALL JFN(onlinePrequential)(JNIEnv* env, jclass c, jlong h, ji
   check(env, st);
 }
 
+// metricsOut[0 .. 11] of the prequential natives from the record
+static void store_prequential(double* o, const mf_prequential* m) {
+  o[0] = (double)m->events;
+  o[1] = (double)m->evaluated;
+  o[2] = (double)m->cold;
+  o[3] = (double)m->excluded;
+  o[4] = (double)m->hits;
+  o[5] = m->sum_ndcg;
+  o[6] = m->sum_rr;
+  o[7] = m->sum_pr;
+  o[8] = m->ndcg;
+  o[9] = m->mrr;
+  o[10] = m->hit_rate;
+  o[11] = m->mpr;
+}
+
+// the negatives' count against MF_NEG_MAX and the length of sampledOut (may be null)
+static int sampled_shape(JNIEnv* env, jsize n, jint negatives, jintArray sampled) {
+  if (require(env, negatives >= 0 && negatives <= MF_NEG_MAX, "negatives must be in 0 .. 64")) return 1;
+  return require(env, !sampled || (jlong)len(env, sampled) >= (jlong)n * negatives,
+                 "sampledOut must be null or hold users.length * negatives entries");
+}
+
+JNIEXPORT void JNICALL JFN(onlineUpdateSampled)(JNIEnv* env, jclass c, jlong h, jintArray u, jintArray i,
+                                                jdoubleArray r, jint flavour, jint negatives, jdouble negRating,
+                                                jlong seed, jlong firstEvent, jintArray sampled) {
+  jsize n = 0;
+  if (rating_columns(env, u, i, r, &n)) return;
+  if (sampled_shape(env, n, negatives, sampled)) return;
+  Elems e[4];
+  const jarray arr[4] = {u, i, r, sampled};
+  const int kind[4] = {kInt, kInt, kDouble, kInt};
+  if (acquire_all(env, e, arr, kind, 4)) return;
+  int st = mf_online_update_sampled(CTX(h), (const int32_t*)e[0].p, (const int32_t*)e[1].p, (const double*)e[2].p, n,
+                                    flavour, negatives, negRating, seed, firstEvent, (int32_t*)e[3].p, NULL, NULL);
+  release(env, &e[3], st == MF_OK ? 0 : JNI_ABORT);
+  for (int x = 2; x >= 0; --x) release(env, &e[x], JNI_ABORT);
+  check(env, st);
+}
+
+JNIEXPORT void JNICALL JFN(onlinePrequentialSampled)(JNIEnv* env, jclass c, jlong h, jintArray u, jintArray i,
+                                                     jdoubleArray r, jint flavour, jint top, jintArray xu,
+                                                     jintArray xi, jdoubleArray metrics, jintArray ranks,
+                                                     jint negatives, jdouble negRating, jlong seed, jlong firstEvent,
+                                                     jintArray sampled) {
+  if (require(env, u && i && r && len(env, u) == len(env, i) && len(env, u) == len(env, r),
+              "users, items and ratings must match in length"))
+    return;
+  const jsize n = len(env, u), ne = xu ? len(env, xu) : 0;
+  if (require(env, metrics && len(env, metrics) >= 12, "metricsOut must hold 12 entries")) return;
+  if (require(env, !ranks || len(env, ranks) >= n, "ranksOut must be null or hold one entry per event")) return;
+  if (require(env, (!xu && !xi) || (xu && xi && len(env, xu) == len(env, xi)),
+              "exclUser and exclItem must both be null or match in length"))
+    return;
+  if (sampled_shape(env, n, negatives, sampled)) return;
+  Elems e[8];
+  const jarray arr[8] = {u, i, r, xu, xi, metrics, ranks, sampled};
+  const int kind[8] = {kInt, kInt, kDouble, kInt, kInt, kDouble, kInt, kInt};
+  if (acquire_all(env, e, arr, kind, 8)) return;
+  mf_prequential m;
+  int st = mf_online_prequential_sampled(CTX(h), n ? (const int32_t*)e[0].p : NULL, n ? (const int32_t*)e[1].p : NULL,
+                                         n ? (const double*)e[2].p : NULL, n, flavour, top,
+                                         ne ? (const int32_t*)e[3].p : NULL, ne ? (const int32_t*)e[4].p : NULL, ne, &m,
+                                         (int32_t*)e[6].p, NULL, NULL, negatives, negRating, seed, firstEvent,
+                                         (int32_t*)e[7].p);
+  if (st == MF_OK) store_prequential((double*)e[5].p, &m);
+  for (int x = 7; x >= 5; --x) release(env, &e[x], st == MF_OK ? 0 : JNI_ABORT);
+  for (int x = 4; x >= 0; --x) release(env, &e[x], JNI_ABORT);
+  check(env, st);
+}
+
 typedef int (*eval_fn)(JNIEnv*, jlong, const int32_t*, const int32_t*, const double*, jsize, jdouble, double*);
 
 static int call_rmse(JNIEnv* env, jlong h, const int32_t* u, const int32_t* i, const double* r, jsize n, jdouble unused,

@@ -12,6 +12,7 @@
 #include "context.hpp"
 #include "jvm_random.hpp"
 #include "kernels.hpp"
+#include "neg_sample.hpp"
 #include "plan.hpp"
 
 using namespace mfhip;
@@ -322,6 +323,37 @@ int mf_online_prequential(mf_ctx* ctx, const int32_t* u, const int32_t* i, const
   });
 }
 
+int mf_online_prequential_sampled(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n,
+                                  int flavour, int32_t top_n, const int32_t* excl_user, const int32_t* excl_item,
+                                  int64_t n_excl, mf_prequential* out, int32_t* rank_out, int64_t* touched_users,
+                                  int64_t* touched_items, int32_t negatives, double negative_rating, int64_t seed,
+                                  int64_t first_event, int32_t* sampled_items_out) {
+  return guarded([&] {
+    // everything mf_online_update_sampled would refuse is refused here, before the model is touched
+    const NegSampling neg{negatives, negative_rating, seed, first_event};
+    check_negative_sampling(neg);
+    MF_REQUIRE(ctx, "null context");
+    MF_REQUIRE(out, "out is null");
+    MF_REQUIRE(top_n >= 1 && top_n <= MF_RECOMMEND_MAX_TOP,
+               "top_n must be in [1, " + std::to_string(MF_RECOMMEND_MAX_TOP) + "]");
+    MF_REQUIRE(n >= 0 && n_excl >= 0, "negative count");
+    MF_REQUIRE(n == 0 || (u && i && r), "bad rating arrays");
+    MF_REQUIRE(n_excl == 0 || (excl_user && excl_item), "null exclusion list");
+    if (ctx->rank_mode)
+      fail(MF_ERR_STATE, "mf_online_prequential_sampled runs on a single-process context; a rank-mode context "
+                         "(mf_create_rank) holds only its own users' rows");
+    MF_REQUIRE(ctx->shards.size() == 1, "online updates run on a single-device context");
+    MF_REQUIRE(flavour >= MF_ONLINE_NEXT_FACTORS && flavour < MF_ONLINE_SPARK_SWEEP,
+               "MF_ONLINE_NEXT_FACTORS or MF_ONLINE_DELTA: MF_ONLINE_SPARK_SWEEP has no sampled form");
+    MF_REQUIRE(n < (int64_t{1} << 31) && n * (1 + negatives) < (int64_t{1} << 31),
+               "a sampled batch holds fewer than 2^31 updates");
+    require_healthy(ctx);
+    det_spec_wait(ctx, true);  // new ids change the layouts the builds read
+    online_prequential_sampled(ctx, u, i, r, n, flavour, top_n, excl_user, excl_item, n_excl, neg, sampled_items_out,
+                               out, rank_out, touched_users, touched_items);
+  });
+}
+
 int mf_debug_rank_csr(mf_ctx* ctx, int query_side, int ground_truth, const int32_t* query, const int32_t* cand,
                       int64_t n, int32_t* q_ids_out, int64_t* off_out, int32_t* entries_out, int64_t cap_q,
                       int64_t cap_e, int64_t* nq_out, int64_t* ne_out) {
@@ -429,6 +461,38 @@ int mf_online_update(mf_ctx* ctx, const int32_t* u, const int32_t* i, const doub
     MF_REQUIRE(ctx, "null context");
     det_spec_wait(ctx, true);  // new ids change the layouts the builds read
     online_update(ctx, u, i, r, n, flavour, num_partitions, touched_users, touched_items);
+  });
+}
+
+int mf_online_update_sampled(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n, int flavour,
+                             int32_t negatives, double negative_rating, int64_t seed, int64_t first_event,
+                             int32_t* sampled_items_out, int64_t* touched_users, int64_t* touched_items) {
+  return guarded([&] {
+    const NegSampling neg{negatives, negative_rating, seed, first_event};
+    check_negative_sampling(neg);
+    MF_REQUIRE(ctx, "null context");
+    det_spec_wait(ctx, true);  // new ids change the layouts the builds read
+    online_update_sampled(ctx, u, i, r, n, flavour, neg, sampled_items_out, touched_users, touched_items);
+  });
+}
+
+int mf_negative_draws(int64_t seed, int64_t first_event, int64_t n, int32_t negatives, int64_t pool,
+                      const int32_t* pos_row, int32_t* rows_out) {
+  return guarded([&] {
+    MF_REQUIRE(n >= 0, "negative count");
+    MF_REQUIRE(negatives >= 0 && negatives <= kNegMax, "negatives must be in [0, " + std::to_string(kNegMax) + "]");
+    MF_REQUIRE(first_event >= 0, "first_event must not be negative");
+    MF_REQUIRE(pool >= 1 && pool <= (int64_t{1} << 31), "pool must be in [1, 2^31]");
+    if (n == 0 || negatives == 0) return;
+    MF_REQUIRE(pos_row && rows_out, "null argument");
+    MF_REQUIRE(pool >= 2, "a pool of one row holds no negative");
+    for (int64_t j = 0; j < n; ++j) {
+      MF_REQUIRE(pos_row[j] >= 0 && pos_row[j] < pool, "pos_row outside the pool");
+      for (int32_t s = 0; s < negatives; ++s)
+        rows_out[j * negatives + s] = static_cast<int32_t>(
+            neg_row(static_cast<uint64_t>(seed), static_cast<uint64_t>(first_event) + static_cast<uint64_t>(j),
+                    static_cast<uint32_t>(s), static_cast<uint32_t>(pool), static_cast<uint32_t>(pos_row[j])));
+    }
   });
 }
 

@@ -122,6 +122,7 @@ struct OnlineSweepScratch {
   DevBuf icnt, iwave;                      // per item row: sampled update counts, own wave (-1: none)
   DevBuf soa, multi, waves;                // the f64 sweep's entry arrays, multi-item flags, wave table
   DevBuf miss;                             // the device id lookup's miss count
+  DevBuf pos;                              // a sampled batch's events as uploaded (k_neg_expand writes `in`)
   // the plan's independent parts run side by side: the tickets' user sort on s2, the touched-item
   // flags on s3 (each with its own scratch), joined back into the caller's stream
   DevBuf tmp2, tmp3, iota2, iflag;

@@ -333,6 +333,15 @@ void consolidate(mf_ctx* ctx, Shard& dst);
 // online.cpp
 void online_update(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n, int flavour,
                    int num_partitions, int64_t* tu, int64_t* ti, double* uout = nullptr, double* iout = nullptr);
+// mf_online_update_sampled: the batch with `negatives` drawn updates (neg_sample.hpp) behind every event
+struct NegSampling {
+  int32_t negatives = 0;
+  double rating = 0.0;
+  int64_t seed = 0, first_event = 0;
+};
+void check_negative_sampling(const NegSampling& neg);
+void online_update_sampled(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n, int flavour,
+                           const NegSampling& neg, int32_t* sampled_out, int64_t* tu, int64_t* ti);
 void block_update(mf_ctx* ctx, const double* r, const int32_t* uidx, const int32_t* iidx, int64_t len, double* users,
                   const int32_t* uomega, int64_t nu, double* items, const int32_t* iomega, int64_t ni, int k,
                   int iteration, int rating_block_id, int64_t seed, double lr, int lr_method, double lr_arg,
@@ -365,6 +374,11 @@ int64_t pair_ranks(mf_ctx* ctx, int qside, const int32_t* q, const int32_t* c, i
 void online_prequential(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n, int flavour,
                         int num_partitions, int32_t top_n, const int32_t* eu, const int32_t* ei, int64_t ne,
                         mf_prequential* out, int32_t* rank_out, int64_t* tu, int64_t* ti);
+// ... with online_update_sampled as step 2
+void online_prequential_sampled(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n,
+                                int flavour, int32_t top_n, const int32_t* eu, const int32_t* ei, int64_t ne,
+                                const NegSampling& neg, int32_t* sampled_out, mf_prequential* out, int32_t* rank_out,
+                                int64_t* tu, int64_t* ti);
 
 // als.cpp
 void als_check(const mf_ctx* ctx);

@@ -116,6 +116,17 @@ void launch_id_lookup(hipStream_t st, uint32_t* in, int64_t n, const void* uslot
                       uint64_t imask, int32_t* misses);
 // slots[pos[j]] = vals[j] (8-B slots): the mirror takes the host table's writes since its last sync
 void launch_id_scatter(hipStream_t st, void* slots, const uint32_t* pos, const void* vals, int64_t m);
+
+// ---- kernels_negsample.hip: the sampled online batch ---------------------------------------------
+// mf_online_update_sampled's expansion (kernels_negsample.hip): pos holds the n_in events as
+// launch_id_lookup leaves them (user rows, item rows, ratings -- floats when rf32); out receives the
+// N = n_in * (1 + negatives) updates in the same layout, event j's own record followed by its negatives
+// (the event's user row, neg_row(seed, first_event + j, s, pool, its item row) of neg_sample.hpp,
+// neg_rating), the batch online_sweep_plan takes.  pool: the item rows of the model.  skip (may be
+// null): nothing is written when *skip != 0 (the lookup's miss count, read on the device).
+void launch_neg_expand(hipStream_t st, const uint32_t* pos, int64_t n_in, int32_t negatives, uint32_t pool,
+                       int64_t seed, int64_t first_event, double neg_rating, bool rf32, uint32_t* out,
+                       const int32_t* skip);
 // The f64 online batch on the deterministic sweep (kernels_detsweep.hip): the plan's entries as
 // SoA arrays in sc.soa (eu / ei / eq / er, padded by kDetPad) and one DetWave per wave (single-item
 // flag from the entries) into waves[0 .. W).  Call after online_sweep_plan on the same scratch.

@@ -1,4 +1,5 @@
-// online.cpp -- online micro-batches (mf_online_update / mf_online_update_out), mf_block_update,
+// online.cpp -- online micro-batches (mf_online_update / mf_online_update_out, and
+// mf_online_update_sampled, which follows every event with sampled negatives), mf_block_update,
 // which runs one rating block through the same device plan, and mf_set_factors.
 #include <algorithm>
 #include <atomic>
@@ -12,6 +13,7 @@
 #include "context.hpp"
 #include "jvm_random.hpp"
 #include "kernels.hpp"
+#include "neg_sample.hpp"
 #include "plan.hpp"
 
 namespace mfhip {
@@ -133,16 +135,22 @@ constexpr uint32_t kMiss = 0xFFFFFFFFu;  // a rating's row while its id is not i
 // One online batch on its way through online_update's stages: the caller's arrays, the kernel
 // chosen for it, the upload's layout, the factor rows of its ratings and what is queued on the
 // shard's stream so far.
+// A batch has n_in events (the caller's arrays: what is staged, looked up and given new rows) and n
+// updates (what is planned, swept and counted).  They differ only for a sampled batch (neg.negatives
+// > 0, n = n_in * (1 + negatives)): its expansion -- on the device behind the id lookup, else on
+// the host (expand_host) -- turns the events' rows into the updates, and from there it is an ordinary
+// batch of n.
 struct OnlineBatch {
   mf_ctx* ctx;
   Shard& s;
   const int32_t* u;
   const int32_t* i;
   const double* r;
-  int64_t n;
+  int64_t n_in, n;
   int flavour, num_partitions;
   int64_t *tu, *ti;
   double *uout, *iout;
+  NegSampling neg;
   int k = ctx->P.num_factors;
   int64_t u0 = ctx->U.rows(), i0 = ctx->I.rows();  // rows before this batch
   PhaseClock clk;
@@ -173,9 +181,16 @@ struct OnlineBatch {
   uint32_t nsingle = 0;  // waves [0, nsingle) hold one item each: k_online_f32's lean single-item path
   DetEntries det;
 
+  std::vector<uint32_t> xu, xi;  // a sampled batch expanded for the level replay: rows and ratings
+  std::vector<double> xr;
+
   bool outs() const { return uout || iout; }
   bool sweeps() const { return path != OnlinePath::kLevels; }
-  // ratings [lo, hi) into the upload's rating array
+  bool sampled() const { return neg.negatives > 0; }
+  // the expansion runs on the device, behind the lookup that found the events' rows there
+  bool dev_expand() const { return sampled() && dev_lookup; }
+  size_t event_bytes() const { return static_cast<size_t>(n_in) * (rf32 ? 12 : 16); }
+  // the events' ratings [lo, hi) into the upload's rating array
   void stage_ratings(void* dst, int64_t lo, int64_t hi) const {
     if (rf32) {
       float* f = static_cast<float*>(dst);
@@ -234,8 +249,10 @@ void choose_online_path(OnlineBatch& b) {
 void open_row_arrays(OnlineBatch& b) {
   mf_ctx* ctx = b.ctx;
   Shard& s = b.s;
-  const int64_t n = b.n;
-  if (b.direct) {
+  const int64_t n = b.n_in;
+  // (a sampled batch expanded on the host keeps its events' rows in the context's arrays: the pinned
+  // upload takes the expanded batch, expand_host)
+  if (b.direct && (!b.sampled() || b.dev_lookup)) {
     DeviceGuard g(s.device);
     MF_HIP(hipStreamSynchronize(s.stream));  // det_pin may still feed an earlier copy
     s.det_pin.alloc(static_cast<size_t>(n) * 16);
@@ -293,20 +310,32 @@ void finish_sweep(OnlineBatch& b) {
   b.ctx->stats.updates += b.n;
 }
 
+// A sampled batch's events in sc.pos (rows as the lookup left them, or as the host has completed them)
+// into the n updates in sc.in, with the model's item rows as they stand now as the pool; skip: the
+// lookup's miss count, as queue_f32_sweep takes it.
+void queue_expansion(OnlineBatch& b, const int32_t* skip) {
+  OnlineSweepScratch& sc = b.s.online_sc;
+  launch_neg_expand(b.s.stream, sc.pos.as<uint32_t>(), b.n_in, b.neg.negatives, static_cast<uint32_t>(b.ctx->I.rows()),
+                    b.neg.seed, b.neg.first_event, b.neg.rating, b.rf32, sc.in.as<uint32_t>(), skip);
+}
+
 // The direct path with the device lookup: the ids go up as they are, the device replaces them by
 // their rows and counts the misses; the plan and -- f32 -- the sweep, or -- f64 -- the sweep's
 // entries, are queued behind the lookup, and one sync brings back the miss count with whatever
-// they read back.  True when the batch is done (f32, no new id).
+// they read back.  A sampled batch's events go to sc.pos instead, and its expansion into sc.in is
+// queued between the lookup and the plan.  True when the batch is done (f32, no new id).
 bool stage_and_lookup_device(OnlineBatch& b) {
   mf_ctx* ctx = b.ctx;
   Shard& s = b.s;
-  const int64_t n = b.n;
+  const int64_t n = b.n_in;
   uint32_t *ur = b.ur, *ir = b.ir;
   DeviceGuard g(s.device);
   OnlineSweepScratch& sc = s.online_sc;
   sync_dev_index(s, ctx->U.index, s.didx[0]);
   sync_dev_index(s, ctx->I.index, s.didx[1]);
   sc.in.alloc(b.in_bytes);
+  DevBuf& up = b.sampled() ? sc.pos : sc.in;
+  up.alloc(b.event_bytes());
   // (staging in pieces with each piece's upload queued behind it was slower: 2-3 ms against ~1 ms
   // per NFLX batch, gpurun_out/r6d)
   parallel_for(n, [&](int64_t lo2, int64_t hi2, int) {
@@ -315,14 +344,15 @@ bool stage_and_lookup_device(OnlineBatch& b) {
     std::memcpy(ir + lo2, b.i + lo2, c * 4);
     b.stage_ratings(ir + n, lo2, hi2);
   });
-  MF_HIP(hipMemcpyAsync(sc.in.get(), ur, b.in_bytes, hipMemcpyHostToDevice, s.stream));
+  MF_HIP(hipMemcpyAsync(up.get(), ur, b.event_bytes(), hipMemcpyHostToDevice, s.stream));
   b.clk.lap("online: staging + upload");
   sc.miss.alloc(4);
   MF_HIP(hipMemsetAsync(sc.miss.get(), 0, 4, s.stream));
   const DevIndex &du = s.didx[0], &di = s.didx[1];
-  launch_id_lookup(s.stream, sc.in.as<uint32_t>(), n, du.cap ? du.slots.get() : nullptr, du.cap - 1,
+  launch_id_lookup(s.stream, up.as<uint32_t>(), n, du.cap ? du.slots.get() : nullptr, du.cap - 1,
                    di.cap ? di.slots.get() : nullptr, di.cap - 1, sc.miss.as<int32_t>());
   MF_HIP(hipMemcpyAsync(b.pin4, sc.miss.get(), 4, hipMemcpyDeviceToHost, s.stream));
+  if (b.sampled()) queue_expansion(b, sc.miss.as<int32_t>());  // (void with the plan when there are misses)
   b.plan();  // (the plan's kernels skip rows past the tables: the misses)
   // f32: the sweep goes right behind the plan, so the batch runs through without the host in the
   // loop; a batch with misses skips it on the device and takes the host's path
@@ -344,7 +374,7 @@ bool stage_and_lookup_device(OnlineBatch& b) {
   }
   if (m > 0) {  // the rows as found (kMiss where absent) back into the pinned buffer
     b.planned = b.det_queued = false;
-    MF_HIP(hipMemcpyAsync(ur, sc.in.get(), static_cast<size_t>(n) * 8, hipMemcpyDeviceToHost, s.stream));
+    MF_HIP(hipMemcpyAsync(ur, up.get(), static_cast<size_t>(n) * 8, hipMemcpyDeviceToHost, s.stream));
     MF_HIP(hipStreamSynchronize(s.stream));
   }
   b.uploaded = m == 0;
@@ -354,13 +384,13 @@ bool stage_and_lookup_device(OnlineBatch& b) {
 // Rows of known ids in parallel (the index is only read; kMiss marks the others).
 void lookup_host(OnlineBatch& b) {
   mf_ctx* ctx = b.ctx;
-  const int64_t n = b.n;
+  const int64_t n = b.n_in;
   uint32_t *ur = b.ur, *ir = b.ir;
   std::atomic<int64_t> misses{0};
   parallel_for(n, [&](int64_t lo2, int64_t hi2, int) {
     ctx->U.index.find_many(b.u + lo2, hi2 - lo2, ur + lo2);
     ctx->I.index.find_many(b.i + lo2, hi2 - lo2, ir + lo2);
-    if (b.direct) b.stage_ratings(ir + n, lo2, hi2);
+    if (b.direct && !b.sampled()) b.stage_ratings(ir + n, lo2, hi2);
     int64_t m = 0;
     for (int64_t j = lo2; j < hi2; ++j) m += (ur[j] == kMiss) + (ir[j] == kMiss);
     misses += m;
@@ -373,11 +403,57 @@ void lookup_host(OnlineBatch& b) {
 void assign_new_rows(OnlineBatch& b) {
   mf_ctx* ctx = b.ctx;
   if (b.misses > 0)
-    for (int64_t j = 0; j < b.n; ++j) {
+    for (int64_t j = 0; j < b.n_in; ++j) {
       if (b.ur[j] == kMiss) b.ur[j] = static_cast<uint32_t>(online_row(ctx, ctx->U, b.u[j], b.fu));
       if (b.ir[j] == kMiss) b.ir[j] = static_cast<uint32_t>(online_row(ctx, ctx->I, b.i[j], b.fi));
     }
   b.clk.lap("online: id lookup");
+}
+
+// A sampled batch off the device-lookup path (MFHIP_TEST online_lookup=host, the level replay): the
+// events' final rows into the n updates, the draws of k_neg_expand (neg_sample.hpp) -- into the pinned
+// upload for a sweep, into the batch's own arrays for the levels.  From here b.ur / b.ir / b.r are the
+// updates'.
+void expand_host(OnlineBatch& b) {
+  Shard& s = b.s;
+  const int64_t N = b.n, per = 1 + b.neg.negatives;
+  const uint32_t pool = static_cast<uint32_t>(b.ctx->I.rows());
+  uint32_t *pu, *pi;
+  double* pr = nullptr;
+  float* prf = nullptr;
+  if (b.direct) {
+    DeviceGuard g(s.device);
+    MF_HIP(hipStreamSynchronize(s.stream));  // det_pin may still feed an earlier copy
+    s.det_pin.alloc(b.in_bytes);
+    pu = s.det_pin.as<uint32_t>();
+    pi = pu + N;
+    if (b.rf32) prf = reinterpret_cast<float*>(pi + N);
+    else pr = reinterpret_cast<double*>(pi + N);
+  } else {
+    b.xu.resize(N);
+    b.xi.resize(N);
+    b.xr.resize(N);
+    pu = b.xu.data();
+    pi = b.xi.data();
+    pr = b.xr.data();
+  }
+  const uint32_t *eu = b.ur, *ei = b.ir;
+  const double* er = b.r;
+  const uint64_t seed = static_cast<uint64_t>(b.neg.seed), t0 = static_cast<uint64_t>(b.neg.first_event);
+  parallel_for(N, [&](int64_t lo2, int64_t hi2, int) {
+    for (int64_t x = lo2; x < hi2; ++x) {
+      const int64_t j = x / per, sx = x - j * per;
+      pu[x] = eu[j];
+      pi[x] = sx == 0 ? ei[j] : neg_row(seed, t0 + static_cast<uint64_t>(j), static_cast<uint32_t>(sx - 1), pool, ei[j]);
+      const double rv = sx == 0 ? er[j] : b.neg.rating;
+      if (prf) prf[x] = static_cast<float>(rv);
+      else pr[x] = rv;
+    }
+  });
+  b.ur = pu;
+  b.ir = pi;
+  if (!b.direct) b.r = pr;
+  b.clk.lap("online: negatives (host)");
 }
 
 // Touched-row counts (UpdateSeparatedHashMap.updates, OfflineSpark.scala:33-67) on the host; the
@@ -488,7 +564,12 @@ void run_sweep(OnlineBatch& b, const std::vector<int32_t>& order) {
   DeviceGuard g(s.device);
   OnlineSweepScratch& sc = s.online_sc;
   if (!b.direct) stage_in_order(b, order);
-  if (!b.uploaded) {  // (the device lookup left the batch's rows in sc.in already)
+  if (!b.uploaded && b.dev_expand()) {
+    // the events' rows, now complete, beside their ratings in sc.pos; expanded again with the final pool
+    MF_HIP(hipMemcpyAsync(sc.pos.get(), s.det_pin.as<uint32_t>(), static_cast<size_t>(b.n_in) * 8,
+                          hipMemcpyHostToDevice, s.stream));
+    queue_expansion(b, nullptr);
+  } else if (!b.uploaded) {  // (the device lookup left the batch's rows in sc.in already)
     sc.in.alloc(b.in_bytes);
     MF_HIP(hipMemcpyAsync(sc.in.get(), s.det_pin.as<uint32_t>(), b.in_bytes, hipMemcpyHostToDevice, s.stream));
   }
@@ -588,23 +669,24 @@ void run_levels(OnlineBatch& b, const std::vector<int32_t>& order) {
   ctx->stats.updates += n;
 }
 
-}  // namespace
-
-void online_update(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n, int flavour,
-                   int num_partitions, int64_t* tu, int64_t* ti, double* uout, double* iout) {
+void check_online_call(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n, int flavour) {
   MF_REQUIRE(ctx->shards.size() == 1 && !ctx->rank_mode, "online updates run on a single-device context");
   MF_REQUIRE(flavour >= MF_ONLINE_NEXT_FACTORS && flavour <= MF_ONLINE_SPARK_SWEEP, "unknown online flavour");
   MF_REQUIRE(n >= 0 && (n == 0 || (u && i && r)), "bad rating arrays");
-  MF_REQUIRE(!(uout || iout) || flavour != MF_ONLINE_SPARK_SWEEP,
-             "MF_ONLINE_SPARK_SWEEP emits touched rows only (OfflineSpark.scala:33-67): no per-rating outputs");
-  require_healthy(ctx);
+}
+
+// The batch through its stages; neg.negatives > 0: every event followed by its sampled negatives.
+void run_online_batch(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n, int flavour,
+                      int num_partitions, int64_t* tu, int64_t* ti, double* uout, double* iout,
+                      const NegSampling& neg) {
   if (!ctx->have_model) {
     ctx->U = SideLayout();
     ctx->I = SideLayout();
     ctx->have_model = true;
     ++ctx->layout_gen;
   }
-  OnlineBatch b{ctx, ctx->shards[0], u, i, r, n, flavour, num_partitions, tu, ti, uout, iout};
+  OnlineBatch b{ctx, ctx->shards[0], u, i, r, n, n * (1 + neg.negatives), flavour, num_partitions, tu, ti, uout, iout,
+                neg};
   choose_online_path(b);
   open_row_arrays(b);
   if (b.dev_lookup) {
@@ -613,6 +695,7 @@ void online_update(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double
     lookup_host(b);
   }
   assign_new_rows(b);
+  if (b.sampled() && !b.dev_expand()) expand_host(b);
   if (!b.sweeps()) count_touched_host(b);
   init_new_rows(b);
   if (n == 0) return;
@@ -620,6 +703,61 @@ void online_update(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double
   if (!b.direct) spark_sweep_order(b, order);
   if (b.sweeps()) run_sweep(b, order);
   else run_levels(b, order);
+}
+
+// True when the model will hold a single item row once the batch's new ids have theirs: no row to
+// draw a negative from.  Only a model of at most one item can end so, and then only when every event
+// names the same item.
+bool single_item_pool(const mf_ctx* ctx, const int32_t* i, int64_t n) {
+  if (!ctx->have_model || ctx->I.rows() == 0) return std::all_of(i, i + n, [&](int32_t x) { return x == i[0]; });
+  if (ctx->I.rows() > 1) return false;
+  const int32_t only = ctx->I.row_id[0];
+  return std::all_of(i, i + n, [&](int32_t x) { return x == only; });
+}
+}  // namespace
+
+void online_update(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n, int flavour,
+                   int num_partitions, int64_t* tu, int64_t* ti, double* uout, double* iout) {
+  check_online_call(ctx, u, i, r, n, flavour);
+  MF_REQUIRE(!(uout || iout) || flavour != MF_ONLINE_SPARK_SWEEP,
+             "MF_ONLINE_SPARK_SWEEP emits touched rows only (OfflineSpark.scala:33-67): no per-rating outputs");
+  require_healthy(ctx);
+  run_online_batch(ctx, u, i, r, n, flavour, num_partitions, tu, ti, uout, iout, NegSampling{});
+}
+
+void check_negative_sampling(const NegSampling& neg) {
+  MF_REQUIRE(neg.negatives >= 0 && neg.negatives <= kNegMax,
+             "negatives must be in [0, " + std::to_string(kNegMax) + "]");
+  MF_REQUIRE(std::isfinite(neg.rating), "negative_rating must be finite");
+  MF_REQUIRE(neg.first_event >= 0, "first_event must not be negative");
+}
+
+void online_update_sampled(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n, int flavour,
+                           const NegSampling& neg, int32_t* sampled_out, int64_t* tu, int64_t* ti) {
+  check_negative_sampling(neg);
+  check_online_call(ctx, u, i, r, n, flavour);
+  MF_REQUIRE(flavour != MF_ONLINE_SPARK_SWEEP,
+             "MF_ONLINE_SPARK_SWEEP has no sampled form: its sequence is not the arrival order");
+  MF_REQUIRE(n < (int64_t{1} << 31) && n * (1 + neg.negatives) < (int64_t{1} << 31),
+             "a sampled batch holds fewer than 2^31 updates");
+  require_healthy(ctx);
+  NegSampling use = neg;
+  if (n == 0 || single_item_pool(ctx, i, n)) use.negatives = 0;  // nothing to draw (from): the plain batch
+  run_online_batch(ctx, u, i, r, n, flavour, 0, tu, ti, nullptr, nullptr, use);
+  if (!sampled_out || use.negatives == 0) return;
+  // the drawn rows as ids: the events' rows again (the device path never brought them to the host)
+  const SideLayout& I = ctx->I;
+  const uint32_t pool = static_cast<uint32_t>(I.rows());
+  const uint64_t seed = static_cast<uint64_t>(neg.seed), t0 = static_cast<uint64_t>(neg.first_event);
+  const int64_t per = neg.negatives;
+  parallel_for(n, [&](int64_t lo2, int64_t hi2, int) {
+    std::vector<uint32_t> rows(static_cast<size_t>(hi2 - lo2));
+    I.index.find_many(i + lo2, hi2 - lo2, rows.data());
+    for (int64_t j = lo2; j < hi2; ++j)
+      for (int64_t sx = 0; sx < per; ++sx)
+        sampled_out[j * per + sx] =
+            I.row_id[neg_row(seed, t0 + static_cast<uint64_t>(j), static_cast<uint32_t>(sx), pool, rows[j - lo2])];
+  });
 }
 
 // mf_block_update: one rating block's updateLocalFactors (DSGDforMF.scala:378-418) on caller

@@ -137,10 +137,10 @@ int64_t pair_ranks(mf_ctx* ctx, int qside, const int32_t* q, const int32_t* c, i
 }
 
 // Step 1: the events' ranks (pair_ranks), their metrics and the fixed-order sums, all complete before
-// step 2, online_update, queues its first kernel.
-void online_prequential(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n, int flavour,
-                        int num_partitions, int32_t top_n, const int32_t* eu, const int32_t* ei, int64_t ne,
-                        mf_prequential* out, int32_t* rank_out, int64_t* tu, int64_t* ti) {
+// step 2, the online update, queues its first kernel.
+namespace {
+void prequential_ranks(mf_ctx* ctx, const int32_t* u, const int32_t* i, int64_t n, int32_t top_n, const int32_t* eu,
+                       const int32_t* ei, int64_t ne, mf_prequential* out, int32_t* rank_out) {
   *out = mf_prequential{};
   out->events = n;
   out->cold = n;
@@ -187,7 +187,22 @@ void online_prequential(mf_ctx* ctx, const int32_t* u, const int32_t* i, const d
     out->hit_rate = static_cast<double>(out->hits) / de;
     out->mpr = out->sum_pr / de;
   }
+}
+}  // namespace
+
+void online_prequential(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n, int flavour,
+                        int num_partitions, int32_t top_n, const int32_t* eu, const int32_t* ei, int64_t ne,
+                        mf_prequential* out, int32_t* rank_out, int64_t* tu, int64_t* ti) {
+  prequential_ranks(ctx, u, i, n, top_n, eu, ei, ne, out, rank_out);
   online_update(ctx, u, i, r, n, flavour, num_partitions, tu, ti);
+}
+
+void online_prequential_sampled(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n,
+                                int flavour, int32_t top_n, const int32_t* eu, const int32_t* ei, int64_t ne,
+                                const NegSampling& neg, int32_t* sampled_out, mf_prequential* out, int32_t* rank_out,
+                                int64_t* tu, int64_t* ti) {
+  prequential_ranks(ctx, u, i, n, top_n, eu, ei, ne, out, rank_out);
+  online_update_sampled(ctx, u, i, r, n, flavour, neg, sampled_out, tu, ti);
 }
 
 }  // namespace mfhip

@@ -3,7 +3,7 @@
 The compute path is libmfhip.so (hand-written HIP for gfx950 behind a C ABI, include/mfhip.h);
 this package is the Python equivalent of the Scala entry points that bind it.
 """
-from . import _lib, jvm, synth
+from . import _lib, jvm, negsample, synth
 from ._lib import MFError, MFNoDeviceError, device_count, version
 from .als import ALS, MatrixFactorizationModel
 from .context import Context, Prequential, RankMetrics, block_update

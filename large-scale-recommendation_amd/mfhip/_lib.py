@@ -43,6 +43,7 @@ ALS_MAX_RANK = 128
 RANK_NMETRICS = 6  # precision, recall, ap, ndcg, rr, hit: a per-query row of mf_rank_eval
 PAIR_RANK_COLD = -1      # mf_pair_ranks: the model does not hold the query id or the candidate id
 PAIR_RANK_EXCLUDED = -2  # ... the pair itself is in the exclusion list
+NEG_MAX = 64             # mf_online_update_sampled: negatives per event at most
 
 
 class MFError(RuntimeError):
@@ -137,7 +138,7 @@ EXPORTS = [
     "mf_learning_rate", "mf_get_params", "mf_read_ratings", "mf_save_model", "mf_load_model",
     "mf_dsgd_restart", "mf_online_update_out", "mf_recommend", "mf_als_fit", "mf_als_prepare",
     "mf_als_run", "mf_als_run_implicit", "mf_als_fit_implicit", "mf_rank_eval", "mf_pair_ranks",
-    "mf_online_prequential",
+    "mf_online_prequential", "mf_online_update_sampled", "mf_negative_draws", "mf_online_prequential_sampled",
 ]
 # The test hooks include/mfhip_testing.h declares (not product surface; same library).
 TESTING_EXPORTS = [
@@ -221,6 +222,12 @@ def lib() -> C.CDLL:
                                     _f64p]),
         "mf_online_prequential": (C.c_int, [_ctxp, _i32p, _i32p, _f64p, C.c_int64, C.c_int, C.c_int, C.c_int32, _i32p,
                                             _i32p, C.c_int64, C.POINTER(mf_prequential), _i32p, _i64p, _i64p]),
+        "mf_online_update_sampled": (C.c_int, [_ctxp, _i32p, _i32p, _f64p, C.c_int64, C.c_int, C.c_int32, C.c_double,
+                                               C.c_int64, C.c_int64, _i32p, _i64p, _i64p]),
+        "mf_negative_draws": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int64, _i32p, _i32p]),
+        "mf_online_prequential_sampled": (C.c_int, [_ctxp, _i32p, _i32p, _f64p, C.c_int64, C.c_int, C.c_int32, _i32p,
+                                                    _i32p, C.c_int64, C.POINTER(mf_prequential), _i32p, _i64p, _i64p,
+                                                    C.c_int32, C.c_double, C.c_int64, C.c_int64, _i32p]),
         "mf_debug_rank_csr": (C.c_int, [_ctxp, C.c_int, C.c_int, _i32p, _i32p, C.c_int64, _i32p, _i64p, _i32p,
                                         C.c_int64, C.c_int64, _i64p, _i64p]),
         "mf_als_fit": (C.c_int, [_ctxp, _i32p, _i32p, _f64p, C.c_int64, C.c_int32, C.c_double, C.c_int32]),

@@ -365,6 +365,61 @@ class Context:
                            mrr=out.mrr, hit_rate=out.hit_rate, mpr=out.mpr, touched_users=tu.value,
                            touched_items=ti.value, ranks=rk[:n] if ranks else None)
 
+    def _sampled_ids(self, buf, n: int, negatives: int):
+        # a batch that leaves the model with one item has no negatives (mf_online_update_sampled)
+        drawn = n > 0 and negatives > 0 and self.num_factors(L.SIDE_ITEM) >= 2
+        return buf[:n * negatives].reshape(n, negatives) if drawn else np.zeros((n, 0), np.int32)
+
+    def online_update_sampled(self, u, i, r, negatives: int, negative_rating: float = 0.0, seed: int = 0,
+                              first_event: int = 0, flavour: int = L.ONLINE_NEXT_FACTORS, sampled: bool = False):
+        """mf_online_update_sampled: online_update on the batch in which every event (u[j], i[j], r[j]) is
+        followed by `negatives` updates (u[j], another item, negative_rating), drawn and expanded on the
+        device (negsample.draws is the draw: event first_event + j, a row of the model's items other than
+        the event's own).  The caller advances first_event by len(u) from call to call.  Returns (touched
+        users, touched items) of the expanded batch, and with sampled=True also the drawn item ids
+        [n, negatives] ([n, 0] when the model ends the batch with a single item: nothing to draw from)."""
+        u, i, r = as_i32(u), as_i32(i), as_f64(r)
+        n = same_length(u, i, r)
+        negatives = int(negatives)
+        ids = np.zeros(max(n * max(negatives, 0), 1), np.int32) if sampled else None
+        tu, ti = C.c_int64(0), C.c_int64(0)
+        check(L.lib().mf_online_update_sampled(self._h, ptr(u, C.c_int32), ptr(i, C.c_int32), ptr(r, C.c_double), n,
+                                               int(flavour), negatives, float(negative_rating), int(seed),
+                                               int(first_event), ptr(ids, C.c_int32) if sampled else None,
+                                               C.byref(tu), C.byref(ti)))
+        if sampled:
+            return tu.value, ti.value, self._sampled_ids(ids, n, negatives)
+        return tu.value, ti.value
+
+    def online_prequential_sampled(self, u, i, r, top_n: int, negatives: int, negative_rating: float = 0.0,
+                                   seed: int = 0, first_event: int = 0, flavour: int = L.ONLINE_NEXT_FACTORS,
+                                   exclude=None, ranks: bool = False, sampled: bool = False):
+        """mf_online_prequential_sampled: online_prequential's step 1 unchanged (the events ranked against
+        the model as it stands), then online_update_sampled.  Returns the Prequential record, and with
+        sampled=True (record, drawn item ids [n, negatives])."""
+        u, i, r = as_i32(u), as_i32(i), as_f64(r)
+        n = same_length(u, i, r)
+        negatives = int(negatives)
+        eq = ec = None
+        ne = 0
+        if exclude is not None:
+            eq, ec = as_i32(exclude[0]), as_i32(exclude[1])
+            ne = same_length(eq, ec)
+        out = L.mf_prequential()
+        rk = np.zeros(max(n, 1), np.int32) if ranks else None
+        ids = np.zeros(max(n * max(negatives, 0), 1), np.int32) if sampled else None
+        tu, ti = C.c_int64(0), C.c_int64(0)
+        check(L.lib().mf_online_prequential_sampled(
+            self._h, ptr(u, C.c_int32), ptr(i, C.c_int32), ptr(r, C.c_double), n, int(flavour), int(top_n),
+            ptr(eq, C.c_int32) if ne else None, ptr(ec, C.c_int32) if ne else None, ne, C.byref(out),
+            ptr(rk, C.c_int32) if ranks else None, C.byref(tu), C.byref(ti), negatives, float(negative_rating),
+            int(seed), int(first_event), ptr(ids, C.c_int32) if sampled else None))
+        rec = Prequential(events=out.events, evaluated=out.evaluated, cold=out.cold, excluded=out.excluded,
+                          hits=out.hits, sum_ndcg=out.sum_ndcg, sum_rr=out.sum_rr, sum_pr=out.sum_pr, ndcg=out.ndcg,
+                          mrr=out.mrr, hit_rate=out.hit_rate, mpr=out.mpr, touched_users=tu.value,
+                          touched_items=ti.value, ranks=rk[:n] if ranks else None)
+        return (rec, self._sampled_ids(ids, n, negatives)) if sampled else rec
+
     def online_update_out(self, u, i, r, flavour: int = L.ONLINE_NEXT_FACTORS, items: bool = True):
         """online_update plus the per-rating records the operators emit (mf_online_update_out):
         NEXT_FACTORS -> (user', item') per rating (FlinkOnlineMF.scala:131-135); DELTA ->

@@ -70,18 +70,32 @@ class PrequentialEvaluator:
     """Test-then-train over a stream of micro-batches on one Context: process() is one
     mf_online_prequential, and one record per batch is kept (`batches`).  The cumulative values are
     sums over the records' sums divided by the evaluated events, so adding batches is exact in the
-    counts and a plain left-to-right f64 sum of the per-batch sums."""
+    counts and a plain left-to-right f64 sum of the per-batch sums.
+    negatives > 0 (implicit feedback): the training step is mf_online_update_sampled -- every event is
+    followed by `negatives` sampled updates (user, another item, negative_rating) drawn with `seed`; the
+    evaluator counts the events it has processed and passes that count as first_event."""
 
-    def __init__(self, ctx: Context, top_n: int, flavour: int = L.ONLINE_NEXT_FACTORS, num_partitions: int = 0):
+    def __init__(self, ctx: Context, top_n: int, flavour: int = L.ONLINE_NEXT_FACTORS, num_partitions: int = 0,
+                 negatives: int = 0, negative_rating: float = 0.0, seed: int = 0):
         self.ctx = ctx
         self.top_n = int(top_n)
         self.flavour = flavour
         self.num_partitions = num_partitions
+        self.negatives = int(negatives)
+        self.negative_rating = float(negative_rating)
+        self.seed = int(seed)
+        self.first_event = 0  # of the next batch: the events processed so far
         self.batches: List[Prequential] = []
 
     def process(self, u, i, r, exclude=None, ranks: bool = False) -> Prequential:
-        rec = self.ctx.online_prequential(u, i, r, self.top_n, self.flavour, self.num_partitions, exclude=exclude,
-                                          ranks=ranks)
+        if self.negatives > 0:
+            rec = self.ctx.online_prequential_sampled(u, i, r, self.top_n, self.negatives, self.negative_rating,
+                                                      self.seed, self.first_event, self.flavour, exclude=exclude,
+                                                      ranks=ranks)
+        else:
+            rec = self.ctx.online_prequential(u, i, r, self.top_n, self.flavour, self.num_partitions,
+                                              exclude=exclude, ranks=ranks)
+        self.first_event += rec.events
         self.add(rec)
         return rec
 
