@@ -351,10 +351,10 @@ int mf_online_prequential(mf_ctx* ctx, const int32_t* users, const int32_t* item
    MLlib's own initial factors (normalised |Gaussian| draws from a per-partition XORShift stream)
    are NOT reproduced: MLlib is not part of the reference tree and its stream depends on Spark's
    partitioning, so factors agree with MLlib's in quality, not in bits.
-   Errors.  MF_ERR_INVALID: lambda <= 0, a negative count, an unknown reg, or a rank above 128 (the
-   k x k normal matrix of a row is kept in LDS).  MF_ERR_STATE: mf_als_run before mf_als_prepare (or
-   after a later mf_dsgd_prepare / mf_dsgd_fit, which rebuilds the rows), a rank-mode context, or a
-   context on more than one device. */
+   Errors.  MF_ERR_INVALID: lambda <= 0, a negative count, an unknown reg, or a rank above 256 (up
+   to 128 the k x k normal matrix of a row is kept in LDS, from 129 to 256 in global memory).
+   MF_ERR_STATE: mf_als_run before mf_als_prepare (or after a later mf_dsgd_prepare / mf_dsgd_fit,
+   which rebuilds the rows), a rank-mode context, or a context on more than one device. */
 int mf_als_fit(mf_ctx* ctx, const int32_t* users, const int32_t* items, const double* ratings, int64_t n,
                int32_t iterations, double lambda, int32_t reg);
 int mf_als_prepare(mf_ctx* ctx, const int32_t* users, const int32_t* items, const double* ratings,

@@ -35,7 +35,7 @@ void als_check(const mf_ctx* ctx) {
     fail(MF_ERR_STATE, "ALS runs on a single-process context on one device");
   MF_REQUIRE(ctx->P.num_factors <= kAlsMaxRank,
              "ALS supports a rank of at most " + std::to_string(kAlsMaxRank) +
-                 " (the k x k normal matrix of a row is kept in LDS); this context has k = " +
+                 " (the widest instance of the half-sweep kernels); this context has k = " +
                  std::to_string(ctx->P.num_factors));
 }
 
@@ -166,6 +166,9 @@ void als_prepare(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* 
   ctx->als_gram_slice = kAlsGramSlice;
   if (const std::string v = test_knob("als_gram_slice"); !v.empty())
     ctx->als_gram_slice = std::min<int64_t>(std::max<int64_t>(1, std::atoll(v.c_str())), 1 << 30);
+  ctx->als_slabs = als_wide_slabs(k, ctx->f64, static_cast<int>(device_cu_count(s.device)));
+  if (const std::string v = test_knob("als_slabs"); !v.empty())
+    ctx->als_slabs = std::min<int64_t>(ctx->als_slabs, std::max<int64_t>(1, std::atoll(v.c_str())));
   if (ctx->f64) {
     als_build_side<double>(ctx, s, kSideU, ur, ir, r, n, ctx->U.rows(), chunk, batch);
     als_build_side<double>(ctx, s, MF_SIDE_ITEM, ir, ur, r, n, ctx->I.rows(), chunk, batch);
@@ -207,6 +210,9 @@ bool als_half(mf_ctx* ctx, int side, double lambda, int32_t reg, double alpha, i
   const AlsItem* d_items = s.als_items[side].as<AlsItem>();
   const AlsSplit* d_splits = s.als_splits[side].as<AlsSplit>();
   const bool weighted = reg == MF_ALS_REG_WEIGHTED;
+  // k > 128: one normal matrix in global memory per workgroup of the grid, however many rows there are
+  const int slabs = static_cast<int>(std::min<int64_t>(ctx->als_slabs, static_cast<int64_t>(A.items.size())));
+  if (slabs > 0) s.als_slab.alloc(static_cast<size_t>(slabs) * als_gram_elems(k) * ctx->es);
   if (only_row >= 0) {
     auto lo = std::lower_bound(A.items.begin(), A.items.end(), only_row,
                                [](const AlsItem& a, int64_t row) { return a.row < row; });
@@ -221,7 +227,7 @@ bool als_half(mf_ctx* ctx, int side, double lambda, int32_t reg, double alpha, i
     launch_als(s.stream, d_items + (lo - A.items.begin()), static_cast<int>(hi - lo),
                d_splits + (sp - A.splits.begin()), split ? 1 : 0, s.als_cols[side].as<int32_t>(),
                s.als_vals[side].get(), Q, X, k, lambda, weighted, ctx->f64, s.als_part.get(), s.als_dump.get(),
-               implicit ? s.als_gram.get() : nullptr, alpha);
+               implicit ? s.als_gram.get() : nullptr, alpha, s.als_slab.get(), slabs);
     MF_HIP(hipGetLastError());
     return true;
   }
@@ -233,7 +239,7 @@ bool als_half(mf_ctx* ctx, int side, double lambda, int32_t reg, double alpha, i
   for (const mf_ctx::AlsBatch& b : A.batches) {
     launch_als(s.stream, d_items + b.item0, static_cast<int>(b.items), d_splits + b.split0, static_cast<int>(b.splits),
                s.als_cols[side].as<int32_t>(), s.als_vals[side].get(), Q, X, k, lambda, weighted, ctx->f64,
-               s.als_part.get(), nullptr, implicit ? s.als_gram.get() : nullptr, alpha);
+               s.als_part.get(), nullptr, implicit ? s.als_gram.get() : nullptr, alpha, s.als_slab.get(), slabs);
     MF_HIP(hipGetLastError());
     ctx->stats.kernel_launches += 1 + (b.splits > 0);
   }

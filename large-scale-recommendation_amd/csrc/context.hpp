@@ -140,6 +140,8 @@ struct Shard {
   // ALS (mf_als_prepare): per solved side [user, item] the CSR (counterpart rows, ratings) and the
   // work lists; the long rows' partial systems of one launch; the testing hook's output
   DevBuf als_cols[2], als_vals[2], als_items[2], als_splits[2], als_part, als_dump;
+  // ... at a rank above 128 the normal matrices of the resident workgroups (kernels_als_wide.hip)
+  DevBuf als_slab;
   // ... the implicit half-sweep: per side its rated rows, the Gram partials of one side and G itself
   DevBuf als_rated[2], als_gram_part, als_gram;
   // profiling
@@ -212,6 +214,9 @@ struct mf_ctx {
     int64_t rated = 0;  // rows with at least one rating (the length of Shard::als_rated)
   } als[2];
   int64_t als_gram_slice = 0;  // rated rows per workgroup of k_als_gram (fixed in mf_als_prepare)
+  // k > 128: normal-matrix slabs = workgroups per launch of the wide kernels (fixed in mf_als_prepare
+  // from the device's CU count; MFHIP_TEST als_slabs=N caps it, results do not depend on it)
+  int64_t als_slabs = 0;
   bool als_prepared = false;
   int64_t als_half_sweeps = 0;  // half-sweeps run since mf_als_prepare (even: the item side is next)
   std::future<void> det_spec[mfhip::kDetSlots];

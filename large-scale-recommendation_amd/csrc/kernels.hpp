@@ -321,7 +321,7 @@ void launch_pair_metrics(hipStream_t st, const int32_t* rank, const int32_t* val
 // gram != null: the implicit-feedback half-sweep (mf_als_run_implicit), (G + sum w q q^T + lambda' I) x
 // = sum_{r > 0} (1 + w) q with w = alpha |r|; gram is G, als_gram_elems(k) elements (launch_als_gram),
 // lambda' = lambda * npos when weighted, and a row with npos == 0 is set to zero.
-constexpr int kAlsMaxRank = 128;
+constexpr int kAlsMaxRank = 256;
 struct AlsItem {
   int64_t begin;  // first rating of the item in cols / vals
   int32_t row;
@@ -337,7 +337,8 @@ struct AlsSplit {
 size_t als_partial_elems(int k);
 void launch_als(hipStream_t st, const AlsItem* items, int n_items, const AlsSplit* splits, int n_splits,
                 const int32_t* cols, const void* vals, const void* Q, void* X, int k, double lambda, bool weighted,
-                bool f64, void* partial, void* dump, const void* gram = nullptr, double alpha = 0.0);
+                bool f64, void* partial, void* dump, const void* gram = nullptr, double alpha = 0.0,
+                void* slab = nullptr, int slabs = 0);
 // G = sum of y y^T over rows rated[0 .. m) of Y, KP x KP (KP = k rounded up to 32, full symmetric,
 // zero past k): workgroup b sums rows [b * slice, (b + 1) * slice) into part[b] (als_gram_slices(m,
 // slice) partials of als_gram_elems(k) elements), then one launch adds them in ascending order.
@@ -345,5 +346,17 @@ size_t als_gram_elems(int k);
 int als_gram_slices(int m, int slice);
 void launch_als_gram(hipStream_t st, const int32_t* rated, int m, int slice, const void* Y, int k, bool f64, void* part,
                      void* G);
+
+// ---- kernels_als_wide.hip: the same at ranks 129..256 ------------------------------------------
+// launch_als and launch_als_gram hand these ranks on.  The normal matrix of a row lives in global
+// memory: slab holds `slabs` matrices of als_gram_elems(k) elements, one per workgroup of the grid,
+// which strides over the work items; als_wide_slabs is the count for a device of `cus` CUs (0 at a
+// rank the narrow kernels take).  launch_als_gram_wide stores the slice partials only.
+int als_wide_slabs(int k, bool f64, int cus);
+void launch_als_wide(hipStream_t st, const AlsItem* items, int n_items, const AlsSplit* splits, int n_splits,
+                     const int32_t* cols, const void* vals, const void* Q, void* X, int k, double lambda, bool weighted,
+                     bool f64, void* partial, void* dump, const void* gram, double alpha, void* slab, int slabs);
+void launch_als_gram_wide(hipStream_t st, const int32_t* rated, int m, int slice, const void* Y, int k, bool f64,
+                          void* part);
 
 }  // namespace mfhip

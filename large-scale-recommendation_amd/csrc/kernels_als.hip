@@ -28,6 +28,9 @@
 // summed partials (split rows) go to the LDS matrix.  k_als_gram computes G: each workgroup takes a
 // contiguous slice of the rated-row list through the same tiles and GramAcc and stores a KP x KP
 // partial; k_als_gram_reduce adds the partials in ascending slice order.
+//
+// These kernels take ranks 1..128 (rank buckets NB = 1..4).  Ranks 129..256, where the normal matrix no
+// longer fits in LDS, go to kernels_als_wide.hip: launch_als and launch_als_gram hand them on.
 #include <hip/hip_runtime.h>
 
 #include <limits>
@@ -497,7 +500,7 @@ void launch_gram_t(hipStream_t st, const int32_t* rated, int m, int slice, const
     case 2: hipLaunchKernelGGL((k_als_gram<T, 2>), grid, block, 0, st, rated, m, slice, y, k, p); break;
     case 3: hipLaunchKernelGGL((k_als_gram<T, 3>), grid, block, 0, st, rated, m, slice, y, k, p); break;
     case 4: hipLaunchKernelGGL((k_als_gram<T, 4>), grid, block, 0, st, rated, m, slice, y, k, p); break;
-    default: fail(MF_ERR_INVALID, "ALS supports a rank of at most " + std::to_string(kAlsMaxRank));
+    default: launch_als_gram_wide(st, rated, m, slice, Y, k, sizeof(T) == 8, part);  // refuses a rank above kAlsMaxRank
   }
   hipLaunchKernelGGL((k_als_gram_reduce<T>), dim3(static_cast<unsigned>((kp * kp + kThreads - 1) / kThreads)), block, 0,
                      st, static_cast<const T*>(part), slices, kp, static_cast<T*>(G));
@@ -519,7 +522,10 @@ int als_gram_slices(int m, int slice) { return static_cast<int>((static_cast<int
 
 void launch_als(hipStream_t st, const AlsItem* items, int n_items, const AlsSplit* splits, int n_splits,
                 const int32_t* cols, const void* vals, const void* Q, void* X, int k, double lambda, bool weighted,
-                bool f64, void* partial, void* dump, const void* gram, double alpha) {
+                bool f64, void* partial, void* dump, const void* gram, double alpha, void* slab, int slabs) {
+  if (k > 128)  // kernels_als_wide.hip
+    return launch_als_wide(st, items, n_items, splits, n_splits, cols, vals, Q, X, k, lambda, weighted, f64, partial, dump,
+                           gram, alpha, slab, slabs);
   if (f64) launch_t<double>(st, items, n_items, splits, n_splits, cols, vals, Q, X, k, lambda, weighted ? 1 : 0, partial, dump, gram, alpha);
   else launch_t<float>(st, items, n_items, splits, n_splits, cols, vals, Q, X, k, lambda, weighted ? 1 : 0, partial, dump, gram, alpha);
 }

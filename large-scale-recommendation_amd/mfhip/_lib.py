@@ -39,7 +39,7 @@ UID_BYTES = 128
 RECOMMEND_MAX_TOP = 128
 ALS_REG_WEIGHTED = 0
 ALS_REG_PLAIN = 1
-ALS_MAX_RANK = 128
+ALS_MAX_RANK = 256
 RANK_NMETRICS = 6  # precision, recall, ap, ndcg, rr, hit: a per-query row of mf_rank_eval
 PAIR_RANK_COLD = -1      # mf_pair_ranks: the model does not hold the query id or the candidate id
 PAIR_RANK_EXCLUDED = -2  # ... the pair itself is in the exclusion list

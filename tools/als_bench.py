@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""ALS iterations on the NFLX-shaped synthetic (480,189 x 17,770, the training split, k = 128), fast mode.
+"""ALS iterations on the NFLX-shaped synthetic (480,189 x 17,770, the training split, k = --k, 128 by
+default), fast mode.
 
 mf_als_prepare once (its host time is reported), one warm-up iteration, then --iters full iterations
 (item half-sweep + user half-sweep) timed twice over: with the host clock around the blocking
@@ -20,7 +21,12 @@ process with the ratings shifted by -3 so that they straddle zero (all three rat
 two Gram launches of a half-sweep are inside its time; they are also timed alone, through
 mf_debug_als_gram under the same device events.
 
-Writes profiles/als_bench.json.
+--k K runs at another rank (129..256 take the kernels of kernels_als_wide.hip); --det also times one
+deterministic-mode (f64) iteration after one warm-up.
+
+Writes profiles/als_bench.json.  At the default rank this run's fields replace the file's own and every
+other key of the file stays; at another rank the same fields go under the key "k<K>", beside what it
+holds.
 """
 import argparse
 import json
@@ -36,8 +42,8 @@ sys.path.insert(0, os.path.join(ROOT, "large-scale-recommendation_amd"))
 F32_MFMA_PEAK = 157.3e12  # MI355X, v_mfma_f32_32x32x2_f32 (f32 in, f32 accumulate)
 
 
-def als_run(train, k, iters, lam, chunk, alpha=None):
-    """alpha None: explicit iterations; else implicit ones on the ratings as given."""
+def als_run(train, k, iters, lam, chunk, alpha=None, det=False):
+    """alpha None: explicit iterations; else implicit ones on the ratings as given.  det: deterministic mode."""
     from mfhip import _lib as L
     from mfhip.context import Context
 
@@ -48,7 +54,7 @@ def als_run(train, k, iters, lam, chunk, alpha=None):
         os.environ.pop("MFHIP_TEST", None)
     p = L.default_params()
     p.num_factors = k
-    p.mode = L.MODE_FAST_F32
+    p.mode = L.MODE_DETERMINISTIC_F64 if det else L.MODE_FAST_F32
     nnz = len(u)
     rows = {"item": len(np.unique(i)), "user": len(np.unique(u))}
     flop = {s: 2.0 * nnz * k * k + (2.0 / 3.0) * k ** 3 * rows[s] for s in rows}
@@ -100,6 +106,7 @@ def als_run(train, k, iters, lam, chunk, alpha=None):
     res["tflops"]["iteration"] = (flop["item"] + flop["user"]) / (res["iteration_ms_device"] * 1e-3) / 1e12
     res["fraction_of_f32_mfma_peak"] = res["tflops"]["iteration"] * 1e12 / F32_MFMA_PEAK
     kind = "ALS" if alpha is None else f"implicit ALS (alpha {alpha})"
+    kind += (f" k {k}" if k != 128 else "") + (" deterministic" if det else "")
     print(f"{kind} chunk {res['chunk']}: {res['iteration_ms_device']:.1f} ms / iteration on the device "
           f"(item half {ms['item']:.1f} ms, {res['tflops']['item']:.1f} TFLOP/s; user half {ms['user']:.1f} ms, "
           f"{res['tflops']['user']:.1f} TFLOP/s), host call {res['iteration_ms_host_call']:.1f} ms; "
@@ -145,6 +152,8 @@ def main():
     ap.add_argument("--dsgd", action="store_true", help="also time a fast DSGD epoch on the same data")
     ap.add_argument("--implicit", action="store_true", help="also time implicit iterations on the shifted ratings")
     ap.add_argument("--alpha", type=float, default=1.0, help="the implicit runs' alpha")
+    ap.add_argument("--k", type=int, default=128, help="the rank (default 128)")
+    ap.add_argument("--det", action="store_true", help="also time one deterministic-mode iteration")
     ap.add_argument("--scale", type=float, default=1.0, help="shrink the synthetic (rehearsal only)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "als_bench.json"))
     a = ap.parse_args()
@@ -155,7 +164,8 @@ def main():
             raise L.MFNoDeviceError(L.MF_ERR_NO_DEVICE, "no device")
     except L.MFNoDeviceError:
         sys.exit("als_bench needs a GPU: there is no CPU path to time")
-    nu, ni, nr, k, nb = synth.CONFIGS["NFLX"]
+    nu, ni, nr, k0, nb = synth.CONFIGS["NFLX"]
+    k = a.k
     train, _ = synth.generate(max(1, int(nu * a.scale)), max(1, int(ni * a.scale)), max(1, int(nr * a.scale))).split()
     out = {"shape": "NFLX", "scale": a.scale, "runs": []}
     for c in [int(x) for x in a.chunks.split(",") if x] or [0]:
@@ -165,9 +175,20 @@ def main():
         shifted = (u, i, np.asarray(r, np.float64) - 3.0)
         out["implicit_runs"] = [als_run(shifted, k, a.iters, a.lam, c, a.alpha)
                                 for c in [int(x) for x in a.chunks.split(",") if x] or [0]]
+    if a.det:
+        out["deterministic_run"] = als_run(train, k, 1, a.lam, 0, det=True)
     if a.dsgd:
         out["dsgd_fast"] = dsgd_epoch(train, k, nb)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    old = {}
+    if os.path.exists(a.out):
+        with open(a.out) as f:
+            old = json.load(f)
+    if k != k0:  # beside what the file holds
+        old[f"k{k}"] = out
+        out = old
+    else:        # the file is this run; whatever else it holds (other ranks, comparisons) stays
+        out.update({key: v for key, v in old.items() if key not in out})
     with open(a.out, "w") as f:
         json.dump(out, f, indent=1)
     print("wrote", a.out)
