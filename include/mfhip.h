@@ -392,6 +392,51 @@ int mf_als_run_implicit(mf_ctx* ctx, int64_t half_sweeps, double lambda, int32_t
 int mf_als_fit_implicit(mf_ctx* ctx, const int32_t* users, const int32_t* items, const double* ratings,
                         int64_t n, int32_t iterations, double lambda, int32_t reg, double alpha);
 
+/* The same half-sweeps by conjugate gradients (Hu, Koren, Volinsky 2008 with the solve of Takacs,
+   Pilaszy, Tikk 2011): every rated row takes cg_steps CG steps on its normal equations, starting from
+   its current value, and its k x k matrix is never formed.  About 4 (cg_steps + 1) nnz k flops per
+   half-sweep instead of 2 nnz k^2 and a factorisation per row; an approximate solve, exact in at most k
+   steps in exact arithmetic.  Every rank 1..256 runs the same kernels.
+   Shared with mf_als_run / mf_als_run_implicit: the data mf_als_prepare built, the half-sweep order
+   (item side first) and the half-sweep counter -- the four kinds of run call may be mixed --, the state
+   rules and errors, lambda', n+ and G, and that a row with no rating is left untouched and every row of
+   a half-sweep reads the counterpart's factors as they stand when the half-sweep begins.
+   mf_als_fit_cg / mf_als_fit_implicit_cg are mf_als_prepare followed by the run call with
+   2 * iterations half-sweeps (n == 0: a no-op).
+   Arithmetic.  Per row a with ratings j in CSR order, counterpart rows q_j, current value x, S = cg_steps:
+       explicit:  A = sum_j q_j q_j^T + lambda' I           b = sum_j r_j q_j
+       implicit:  A = G + sum_j w_j q_j q_j^T + lambda' I   b = sum_j c_j q_j
+                  w_j = alpha |r_j|,  c_j = 1 + w_j where r_j > 0 and 0 elsewhere
+       r = b - A x, in one pass:  r = sum_j e_j q_j [- G x] - lambda' x,  e_j = r_j - q_j.x  (implicit: c_j - w_j (q_j.x))
+       p = r;  rs = r.r
+       S times:  Ap = sum_j e_j q_j [+ G p] + lambda' p,  e_j = q_j.p  (implicit: w_j (q_j.p))
+                 a = rs / (p.Ap);  x = fma(a, p, x);  r = fma(-a, Ap, r);  rs' = r.r;  p = fma(rs'/rs, p, r);  rs = rs'
+   An implicit row with no positive rating is set to +0 without iterating.  Before a step, rs == 0 ends the
+   row's iterations and keeps x; so does p.Ap == 0.  An rs or p.Ap that is not finite makes the row NaN
+   (mf_als_run's rule for a bad pivot).
+   Order.  q_j.v: 64 partial sums, partial l an fma chain from 0 over f = l, l + 64, l + 128, l + 192 (< k),
+   added pairwise: partial l with l ^ 32, then ^ 16, ^ 8, ^ 4, ^ 2, ^ 1.  sum_j e_j q_j: per factor an fma chain from 0
+   over the ratings in CSR order; a row longer than the chunk of mf_als_prepare takes one such chain per
+   chunk and adds the chunks' sums to 0 in ascending order.  (G v)[f]: an fma chain from 0 over g = 0 .. k-1
+   of G[g][f] v[g].  Then, in this order, [-/+ G v] and -/+ lambda' v (a product, then a sum).  r.r and
+   p.Ap: the products of factors 64 g .. 64 g + 63 form group g = 0 .. 3 (factors past k count 0), each
+   group is added by the same pairwise scheme, then ((g0 + g1) + g2) + g3.  Deterministic contexts
+   compute in f64, fast contexts in f32 throughout (lambda, alpha and the ratings rounded to f32).
+   No floating-point atomics: results are bitwise reproducible from run to run and do not depend on the
+   device, on how the rows are cut into launches, or on whether a row's vectors were kept on chip; they
+   depend on the chunk length as mf_als_run's do.
+   Errors.  MF_ERR_INVALID: cg_steps outside 1 .. MF_ALS_CG_MAX_STEPS; otherwise exactly those of
+   mf_als_run / mf_als_run_implicit / mf_als_fit / mf_als_fit_implicit. */
+#define MF_ALS_CG_MAX_STEPS 256
+int mf_als_run_cg(mf_ctx* ctx, int64_t half_sweeps, double lambda, int32_t reg, int32_t cg_steps);
+int mf_als_run_implicit_cg(mf_ctx* ctx, int64_t half_sweeps, double lambda, int32_t reg, double alpha,
+                           int32_t cg_steps);
+int mf_als_fit_cg(mf_ctx* ctx, const int32_t* users, const int32_t* items, const double* ratings, int64_t n,
+                  int32_t iterations, double lambda, int32_t reg, int32_t cg_steps);
+int mf_als_fit_implicit_cg(mf_ctx* ctx, const int32_t* users, const int32_t* items, const double* ratings,
+                           int64_t n, int32_t iterations, double lambda, int32_t reg, double alpha,
+                           int32_t cg_steps);
+
 /* Exact updateLocalFactors replacement (DSGDforMF.scala:378-418) on caller buffers:
    users[nu x k], items[ni x k] are updated in place; omegas are per row.  Reentrant
    on disjoint buffers with distinct contexts, as Flink calls it per task slot. */

@@ -87,6 +87,17 @@ int mf_debug_als_normal_eq(mf_ctx* ctx, int side, int32_t id, double lambda, int
 int mf_debug_als_gram(mf_ctx* ctx, int side, double* G_out);
 int mf_debug_als_normal_eq_implicit(mf_ctx* ctx, int side, int32_t id, double lambda, int32_t reg, double alpha,
                                     double* A_out, double* b_out);
+/* mf_debug_als_cg_matvec: after mf_als_prepare, for `id` of `side` and a vector v[k]: Av_out[k] = A v and
+   b_out[k] = b of the system mf_als_run_cg (alpha < 0) or mf_als_run_implicit_cg (alpha >= 0) iterates
+   on, from the current factors, through the half-sweep's own kernels -- the row's vectors staged in
+   LDS, gathered again in every pass (MFHIP_TEST als_cg_stage=0, or a row past the LDS budget) or the
+   chunked path of a long row -- in the order mfhip.h documents, widened to f64.  Fast contexts round v
+   to f32.  The factors are not changed.  MF_ERR_INVALID as for mf_debug_als_normal_eq.
+   mf_debug_als_cg_capacity: the most ratings of a row whose vectors are staged at this context's rank
+   and precision. */
+int mf_debug_als_cg_matvec(mf_ctx* ctx, int side, int32_t id, double lambda, int32_t reg, double alpha,
+                           const double* v, double* Av_out, double* b_out);
+int mf_debug_als_cg_capacity(mf_ctx* ctx, int32_t* ratings_out);
 /* mf_debug_rank_csr: the pair table mf_rank_eval builds on the device for one pair list, copied back.
    The evaluated queries are the distinct ids of query[] the model holds on query_side, in ascending
    factor-row order: q_ids_out[*nq_out].  off_out[*nq_out + 1] and entries_out[*ne_out] are the table:

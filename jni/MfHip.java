@@ -40,6 +40,18 @@ public final class MfHip {
   // 1 + alpha |r|, preferences r > 0; reg as above, with n_row counting the ratings r > 0
   public static native void alsFitImplicit(long ctx, int[] users, int[] items, double[] ratings,
                                            int iterations, double lambda, int reg, double alpha);
+  // The same half-sweeps by conjugate gradients (mf_als_fit_cg / mf_als_fit_implicit_cg): cgSteps
+  // (1..256) CG steps per row from its current value instead of a factorisation.  alsPrepare
+  // (mf_als_prepare) keeps the ratings on the device; alsRunCg / alsRunImplicitCg then run half-sweeps
+  // (item side first, one counter shared by every kind of run call).
+  public static native void alsPrepare(long ctx, int[] users, int[] items, double[] ratings);
+  public static native void alsFitCg(long ctx, int[] users, int[] items, double[] ratings,
+                                     int iterations, double lambda, int reg, int cgSteps);
+  public static native void alsFitImplicitCg(long ctx, int[] users, int[] items, double[] ratings,
+                                             int iterations, double lambda, int reg, double alpha, int cgSteps);
+  public static native void alsRunCg(long ctx, long halfSweeps, double lambda, int reg, int cgSteps);
+  public static native void alsRunImplicitCg(long ctx, long halfSweeps, double lambda, int reg, double alpha,
+                                             int cgSteps);
   // unblock (DSGDforMF.scala:245-255) and checkpoint restore
   public static native long numFactors(long ctx, int side);
   public static native long getFactors(long ctx, int side, int[] idsOut, double[] vecsOut);

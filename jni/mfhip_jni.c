@@ -204,6 +204,59 @@ JNIEXPORT void JNICALL JFN(alsFitImplicit)(JNIEnv* env, jclass c, jlong h, jintA
   check(env, st);
 }
 
+/* The conjugate-gradient half-sweeps: alsPrepare (mf_als_prepare) once, then run calls of any kind; the fit
+   calls are prepare + 2 * iterations half-sweeps.  alpha < 0 in als_cg_call: the explicit calls. */
+static void als_cg_call(JNIEnv* env, jlong h, jintArray u, jintArray i, jdoubleArray r, int fit, jint iterations,
+                        jdouble lambda, jint reg, jdouble alpha, jint cgSteps) {
+  jsize n = 0;
+  if (rating_columns(env, u, i, r, &n)) return;
+  Elems eu = {0}, ei = {0}, er = {0};
+  if (acquire(env, &eu, u, kInt) || acquire(env, &ei, i, kInt) || acquire(env, &er, r, kDouble)) {
+    release(env, &eu, JNI_ABORT);
+    release(env, &ei, JNI_ABORT);
+    return;
+  }
+  const int32_t* pu = (const int32_t*)eu.p;
+  const int32_t* pi = (const int32_t*)ei.p;
+  const double* pr = (const double*)er.p;
+  int st;
+  if (!fit) st = mf_als_prepare(CTX(h), pu, pi, pr, n);
+  else if (alpha < 0) st = mf_als_fit_cg(CTX(h), pu, pi, pr, n, iterations, lambda, reg, cgSteps);
+  else st = mf_als_fit_implicit_cg(CTX(h), pu, pi, pr, n, iterations, lambda, reg, alpha, cgSteps);
+  release(env, &er, JNI_ABORT);
+  release(env, &ei, JNI_ABORT);
+  release(env, &eu, JNI_ABORT);
+  check(env, st);
+}
+
+JNIEXPORT void JNICALL JFN(alsPrepare)(JNIEnv* env, jclass c, jlong h, jintArray u, jintArray i, jdoubleArray r) {
+  als_cg_call(env, h, u, i, r, 0, 0, 0.0, 0, -1.0, 0);
+}
+
+JNIEXPORT void JNICALL JFN(alsFitCg)(JNIEnv* env, jclass c, jlong h, jintArray u, jintArray i, jdoubleArray r,
+                                     jint iterations, jdouble lambda, jint reg, jint cgSteps) {
+  als_cg_call(env, h, u, i, r, 1, iterations, lambda, reg, -1.0, cgSteps);
+}
+
+JNIEXPORT void JNICALL JFN(alsFitImplicitCg)(JNIEnv* env, jclass c, jlong h, jintArray u, jintArray i, jdoubleArray r,
+                                             jint iterations, jdouble lambda, jint reg, jdouble alpha, jint cgSteps) {
+  if (alpha < 0) {  /* (the helper reads a negative alpha as "explicit") */
+    check(env, mf_als_run_implicit_cg(CTX(h), 0, lambda, reg, alpha, cgSteps));
+    return;
+  }
+  als_cg_call(env, h, u, i, r, 1, iterations, lambda, reg, alpha, cgSteps);
+}
+
+JNIEXPORT void JNICALL JFN(alsRunCg)(JNIEnv* env, jclass c, jlong h, jlong halfSweeps, jdouble lambda, jint reg,
+                                     jint cgSteps) {
+  check(env, mf_als_run_cg(CTX(h), halfSweeps, lambda, reg, cgSteps));
+}
+
+JNIEXPORT void JNICALL JFN(alsRunImplicitCg)(JNIEnv* env, jclass c, jlong h, jlong halfSweeps, jdouble lambda, jint reg,
+                                             jdouble alpha, jint cgSteps) {
+  check(env, mf_als_run_implicit_cg(CTX(h), halfSweeps, lambda, reg, alpha, cgSteps));
+}
+
 JNIEXPORT void JNICALL JFN(dsgdRun)(JNIEnv* env, jclass c, jlong h, jlong supersteps) {
   check(env, mf_dsgd_run(CTX(h), supersteps));
 }

@@ -417,6 +417,69 @@ int mf_als_fit_implicit(mf_ctx* ctx, const int32_t* u, const int32_t* i, const d
   });
 }
 
+int mf_als_run_cg(mf_ctx* ctx, int64_t half_sweeps, double lambda, int32_t reg, int32_t cg_steps) {
+  return guarded([&] {
+    MF_REQUIRE(ctx, "null context");
+    als_run_cg(ctx, half_sweeps, lambda, reg, -1.0, cg_steps);
+  });
+}
+
+int mf_als_fit_cg(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n, int32_t iterations,
+                  double lambda, int32_t reg, int32_t cg_steps) {
+  return guarded([&] {
+    MF_REQUIRE(ctx, "null context");
+    MF_REQUIRE(n >= 0 && iterations >= 0, "negative count");
+    als_check_run(lambda, reg);
+    als_check_cg(cg_steps);
+    als_check(ctx);
+    if (n == 0) return;
+    als_prepare(ctx, u, i, r, n);
+    als_run_cg(ctx, 2 * static_cast<int64_t>(iterations), lambda, reg, -1.0, cg_steps);
+  });
+}
+
+int mf_als_run_implicit_cg(mf_ctx* ctx, int64_t half_sweeps, double lambda, int32_t reg, double alpha,
+                           int32_t cg_steps) {
+  return guarded([&] {
+    MF_REQUIRE(ctx, "null context");
+    als_check_alpha(alpha);
+    als_run_cg(ctx, half_sweeps, lambda, reg, alpha, cg_steps);
+  });
+}
+
+int mf_als_fit_implicit_cg(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n,
+                           int32_t iterations, double lambda, int32_t reg, double alpha, int32_t cg_steps) {
+  return guarded([&] {
+    MF_REQUIRE(ctx, "null context");
+    MF_REQUIRE(n >= 0 && iterations >= 0, "negative count");
+    als_check_alpha(alpha);
+    als_check_run(lambda, reg);
+    als_check_cg(cg_steps);
+    als_check(ctx);
+    if (n == 0) return;
+    als_prepare(ctx, u, i, r, n);
+    als_run_cg(ctx, 2 * static_cast<int64_t>(iterations), lambda, reg, alpha, cg_steps);
+  });
+}
+
+int mf_debug_als_cg_matvec(mf_ctx* ctx, int side, int32_t id, double lambda, int32_t reg, double alpha, const double* v,
+                           double* Av_out, double* b_out) {
+  return guarded([&] {
+    MF_REQUIRE(ctx && v && Av_out && b_out, "null argument");
+    MF_REQUIRE(side == MF_SIDE_USER || side == MF_SIDE_ITEM, "bad side");
+    MF_REQUIRE(alpha < 0.0 || std::isfinite(alpha), "implicit ALS needs a finite alpha >= 0");
+    als_cg_matvec(ctx, side, id, lambda, reg, alpha < 0.0 ? -1.0 : alpha, v, Av_out, b_out);
+  });
+}
+
+int mf_debug_als_cg_capacity(mf_ctx* ctx, int32_t* ratings_out) {
+  return guarded([&] {
+    MF_REQUIRE(ctx && ratings_out, "null argument");
+    als_check(ctx);
+    *ratings_out = als_cg_capacity(ctx->P.num_factors, ctx->f64);
+  });
+}
+
 int mf_debug_als_gram(mf_ctx* ctx, int side, double* G_out) {
   return guarded([&] {
     MF_REQUIRE(ctx && G_out, "null argument");

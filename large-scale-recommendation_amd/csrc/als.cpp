@@ -295,6 +295,161 @@ void als_normal_eq(mf_ctx* ctx, int side, int32_t id, double lambda, int32_t reg
   std::memcpy(b_out, h.data() + k * k, k * 8);
 }
 
+// ---------------------------------------------------------------------------------------
+// The conjugate-gradient half-sweeps (mf_als_run_cg / mf_als_run_implicit_cg; kernels_als_cg.hip) on
+// the same prepared data: the work lists, batches and partial slots of als_half, G for the implicit half.
+void als_check_cg(int32_t cg_steps) {
+  MF_REQUIRE(cg_steps >= 1 && cg_steps <= MF_ALS_CG_MAX_STEPS,
+             "cg_steps must lie in 1 .. " + std::to_string(MF_ALS_CG_MAX_STEPS));
+}
+
+namespace {
+
+// The chunk items of `side`'s long rows, per batch, with the index of each one's row among the batch's splits.
+void als_cg_lists(mf_ctx* ctx, Shard& s, int side) {
+  mf_ctx::AlsSide& A = ctx->als[side];
+  if (A.cg_ready) return;
+  A.cg_work.clear();
+  A.cg_work0.assign(1, 0);
+  A.cg_max_splits = 0;
+  for (const mf_ctx::AlsBatch& b : A.batches) {
+    int64_t sp = b.split0;
+    for (int64_t x = b.item0; x < b.item0 + b.items; ++x) {
+      const AlsItem& it = A.items[static_cast<size_t>(x)];
+      if (it.slot < 0) continue;
+      while (A.splits[static_cast<size_t>(sp)].row != it.row) ++sp;  // both lists are in row order
+      A.cg_work.push_back({static_cast<int32_t>(x - b.item0), static_cast<int32_t>(sp - b.split0)});
+    }
+    A.cg_work0.push_back(static_cast<int64_t>(A.cg_work.size()));
+    A.cg_max_splits = std::max(A.cg_max_splits, b.splits);
+  }
+  s.als_cg_work[side].alloc(std::max<size_t>(A.cg_work.size() * sizeof(AlsCgWork), 16));
+  if (!A.cg_work.empty())
+    MF_HIP(hipMemcpy(s.als_cg_work[side].get(), A.cg_work.data(), A.cg_work.size() * sizeof(AlsCgWork),
+                     hipMemcpyHostToDevice));
+  A.cg_ready = true;
+}
+
+bool als_cg_stage() { return test_knob("als_cg_stage") != "0"; }
+
+// als_half's counterpart.  only_row >= 0 (the testing hook): A v and b of that row for the v in
+// s.als_cg_v, stored to s.als_dump; false if the row has no rating.
+bool als_half_cg(mf_ctx* ctx, int side, double lambda, int32_t reg, double alpha, int steps, int64_t only_row = -1) {
+  Shard& s = ctx->shards[0];
+  DeviceGuard g(s.device);
+  mf_ctx::AlsSide& A = ctx->als[side];
+  const int k = ctx->P.num_factors;
+  const bool implicit = alpha >= 0.0;
+  const int other = side == kSideU ? MF_SIDE_ITEM : kSideU;
+  als_cg_lists(ctx, s, side);
+  s.als_part.alloc(std::max<size_t>(static_cast<size_t>(A.max_slots) * als_partial_elems(k) * ctx->es, 16));
+  s.als_cg_state.alloc(std::max<size_t>(static_cast<size_t>(std::max<int64_t>(A.cg_max_splits, 1)) *
+                                            als_cg_state_elems(k) * ctx->es, 16));
+  const void* Q = side == kSideU ? s.itf.get() : s.uf.get();
+  void* X = side == kSideU ? s.uf.get() : s.itf.get();
+  const AlsItem* d_items = s.als_items[side].as<AlsItem>();
+  const AlsSplit* d_splits = s.als_splits[side].as<AlsSplit>();
+  const AlsCgWork* d_work = s.als_cg_work[side].as<AlsCgWork>();
+  const bool weighted = reg == MF_ALS_REG_WEIGHTED, stage = als_cg_stage();
+  if (only_row >= 0) {
+    auto lo = std::lower_bound(A.items.begin(), A.items.end(), only_row,
+                               [](const AlsItem& a, int64_t row) { return a.row < row; });
+    if (lo == A.items.end() || lo->row != only_row) return false;
+    auto hi = lo;
+    while (hi != A.items.end() && hi->row == only_row) ++hi;
+    auto sp = std::lower_bound(A.splits.begin(), A.splits.end(), only_row,
+                               [](const AlsSplit& a, int64_t row) { return a.row < row; });
+    const bool split = sp != A.splits.end() && sp->row == only_row;
+    const int n = static_cast<int>(hi - lo);
+    if (split) {  // the row's chunks, as items [0, n) of the launch and long row 0
+      std::vector<AlsCgWork> w(static_cast<size_t>(n));
+      for (int x = 0; x < n; ++x) w[static_cast<size_t>(x)] = {x, 0};
+      s.als_cg_hook_work.alloc(w.size() * sizeof(AlsCgWork));
+      MF_HIP(hipMemcpy(s.als_cg_hook_work.get(), w.data(), w.size() * sizeof(AlsCgWork), hipMemcpyHostToDevice));
+    }
+    s.als_dump.alloc(std::max<size_t>((static_cast<size_t>(k) * k + k) * ctx->es, 16));
+    if (implicit) als_gram_launch(ctx, s, other);
+    launch_als_cg(s.stream, d_items + (lo - A.items.begin()), n, d_splits + (sp - A.splits.begin()), split ? 1 : 0,
+                  split ? s.als_cg_hook_work.as<AlsCgWork>() : nullptr, split ? n : 0, s.als_cols[side].as<int32_t>(),
+                  s.als_vals[side].get(), Q, X, k, lambda, weighted, ctx->f64, s.als_part.get(),
+                  implicit ? s.als_gram.get() : nullptr, alpha, 1, stage, s.als_cg_state.get(), s.als_cg_v.get(),
+                  s.als_dump.get());
+    MF_HIP(hipGetLastError());
+    return true;
+  }
+  LaunchTimer t(s, ctx->profiling);
+  if (implicit && !A.batches.empty()) {
+    als_gram_launch(ctx, s, other);
+    ctx->stats.kernel_launches += 2;
+  }
+  for (size_t b = 0; b < A.batches.size(); ++b) {
+    const mf_ctx::AlsBatch& B = A.batches[b];
+    const int64_t w0 = A.cg_work0[b], nw = A.cg_work0[b + 1] - w0;
+    launch_als_cg(s.stream, d_items + B.item0, static_cast<int>(B.items), d_splits + B.split0,
+                  static_cast<int>(B.splits), d_work + w0, static_cast<int>(nw), s.als_cols[side].as<int32_t>(),
+                  s.als_vals[side].get(), Q, X, k, lambda, weighted, ctx->f64, s.als_part.get(),
+                  implicit ? s.als_gram.get() : nullptr, alpha, steps, stage, s.als_cg_state.get(), nullptr, nullptr);
+    MF_HIP(hipGetLastError());
+    ctx->stats.kernel_launches += 1 + (B.splits > 0 ? 2 * (steps + 1) : 0);
+  }
+  return true;
+}
+
+}  // namespace
+
+void als_run_cg(mf_ctx* ctx, int64_t half_sweeps, double lambda, int32_t reg, double alpha, int32_t cg_steps) {
+  MF_REQUIRE(half_sweeps >= 0, "negative half-sweep count");
+  als_check_run(lambda, reg);
+  als_check_cg(cg_steps);
+  als_check(ctx);
+  if (!ctx->als_prepared)
+    fail(MF_ERR_STATE,
+         std::string(alpha >= 0.0 ? "mf_als_run_implicit_cg" : "mf_als_run_cg") + " before mf_als_prepare");
+  require_healthy(ctx);
+  sync_all(ctx);
+  for (int64_t h = 0; h < half_sweeps; ++h) {
+    als_half_cg(ctx, ctx->als_half_sweeps % 2 == 0 ? MF_SIDE_ITEM : kSideU, lambda, reg, alpha, cg_steps);
+    ++ctx->als_half_sweeps;  // mf_als_run's counter
+  }
+  DeviceGuard g(ctx->shards[0].device);
+  MF_HIP(hipStreamSynchronize(ctx->shards[0].stream));
+}
+
+// A v and b of one row through the conjugate-gradient half-sweep's own kernels (mf_debug_als_cg_matvec).
+void als_cg_matvec(mf_ctx* ctx, int side, int32_t id, double lambda, int32_t reg, double alpha, const double* v,
+                   double* Av_out, double* b_out) {
+  als_check_run(lambda, reg);
+  als_check(ctx);
+  if (!ctx->als_prepared) fail(MF_ERR_STATE, "mf_debug_als_cg_matvec before mf_als_prepare");
+  require_healthy(ctx);
+  sync_all(ctx);
+  const int32_t row = side_of(ctx, side).index.find(id);
+  MF_REQUIRE(row >= 0, "unknown id");
+  Shard& s = ctx->shards[0];
+  DeviceGuard g(s.device);
+  const size_t k = static_cast<size_t>(ctx->P.num_factors);
+  s.als_cg_v.alloc(std::max<size_t>(k * ctx->es, 16));
+  if (ctx->f64) {
+    MF_HIP(hipMemcpy(s.als_cg_v.get(), v, k * 8, hipMemcpyHostToDevice));
+  } else {
+    std::vector<float> f(k);
+    for (size_t x = 0; x < k; ++x) f[x] = static_cast<float>(v[x]);
+    MF_HIP(hipMemcpy(s.als_cg_v.get(), f.data(), k * 4, hipMemcpyHostToDevice));
+  }
+  MF_REQUIRE(als_half_cg(ctx, side, lambda, reg, alpha, 1, row), "the id has no rating in the prepared data");
+  MF_HIP(hipStreamSynchronize(s.stream));
+  std::vector<double> h(2 * k);
+  if (ctx->f64) {
+    MF_HIP(hipMemcpy(h.data(), s.als_dump.get(), 2 * k * 8, hipMemcpyDeviceToHost));
+  } else {
+    std::vector<float> f(2 * k);
+    MF_HIP(hipMemcpy(f.data(), s.als_dump.get(), 2 * k * 4, hipMemcpyDeviceToHost));
+    for (size_t x = 0; x < 2 * k; ++x) h[x] = static_cast<double>(f[x]);
+  }
+  std::memcpy(Av_out, h.data(), k * 8);
+  std::memcpy(b_out, h.data() + k, k * 8);
+}
+
 // G of one side's rated rows through the half-sweep's own launches (mf_debug_als_gram).
 void als_gram(mf_ctx* ctx, int side, double* G_out) {
   als_check(ctx);

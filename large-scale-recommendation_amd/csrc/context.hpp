@@ -144,6 +144,9 @@ struct Shard {
   DevBuf als_slab;
   // ... the implicit half-sweep: per side its rated rows, the Gram partials of one side and G itself
   DevBuf als_rated[2], als_gram_part, als_gram;
+  // ... the conjugate-gradient half-sweeps: per side the chunk items of its long rows, the state of one
+  // launch's long rows, the testing hook's vector and chunk list
+  DevBuf als_cg_work[2], als_cg_state, als_cg_v, als_cg_hook_work;
   // profiling
   std::vector<hipEvent_t> ev;
   size_t ev_used = 0;
@@ -212,6 +215,12 @@ struct mf_ctx {
     std::vector<AlsBatch> batches;
     int64_t max_slots = 0;
     int64_t rated = 0;  // rows with at least one rating (the length of Shard::als_rated)
+    // the conjugate-gradient half-sweeps (built on first use): the chunk items of every batch, batch b's
+    // at [cg_work0[b], cg_work0[b + 1]), and the most long rows of one batch
+    std::vector<mfhip::AlsCgWork> cg_work;
+    std::vector<int64_t> cg_work0;
+    int64_t cg_max_splits = 0;
+    bool cg_ready = false;
   } als[2];
   int64_t als_gram_slice = 0;  // rated rows per workgroup of k_als_gram (fixed in mf_als_prepare)
   // k > 128: normal-matrix slabs = workgroups per launch of the wide kernels (fixed in mf_als_prepare
@@ -395,5 +404,9 @@ void als_run(mf_ctx* ctx, int64_t half_sweeps, double lambda, int32_t reg, doubl
 void als_normal_eq(mf_ctx* ctx, int side, int32_t id, double lambda, int32_t reg, double* A_out, double* b_out,
                    double alpha = -1.0);
 void als_gram(mf_ctx* ctx, int side, double* G_out);
+void als_check_cg(int32_t cg_steps);
+void als_run_cg(mf_ctx* ctx, int64_t half_sweeps, double lambda, int32_t reg, double alpha, int32_t cg_steps);
+void als_cg_matvec(mf_ctx* ctx, int side, int32_t id, double lambda, int32_t reg, double alpha, const double* v,
+                   double* Av_out, double* b_out);
 
 }  // namespace mfhip

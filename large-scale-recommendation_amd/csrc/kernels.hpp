@@ -359,4 +359,26 @@ void launch_als_wide(hipStream_t st, const AlsItem* items, int n_items, const Al
 void launch_als_gram_wide(hipStream_t st, const int32_t* rated, int m, int slice, const void* Y, int k, bool f64,
                           void* part);
 
+// ---- kernels_als_cg.hip: ALS half-sweeps by conjugate gradients ---------------------------------
+// The work lists, CSR, partial slots and G of launch_als, every rank 1..kAlsMaxRank in one code path
+// (mf_als_run_cg; gram != null: mf_als_run_implicit_cg).  Whole rows (slot < 0) take `steps` CG steps
+// from X[row] in one launch; a row of at most als_cg_capacity(k, f64) ratings keeps its counterpart
+// vectors in LDS for all of them when `stage` is set, a longer one gathers them again in every pass
+// (the same arithmetic).  Long rows: work[0 .. n_work) names the launch's chunk items and, for each, the
+// index of its row in splits[]; their state (als_cg_state_elems(k) elements per row of splits[]) lives
+// in `state`, and every pass is two launches (a k-vector per chunk into partial[slot], then the row's
+// update): 2 * (steps + 1) launches.
+// dump != null (the testing hook, one row): dump[0 .. k) = A v and dump[k .. 2k) = b for v = hook_v
+// (device, k elements); X is not written.
+struct AlsCgWork {
+  int32_t item;   // index into items[]
+  int32_t split;  // index into splits[]
+};
+size_t als_cg_state_elems(int k);
+int als_cg_capacity(int k, bool f64);
+void launch_als_cg(hipStream_t st, const AlsItem* items, int n_items, const AlsSplit* splits, int n_splits,
+                   const AlsCgWork* work, int n_work, const int32_t* cols, const void* vals, const void* Q, void* X, int k,
+                   double lambda, bool weighted, bool f64, void* partial, const void* gram, double alpha, int steps,
+                   bool stage, void* state, const void* hook_v, void* dump);
+
 }  // namespace mfhip

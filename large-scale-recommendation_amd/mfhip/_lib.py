@@ -39,6 +39,7 @@ UID_BYTES = 128
 RECOMMEND_MAX_TOP = 128
 ALS_REG_WEIGHTED = 0
 ALS_REG_PLAIN = 1
+ALS_CG_MAX_STEPS = 256
 ALS_MAX_RANK = 256
 RANK_NMETRICS = 6  # precision, recall, ap, ndcg, rr, hit: a per-query row of mf_rank_eval
 PAIR_RANK_COLD = -1      # mf_pair_ranks: the model does not hold the query id or the candidate id
@@ -139,13 +140,15 @@ EXPORTS = [
     "mf_dsgd_restart", "mf_online_update_out", "mf_recommend", "mf_als_fit", "mf_als_prepare",
     "mf_als_run", "mf_als_run_implicit", "mf_als_fit_implicit", "mf_rank_eval", "mf_pair_ranks",
     "mf_online_prequential", "mf_online_update_sampled", "mf_negative_draws", "mf_online_prequential_sampled",
+    "mf_als_run_cg", "mf_als_run_implicit_cg", "mf_als_fit_cg", "mf_als_fit_implicit_cg",
 ]
 # The test hooks include/mfhip_testing.h declares (not product surface; same library).
 TESTING_EXPORTS = [
     "mf_debug_levels", "mf_debug_fast_schedule", "mf_debug_fast_split", "mf_debug_ring_schedule",
     "mf_debug_plan_digest", "mf_fast_plan_window", "mf_fast_kernel_name", "mf_debug_build_flags",
     "mf_debug_device_bytes", "mf_debug_als_normal_eq", "mf_debug_als_gram", "mf_debug_als_normal_eq_implicit",
-    "mf_debug_det_slot_table", "mf_debug_sys_placement", "mf_debug_rank_csr",
+    "mf_debug_det_slot_table", "mf_debug_sys_placement", "mf_debug_rank_csr", "mf_debug_als_cg_matvec",
+    "mf_debug_als_cg_capacity",
 ]
 
 _i32p = C.POINTER(C.c_int32)
@@ -240,6 +243,15 @@ def lib() -> C.CDLL:
         "mf_debug_als_gram": (C.c_int, [_ctxp, C.c_int, _f64p]),
         "mf_debug_als_normal_eq_implicit": (C.c_int, [_ctxp, C.c_int, C.c_int32, C.c_double, C.c_int32, C.c_double,
                                                       _f64p, _f64p]),
+        "mf_als_run_cg": (C.c_int, [_ctxp, C.c_int64, C.c_double, C.c_int32, C.c_int32]),
+        "mf_als_run_implicit_cg": (C.c_int, [_ctxp, C.c_int64, C.c_double, C.c_int32, C.c_double, C.c_int32]),
+        "mf_als_fit_cg": (C.c_int, [_ctxp, _i32p, _i32p, _f64p, C.c_int64, C.c_int32, C.c_double, C.c_int32,
+                                    C.c_int32]),
+        "mf_als_fit_implicit_cg": (C.c_int, [_ctxp, _i32p, _i32p, _f64p, C.c_int64, C.c_int32, C.c_double, C.c_int32,
+                                             C.c_double, C.c_int32]),
+        "mf_debug_als_cg_matvec": (C.c_int, [_ctxp, C.c_int, C.c_int32, C.c_double, C.c_int32, C.c_double, _f64p,
+                                             _f64p, _f64p]),
+        "mf_debug_als_cg_capacity": (C.c_int, [_ctxp, _i32p]),
         "mf_debug_ring_schedule": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, _i32p, _i32p, _i32p, _i32p]),
         "mf_debug_det_slot_table": (C.c_int, [_i64p, _i32p, _i32p, C.c_int64, C.c_int64, C.c_int32, C.c_int64, _i64p,
                                               _i32p, _i32p, _i64p]),

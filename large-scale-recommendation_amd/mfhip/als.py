@@ -9,6 +9,12 @@ MatrixFactorizationModel, backed by mf_als_fit (alternating least squares on the
 ALS.trainImplicit(ratings, rank, iterations, lambda, alpha) is the implicit-feedback sibling
 (mf_als_fit_implicit): confidences 1 + alpha |r|, preferences r > 0.
 
+ALS.withSolver("cg", cg_steps=3) gives the same two entry points on the conjugate-gradient half-sweeps
+(mf_als_fit_cg / mf_als_fit_implicit_cg): a few CG steps per row from its current value instead of a
+factorisation.  ALS.train / ALS.trainImplicit themselves keep the Cholesky solve.
+
+    model = ALS.withSolver("cg", cg_steps=3).train(ratings, rank=128)
+
 Weighted-lambda regularisation (ALS-WR), as ALS.train uses.  The initial factors are this library's
 (k x nextDouble of new Random(id ^ seed)), not MLlib's partition-dependent XORShift draws.
 """
@@ -112,6 +118,11 @@ class ALS:
         return MatrixFactorizationModel(ctx)
 
     @staticmethod
+    def withSolver(solver: str = "cholesky", cg_steps: int = 3) -> "_SolverALS":
+        """train / trainImplicit on the named solver: "cholesky" (ALS.train's own) or "cg"."""
+        return _SolverALS(solver, cg_steps)
+
+    @staticmethod
     def _context(rank: int, mode: str, seed: int) -> Context:
         p = L.default_params()
         p.num_factors = int(rank)
@@ -119,3 +130,45 @@ class ALS:
         p.seed = int(seed)
         p.mode = L.MODE_FAST_F32 if mode == "fast" else L.MODE_DETERMINISTIC_F64
         return Context(p)
+
+
+SOLVERS = ("cholesky", "cg")
+
+
+class _SolverALS:
+    """ALS.train / ALS.trainImplicit with the solver of the half-sweeps chosen (ALS.withSolver)."""
+
+    def __init__(self, solver: str = "cholesky", cg_steps: int = 3):
+        if solver not in SOLVERS:
+            raise ValueError(f"unknown ALS solver {solver!r}: one of {SOLVERS}")
+        if not 1 <= int(cg_steps) <= L.ALS_CG_MAX_STEPS:
+            raise ValueError(f"cg_steps must lie in 1 .. {L.ALS_CG_MAX_STEPS}")
+        self.solver = solver
+        self.cg_steps = int(cg_steps)
+
+    def train(self, ratings, rank: int, iterations: int = 10, lambda_: float = 0.01, mode: str = "deterministic",
+              seed: int = 0) -> MatrixFactorizationModel:
+        if self.solver == "cholesky":
+            return ALS.train(ratings, rank, iterations, lambda_, mode, seed)
+        u, i, r = _columns(ratings)
+        ctx = ALS._context(rank, mode, seed)
+        try:
+            ctx.als_fit_cg(u, i, r, int(iterations), float(lambda_), L.ALS_REG_WEIGHTED, self.cg_steps)
+        except Exception:
+            ctx.close()
+            raise
+        return MatrixFactorizationModel(ctx)
+
+    def trainImplicit(self, ratings, rank: int, iterations: int = 10, lambda_: float = 0.01, alpha: float = 0.01,
+                      mode: str = "deterministic", seed: int = 0) -> MatrixFactorizationModel:
+        if self.solver == "cholesky":
+            return ALS.trainImplicit(ratings, rank, iterations, lambda_, alpha, mode, seed)
+        u, i, r = _columns(ratings)
+        ctx = ALS._context(rank, mode, seed)
+        try:
+            ctx.als_fit_implicit_cg(u, i, r, int(iterations), float(lambda_), float(alpha), L.ALS_REG_WEIGHTED,
+                                    self.cg_steps)
+        except Exception:
+            ctx.close()
+            raise
+        return MatrixFactorizationModel(ctx)

@@ -180,6 +180,51 @@ class Context:
                                                       ptr(A, C.c_double), ptr(b, C.c_double)))
         return A, b
 
+    def als_run_cg(self, half_sweeps: int, lam: float, reg: int = L.ALS_REG_WEIGHTED, cg_steps: int = 3) -> None:
+        """mf_als_run_cg: als_run's half-sweeps with cg_steps conjugate-gradient steps per row from its
+        current value instead of a factorisation; the counter is als_run's."""
+        check(L.lib().mf_als_run_cg(self._h, int(half_sweeps), float(lam), int(reg), int(cg_steps)))
+
+    def als_run_implicit_cg(self, half_sweeps: int, lam: float, alpha: float, reg: int = L.ALS_REG_WEIGHTED,
+                            cg_steps: int = 3) -> None:
+        """mf_als_run_implicit_cg: als_run_implicit's half-sweeps by conjugate gradients."""
+        check(L.lib().mf_als_run_implicit_cg(self._h, int(half_sweeps), float(lam), int(reg), float(alpha),
+                                             int(cg_steps)))
+
+    def als_fit_cg(self, u, i, r, iterations: int, lam: float, reg: int = L.ALS_REG_WEIGHTED, cg_steps: int = 3) -> None:
+        """mf_als_fit_cg: als_prepare + als_run_cg(2 * iterations)."""
+        u, i, r = as_i32(u), as_i32(i), as_f64(r)
+        same_length(u, i, r)
+        check(L.lib().mf_als_fit_cg(self._h, ptr(u, C.c_int32), ptr(i, C.c_int32), ptr(r, C.c_double), len(u),
+                                    int(iterations), float(lam), int(reg), int(cg_steps)))
+
+    def als_fit_implicit_cg(self, u, i, r, iterations: int, lam: float, alpha: float, reg: int = L.ALS_REG_WEIGHTED,
+                            cg_steps: int = 3) -> None:
+        """mf_als_fit_implicit_cg: als_prepare + als_run_implicit_cg(2 * iterations)."""
+        u, i, r = as_i32(u), as_i32(i), as_f64(r)
+        same_length(u, i, r)
+        check(L.lib().mf_als_fit_implicit_cg(self._h, ptr(u, C.c_int32), ptr(i, C.c_int32), ptr(r, C.c_double),
+                                             len(u), int(iterations), float(lam), int(reg), float(alpha),
+                                             int(cg_steps)))
+
+    def als_cg_matvec(self, side: int, id_: int, lam: float, v, alpha: float = -1.0, reg: int = L.ALS_REG_WEIGHTED):
+        """(A v [k], b [k]) of one row through the conjugate-gradient half-sweep's kernels
+        (mf_debug_als_cg_matvec); alpha < 0: the explicit system."""
+        v = np.ascontiguousarray(v, np.float64)
+        if v.shape != (self.k,):
+            raise ValueError("v must hold k values")
+        Av = np.empty(self.k, np.float64)
+        b = np.empty(self.k, np.float64)
+        check(L.lib().mf_debug_als_cg_matvec(self._h, int(side), int(id_), float(lam), int(reg), float(alpha),
+                                             ptr(v, C.c_double), ptr(Av, C.c_double), ptr(b, C.c_double)))
+        return Av, b
+
+    def als_cg_capacity(self) -> int:
+        """The most ratings of a row whose vectors the CG half-sweep stages in LDS (mf_debug_als_cg_capacity)."""
+        n = C.c_int32(0)
+        check(L.lib().mf_debug_als_cg_capacity(self._h, C.byref(n)))
+        return int(n.value)
+
     # -- factors ---------------------------------------------------------------
     def num_factors(self, side: int) -> int:
         v = C.c_int64(0)

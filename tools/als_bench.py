@@ -24,6 +24,13 @@ mf_debug_als_gram under the same device events.
 --k K runs at another rank (129..256 take the kernels of kernels_als_wide.hip); --det also times one
 deterministic-mode (f64) iteration after one warm-up.
 
+--solver cg --cg-steps S instead compares the conjugate-gradient half-sweeps (mf_als_run_cg, S steps per
+row) with mf_als_run in one process: two contexts on the same data, one warm-up iteration each, then
+--iters rounds in which the solvers alternate, every half-sweep under the device events (medians are
+reported); both then run on to 10 iterations and report the training RMSE (first 2M ratings).  With
+--implicit the same for the implicit calls on the shifted ratings, with --det also in deterministic mode.
+The result goes under the key "cg" (of "k<K>" at another rank), beside what the file holds.
+
 Writes profiles/als_bench.json.  At the default rank this run's fields replace the file's own and every
 other key of the file stays; at another rank the same fields go under the key "k<K>", beside what it
 holds.
@@ -120,6 +127,63 @@ def als_run(train, k, iters, lam, chunk, alpha=None, det=False):
     return res
 
 
+def cg_compare(train, k, rounds, lam, steps, alpha=None, det=False, total_iters=10):
+    """mf_als_run against mf_als_run_cg(steps), alternating in one process; alpha None: explicit."""
+    from mfhip import _lib as L
+    from mfhip.context import Context
+
+    u, i, r = train
+    os.environ.pop("MFHIP_TEST", None)
+    p = L.default_params()
+    p.num_factors = k
+    p.mode = L.MODE_DETERMINISTIC_F64 if det else L.MODE_FAST_F32
+    res = {"k": k, "cg_steps": steps, "lambda": lam, "rounds": rounds, "deterministic": det, "nnz": len(u)}
+    if alpha is not None:
+        res["alpha"] = alpha
+    with Context(p) as chol, Context(p) as cg:
+        cap = cg.als_cg_capacity()
+        res["staged_capacity"] = cap
+        res["staged_share_of_rows"] = {
+            side: float((c[c > 0] <= cap).mean()) for side, c in (("item", np.bincount(i)), ("user", np.bincount(u)))}
+        for ctx in (chol, cg):
+            ctx.als_prepare(u, i, r)
+
+        def run(ctx, n):
+            if ctx is chol:
+                ctx.als_run(n, lam) if alpha is None else ctx.als_run_implicit(n, lam, alpha)
+            else:
+                ctx.als_run_cg(n, lam, cg_steps=steps) if alpha is None else \
+                    ctx.als_run_implicit_cg(n, lam, alpha, cg_steps=steps)
+
+        names = {id(chol): "cholesky", id(cg): "cg"}
+        half = {n: {"item": [], "user": []} for n in names.values()}
+        for ctx in (chol, cg):
+            run(ctx, 2)  # warm-up
+            ctx.set_profiling(True)
+        for _ in range(rounds):
+            for ctx in (chol, cg):
+                for side in ("item", "user"):
+                    ctx.reset_stats()
+                    run(ctx, 1)
+                    half[names[id(ctx)]][side].append(ctx.stats()["kernel_ms"])
+        for ctx in (chol, cg):
+            ctx.set_profiling(False)
+            run(ctx, 2 * max(0, total_iters - 1 - rounds))
+            res.setdefault("train_rmse_sample_after_%d" % max(total_iters, 1 + rounds), {})[names[id(ctx)]] = \
+                ctx.rmse(u[:2_000_000], i[:2_000_000], r[:2_000_000])[0]
+    res["half_sweep_ms"] = {n: {s: {"median": float(np.median(v)), "all": v} for s, v in half[n].items()} for n in half}
+    it = {n: sum(res["half_sweep_ms"][n][s]["median"] for s in ("item", "user")) for n in half}
+    res["iteration_ms_device"] = it
+    res["cg_speedup"] = it["cholesky"] / it["cg"]
+    kind = ("explicit" if alpha is None else f"implicit (alpha {alpha})") + (" deterministic" if det else " fast")
+    h = res["half_sweep_ms"]
+    print(f"k {k} {kind}: Cholesky {it['cholesky']:.1f} ms / iteration (item {h['cholesky']['item']['median']:.1f}, user "
+          f"{h['cholesky']['user']['median']:.1f}), CG S={steps} {it['cg']:.1f} ms (item {h['cg']['item']['median']:.1f}, "
+          f"user {h['cg']['user']['median']:.1f}): x{res['cg_speedup']:.2f}; staged rows {res['staged_share_of_rows']}; "
+          f"rmse {[v for k_, v in res.items() if k_.startswith('train_rmse')][0]}", flush=True)
+    return res
+
+
 def dsgd_epoch(train, k, nb):
     from mfhip import _lib as L
     from mfhip.context import Context
@@ -154,6 +218,9 @@ def main():
     ap.add_argument("--alpha", type=float, default=1.0, help="the implicit runs' alpha")
     ap.add_argument("--k", type=int, default=128, help="the rank (default 128)")
     ap.add_argument("--det", action="store_true", help="also time one deterministic-mode iteration")
+    ap.add_argument("--solver", choices=("cholesky", "cg"), default="cholesky",
+                    help="cg: compare mf_als_run_cg with mf_als_run instead of the timings above")
+    ap.add_argument("--cg-steps", type=int, default=3, help="CG steps per row (with --solver cg)")
     ap.add_argument("--scale", type=float, default=1.0, help="shrink the synthetic (rehearsal only)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "als_bench.json"))
     a = ap.parse_args()
@@ -167,6 +234,24 @@ def main():
     nu, ni, nr, k0, nb = synth.CONFIGS["NFLX"]
     k = a.k
     train, _ = synth.generate(max(1, int(nu * a.scale)), max(1, int(ni * a.scale)), max(1, int(nr * a.scale))).split()
+    if a.solver == "cg":
+        out = {"scale": a.scale, "runs": [cg_compare(train, k, a.iters, a.lam, a.cg_steps)]}
+        if a.implicit:
+            u, i, r = train
+            shifted = (u, i, np.asarray(r, np.float64) - 3.0)
+            out["runs"].append(cg_compare(shifted, k, a.iters, a.lam, a.cg_steps, a.alpha))
+        if a.det:
+            out["runs"].append(cg_compare(train, k, a.iters, a.lam, a.cg_steps, det=True))
+        old = {}
+        if os.path.exists(a.out):
+            with open(a.out) as f:
+                old = json.load(f)
+        (old if k == k0 else old.setdefault(f"k{k}", {}))["cg"] = out
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(old, f, indent=1)
+        print("wrote", a.out)
+        return
     out = {"shape": "NFLX", "scale": a.scale, "runs": []}
     for c in [int(x) for x in a.chunks.split(",") if x] or [0]:
         out["runs"].append(als_run(train, k, a.iters, a.lam, c))
