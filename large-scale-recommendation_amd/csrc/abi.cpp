@@ -375,100 +375,80 @@ int mf_als_prepare(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double
   });
 }
 
-int mf_als_run(mf_ctx* ctx, int64_t half_sweeps, double lambda, int32_t reg) {
+namespace {
+
+// The cg_steps of a conjugate-gradient entry as AlsParams::cg_steps, where 0 selects Cholesky: the
+// caller's 0 stays out of range.
+int32_t als_cg_entry_steps(int32_t cg_steps) { return cg_steps == 0 ? -1 : cg_steps; }
+
+int als_run_entry(mf_ctx* ctx, int64_t half_sweeps, const AlsParams& P) {
   return guarded([&] {
     MF_REQUIRE(ctx, "null context");
-    als_run(ctx, half_sweeps, lambda, reg);
+    als_run(ctx, half_sweeps, P);
   });
+}
+
+// mf_als_fit and its variants: prepare + 2 * iterations half-sweeps, every argument checked first.
+int als_fit_entry(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n, int32_t iterations,
+                  const AlsParams& P) {
+  return guarded([&] {
+    MF_REQUIRE(ctx, "null context");
+    MF_REQUIRE(n >= 0 && iterations >= 0, "negative count");
+    if (P.implicit) als_check_alpha(P.alpha);
+    als_check_run(P);
+    als_check(ctx);
+    if (n == 0) return;
+    als_prepare(ctx, u, i, r, n);
+    als_run(ctx, 2 * static_cast<int64_t>(iterations), P);
+  });
+}
+
+}  // namespace
+
+int mf_als_run(mf_ctx* ctx, int64_t half_sweeps, double lambda, int32_t reg) {
+  return als_run_entry(ctx, half_sweeps, {lambda, reg});
 }
 
 int mf_als_fit(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n, int32_t iterations,
                double lambda, int32_t reg) {
-  return guarded([&] {
-    MF_REQUIRE(ctx, "null context");
-    MF_REQUIRE(n >= 0 && iterations >= 0, "negative count");
-    als_check_run(lambda, reg);
-    als_check(ctx);
-    if (n == 0) return;
-    als_prepare(ctx, u, i, r, n);
-    als_run(ctx, 2 * static_cast<int64_t>(iterations), lambda, reg);
-  });
+  return als_fit_entry(ctx, u, i, r, n, iterations, {lambda, reg});
 }
 
 int mf_als_run_implicit(mf_ctx* ctx, int64_t half_sweeps, double lambda, int32_t reg, double alpha) {
-  return guarded([&] {
-    MF_REQUIRE(ctx, "null context");
-    als_check_alpha(alpha);
-    als_run(ctx, half_sweeps, lambda, reg, alpha);
-  });
+  return als_run_entry(ctx, half_sweeps, {lambda, reg, true, alpha});
 }
 
 int mf_als_fit_implicit(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n,
                         int32_t iterations, double lambda, int32_t reg, double alpha) {
-  return guarded([&] {
-    MF_REQUIRE(ctx, "null context");
-    MF_REQUIRE(n >= 0 && iterations >= 0, "negative count");
-    als_check_alpha(alpha);
-    als_check_run(lambda, reg);
-    als_check(ctx);
-    if (n == 0) return;
-    als_prepare(ctx, u, i, r, n);
-    als_run(ctx, 2 * static_cast<int64_t>(iterations), lambda, reg, alpha);
-  });
+  return als_fit_entry(ctx, u, i, r, n, iterations, {lambda, reg, true, alpha});
 }
 
 int mf_als_run_cg(mf_ctx* ctx, int64_t half_sweeps, double lambda, int32_t reg, int32_t cg_steps) {
-  return guarded([&] {
-    MF_REQUIRE(ctx, "null context");
-    als_run_cg(ctx, half_sweeps, lambda, reg, -1.0, cg_steps);
-  });
+  return als_run_entry(ctx, half_sweeps, {lambda, reg, false, 0.0, als_cg_entry_steps(cg_steps)});
 }
 
 int mf_als_fit_cg(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n, int32_t iterations,
                   double lambda, int32_t reg, int32_t cg_steps) {
-  return guarded([&] {
-    MF_REQUIRE(ctx, "null context");
-    MF_REQUIRE(n >= 0 && iterations >= 0, "negative count");
-    als_check_run(lambda, reg);
-    als_check_cg(cg_steps);
-    als_check(ctx);
-    if (n == 0) return;
-    als_prepare(ctx, u, i, r, n);
-    als_run_cg(ctx, 2 * static_cast<int64_t>(iterations), lambda, reg, -1.0, cg_steps);
-  });
+  return als_fit_entry(ctx, u, i, r, n, iterations, {lambda, reg, false, 0.0, als_cg_entry_steps(cg_steps)});
 }
 
 int mf_als_run_implicit_cg(mf_ctx* ctx, int64_t half_sweeps, double lambda, int32_t reg, double alpha,
                            int32_t cg_steps) {
-  return guarded([&] {
-    MF_REQUIRE(ctx, "null context");
-    als_check_alpha(alpha);
-    als_run_cg(ctx, half_sweeps, lambda, reg, alpha, cg_steps);
-  });
+  return als_run_entry(ctx, half_sweeps, {lambda, reg, true, alpha, als_cg_entry_steps(cg_steps)});
 }
 
 int mf_als_fit_implicit_cg(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n,
                            int32_t iterations, double lambda, int32_t reg, double alpha, int32_t cg_steps) {
-  return guarded([&] {
-    MF_REQUIRE(ctx, "null context");
-    MF_REQUIRE(n >= 0 && iterations >= 0, "negative count");
-    als_check_alpha(alpha);
-    als_check_run(lambda, reg);
-    als_check_cg(cg_steps);
-    als_check(ctx);
-    if (n == 0) return;
-    als_prepare(ctx, u, i, r, n);
-    als_run_cg(ctx, 2 * static_cast<int64_t>(iterations), lambda, reg, alpha, cg_steps);
-  });
+  return als_fit_entry(ctx, u, i, r, n, iterations, {lambda, reg, true, alpha, als_cg_entry_steps(cg_steps)});
 }
 
+// (alpha < 0: the explicit system; any other alpha, NaN included, is the implicit one's and is checked as such)
 int mf_debug_als_cg_matvec(mf_ctx* ctx, int side, int32_t id, double lambda, int32_t reg, double alpha, const double* v,
                            double* Av_out, double* b_out) {
   return guarded([&] {
     MF_REQUIRE(ctx && v && Av_out && b_out, "null argument");
     MF_REQUIRE(side == MF_SIDE_USER || side == MF_SIDE_ITEM, "bad side");
-    MF_REQUIRE(alpha < 0.0 || std::isfinite(alpha), "implicit ALS needs a finite alpha >= 0");
-    als_cg_matvec(ctx, side, id, lambda, reg, alpha < 0.0 ? -1.0 : alpha, v, Av_out, b_out);
+    als_cg_matvec(ctx, side, id, {lambda, reg, !(alpha < 0.0), alpha, 1}, v, Av_out, b_out);
   });
 }
 
@@ -493,8 +473,7 @@ int mf_debug_als_normal_eq_implicit(mf_ctx* ctx, int side, int32_t id, double la
   return guarded([&] {
     MF_REQUIRE(ctx && A_out && b_out, "null argument");
     MF_REQUIRE(side == MF_SIDE_USER || side == MF_SIDE_ITEM, "bad side");
-    als_check_alpha(alpha);
-    als_normal_eq(ctx, side, id, lambda, reg, A_out, b_out, alpha);
+    als_normal_eq(ctx, side, id, {lambda, reg, true, alpha}, A_out, b_out);
   });
 }
 
@@ -503,7 +482,7 @@ int mf_debug_als_normal_eq(mf_ctx* ctx, int side, int32_t id, double lambda, int
   return guarded([&] {
     MF_REQUIRE(ctx && A_out && b_out, "null argument");
     MF_REQUIRE(side == MF_SIDE_USER || side == MF_SIDE_ITEM, "bad side");
-    als_normal_eq(ctx, side, id, lambda, reg, A_out, b_out);
+    als_normal_eq(ctx, side, id, {lambda, reg}, A_out, b_out);
   });
 }
 

@@ -1,5 +1,5 @@
-// als.cpp -- ALS training (mf_als_prepare / mf_als_run / mf_als_fit, mf_als_run_implicit /
-// mf_als_fit_implicit) and its testing hooks.
+// als.cpp -- ALS training (mf_als_prepare / mf_als_run / mf_als_fit, their _implicit, _cg and
+// _implicit_cg variants) and its testing hooks.
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -43,9 +43,11 @@ void als_check_alpha(double alpha) {
   MF_REQUIRE(alpha >= 0.0 && std::isfinite(alpha), "implicit ALS needs a finite alpha >= 0");
 }
 
-void als_check_run(double lambda, int32_t reg) {
-  MF_REQUIRE(lambda > 0.0 && std::isfinite(lambda), "ALS needs lambda > 0");
-  MF_REQUIRE(reg == MF_ALS_REG_WEIGHTED || reg == MF_ALS_REG_PLAIN, "unknown ALS regularisation (reg)");
+void als_check_run(const AlsParams& P) {
+  MF_REQUIRE(P.lambda > 0.0 && std::isfinite(P.lambda), "ALS needs lambda > 0");
+  MF_REQUIRE(P.reg == MF_ALS_REG_WEIGHTED || P.reg == MF_ALS_REG_PLAIN, "unknown ALS regularisation (reg)");
+  MF_REQUIRE(P.cg_steps >= 0 && P.cg_steps <= MF_ALS_CG_MAX_STEPS,
+             "cg_steps must lie in 1 .. " + std::to_string(MF_ALS_CG_MAX_STEPS));
 }
 
 namespace {
@@ -182,6 +184,39 @@ void als_prepare(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* 
 
 namespace {
 
+// What every entry past mf_als_prepare starts with; `api` is the name in the MF_ERR_STATE text.
+Shard& als_enter(mf_ctx* ctx, const std::string& api) {
+  als_check(ctx);
+  if (!ctx->als_prepared) fail(MF_ERR_STATE, api + " before mf_als_prepare");
+  require_healthy(ctx);
+  sync_all(ctx);
+  return ctx->shards[0];
+}
+
+// n elements of a device buffer in the context's precision as host doubles, and the way back.
+std::vector<double> read_as_f64(const mf_ctx* ctx, const DevBuf& d, size_t n) {
+  std::vector<double> h(n);
+  if (ctx->f64) {
+    MF_HIP(hipMemcpy(h.data(), d.get(), n * 8, hipMemcpyDeviceToHost));
+  } else {
+    std::vector<float> f(n);
+    MF_HIP(hipMemcpy(f.data(), d.get(), n * 4, hipMemcpyDeviceToHost));
+    for (size_t x = 0; x < n; ++x) h[x] = static_cast<double>(f[x]);
+  }
+  return h;
+}
+
+void write_from_f64(const mf_ctx* ctx, DevBuf& d, const double* src, size_t n) {
+  d.alloc(std::max<size_t>(n * ctx->es, 16));
+  if (ctx->f64) {
+    MF_HIP(hipMemcpy(d.get(), src, n * 8, hipMemcpyHostToDevice));
+  } else {
+    std::vector<float> f(n);
+    for (size_t x = 0; x < n; ++x) f[x] = static_cast<float>(src[x]);
+    MF_HIP(hipMemcpy(d.get(), f.data(), n * 4, hipMemcpyHostToDevice));
+  }
+}
+
 // G of `side`'s rated rows into s.als_gram, on the shard's stream: two launches.
 void als_gram_launch(mf_ctx* ctx, Shard& s, int side) {
   const int k = ctx->P.num_factors;
@@ -189,121 +224,10 @@ void als_gram_launch(mf_ctx* ctx, Shard& s, int side) {
   const size_t ge = als_gram_elems(k) * ctx->es;
   s.als_gram_part.alloc(std::max<size_t>(static_cast<size_t>(als_gram_slices(m, slice)) * ge, 16));
   s.als_gram.alloc(ge);
-  launch_als_gram(s.stream, s.als_rated[side].as<int32_t>(), m, slice, side == kSideU ? s.uf.get() : s.itf.get(), k,
-                  ctx->f64, s.als_gram_part.get(), s.als_gram.get());
+  launch_als_gram({s.stream, s.als_rated[side].as<int32_t>(), m, slice, side == kSideU ? s.uf.get() : s.itf.get(), k,
+                   ctx->f64, s.als_gram_part.get(), s.als_gram.get()});
   MF_HIP(hipGetLastError());
 }
-
-// One side solved from the other; alpha >= 0: the implicit half-sweep, after the counterpart's Gram
-// matrix.  only_row >= 0 (the testing hook): that row's work items alone, its system stored to
-// s.als_dump instead of being solved; false if the row has no rating.
-bool als_half(mf_ctx* ctx, int side, double lambda, int32_t reg, double alpha, int64_t only_row = -1) {
-  Shard& s = ctx->shards[0];
-  DeviceGuard g(s.device);
-  const mf_ctx::AlsSide& A = ctx->als[side];
-  const int k = ctx->P.num_factors;
-  const bool implicit = alpha >= 0.0;
-  const int other = side == kSideU ? MF_SIDE_ITEM : kSideU;
-  s.als_part.alloc(std::max<size_t>(static_cast<size_t>(A.max_slots) * als_partial_elems(k) * ctx->es, 16));
-  const void* Q = side == kSideU ? s.itf.get() : s.uf.get();
-  void* X = side == kSideU ? s.uf.get() : s.itf.get();
-  const AlsItem* d_items = s.als_items[side].as<AlsItem>();
-  const AlsSplit* d_splits = s.als_splits[side].as<AlsSplit>();
-  const bool weighted = reg == MF_ALS_REG_WEIGHTED;
-  // k > 128: one normal matrix in global memory per workgroup of the grid, however many rows there are
-  const int slabs = static_cast<int>(std::min<int64_t>(ctx->als_slabs, static_cast<int64_t>(A.items.size())));
-  if (slabs > 0) s.als_slab.alloc(static_cast<size_t>(slabs) * als_gram_elems(k) * ctx->es);
-  if (only_row >= 0) {
-    auto lo = std::lower_bound(A.items.begin(), A.items.end(), only_row,
-                               [](const AlsItem& a, int64_t row) { return a.row < row; });
-    if (lo == A.items.end() || lo->row != only_row) return false;
-    auto hi = lo;
-    while (hi != A.items.end() && hi->row == only_row) ++hi;
-    auto sp = std::lower_bound(A.splits.begin(), A.splits.end(), only_row,
-                               [](const AlsSplit& a, int64_t row) { return a.row < row; });
-    const bool split = sp != A.splits.end() && sp->row == only_row;
-    s.als_dump.alloc((static_cast<size_t>(k) * k + k) * ctx->es);
-    if (implicit) als_gram_launch(ctx, s, other);
-    launch_als(s.stream, d_items + (lo - A.items.begin()), static_cast<int>(hi - lo),
-               d_splits + (sp - A.splits.begin()), split ? 1 : 0, s.als_cols[side].as<int32_t>(),
-               s.als_vals[side].get(), Q, X, k, lambda, weighted, ctx->f64, s.als_part.get(), s.als_dump.get(),
-               implicit ? s.als_gram.get() : nullptr, alpha, s.als_slab.get(), slabs);
-    MF_HIP(hipGetLastError());
-    return true;
-  }
-  LaunchTimer t(s, ctx->profiling);
-  if (implicit && !A.batches.empty()) {
-    als_gram_launch(ctx, s, other);
-    ctx->stats.kernel_launches += 2;
-  }
-  for (const mf_ctx::AlsBatch& b : A.batches) {
-    launch_als(s.stream, d_items + b.item0, static_cast<int>(b.items), d_splits + b.split0, static_cast<int>(b.splits),
-               s.als_cols[side].as<int32_t>(), s.als_vals[side].get(), Q, X, k, lambda, weighted, ctx->f64,
-               s.als_part.get(), nullptr, implicit ? s.als_gram.get() : nullptr, alpha, s.als_slab.get(), slabs);
-    MF_HIP(hipGetLastError());
-    ctx->stats.kernel_launches += 1 + (b.splits > 0);
-  }
-  return true;
-}
-
-}  // namespace
-
-void als_run(mf_ctx* ctx, int64_t half_sweeps, double lambda, int32_t reg, double alpha) {
-  MF_REQUIRE(half_sweeps >= 0, "negative half-sweep count");
-  als_check_run(lambda, reg);
-  als_check(ctx);
-  if (!ctx->als_prepared)
-    fail(MF_ERR_STATE, std::string(alpha >= 0.0 ? "mf_als_run_implicit" : "mf_als_run") + " before mf_als_prepare");
-  require_healthy(ctx);
-  sync_all(ctx);
-  for (int64_t h = 0; h < half_sweeps; ++h) {
-    // MLlib's order: the item side from the user factors first
-    als_half(ctx, ctx->als_half_sweeps % 2 == 0 ? MF_SIDE_ITEM : kSideU, lambda, reg, alpha);
-    ++ctx->als_half_sweeps;
-  }
-  DeviceGuard g(ctx->shards[0].device);
-  MF_HIP(hipStreamSynchronize(ctx->shards[0].stream));
-}
-
-// The normal equations of one row as the kernel accumulates them (mf_debug_als_normal_eq, and with
-// alpha >= 0 mf_debug_als_normal_eq_implicit).
-void als_normal_eq(mf_ctx* ctx, int side, int32_t id, double lambda, int32_t reg, double* A_out, double* b_out,
-                   double alpha) {
-  als_check_run(lambda, reg);
-  als_check(ctx);
-  if (!ctx->als_prepared)
-    fail(MF_ERR_STATE, std::string(alpha >= 0.0 ? "mf_debug_als_normal_eq_implicit" : "mf_debug_als_normal_eq") +
-                           " before mf_als_prepare");
-  require_healthy(ctx);
-  sync_all(ctx);
-  const int32_t row = side_of(ctx, side).index.find(id);
-  MF_REQUIRE(row >= 0, "unknown id");
-  MF_REQUIRE(als_half(ctx, side, lambda, reg, alpha, row), "the id has no rating in the prepared data");
-  Shard& s = ctx->shards[0];
-  DeviceGuard g(s.device);
-  MF_HIP(hipStreamSynchronize(s.stream));
-  const size_t k = static_cast<size_t>(ctx->P.num_factors), m = k * k + k;
-  std::vector<double> h(m);
-  if (ctx->f64) {
-    MF_HIP(hipMemcpy(h.data(), s.als_dump.get(), m * 8, hipMemcpyDeviceToHost));
-  } else {
-    std::vector<float> f(m);
-    MF_HIP(hipMemcpy(f.data(), s.als_dump.get(), m * 4, hipMemcpyDeviceToHost));
-    for (size_t x = 0; x < m; ++x) h[x] = static_cast<double>(f[x]);
-  }
-  std::memcpy(A_out, h.data(), k * k * 8);
-  std::memcpy(b_out, h.data() + k * k, k * 8);
-}
-
-// ---------------------------------------------------------------------------------------
-// The conjugate-gradient half-sweeps (mf_als_run_cg / mf_als_run_implicit_cg; kernels_als_cg.hip) on
-// the same prepared data: the work lists, batches and partial slots of als_half, G for the implicit half.
-void als_check_cg(int32_t cg_steps) {
-  MF_REQUIRE(cg_steps >= 1 && cg_steps <= MF_ALS_CG_MAX_STEPS,
-             "cg_steps must lie in 1 .. " + std::to_string(MF_ALS_CG_MAX_STEPS));
-}
-
-namespace {
 
 // The chunk items of `side`'s long rows, per batch, with the index of each one's row among the batch's splits.
 void als_cg_lists(mf_ctx* ctx, Shard& s, int side) {
@@ -330,133 +254,162 @@ void als_cg_lists(mf_ctx* ctx, Shard& s, int side) {
   A.cg_ready = true;
 }
 
-bool als_cg_stage() { return test_knob("als_cg_stage") != "0"; }
+// The work of one row (the testing hooks) in the form of a batch: its items and, if it is a long row,
+// its split; items == 0 if the row has no rating.
+mf_ctx::AlsBatch als_row_span(const mf_ctx::AlsSide& A, int64_t row) {
+  auto lo = std::lower_bound(A.items.begin(), A.items.end(), row,
+                             [](const AlsItem& a, int64_t r) { return a.row < r; });
+  auto hi = lo;
+  while (hi != A.items.end() && hi->row == row) ++hi;
+  auto sp = std::lower_bound(A.splits.begin(), A.splits.end(), row,
+                             [](const AlsSplit& a, int64_t r) { return a.row < r; });
+  return {lo - A.items.begin(), hi - lo, sp - A.splits.begin(), sp != A.splits.end() && sp->row == row ? 1 : 0};
+}
 
-// als_half's counterpart.  only_row >= 0 (the testing hook): A v and b of that row for the v in
-// s.als_cg_v, stored to s.als_dump; false if the row has no rating.
-bool als_half_cg(mf_ctx* ctx, int side, double lambda, int32_t reg, double alpha, int steps, int64_t only_row = -1) {
+// One side solved from the other (P.implicit: after the counterpart's Gram matrix), by Cholesky or, with
+// P.cg_steps > 0, by conjugate gradients on the same work lists, batches and partial slots.
+// only_row >= 0 (the testing hooks): that row's work items alone, and s.als_dump takes the row's system
+// (Cholesky) or A v and b for the v in s.als_cg_v (conjugate gradients) instead of the row being solved;
+// false if the row has no rating.
+bool als_half(mf_ctx* ctx, int side, const AlsParams& P, int64_t only_row = -1) {
   Shard& s = ctx->shards[0];
   DeviceGuard g(s.device);
   mf_ctx::AlsSide& A = ctx->als[side];
   const int k = ctx->P.num_factors;
-  const bool implicit = alpha >= 0.0;
+  const bool cg = P.cg_steps > 0;
   const int other = side == kSideU ? MF_SIDE_ITEM : kSideU;
-  als_cg_lists(ctx, s, side);
-  s.als_part.alloc(std::max<size_t>(static_cast<size_t>(A.max_slots) * als_partial_elems(k) * ctx->es, 16));
-  s.als_cg_state.alloc(std::max<size_t>(static_cast<size_t>(std::max<int64_t>(A.cg_max_splits, 1)) *
-                                            als_cg_state_elems(k) * ctx->es, 16));
-  const void* Q = side == kSideU ? s.itf.get() : s.uf.get();
-  void* X = side == kSideU ? s.uf.get() : s.itf.get();
   const AlsItem* d_items = s.als_items[side].as<AlsItem>();
   const AlsSplit* d_splits = s.als_splits[side].as<AlsSplit>();
-  const AlsCgWork* d_work = s.als_cg_work[side].as<AlsCgWork>();
-  const bool weighted = reg == MF_ALS_REG_WEIGHTED, stage = als_cg_stage();
+  s.als_part.alloc(std::max<size_t>(static_cast<size_t>(A.max_slots) * als_partial_elems(k) * ctx->es, 16));
+  AlsLaunch L;
+  L.st = s.stream;
+  L.cols = s.als_cols[side].as<int32_t>();
+  L.vals = s.als_vals[side].get();
+  L.Q = side == kSideU ? s.itf.get() : s.uf.get();
+  L.X = side == kSideU ? s.uf.get() : s.itf.get();
+  L.k = k;
+  L.lambda = P.lambda;
+  L.weighted = P.reg == MF_ALS_REG_WEIGHTED;
+  L.f64 = ctx->f64;
+  L.partial = s.als_part.get();
+  L.alpha = P.alpha;
+  if (cg) {
+    als_cg_lists(ctx, s, side);
+    s.als_cg_state.alloc(std::max<size_t>(static_cast<size_t>(std::max<int64_t>(A.cg_max_splits, 1)) *
+                                              als_cg_state_elems(k) * ctx->es, 16));
+    L.steps = P.cg_steps;
+    L.stage = test_knob("als_cg_stage") != "0";
+    L.state = s.als_cg_state.get();
+  } else {
+    // k > 128: one normal matrix in global memory per workgroup of the grid, however many rows there are
+    L.slabs = static_cast<int>(std::min<int64_t>(ctx->als_slabs, static_cast<int64_t>(A.items.size())));
+    if (L.slabs > 0) s.als_slab.alloc(static_cast<size_t>(L.slabs) * als_gram_elems(k) * ctx->es);
+    L.slab = s.als_slab.get();
+  }
+  auto gram = [&] {
+    als_gram_launch(ctx, s, other);
+    L.gram = s.als_gram.get();
+  };
+  auto launch = [&](const mf_ctx::AlsBatch& b) {
+    L.items = d_items + b.item0;
+    L.n_items = static_cast<int>(b.items);
+    L.splits = d_splits + b.split0;
+    L.n_splits = static_cast<int>(b.splits);
+    cg ? launch_als_cg(L) : launch_als(L);
+    MF_HIP(hipGetLastError());
+  };
   if (only_row >= 0) {
-    auto lo = std::lower_bound(A.items.begin(), A.items.end(), only_row,
-                               [](const AlsItem& a, int64_t row) { return a.row < row; });
-    if (lo == A.items.end() || lo->row != only_row) return false;
-    auto hi = lo;
-    while (hi != A.items.end() && hi->row == only_row) ++hi;
-    auto sp = std::lower_bound(A.splits.begin(), A.splits.end(), only_row,
-                               [](const AlsSplit& a, int64_t row) { return a.row < row; });
-    const bool split = sp != A.splits.end() && sp->row == only_row;
-    const int n = static_cast<int>(hi - lo);
-    if (split) {  // the row's chunks, as items [0, n) of the launch and long row 0
-      std::vector<AlsCgWork> w(static_cast<size_t>(n));
-      for (int x = 0; x < n; ++x) w[static_cast<size_t>(x)] = {x, 0};
+    const mf_ctx::AlsBatch row = als_row_span(A, only_row);
+    if (row.items == 0) return false;
+    if (cg && row.splits) {  // the row's chunks, as items [0, n) of the launch and long row 0
+      std::vector<AlsCgWork> w(static_cast<size_t>(row.items));
+      for (int32_t x = 0; x < row.items; ++x) w[static_cast<size_t>(x)] = {x, 0};
       s.als_cg_hook_work.alloc(w.size() * sizeof(AlsCgWork));
       MF_HIP(hipMemcpy(s.als_cg_hook_work.get(), w.data(), w.size() * sizeof(AlsCgWork), hipMemcpyHostToDevice));
+      L.work = s.als_cg_hook_work.as<AlsCgWork>();
+      L.n_work = static_cast<int>(row.items);
     }
     s.als_dump.alloc(std::max<size_t>((static_cast<size_t>(k) * k + k) * ctx->es, 16));
-    if (implicit) als_gram_launch(ctx, s, other);
-    launch_als_cg(s.stream, d_items + (lo - A.items.begin()), n, d_splits + (sp - A.splits.begin()), split ? 1 : 0,
-                  split ? s.als_cg_hook_work.as<AlsCgWork>() : nullptr, split ? n : 0, s.als_cols[side].as<int32_t>(),
-                  s.als_vals[side].get(), Q, X, k, lambda, weighted, ctx->f64, s.als_part.get(),
-                  implicit ? s.als_gram.get() : nullptr, alpha, 1, stage, s.als_cg_state.get(), s.als_cg_v.get(),
-                  s.als_dump.get());
-    MF_HIP(hipGetLastError());
+    L.dump = s.als_dump.get();
+    L.hook_v = s.als_cg_v.get();
+    if (P.implicit) gram();
+    launch(row);
     return true;
   }
   LaunchTimer t(s, ctx->profiling);
-  if (implicit && !A.batches.empty()) {
-    als_gram_launch(ctx, s, other);
+  if (P.implicit && !A.batches.empty()) {
+    gram();
     ctx->stats.kernel_launches += 2;
   }
   for (size_t b = 0; b < A.batches.size(); ++b) {
     const mf_ctx::AlsBatch& B = A.batches[b];
-    const int64_t w0 = A.cg_work0[b], nw = A.cg_work0[b + 1] - w0;
-    launch_als_cg(s.stream, d_items + B.item0, static_cast<int>(B.items), d_splits + B.split0,
-                  static_cast<int>(B.splits), d_work + w0, static_cast<int>(nw), s.als_cols[side].as<int32_t>(),
-                  s.als_vals[side].get(), Q, X, k, lambda, weighted, ctx->f64, s.als_part.get(),
-                  implicit ? s.als_gram.get() : nullptr, alpha, steps, stage, s.als_cg_state.get(), nullptr, nullptr);
-    MF_HIP(hipGetLastError());
-    ctx->stats.kernel_launches += 1 + (B.splits > 0 ? 2 * (steps + 1) : 0);
+    if (cg) {
+      L.work = s.als_cg_work[side].as<AlsCgWork>() + A.cg_work0[b];
+      L.n_work = static_cast<int>(A.cg_work0[b + 1] - A.cg_work0[b]);
+    }
+    launch(B);
+    ctx->stats.kernel_launches += 1 + (B.splits > 0 ? (cg ? 2 * (P.cg_steps + 1) : 1) : 0);
   }
   return true;
 }
 
+// The hooks' row: the id's row on `side`, solved as als_half's only_row.
+void als_hook_row(mf_ctx* ctx, int side, int32_t id, const AlsParams& P) {
+  const int32_t row = side_of(ctx, side).index.find(id);
+  MF_REQUIRE(row >= 0, "unknown id");
+  MF_REQUIRE(als_half(ctx, side, P, row), "the id has no rating in the prepared data");
+  DeviceGuard g(ctx->shards[0].device);
+  MF_HIP(hipStreamSynchronize(ctx->shards[0].stream));
+}
+
 }  // namespace
 
-void als_run_cg(mf_ctx* ctx, int64_t half_sweeps, double lambda, int32_t reg, double alpha, int32_t cg_steps) {
+void als_run(mf_ctx* ctx, int64_t half_sweeps, const AlsParams& P) {
+  if (P.implicit) als_check_alpha(P.alpha);
   MF_REQUIRE(half_sweeps >= 0, "negative half-sweep count");
-  als_check_run(lambda, reg);
-  als_check_cg(cg_steps);
-  als_check(ctx);
-  if (!ctx->als_prepared)
-    fail(MF_ERR_STATE,
-         std::string(alpha >= 0.0 ? "mf_als_run_implicit_cg" : "mf_als_run_cg") + " before mf_als_prepare");
-  require_healthy(ctx);
-  sync_all(ctx);
+  als_check_run(P);
+  als_enter(ctx, std::string("mf_als_run") + (P.implicit ? "_implicit" : "") + (P.cg_steps ? "_cg" : ""));
   for (int64_t h = 0; h < half_sweeps; ++h) {
-    als_half_cg(ctx, ctx->als_half_sweeps % 2 == 0 ? MF_SIDE_ITEM : kSideU, lambda, reg, alpha, cg_steps);
-    ++ctx->als_half_sweeps;  // mf_als_run's counter
+    // MLlib's order: the item side from the user factors first
+    als_half(ctx, ctx->als_half_sweeps % 2 == 0 ? MF_SIDE_ITEM : kSideU, P);
+    ++ctx->als_half_sweeps;
   }
   DeviceGuard g(ctx->shards[0].device);
   MF_HIP(hipStreamSynchronize(ctx->shards[0].stream));
 }
 
-// A v and b of one row through the conjugate-gradient half-sweep's own kernels (mf_debug_als_cg_matvec).
-void als_cg_matvec(mf_ctx* ctx, int side, int32_t id, double lambda, int32_t reg, double alpha, const double* v,
-                   double* Av_out, double* b_out) {
-  als_check_run(lambda, reg);
-  als_check(ctx);
-  if (!ctx->als_prepared) fail(MF_ERR_STATE, "mf_debug_als_cg_matvec before mf_als_prepare");
-  require_healthy(ctx);
-  sync_all(ctx);
-  const int32_t row = side_of(ctx, side).index.find(id);
-  MF_REQUIRE(row >= 0, "unknown id");
-  Shard& s = ctx->shards[0];
+// The normal equations of one row as the kernel accumulates them (mf_debug_als_normal_eq, and with
+// P.implicit mf_debug_als_normal_eq_implicit).
+void als_normal_eq(mf_ctx* ctx, int side, int32_t id, const AlsParams& P, double* A_out, double* b_out) {
+  if (P.implicit) als_check_alpha(P.alpha);
+  als_check_run(P);
+  Shard& s = als_enter(ctx, std::string("mf_debug_als_normal_eq") + (P.implicit ? "_implicit" : ""));
+  als_hook_row(ctx, side, id, P);
   DeviceGuard g(s.device);
   const size_t k = static_cast<size_t>(ctx->P.num_factors);
-  s.als_cg_v.alloc(std::max<size_t>(k * ctx->es, 16));
-  if (ctx->f64) {
-    MF_HIP(hipMemcpy(s.als_cg_v.get(), v, k * 8, hipMemcpyHostToDevice));
-  } else {
-    std::vector<float> f(k);
-    for (size_t x = 0; x < k; ++x) f[x] = static_cast<float>(v[x]);
-    MF_HIP(hipMemcpy(s.als_cg_v.get(), f.data(), k * 4, hipMemcpyHostToDevice));
-  }
-  MF_REQUIRE(als_half_cg(ctx, side, lambda, reg, alpha, 1, row), "the id has no rating in the prepared data");
-  MF_HIP(hipStreamSynchronize(s.stream));
-  std::vector<double> h(2 * k);
-  if (ctx->f64) {
-    MF_HIP(hipMemcpy(h.data(), s.als_dump.get(), 2 * k * 8, hipMemcpyDeviceToHost));
-  } else {
-    std::vector<float> f(2 * k);
-    MF_HIP(hipMemcpy(f.data(), s.als_dump.get(), 2 * k * 4, hipMemcpyDeviceToHost));
-    for (size_t x = 0; x < 2 * k; ++x) h[x] = static_cast<double>(f[x]);
-  }
+  const std::vector<double> h = read_as_f64(ctx, s.als_dump, k * k + k);
+  std::memcpy(A_out, h.data(), k * k * 8);
+  std::memcpy(b_out, h.data() + k * k, k * 8);
+}
+
+// A v and b of one row through the conjugate-gradient half-sweep's own kernels (mf_debug_als_cg_matvec).
+void als_cg_matvec(mf_ctx* ctx, int side, int32_t id, const AlsParams& P, const double* v, double* Av_out,
+                   double* b_out) {
+  if (P.implicit) als_check_alpha(P.alpha);
+  als_check_run(P);
+  Shard& s = als_enter(ctx, "mf_debug_als_cg_matvec");
+  DeviceGuard g(s.device);
+  const size_t k = static_cast<size_t>(ctx->P.num_factors);
+  write_from_f64(ctx, s.als_cg_v, v, k);
+  als_hook_row(ctx, side, id, P);
+  const std::vector<double> h = read_as_f64(ctx, s.als_dump, 2 * k);
   std::memcpy(Av_out, h.data(), k * 8);
   std::memcpy(b_out, h.data() + k, k * 8);
 }
 
 // G of one side's rated rows through the half-sweep's own launches (mf_debug_als_gram).
 void als_gram(mf_ctx* ctx, int side, double* G_out) {
-  als_check(ctx);
-  if (!ctx->als_prepared) fail(MF_ERR_STATE, "mf_debug_als_gram before mf_als_prepare");
-  require_healthy(ctx);
-  sync_all(ctx);
-  Shard& s = ctx->shards[0];
+  Shard& s = als_enter(ctx, "mf_debug_als_gram");
   DeviceGuard g(s.device);
   {
     LaunchTimer t(s, ctx->profiling);
@@ -464,14 +417,7 @@ void als_gram(mf_ctx* ctx, int side, double* G_out) {
   }
   MF_HIP(hipStreamSynchronize(s.stream));
   const size_t k = static_cast<size_t>(ctx->P.num_factors), kp = (k + 31) / 32 * 32;
-  std::vector<double> h(kp * kp);
-  if (ctx->f64) {
-    MF_HIP(hipMemcpy(h.data(), s.als_gram.get(), kp * kp * 8, hipMemcpyDeviceToHost));
-  } else {
-    std::vector<float> f(kp * kp);
-    MF_HIP(hipMemcpy(f.data(), s.als_gram.get(), kp * kp * 4, hipMemcpyDeviceToHost));
-    for (size_t x = 0; x < kp * kp; ++x) h[x] = static_cast<double>(f[x]);
-  }
+  const std::vector<double> h = read_as_f64(ctx, s.als_gram, kp * kp);
   for (size_t a = 0; a < k; ++a) std::memcpy(G_out + a * k, h.data() + a * kp, k * 8);
 }
 

@@ -395,18 +395,22 @@ void online_prequential_sampled(mf_ctx* ctx, const int32_t* u, const int32_t* i,
                                 int64_t* tu, int64_t* ti);
 
 // als.cpp
+// How a half-sweep solves its rows.
+struct AlsParams {
+  double lambda;
+  int32_t reg;            // MF_ALS_REG_*
+  bool implicit = false;  // the implicit-feedback system (mf_als_run_implicit), with confidence scale alpha
+  double alpha = 0.0;
+  int32_t cg_steps = 0;   // 0: Cholesky; 1 .. MF_ALS_CG_MAX_STEPS: that many conjugate-gradient steps
+};
 void als_check(const mf_ctx* ctx);
-void als_check_run(double lambda, int32_t reg);
-void als_prepare(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n);
 void als_check_alpha(double alpha);
-// alpha < 0: the explicit half-sweep / system; alpha >= 0: the implicit one (mf_als_run_implicit)
-void als_run(mf_ctx* ctx, int64_t half_sweeps, double lambda, int32_t reg, double alpha = -1.0);
-void als_normal_eq(mf_ctx* ctx, int side, int32_t id, double lambda, int32_t reg, double* A_out, double* b_out,
-                   double alpha = -1.0);
+void als_check_run(const AlsParams& P);  // lambda, reg, cg_steps
+void als_prepare(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n);
+void als_run(mf_ctx* ctx, int64_t half_sweeps, const AlsParams& P);
+void als_normal_eq(mf_ctx* ctx, int side, int32_t id, const AlsParams& P, double* A_out, double* b_out);
 void als_gram(mf_ctx* ctx, int side, double* G_out);
-void als_check_cg(int32_t cg_steps);
-void als_run_cg(mf_ctx* ctx, int64_t half_sweeps, double lambda, int32_t reg, double alpha, int32_t cg_steps);
-void als_cg_matvec(mf_ctx* ctx, int side, int32_t id, double lambda, int32_t reg, double alpha, const double* v,
-                   double* Av_out, double* b_out);
+void als_cg_matvec(mf_ctx* ctx, int side, int32_t id, const AlsParams& P, const double* v, double* Av_out,
+                   double* b_out);
 
 }  // namespace mfhip

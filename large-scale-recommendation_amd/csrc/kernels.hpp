@@ -4,6 +4,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "plan.hpp"
 
@@ -315,12 +316,6 @@ void launch_pair_metrics(hipStream_t st, const int32_t* rank, const int32_t* val
 // its system is solved in the kernel and x stored to X[row]) or one chunk of a long row (slot >= 0:
 // its partial matrix and right-hand side go to partial[slot], als_partial_elems(k) elements each);
 // an AlsSplit names a long row's partials [slot0, slot0 + chunks), added in that order and solved.
-// cols / vals: the side's CSR (counterpart rows of Q, ratings in the context's precision).
-// dump != null (the testing hook, one row): the row's k x k matrix and right-hand side are
-// stored there instead of being solved.
-// gram != null: the implicit-feedback half-sweep (mf_als_run_implicit), (G + sum w q q^T + lambda' I) x
-// = sum_{r > 0} (1 + w) q with w = alpha |r|; gram is G, als_gram_elems(k) elements (launch_als_gram),
-// lambda' = lambda * npos when weighted, and a row with npos == 0 is set to zero.
 constexpr int kAlsMaxRank = 256;
 struct AlsItem {
   int64_t begin;  // first rating of the item in cols / vals
@@ -334,51 +329,108 @@ struct AlsSplit {
   int32_t count;  // ratings of the whole row (lambda' = lambda * count when weighted)
   int32_t npos;   // of them r > 0
 };
-size_t als_partial_elems(int k);
-void launch_als(hipStream_t st, const AlsItem* items, int n_items, const AlsSplit* splits, int n_splits,
-                const int32_t* cols, const void* vals, const void* Q, void* X, int k, double lambda, bool weighted,
-                bool f64, void* partial, void* dump, const void* gram = nullptr, double alpha = 0.0,
-                void* slab = nullptr, int slabs = 0);
-// G = sum of y y^T over rows rated[0 .. m) of Y, KP x KP (KP = k rounded up to 32, full symmetric,
-// zero past k): workgroup b sums rows [b * slice, (b + 1) * slice) into part[b] (als_gram_slices(m,
-// slice) partials of als_gram_elems(k) elements), then one launch adds them in ascending order.
-size_t als_gram_elems(int k);
-int als_gram_slices(int m, int slice);
-void launch_als_gram(hipStream_t st, const int32_t* rated, int m, int slice, const void* Y, int k, bool f64, void* part,
-                     void* G);
-
-// ---- kernels_als_wide.hip: the same at ranks 129..256 ------------------------------------------
-// launch_als and launch_als_gram hand these ranks on.  The normal matrix of a row lives in global
-// memory: slab holds `slabs` matrices of als_gram_elems(k) elements, one per workgroup of the grid,
-// which strides over the work items; als_wide_slabs is the count for a device of `cus` CUs (0 at a
-// rank the narrow kernels take).  launch_als_gram_wide stores the slice partials only.
-int als_wide_slabs(int k, bool f64, int cus);
-void launch_als_wide(hipStream_t st, const AlsItem* items, int n_items, const AlsSplit* splits, int n_splits,
-                     const int32_t* cols, const void* vals, const void* Q, void* X, int k, double lambda, bool weighted,
-                     bool f64, void* partial, void* dump, const void* gram, double alpha, void* slab, int slabs);
-void launch_als_gram_wide(hipStream_t st, const int32_t* rated, int m, int slice, const void* Y, int k, bool f64,
-                          void* part);
-
-// ---- kernels_als_cg.hip: ALS half-sweeps by conjugate gradients ---------------------------------
-// The work lists, CSR, partial slots and G of launch_als, every rank 1..kAlsMaxRank in one code path
-// (mf_als_run_cg; gram != null: mf_als_run_implicit_cg).  Whole rows (slot < 0) take `steps` CG steps
-// from X[row] in one launch; a row of at most als_cg_capacity(k, f64) ratings keeps its counterpart
-// vectors in LDS for all of them when `stage` is set, a longer one gathers them again in every pass
-// (the same arithmetic).  Long rows: work[0 .. n_work) names the launch's chunk items and, for each, the
-// index of its row in splits[]; their state (als_cg_state_elems(k) elements per row of splits[]) lives
-// in `state`, and every pass is two launches (a k-vector per chunk into partial[slot], then the row's
-// update): 2 * (steps + 1) launches.
-// dump != null (the testing hook, one row): dump[0 .. k) = A v and dump[k .. 2k) = b for v = hook_v
-// (device, k elements); X is not written.
 struct AlsCgWork {
   int32_t item;   // index into items[]
   int32_t split;  // index into splits[]
 };
+// What one ALS launch takes (launch_als, launch_als_wide, launch_als_cg).
+struct AlsLaunch {
+  hipStream_t st = nullptr;
+  const AlsItem* items = nullptr;
+  int n_items = 0;
+  const AlsSplit* splits = nullptr;
+  int n_splits = 0;
+  // the side's CSR (counterpart rows of Q, ratings in the context's precision)
+  const int32_t* cols = nullptr;
+  const void* vals = nullptr;
+  const void* Q = nullptr;
+  void* X = nullptr;
+  int k = 0;
+  double lambda = 0.0;
+  bool weighted = false;  // lambda' = lambda * count (npos in the implicit half-sweep)
+  bool f64 = false;
+  void* partial = nullptr;
+  // dump != null (the testing hook, one row).  Cholesky: the row's k x k matrix and right-hand side are
+  // stored there instead of being solved.  Conjugate gradients: dump[0 .. k) = A v and dump[k .. 2k) = b
+  // for v = hook_v (device, k elements); X is not written.
+  void* dump = nullptr;
+  // gram != null: the implicit-feedback half-sweep (mf_als_run_implicit), (G + sum w q q^T + lambda' I) x
+  // = sum_{r > 0} (1 + w) q with w = alpha |r|; gram is G, als_gram_elems(k) elements (launch_als_gram),
+  // lambda' = lambda * npos when weighted, and a row with npos == 0 is set to zero.
+  const void* gram = nullptr;
+  double alpha = 0.0;
+  // Cholesky at ranks 129..256 (kernels_als_wide.hip).  The normal matrix of a row lives in global
+  // memory: slab holds `slabs` matrices of als_gram_elems(k) elements, one per workgroup of the grid,
+  // which strides over the work items; als_wide_slabs is the count for a device of `cus` CUs (0 at a
+  // rank the narrow kernels take).
+  void* slab = nullptr;
+  int slabs = 0;
+  // Conjugate gradients (kernels_als_cg.hip).  Whole rows (slot < 0) take `steps` CG steps from X[row]
+  // in one launch; a row of at most als_cg_capacity(k, f64) ratings keeps its counterpart vectors in LDS
+  // for all of them when `stage` is set, a longer one gathers them again in every pass (the same
+  // arithmetic).  Long rows: work[0 .. n_work) names the launch's chunk items and, for each, the index of
+  // its row in splits[]; their state (als_cg_state_elems(k) elements per row of splits[]) lives in
+  // `state`, and every pass is two launches (a k-vector per chunk into partial[slot], then the row's
+  // update): 2 * (steps + 1) launches.
+  const AlsCgWork* work = nullptr;
+  int n_work = 0;
+  int steps = 0;
+  bool stage = false;
+  void* state = nullptr;
+  const void* hook_v = nullptr;
+};
+// The runtime (f64, implicit) of a launch as compile-time (T, W): f(T(), std::bool_constant<W>()).
+template <typename F>
+void als_dispatch(bool f64, bool implicit, F&& f) {
+  auto w = [&](auto t) { implicit ? f(t, std::true_type()) : f(t, std::false_type()); };
+  f64 ? w(double()) : w(float());
+}
+// ... and the rank bucket (k + 31) / 32 in NB0 .. NB0 + 3 as NB: f(T(), std::bool_constant<W>(),
+// std::integral_constant<int, NB>()).  Any other bucket is refused.
+[[noreturn]] void als_refuse_rank();
+template <int NB0, typename F>
+void als_dispatch(bool f64, bool implicit, int k, F&& f) {
+  als_dispatch(f64, implicit, [&](auto t, auto w) {
+    switch ((k + 31) / 32 - NB0) {
+      case 0: return f(t, w, std::integral_constant<int, NB0>());
+      case 1: return f(t, w, std::integral_constant<int, NB0 + 1>());
+      case 2: return f(t, w, std::integral_constant<int, NB0 + 2>());
+      case 3: return f(t, w, std::integral_constant<int, NB0 + 3>());
+      default: als_refuse_rank();
+    }
+  });
+}
+size_t als_partial_elems(int k);
+// Ranks above 128 go on to launch_als_wide.
+void launch_als(const AlsLaunch& L);
+// G = sum of y y^T over rows rated[0 .. m) of Y, KP x KP (KP = k rounded up to 32, full symmetric,
+// zero past k): workgroup b sums rows [b * slice, (b + 1) * slice) into part[b] (als_gram_slices(m,
+// slice) partials of als_gram_elems(k) elements), then one launch adds them in ascending order.
+struct AlsGramLaunch {
+  hipStream_t st;
+  const int32_t* rated;
+  int m, slice;
+  const void* Y;
+  int k;
+  bool f64;
+  void* part;
+  void* G;
+};
+size_t als_gram_elems(int k);
+int als_gram_slices(int m, int slice);
+void launch_als_gram(const AlsGramLaunch& L);
+
+// ---- kernels_als_wide.hip: the same at ranks 129..256 ------------------------------------------
+// launch_als and launch_als_gram hand these ranks on.  launch_als_gram_wide stores the slice partials only.
+int als_wide_slabs(int k, bool f64, int cus);
+void launch_als_wide(const AlsLaunch& L);
+void launch_als_gram_wide(const AlsGramLaunch& L);
+
+// ---- kernels_als_cg.hip: ALS half-sweeps by conjugate gradients ---------------------------------
+// The work lists, CSR, partial slots and G of launch_als, every rank 1..kAlsMaxRank in one code path
+// (mf_als_run_cg; gram != null: mf_als_run_implicit_cg).
 size_t als_cg_state_elems(int k);
 int als_cg_capacity(int k, bool f64);
-void launch_als_cg(hipStream_t st, const AlsItem* items, int n_items, const AlsSplit* splits, int n_splits,
-                   const AlsCgWork* work, int n_work, const int32_t* cols, const void* vals, const void* Q, void* X, int k,
-                   double lambda, bool weighted, bool f64, void* partial, const void* gram, double alpha, int steps,
-                   bool stage, void* state, const void* hook_v, void* dump);
+void launch_als_cg(const AlsLaunch& L);
 
 }  // namespace mfhip

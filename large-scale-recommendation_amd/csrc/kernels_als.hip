@@ -36,6 +36,7 @@
 #include <limits>
 #include <string>
 
+#include "als_device.hpp"
 #include "common.hpp"
 #include "kernels.hpp"
 
@@ -43,75 +44,11 @@ namespace mfhip {
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kTile = 32;  // ratings per LDS tile (a multiple of 2: one MFMA takes two ratings)
-
-typedef float v16f __attribute__((ext_vector_type(16)));
 
 template <typename T> struct GramAcc;
 
 // f32: lower-triangle blocks w, w + 4, w + 8 of wave w (at most 3 of the 10 at KP = 128).
-template <> struct GramAcc<float> {
-  v16f acc[3];
-  __device__ void zero() {
-#pragma unroll
-    for (int x = 0; x < 3; ++x)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[x][r] = 0.f;
-  }
-  // block number b -> (bi, bj), bj <= bi, row-major over the triangle
-  __device__ static void block_of(int b, int& bi, int& bj) {
-    bi = 0;
-    while ((bi + 1) * (bi + 2) / 2 <= b) ++bi;  // bi <= 3
-    bj = b - bi * (bi + 1) / 2;
-  }
-  // W: w[t] (LDS) multiplies rating t's A operand
-  template <int NB, bool W = false>
-  __device__ void tile(const float* q, int kp, int rows, const float* w = nullptr) {
-    constexpr int kBlocks = NB * (NB + 1) / 2;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int h = lane >> 5, c = lane & 31;
-#pragma unroll
-    for (int x = 0; x < 3; ++x) {
-      const int b = wave + 4 * x;
-      if (b >= kBlocks) break;
-      int bi, bj;
-      block_of(b, bi, bj);
-      const float* pa = q + h * kp + 32 * bi + c;
-      const float* pb = q + h * kp + 32 * bj + c;
-      if constexpr (W) {
-        for (int t = 0; t < rows; t += 2)
-          acc[x] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[t + h] * pa[t * kp], pb[t * kp], acc[x], 0, 0, 0);
-      } else {
-        for (int t = 0; t < rows; t += 2)
-          acc[x] = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[t * kp], pb[t * kp], acc[x], 0, 0, 0);
-      }
-    }
-  }
-  // accumulators -> M (row stride ld); register r of a block is row (r & 3) + 8 (r >> 2) + 4 h
-  // ADD: plus G (row stride 32 NB) on the way
-  template <int NB, bool ADD = false>
-  __device__ void store(float* M, int ld, const float* G = nullptr) const {
-    constexpr int kBlocks = NB * (NB + 1) / 2;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int h = lane >> 5, c = lane & 31;
-#pragma unroll
-    for (int x = 0; x < 3; ++x) {
-      const int b = wave + 4 * x;
-      if (b >= kBlocks) break;
-      int bi, bj;
-      block_of(b, bi, bj);
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        if constexpr (ADD) {
-          const int row = 32 * bi + (r & 3) + 8 * (r >> 2) + 4 * h;
-          M[row * ld + 32 * bj + c] = acc[x][r] + G[row * (32 * NB) + 32 * bj + c];
-        } else {
-          M[(32 * bi + (r & 3) + 8 * (r >> 2) + 4 * h) * ld + 32 * bj + c] = acc[x][r];
-        }
-      }
-    }
-  }
-};
+template <> struct GramAcc<float> : MfmaAcc<kThreads / 64, 3> {};
 
 // f64: thread (ty, tx) of the 16 x 16 grid, entries (ty + 16 a, tx + 16 b), a >= b, a, b < 2 NB.
 template <> struct GramAcc<double> {
@@ -123,8 +60,8 @@ template <> struct GramAcc<double> {
       for (int b = 0; b < 8; ++b) acc[a][b] = 0.0;
   }
   template <int NB, bool W = false>
-  __device__ void tile(const double* q, int kp, int rows, const double* w = nullptr) {
-    const int ty = threadIdx.x >> 4, tx = threadIdx.x & 15;
+  __device__ void tile(int tid, const double* q, int kp, int rows, const double* w = nullptr) {
+    const int ty = tid >> 4, tx = tid & 15;
     for (int t = 0; t < rows; ++t) {
       const double* row = q + t * kp;
       double qa[2 * NB], qb[2 * NB];
@@ -141,8 +78,8 @@ template <> struct GramAcc<double> {
     }
   }
   template <int NB, bool ADD = false>
-  __device__ void store(double* M, int ld, const double* G = nullptr) const {
-    const int ty = threadIdx.x >> 4, tx = threadIdx.x & 15;
+  __device__ void store(int tid, double* M, int ld, const double* G = nullptr) const {
+    const int ty = tid >> 4, tx = tid & 15;
 #pragma unroll
     for (int a = 0; a < 2 * NB; ++a)
 #pragma unroll
@@ -167,14 +104,7 @@ template <typename T, int NB>
 __device__ void finish_row(T* A, int ld, T* rhs, T* y, T* col, T* colraw, int k, T* x_out, T* dump) {
   constexpr int MB = 2 * NB;
   const int tid = threadIdx.x;
-  if (dump) {  // full symmetric k x k, then the right-hand side
-    for (int e = tid; e < k * k; e += kThreads) {
-      const int i = e / k, j = e % k;
-      dump[e] = i >= j ? A[i * ld + j] : A[j * ld + i];
-    }
-    if (tid < k) dump[k * k + tid] = rhs[tid];
-    return;
-  }
+  if (dump) return als_dump_system<T, kThreads>(tid, A, ld, rhs, k, dump);
   const int ty = tid >> 4, tx = tid & 15;
   T a[MB][MB];
 #pragma unroll
@@ -247,15 +177,18 @@ constexpr size_t als_lds_bytes(int kp) {
   return (static_cast<size_t>(kp) * (kp + 1) + 4 * kp + kTile) * sizeof(T);
 }
 
-// W (the implicit half-sweep): the ratings become confidences w = alpha |r| (rv) and right-hand-side
-// coefficients 1 + w for r > 0, else 0 (cf, which borrows col: the factorisation's scratch is idle
-// while the tiles run); G is the counterpart's Gram matrix, KP x KP.  A row with no positive rating
-// has a zero right-hand side: its x is zero, and nothing is accumulated for it.
+
+// One work item per workgroup.  W (the implicit half-sweep): the ratings become confidences w = alpha |r|
+// (rv) and right-hand-side coefficients 1 + w for r > 0, else 0 (cf, which borrows col: the
+// factorisation's scratch is idle while the tiles run); G is the counterpart's Gram matrix, KP x KP.  A
+// row with no positive rating has a zero right-hand side: its x is zero, and nothing is accumulated
+// for it.  The explicit instances ignore G and alpha.
 template <typename T, int NB, bool W>
-__device__ __forceinline__ void als_item(const AlsItem* __restrict__ items, const int32_t* __restrict__ cols,
-                                         const T* __restrict__ vals, const T* __restrict__ Q, T* __restrict__ X,
-                                         int k, T lambda, int weighted, T* __restrict__ partial,
-                                         T* __restrict__ dump, const T* __restrict__ G, T alpha) {
+__global__ __launch_bounds__(kThreads) void k_als(const AlsItem* __restrict__ items, const int32_t* __restrict__ cols,
+                                                   const T* __restrict__ vals, const T* __restrict__ Q,
+                                                   T* __restrict__ X, int k, T lambda, int weighted,
+                                                   T* __restrict__ partial, T* __restrict__ dump,
+                                                   const T* __restrict__ G, T alpha) {
   constexpr int KP = 32 * NB;
   constexpr int LD = KP + 1;
   extern __shared__ __align__(16) unsigned char smem_raw[];
@@ -299,7 +232,7 @@ __device__ __forceinline__ void als_item(const AlsItem* __restrict__ items, cons
     }
     __syncthreads();
     // (rows past the end are zero: the f32 path always runs whole pairs)
-    g.template tile<NB, W>(M, KP, (rows + 1) & ~1, rv);
+    g.template tile<NB, W>(tid, M, KP, (rows + 1) & ~1, rv);
     if constexpr (W) {
       if (tid < KP)
         for (int t = 0; t < rows; ++t) {
@@ -314,11 +247,11 @@ __device__ __forceinline__ void als_item(const AlsItem* __restrict__ items, cons
   __syncthreads();
   if (it.slot >= 0) {  // a chunk of a long row: the partial system goes to the scratch slab
     T* P = partial + static_cast<size_t>(it.slot) * (KP * KP + KP);
-    g.template store<NB>(P, KP);
+    g.template store<NB>(tid, P, KP);
     if (tid < KP) P[KP * KP + tid] = bacc;
     return;
   }
-  g.template store<NB, W>(M, LD, G);
+  g.template store<NB, W>(tid, M, LD, G);
   if (tid < KP) rhs[tid] = bacc;
   __syncthreads();
   const T lam = weighted ? lambda * static_cast<T>(W ? it.npos : it.count) : lambda;
@@ -327,30 +260,12 @@ __device__ __forceinline__ void als_item(const AlsItem* __restrict__ items, cons
   finish_row<T, NB>(M, LD, rhs, y, col, colraw, k, X + static_cast<size_t>(it.row) * k, dump);
 }
 
-template <typename T, int NB>
-__global__ __launch_bounds__(kThreads) void k_als(const AlsItem* __restrict__ items, const int32_t* __restrict__ cols,
-                                                   const T* __restrict__ vals, const T* __restrict__ Q,
-                                                   T* __restrict__ X, int k, T lambda, int weighted,
-                                                   T* __restrict__ partial, T* __restrict__ dump) {
-  als_item<T, NB, false>(items, cols, vals, Q, X, k, lambda, weighted, partial, dump, nullptr, T(0));
-}
-
-template <typename T, int NB>
-__global__ __launch_bounds__(kThreads) void k_als_implicit(const AlsItem* __restrict__ items,
-                                                            const int32_t* __restrict__ cols,
-                                                            const T* __restrict__ vals, const T* __restrict__ Q,
-                                                            T* __restrict__ X, int k, T lambda, int weighted,
-                                                            T* __restrict__ partial, T* __restrict__ dump,
-                                                            const T* __restrict__ G, T alpha) {
-  als_item<T, NB, true>(items, cols, vals, Q, X, k, lambda, weighted, partial, dump, G, alpha);
-}
-
 // One workgroup per split row: partials [slot0, slot0 + chunks) added in ascending order.
 // W: plus G, once, after the partial sum; a row with no positive rating is set to zero.
 template <typename T, int NB, bool W>
-__device__ __forceinline__ void als_split(const AlsSplit* __restrict__ rows, const T* __restrict__ partial,
-                                          T* __restrict__ X, int k, T lambda, int weighted, T* __restrict__ dump,
-                                          const T* __restrict__ G) {
+__global__ __launch_bounds__(kThreads) void k_als_reduce(const AlsSplit* __restrict__ rows, const T* __restrict__ partial,
+                                                          T* __restrict__ X, int k, T lambda, int weighted,
+                                                          T* __restrict__ dump, const T* __restrict__ G) {
   constexpr int KP = 32 * NB;
   constexpr int LD = KP + 1;
   extern __shared__ __align__(16) unsigned char smem_raw[];
@@ -367,38 +282,12 @@ __device__ __forceinline__ void als_split(const AlsSplit* __restrict__ rows, con
       return;
     }
   }
-  constexpr size_t kStride = static_cast<size_t>(KP) * KP + KP;
-  for (int e = tid; e < KP * KP + KP; e += kThreads) {
-    const int i = e / KP, j = e % KP;
-    if (i < KP && j > i) continue;  // only the lower triangle is defined
-    T sum = T(0);
-    for (int c = 0; c < sp.chunks; ++c) sum += partial[(static_cast<size_t>(sp.slot0) + c) * kStride + e];
-    if constexpr (W) {
-      if (i < KP) sum += G[e];
-    }
-    if (i < KP) M[i * LD + j] = sum;
-    else rhs[j] = sum;
-  }
+  als_sum_partials<T, KP, kThreads, W>(tid, sp, partial, G, M, LD, rhs);
   __syncthreads();
   const T lam = weighted ? lambda * static_cast<T>(W ? sp.npos : sp.count) : lambda;
   if (tid < k) M[tid * LD + tid] += lam;
   __syncthreads();
   finish_row<T, NB>(M, LD, rhs, y, col, colraw, k, X + static_cast<size_t>(sp.row) * k, dump);
-}
-
-template <typename T, int NB>
-__global__ __launch_bounds__(kThreads) void k_als_reduce(const AlsSplit* __restrict__ rows, const T* __restrict__ partial,
-                                                          T* __restrict__ X, int k, T lambda, int weighted,
-                                                          T* __restrict__ dump) {
-  als_split<T, NB, false>(rows, partial, X, k, lambda, weighted, dump, nullptr);
-}
-
-template <typename T, int NB>
-__global__ __launch_bounds__(kThreads) void k_als_reduce_implicit(const AlsSplit* __restrict__ rows,
-                                                                   const T* __restrict__ partial, T* __restrict__ X,
-                                                                   int k, T lambda, int weighted, T* __restrict__ dump,
-                                                                   const T* __restrict__ G) {
-  als_split<T, NB, true>(rows, partial, X, k, lambda, weighted, dump, G);
 }
 
 // G = sum over the rated rows of Y of y y^T.  Workgroup b takes rows [b * slice, (b + 1) * slice) of
@@ -425,9 +314,9 @@ __global__ __launch_bounds__(kThreads) void k_als_gram(const int32_t* __restrict
       tile[e] = v;
     }
     __syncthreads();
-    g.template tile<NB>(tile, KP, (rows + 1) & ~1);
+    g.template tile<NB>(tid, tile, KP, (rows + 1) & ~1);
   }
-  g.template store<NB>(part + static_cast<size_t>(blockIdx.x) * KP * KP, KP);
+  g.template store<NB>(tid, part + static_cast<size_t>(blockIdx.x) * KP * KP, KP);
 }
 
 template <typename T>
@@ -442,71 +331,32 @@ __global__ __launch_bounds__(kThreads) void k_als_gram_reduce(const T* __restric
   G[e] = sum;
 }
 
-template <typename T, int NB>
-void launch_nb(hipStream_t st, const AlsItem* items, int n_items, const AlsSplit* splits, int n_splits,
-               const int32_t* cols, const void* vals, const void* Q, void* X, int k, double lambda, int weighted,
-               void* partial, void* dump, const void* gram, double alpha) {
-  constexpr int KP = 32 * NB;
-  const size_t smem = als_lds_bytes<T>(KP);
-  const void* f1 = gram ? reinterpret_cast<const void*>(&k_als_implicit<T, NB>) : reinterpret_cast<const void*>(&k_als<T, NB>);
-  const void* f2 = gram ? reinterpret_cast<const void*>(&k_als_reduce_implicit<T, NB>)
-                        : reinterpret_cast<const void*>(&k_als_reduce<T, NB>);
+template <typename T, int NB, bool W>
+void launch_nb(const AlsLaunch& L) {
+  const size_t smem = als_lds_bytes<T>(32 * NB);
   if (smem > 64 * 1024)
-    for (const void* fn : {f1, f2})
+    for (const void* fn : {reinterpret_cast<const void*>(&k_als<T, NB, W>),
+                           reinterpret_cast<const void*>(&k_als_reduce<T, NB, W>)})
       if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(smem)) != hipSuccess)
         fail(MF_ERR_HIP, "k_als: " + std::to_string(smem) + " bytes of LDS refused");
-  const dim3 gi(static_cast<unsigned>(n_items)), gs(static_cast<unsigned>(n_splits));
-  if (n_items > 0 && !gram)
-    hipLaunchKernelGGL((k_als<T, NB>), gi, dim3(kThreads), smem, st, items, cols,
-                       static_cast<const T*>(vals), static_cast<const T*>(Q), static_cast<T*>(X), k,
-                       static_cast<T>(lambda), weighted, static_cast<T*>(partial), static_cast<T*>(dump));
-  if (n_items > 0 && gram)
-    hipLaunchKernelGGL((k_als_implicit<T, NB>), gi, dim3(kThreads), smem, st, items, cols,
-                       static_cast<const T*>(vals), static_cast<const T*>(Q), static_cast<T*>(X), k,
-                       static_cast<T>(lambda), weighted, static_cast<T*>(partial), static_cast<T*>(dump),
-                       static_cast<const T*>(gram), static_cast<T>(alpha));
-  if (n_splits > 0 && !gram)
-    hipLaunchKernelGGL((k_als_reduce<T, NB>), gs, dim3(kThreads), smem, st, splits,
-                       static_cast<const T*>(partial), static_cast<T*>(X), k, static_cast<T>(lambda), weighted,
-                       static_cast<T*>(dump));
-  if (n_splits > 0 && gram)
-    hipLaunchKernelGGL((k_als_reduce_implicit<T, NB>), gs, dim3(kThreads), smem, st, splits,
-                       static_cast<const T*>(partial), static_cast<T*>(X), k, static_cast<T>(lambda), weighted,
-                       static_cast<T*>(dump), static_cast<const T*>(gram));
-}
-
-template <typename T>
-void launch_t(hipStream_t st, const AlsItem* items, int n_items, const AlsSplit* splits, int n_splits,
-              const int32_t* cols, const void* vals, const void* Q, void* X, int k, double lambda, int weighted,
-              void* partial, void* dump, const void* gram, double alpha) {
-  switch ((k + 31) / 32) {
-    case 1: return launch_nb<T, 1>(st, items, n_items, splits, n_splits, cols, vals, Q, X, k, lambda, weighted, partial, dump, gram, alpha);
-    case 2: return launch_nb<T, 2>(st, items, n_items, splits, n_splits, cols, vals, Q, X, k, lambda, weighted, partial, dump, gram, alpha);
-    case 3: return launch_nb<T, 3>(st, items, n_items, splits, n_splits, cols, vals, Q, X, k, lambda, weighted, partial, dump, gram, alpha);
-    case 4: return launch_nb<T, 4>(st, items, n_items, splits, n_splits, cols, vals, Q, X, k, lambda, weighted, partial, dump, gram, alpha);
-    default: fail(MF_ERR_INVALID, "ALS supports a rank of at most " + std::to_string(kAlsMaxRank));
-  }
-}
-
-template <typename T>
-void launch_gram_t(hipStream_t st, const int32_t* rated, int m, int slice, const void* Y, int k, void* part, void* G) {
-  const int nb = (k + 31) / 32, kp = 32 * nb;
-  const int slices = als_gram_slices(m, slice);
-  const dim3 grid(static_cast<unsigned>(slices)), block(kThreads);
-  const T* y = static_cast<const T*>(Y);
-  T* p = static_cast<T*>(part);
-  if (slices > 0) switch (nb) {
-    case 1: hipLaunchKernelGGL((k_als_gram<T, 1>), grid, block, 0, st, rated, m, slice, y, k, p); break;
-    case 2: hipLaunchKernelGGL((k_als_gram<T, 2>), grid, block, 0, st, rated, m, slice, y, k, p); break;
-    case 3: hipLaunchKernelGGL((k_als_gram<T, 3>), grid, block, 0, st, rated, m, slice, y, k, p); break;
-    case 4: hipLaunchKernelGGL((k_als_gram<T, 4>), grid, block, 0, st, rated, m, slice, y, k, p); break;
-    default: launch_als_gram_wide(st, rated, m, slice, Y, k, sizeof(T) == 8, part);  // refuses a rank above kAlsMaxRank
-  }
-  hipLaunchKernelGGL((k_als_gram_reduce<T>), dim3(static_cast<unsigned>((kp * kp + kThreads - 1) / kThreads)), block, 0,
-                     st, static_cast<const T*>(part), slices, kp, static_cast<T*>(G));
+  T* X = static_cast<T*>(L.X);
+  T* partial = static_cast<T*>(L.partial);
+  T* dump = static_cast<T*>(L.dump);
+  const T* G = static_cast<const T*>(L.gram);
+  const T lambda = static_cast<T>(L.lambda);
+  const int weighted = L.weighted ? 1 : 0;
+  if (L.n_items > 0)
+    hipLaunchKernelGGL((k_als<T, NB, W>), dim3(static_cast<unsigned>(L.n_items)), dim3(kThreads), smem, L.st, L.items,
+                       L.cols, static_cast<const T*>(L.vals), static_cast<const T*>(L.Q), X, L.k, lambda, weighted,
+                       partial, dump, G, static_cast<T>(L.alpha));
+  if (L.n_splits > 0)
+    hipLaunchKernelGGL((k_als_reduce<T, NB, W>), dim3(static_cast<unsigned>(L.n_splits)), dim3(kThreads), smem, L.st,
+                       L.splits, partial, X, L.k, lambda, weighted, dump, G);
 }
 
 }  // namespace
+
+void als_refuse_rank() { fail(MF_ERR_INVALID, "ALS supports a rank of at most " + std::to_string(kAlsMaxRank)); }
 
 size_t als_partial_elems(int k) {
   const size_t kp = static_cast<size_t>((k + 31) / 32) * 32;
@@ -520,20 +370,28 @@ size_t als_gram_elems(int k) {
 
 int als_gram_slices(int m, int slice) { return static_cast<int>((static_cast<int64_t>(m) + slice - 1) / slice); }
 
-void launch_als(hipStream_t st, const AlsItem* items, int n_items, const AlsSplit* splits, int n_splits,
-                const int32_t* cols, const void* vals, const void* Q, void* X, int k, double lambda, bool weighted,
-                bool f64, void* partial, void* dump, const void* gram, double alpha, void* slab, int slabs) {
-  if (k > 128)  // kernels_als_wide.hip
-    return launch_als_wide(st, items, n_items, splits, n_splits, cols, vals, Q, X, k, lambda, weighted, f64, partial, dump,
-                           gram, alpha, slab, slabs);
-  if (f64) launch_t<double>(st, items, n_items, splits, n_splits, cols, vals, Q, X, k, lambda, weighted ? 1 : 0, partial, dump, gram, alpha);
-  else launch_t<float>(st, items, n_items, splits, n_splits, cols, vals, Q, X, k, lambda, weighted ? 1 : 0, partial, dump, gram, alpha);
+void launch_als(const AlsLaunch& L) {
+  if (L.k > 128) return launch_als_wide(L);  // kernels_als_wide.hip
+  als_dispatch<1>(L.f64, L.gram != nullptr, L.k, [&](auto t, auto w, auto nb) {
+    launch_nb<decltype(t), decltype(nb)::value, decltype(w)::value>(L);
+  });
 }
 
-void launch_als_gram(hipStream_t st, const int32_t* rated, int m, int slice, const void* Y, int k, bool f64, void* part,
-                     void* G) {
-  if (f64) launch_gram_t<double>(st, rated, m, slice, Y, k, part, G);
-  else launch_gram_t<float>(st, rated, m, slice, Y, k, part, G);
+void launch_als_gram(const AlsGramLaunch& L) {
+  const int kp = (L.k + 31) / 32 * 32;
+  const int slices = als_gram_slices(L.m, L.slice);
+  if (slices > 0 && L.k > 128) launch_als_gram_wide(L);  // refuses a rank above kAlsMaxRank
+  if (slices > 0 && L.k <= 128)
+    als_dispatch<1>(L.f64, false, L.k, [&](auto t, auto, auto nb) {
+      using T = decltype(t);
+      hipLaunchKernelGGL((k_als_gram<T, decltype(nb)::value>), dim3(static_cast<unsigned>(slices)), dim3(kThreads), 0,
+                         L.st, L.rated, L.m, L.slice, static_cast<const T*>(L.Y), L.k, static_cast<T*>(L.part));
+    });
+  als_dispatch(L.f64, false, [&](auto t, auto) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((k_als_gram_reduce<T>), dim3(static_cast<unsigned>((kp * kp + kThreads - 1) / kThreads)),
+                       dim3(kThreads), 0, L.st, static_cast<const T*>(L.part), slices, kp, static_cast<T*>(L.G));
+  });
 }
 
 }  // namespace mfhip

@@ -377,37 +377,36 @@ __global__ __launch_bounds__(kThreads) void k_als_cg_update(const AlsSplit* __re
 }
 
 template <typename T, bool W>
-void launch_cg(hipStream_t st, const AlsItem* items, int n_items, const AlsSplit* splits, int n_splits,
-               const AlsCgWork* work, int n_work, const int32_t* cols, const void* vals_, const void* Q_, void* X_, int k,
-               double lambda, int weighted, void* partial_, const void* gram, double alpha, int steps, bool stage,
-               void* state_, const void* hook_v, void* dump_) {
-  const T* vals = static_cast<const T*>(vals_);
-  const T* Q = static_cast<const T*>(Q_);
-  T* X = static_cast<T*>(X_);
-  T* partial = static_cast<T*>(partial_);
-  T* state = static_cast<T*>(state_);
-  T* dump = static_cast<T*>(dump_);
-  const T* G = static_cast<const T*>(gram);
-  const T lam = static_cast<T>(lambda), al = static_cast<T>(alpha);
+void launch_cg(const AlsLaunch& L) {
+  const hipStream_t st = L.st;
+  const T* vals = static_cast<const T*>(L.vals);
+  const T* Q = static_cast<const T*>(L.Q);
+  T* X = static_cast<T*>(L.X);
+  T* partial = static_cast<T*>(L.partial);
+  T* state = static_cast<T*>(L.state);
+  T* dump = static_cast<T*>(L.dump);
+  const T* G = static_cast<const T*>(L.gram);
+  const T lam = static_cast<T>(L.lambda), al = static_cast<T>(L.alpha);
+  const int k = L.k, steps = L.steps, weighted = L.weighted ? 1 : 0;
   const int cap = cg_capacity<T>(k);
   const size_t pstride = als_partial_elems(k);
   const int kp = (k + 31) / 32 * 32;
-  const dim3 block(kThreads), gi(static_cast<unsigned>(n_items)), gw(static_cast<unsigned>(n_work)),
-      gs(static_cast<unsigned>(n_splits));
-  if (n_items > 0)
-    hipLaunchKernelGGL((k_als_cg<T, W>), gi, block, kCgLdsBytes, st, items, cols, vals, Q, X, k, lam, weighted, steps, cap,
-                       stage ? 1 : 0, G, al, static_cast<const T*>(hook_v), dump);
-  if (n_work == 0 || n_splits == 0) return;
+  const dim3 block(kThreads), gi(static_cast<unsigned>(L.n_items)), gw(static_cast<unsigned>(L.n_work)),
+      gs(static_cast<unsigned>(L.n_splits));
+  if (L.n_items > 0)
+    hipLaunchKernelGGL((k_als_cg<T, W>), gi, block, kCgLdsBytes, st, L.items, L.cols, vals, Q, X, k, lam, weighted, steps,
+                       cap, L.stage ? 1 : 0, G, al, static_cast<const T*>(L.hook_v), dump);
+  if (L.n_work == 0 || L.n_splits == 0) return;
   auto chunk = [&](int pass) {
-    hipLaunchKernelGGL((k_als_cg_chunk<T, W>), gw, block, kCgLdsBytes, st, work, items, cols, vals, Q, X, k, cap, al,
+    hipLaunchKernelGGL((k_als_cg_chunk<T, W>), gw, block, kCgLdsBytes, st, L.work, L.items, L.cols, vals, Q, X, k, cap, al,
                        pass, dump ? 1 : 0, state, partial, pstride);
   };
   auto update = [&](int mode, int last) {
-    hipLaunchKernelGGL((k_als_cg_update<T, W>), gs, block, 0, st, splits, partial, pstride, X, k, lam, weighted, G, state,
-                       mode, last, dump);
+    hipLaunchKernelGGL((k_als_cg_update<T, W>), gs, block, 0, st, L.splits, partial, pstride, X, k, lam, weighted, G,
+                       state, mode, last, dump);
   };
   if (dump) {  // one long row: v becomes the p of its state
-    if (hipMemcpyAsync(state + 2 * kp, hook_v, static_cast<size_t>(k) * sizeof(T), hipMemcpyDeviceToDevice, st) !=
+    if (hipMemcpyAsync(state + 2 * kp, L.hook_v, static_cast<size_t>(k) * sizeof(T), hipMemcpyDeviceToDevice, st) !=
         hipSuccess)
       fail(MF_ERR_HIP, "k_als_cg: the hook's vector could not be copied");
     chunk(kPassB);
@@ -430,19 +429,9 @@ size_t als_cg_state_elems(int k) { return 4 * static_cast<size_t>((k + 31) / 32 
 
 int als_cg_capacity(int k, bool f64) { return f64 ? cg_capacity<double>(k) : cg_capacity<float>(k); }
 
-void launch_als_cg(hipStream_t st, const AlsItem* items, int n_items, const AlsSplit* splits, int n_splits,
-                   const AlsCgWork* work, int n_work, const int32_t* cols, const void* vals, const void* Q, void* X, int k,
-                   double lambda, bool weighted, bool f64, void* partial, const void* gram, double alpha, int steps,
-                   bool stage, void* state, const void* hook_v, void* dump) {
-  if (k < 1 || k > kAlsMaxRank) fail(MF_ERR_INVALID, "ALS supports a rank of at most " + std::to_string(kAlsMaxRank));
-  const int w = weighted ? 1 : 0;
-  if (f64) {
-    if (gram) launch_cg<double, true>(st, items, n_items, splits, n_splits, work, n_work, cols, vals, Q, X, k, lambda, w, partial, gram, alpha, steps, stage, state, hook_v, dump);
-    else launch_cg<double, false>(st, items, n_items, splits, n_splits, work, n_work, cols, vals, Q, X, k, lambda, w, partial, gram, alpha, steps, stage, state, hook_v, dump);
-  } else {
-    if (gram) launch_cg<float, true>(st, items, n_items, splits, n_splits, work, n_work, cols, vals, Q, X, k, lambda, w, partial, gram, alpha, steps, stage, state, hook_v, dump);
-    else launch_cg<float, false>(st, items, n_items, splits, n_splits, work, n_work, cols, vals, Q, X, k, lambda, w, partial, gram, alpha, steps, stage, state, hook_v, dump);
-  }
+void launch_als_cg(const AlsLaunch& L) {
+  if (L.k < 1 || L.k > kAlsMaxRank) als_refuse_rank();
+  als_dispatch(L.f64, L.gram != nullptr, [&](auto t, auto w) { launch_cg<decltype(t), decltype(w)::value>(L); });
 }
 
 }  // namespace mfhip

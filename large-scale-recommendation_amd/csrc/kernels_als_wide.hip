@@ -27,6 +27,7 @@
 #include <limits>
 #include <string>
 
+#include "als_device.hpp"
 #include "common.hpp"
 #include "kernels.hpp"
 
@@ -34,70 +35,13 @@ namespace mfhip {
 namespace {
 
 constexpr int kWThreads = 512;
-constexpr int kWaves = kWThreads / 64;
 constexpr int kRY = kWThreads / 32;  // rows of the thread grid (32 columns)
-constexpr int kTile = 32;   // ratings per LDS tile (a multiple of 2: one MFMA takes two ratings)
 constexpr int kPLd = 33;    // row stride of a 32-column panel in LDS
-
-typedef float v16f __attribute__((ext_vector_type(16)));
 
 template <typename T> struct WideAcc;
 
 // f32: lower-triangle blocks w, w + 8, ..., w + 32 of wave w (36 blocks at KP = 256: at most 5).
-template <> struct WideAcc<float> {
-  static constexpr int kMax = 5;
-  v16f acc[kMax];
-  __device__ void zero() {
-#pragma unroll
-    for (int x = 0; x < kMax; ++x)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[x][r] = 0.f;
-  }
-  // block number b -> (bi, bj), bj <= bi, row-major over the triangle
-  __device__ static void block_of(int b, int& bi, int& bj) {
-    bi = 0;
-    while ((bi + 1) * (bi + 2) / 2 <= b) ++bi;  // bi <= 7
-    bj = b - bi * (bi + 1) / 2;
-  }
-  template <int NB, bool W = false>
-  __device__ void tile(int tid, const float* q, int kp, int rows, const float* w = nullptr) {
-    constexpr int kBlocks = NB * (NB + 1) / 2;
-    const int lane = tid & 63, wave = tid >> 6;
-    const int h = lane >> 5, c = lane & 31;
-#pragma unroll
-    for (int x = 0; x < kMax; ++x) {
-      const int b = wave + kWaves * x;
-      if (b >= kBlocks) break;
-      int bi, bj;
-      block_of(b, bi, bj);
-      const float* pa = q + h * kp + 32 * bi + c;
-      const float* pb = q + h * kp + 32 * bj + c;
-      if constexpr (W) {
-        for (int t = 0; t < rows; t += 2)
-          acc[x] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[t + h] * pa[t * kp], pb[t * kp], acc[x], 0, 0, 0);
-      } else {
-        for (int t = 0; t < rows; t += 2)
-          acc[x] = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[t * kp], pb[t * kp], acc[x], 0, 0, 0);
-      }
-    }
-  }
-  // register r of a block is row (r & 3) + 8 (r >> 2) + 4 h
-  template <int NB>
-  __device__ void store(int tid, float* M, int ld) const {
-    constexpr int kBlocks = NB * (NB + 1) / 2;
-    const int lane = tid & 63, wave = tid >> 6;
-    const int h = lane >> 5, c = lane & 31;
-#pragma unroll
-    for (int x = 0; x < kMax; ++x) {
-      const int b = wave + kWaves * x;
-      if (b >= kBlocks) break;
-      int bi, bj;
-      block_of(b, bi, bj);
-#pragma unroll
-      for (int r = 0; r < 16; ++r) M[(32 * bi + (r & 3) + 8 * (r >> 2) + 4 * h) * ld + 32 * bj + c] = acc[x][r];
-    }
-  }
-};
+template <> struct WideAcc<float> : MfmaAcc<kWThreads / 64, 5> {};
 
 // f64: thread (ty, tx) of the 16 x 32 grid, entries (ty + 16 a, tx + 32 b), a < 2 NB, b <= a * kRY / 32.
 template <> struct WideAcc<double> {
@@ -148,14 +92,7 @@ __device__ __forceinline__ void finish_wide(T* S, T* P, T* stage, T* rhs, T* y, 
   // hoisted out of the caller's item loop to be spilled across them)
   int tid = threadIdx.x;
   asm volatile("" : "+v"(tid) : : "memory");
-  if (dump) {  // full symmetric k x k, then the right-hand side
-    for (int e = tid; e < k * k; e += kWThreads) {
-      const int i = e / k, j = e % k;
-      dump[e] = i >= j ? S[i * KP + j] : S[j * KP + i];
-    }
-    if (tid < k) dump[k * k + tid] = rhs[tid];
-    return;
-  }
+  if (dump) return als_dump_system<T, kWThreads>(tid, S, KP, rhs, k, dump);
   const int ty = tid >> 5, tx = tid & 31;
   bool bad = false;
 #pragma unroll 1
@@ -271,13 +208,13 @@ struct WideLds {
   }
 };
 
-// The work items blockIdx.x, blockIdx.x + gridDim.x, ... of the launch; W as in kernels_als.hip.
+// The work items blockIdx.x, blockIdx.x + gridDim.x, ... of the launch; W, G and alpha as in kernels_als.hip.
 template <typename T, int NB, bool W>
-__device__ __forceinline__ void wide_items(const AlsItem* __restrict__ items, int n_items,
-                                           const int32_t* __restrict__ cols, const T* __restrict__ vals,
-                                           const T* __restrict__ Q, T* __restrict__ X, int k, T lambda, int weighted,
-                                           T* __restrict__ partial, T* __restrict__ dump, const T* __restrict__ G,
-                                           T alpha, T* __restrict__ slab) {
+__global__ __launch_bounds__(kWThreads) void k_als_wide(const AlsItem* __restrict__ items, int n_items,
+                                                         const int32_t* __restrict__ cols, const T* __restrict__ vals,
+                                                         const T* __restrict__ Q, T* __restrict__ X, int k, T lambda,
+                                                         int weighted, T* __restrict__ partial, T* __restrict__ dump,
+                                                         const T* __restrict__ G, T alpha, T* __restrict__ slab) {
   constexpr int KP = 32 * NB;
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const WideLds<T, KP> L(smem_raw);
@@ -362,40 +299,19 @@ __device__ __forceinline__ void wide_items(const AlsItem* __restrict__ items, in
   }
 }
 
-template <typename T, int NB>
-__global__ __launch_bounds__(kWThreads) void k_als_wide(const AlsItem* __restrict__ items, int n_items,
-                                                         const int32_t* __restrict__ cols, const T* __restrict__ vals,
-                                                         const T* __restrict__ Q, T* __restrict__ X, int k, T lambda,
-                                                         int weighted, T* __restrict__ partial, T* __restrict__ dump,
-                                                         T* __restrict__ slab) {
-  wide_items<T, NB, false>(items, n_items, cols, vals, Q, X, k, lambda, weighted, partial, dump, nullptr, T(0), slab);
-}
-
-template <typename T, int NB>
-__global__ __launch_bounds__(kWThreads) void k_als_wide_implicit(const AlsItem* __restrict__ items, int n_items,
-                                                                  const int32_t* __restrict__ cols,
-                                                                  const T* __restrict__ vals, const T* __restrict__ Q,
-                                                                  T* __restrict__ X, int k, T lambda, int weighted,
-                                                                  T* __restrict__ partial, T* __restrict__ dump,
-                                                                  const T* __restrict__ G, T alpha,
-                                                                  T* __restrict__ slab) {
-  wide_items<T, NB, true>(items, n_items, cols, vals, Q, X, k, lambda, weighted, partial, dump, G, alpha, slab);
-}
-
 // The split rows blockIdx.x, blockIdx.x + gridDim.x, ...: partials [slot0, slot0 + chunks) added in
 // ascending order into the slab.  W: plus G, once, after the partial sum; a row with no positive
 // rating is set to zero.
 template <typename T, int NB, bool W>
-__device__ __forceinline__ void wide_splits(const AlsSplit* __restrict__ rows, int n_rows,
-                                            const T* __restrict__ partial, T* __restrict__ X, int k, T lambda,
-                                            int weighted, T* __restrict__ dump, const T* __restrict__ G,
-                                            T* __restrict__ slab) {
+__global__ __launch_bounds__(kWThreads) void k_als_reduce_wide(const AlsSplit* __restrict__ rows, int n_rows,
+                                                                const T* __restrict__ partial, T* __restrict__ X, int k,
+                                                                T lambda, int weighted, T* __restrict__ dump,
+                                                                const T* __restrict__ G, T* __restrict__ slab) {
   constexpr int KP = 32 * NB;
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const WideLds<T, KP> L(smem_raw);
   T* S = slab + static_cast<size_t>(blockIdx.x) * KP * KP;
   const int tid = threadIdx.x;
-  constexpr size_t kStride = static_cast<size_t>(KP) * KP + KP;
   for (int wi = blockIdx.x; wi < n_rows; wi += gridDim.x) {
     __syncthreads();  // the previous row has left LDS
     const AlsSplit sp = rows[wi];
@@ -405,40 +321,13 @@ __device__ __forceinline__ void wide_splits(const AlsSplit* __restrict__ rows, i
         continue;
       }
     }
-    for (int e = tid; e < KP * KP + KP; e += kWThreads) {
-      const int i = e / KP, j = e % KP;
-      if (i < KP && j > i) continue;  // only the lower triangle is defined
-      T sum = T(0);
-      for (int c = 0; c < sp.chunks; ++c) sum += partial[(static_cast<size_t>(sp.slot0) + c) * kStride + e];
-      if constexpr (W) {
-        if (i < KP) sum += G[e];
-      }
-      if (i < KP) S[e] = sum;
-      else L.rhs[j] = sum;
-    }
+    als_sum_partials<T, KP, kWThreads, W>(tid, sp, partial, G, S, KP, L.rhs);
     __syncthreads();
     const T lam = weighted ? lambda * static_cast<T>(W ? sp.npos : sp.count) : lambda;
     if (tid < k) S[tid * KP + tid] += lam;
     __syncthreads();
     finish_wide<T, NB>(S, L.P, L.stage, L.rhs, L.y, L.col, L.colraw, k, X + static_cast<size_t>(sp.row) * k, dump);
   }
-}
-
-template <typename T, int NB>
-__global__ __launch_bounds__(kWThreads) void k_als_reduce_wide(const AlsSplit* __restrict__ rows, int n_rows,
-                                                                const T* __restrict__ partial, T* __restrict__ X, int k,
-                                                                T lambda, int weighted, T* __restrict__ dump,
-                                                                T* __restrict__ slab) {
-  wide_splits<T, NB, false>(rows, n_rows, partial, X, k, lambda, weighted, dump, nullptr, slab);
-}
-
-template <typename T, int NB>
-__global__ __launch_bounds__(kWThreads) void k_als_reduce_wide_implicit(const AlsSplit* __restrict__ rows, int n_rows,
-                                                                         const T* __restrict__ partial,
-                                                                         T* __restrict__ X, int k, T lambda,
-                                                                         int weighted, T* __restrict__ dump,
-                                                                         const T* __restrict__ G, T* __restrict__ slab) {
-  wide_splits<T, NB, true>(rows, n_rows, partial, X, k, lambda, weighted, dump, G, slab);
 }
 
 // k_als_gram of kernels_als.hip with the wide accumulators; the tile is dynamic LDS (64 KiB in f64
@@ -469,87 +358,14 @@ __global__ __launch_bounds__(kWThreads) void k_als_gram_wide(const int32_t* __re
   g.template store<NB>(tid, part + static_cast<size_t>(blockIdx.x) * KP * KP, KP);
 }
 
-void set_lds(const void* fn, size_t bytes) {
-  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes)) != hipSuccess)
-    fail(MF_ERR_HIP, "k_als_wide: " + std::to_string(bytes) + " bytes of LDS refused");
-}
-
-template <typename T, int NB>
-void launch_wide_nb(hipStream_t st, const AlsItem* items, int n_items, const AlsSplit* splits, int n_splits,
-                    const int32_t* cols, const void* vals, const void* Q, void* X, int k, double lambda, int weighted,
-                    void* partial, void* dump, const void* gram, double alpha, void* slab, int slabs) {
-  constexpr int KP = 32 * NB;
-  const size_t smem = wide_lds_bytes<T>(KP);
-  const dim3 gi(static_cast<unsigned>(std::min(n_items, slabs))), gs(static_cast<unsigned>(std::min(n_splits, slabs)));
-  const dim3 block(kWThreads);
-  if (n_items > 0 && !gram) {
-    set_lds(reinterpret_cast<const void*>(&k_als_wide<T, NB>), smem);
-    hipLaunchKernelGGL((k_als_wide<T, NB>), gi, block, smem, st, items, n_items, cols, static_cast<const T*>(vals),
-                       static_cast<const T*>(Q), static_cast<T*>(X), k, static_cast<T>(lambda), weighted,
-                       static_cast<T*>(partial), static_cast<T*>(dump), static_cast<T*>(slab));
-  }
-  if (n_items > 0 && gram) {
-    set_lds(reinterpret_cast<const void*>(&k_als_wide_implicit<T, NB>), smem);
-    hipLaunchKernelGGL((k_als_wide_implicit<T, NB>), gi, block, smem, st, items, n_items, cols,
-                       static_cast<const T*>(vals), static_cast<const T*>(Q), static_cast<T*>(X), k,
-                       static_cast<T>(lambda), weighted, static_cast<T*>(partial), static_cast<T*>(dump),
-                       static_cast<const T*>(gram), static_cast<T>(alpha), static_cast<T*>(slab));
-  }
-  if (n_splits > 0 && !gram) {
-    set_lds(reinterpret_cast<const void*>(&k_als_reduce_wide<T, NB>), smem);
-    hipLaunchKernelGGL((k_als_reduce_wide<T, NB>), gs, block, smem, st, splits, n_splits,
-                       static_cast<const T*>(partial), static_cast<T*>(X), k, static_cast<T>(lambda), weighted,
-                       static_cast<T*>(dump), static_cast<T*>(slab));
-  }
-  if (n_splits > 0 && gram) {
-    set_lds(reinterpret_cast<const void*>(&k_als_reduce_wide_implicit<T, NB>), smem);
-    hipLaunchKernelGGL((k_als_reduce_wide_implicit<T, NB>), gs, block, smem, st, splits, n_splits,
-                       static_cast<const T*>(partial), static_cast<T*>(X), k, static_cast<T>(lambda), weighted,
-                       static_cast<T*>(dump), static_cast<const T*>(gram), static_cast<T*>(slab));
-  }
-}
-
-template <typename T>
-void launch_wide_t(hipStream_t st, const AlsItem* items, int n_items, const AlsSplit* splits, int n_splits,
-                   const int32_t* cols, const void* vals, const void* Q, void* X, int k, double lambda, int weighted,
-                   void* partial, void* dump, const void* gram, double alpha, void* slab, int slabs) {
-  switch ((k + 31) / 32) {
-    case 5: return launch_wide_nb<T, 5>(st, items, n_items, splits, n_splits, cols, vals, Q, X, k, lambda, weighted, partial, dump, gram, alpha, slab, slabs);
-    case 6: return launch_wide_nb<T, 6>(st, items, n_items, splits, n_splits, cols, vals, Q, X, k, lambda, weighted, partial, dump, gram, alpha, slab, slabs);
-    case 7: return launch_wide_nb<T, 7>(st, items, n_items, splits, n_splits, cols, vals, Q, X, k, lambda, weighted, partial, dump, gram, alpha, slab, slabs);
-    case 8: return launch_wide_nb<T, 8>(st, items, n_items, splits, n_splits, cols, vals, Q, X, k, lambda, weighted, partial, dump, gram, alpha, slab, slabs);
-    default: fail(MF_ERR_INVALID, "ALS supports a rank of at most " + std::to_string(kAlsMaxRank));
-  }
-}
-
-template <typename T>
-void launch_gram_wide_t(hipStream_t st, const int32_t* rated, int m, int slice, const void* Y, int k, void* part) {
-  const int nb = (k + 31) / 32;
-  const int slices = als_gram_slices(m, slice);
-  const dim3 grid(static_cast<unsigned>(slices)), block(kWThreads);
-  const T* y = static_cast<const T*>(Y);
-  T* p = static_cast<T*>(part);
-  const size_t smem = static_cast<size_t>(kTile) * 32 * nb * sizeof(T);
-  if (nb < 5 || nb > 8) fail(MF_ERR_INVALID, "ALS supports a rank of at most " + std::to_string(kAlsMaxRank));
-  if (slices <= 0) return;
-  switch (nb) {
-    case 5:
-      set_lds(reinterpret_cast<const void*>(&k_als_gram_wide<T, 5>), smem);
-      hipLaunchKernelGGL((k_als_gram_wide<T, 5>), grid, block, smem, st, rated, m, slice, y, k, p);
-      break;
-    case 6:
-      set_lds(reinterpret_cast<const void*>(&k_als_gram_wide<T, 6>), smem);
-      hipLaunchKernelGGL((k_als_gram_wide<T, 6>), grid, block, smem, st, rated, m, slice, y, k, p);
-      break;
-    case 7:
-      set_lds(reinterpret_cast<const void*>(&k_als_gram_wide<T, 7>), smem);
-      hipLaunchKernelGGL((k_als_gram_wide<T, 7>), grid, block, smem, st, rated, m, slice, y, k, p);
-      break;
-    default:
-      set_lds(reinterpret_cast<const void*>(&k_als_gram_wide<T, 8>), smem);
-      hipLaunchKernelGGL((k_als_gram_wide<T, 8>), grid, block, smem, st, rated, m, slice, y, k, p);
-      break;
-  }
+// One launch of `grid` workgroups with `smem` bytes of dynamic LDS; the arguments are converted to the
+// kernel's parameter types (the launch description holds void pointers and doubles).
+template <typename... P, typename... A>
+void launch_wide_kernel(void (*fn)(P...), int grid, size_t smem, hipStream_t st, A... args) {
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          static_cast<int>(smem)) != hipSuccess)
+    fail(MF_ERR_HIP, "k_als_wide: " + std::to_string(smem) + " bytes of LDS refused");
+  hipLaunchKernelGGL(fn, dim3(static_cast<unsigned>(grid)), dim3(kWThreads), smem, st, static_cast<P>(args)...);
 }
 
 }  // namespace
@@ -559,18 +375,32 @@ int als_wide_slabs(int k, bool f64, int cus) {
   return f64 ? cus : 2 * cus;  // the workgroups one CU's LDS holds at once (141 KiB f64, 70 KiB f32 at KP = 256)
 }
 
-void launch_als_wide(hipStream_t st, const AlsItem* items, int n_items, const AlsSplit* splits, int n_splits,
-                     const int32_t* cols, const void* vals, const void* Q, void* X, int k, double lambda, bool weighted,
-                     bool f64, void* partial, void* dump, const void* gram, double alpha, void* slab, int slabs) {
-  if (!slab || slabs <= 0) fail(MF_ERR_INVALID, "launch_als_wide: no matrix slabs");
-  if (f64) launch_wide_t<double>(st, items, n_items, splits, n_splits, cols, vals, Q, X, k, lambda, weighted ? 1 : 0, partial, dump, gram, alpha, slab, slabs);
-  else launch_wide_t<float>(st, items, n_items, splits, n_splits, cols, vals, Q, X, k, lambda, weighted ? 1 : 0, partial, dump, gram, alpha, slab, slabs);
+void launch_als_wide(const AlsLaunch& L) {
+  if (!L.slab || L.slabs <= 0) fail(MF_ERR_INVALID, "launch_als_wide: no matrix slabs");
+  als_dispatch<5>(L.f64, L.gram != nullptr, L.k, [&](auto t, auto w, auto nb) {
+    using T = decltype(t);
+    constexpr int NB = decltype(nb)::value;
+    constexpr bool W = decltype(w)::value;
+    const size_t smem = wide_lds_bytes<T>(32 * NB);
+    if (L.n_items > 0)
+      launch_wide_kernel(&k_als_wide<T, NB, W>, std::min(L.n_items, L.slabs), smem, L.st, L.items, L.n_items, L.cols,
+                         L.vals, L.Q, L.X, L.k, L.lambda, L.weighted, L.partial, L.dump, L.gram, L.alpha, L.slab);
+    if (L.n_splits > 0)
+      launch_wide_kernel(&k_als_reduce_wide<T, NB, W>, std::min(L.n_splits, L.slabs), smem, L.st, L.splits, L.n_splits,
+                         L.partial, L.X, L.k, L.lambda, L.weighted, L.dump, L.gram, L.slab);
+  });
 }
 
-void launch_als_gram_wide(hipStream_t st, const int32_t* rated, int m, int slice, const void* Y, int k, bool f64,
-                          void* part) {
-  if (f64) launch_gram_wide_t<double>(st, rated, m, slice, Y, k, part);
-  else launch_gram_wide_t<float>(st, rated, m, slice, Y, k, part);
+void launch_als_gram_wide(const AlsGramLaunch& L) {
+  const int slices = als_gram_slices(L.m, L.slice);
+  als_dispatch<5>(L.f64, false, L.k, [&](auto t, auto, auto nb) {
+    using T = decltype(t);
+    constexpr int NB = decltype(nb)::value;
+    if (slices > 0)
+      launch_wide_kernel(&k_als_gram_wide<T, NB>, slices, static_cast<size_t>(kTile) * 32 * NB * sizeof(T), L.st,
+                         L.rated, L.m, L.slice, L.Y, L.k, L.part);
+  });
 }
 
 }  // namespace mfhip
+

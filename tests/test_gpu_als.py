@@ -9,6 +9,8 @@ import pytest
 
 import mf_oracle as O
 import mfhip
+from als_support import (MODES, REGS, bits, make_ctx, normal_eq_reference, numpy_half_sweep, objective, rows_of,
+                         shuffled_ids, small_problem)
 from conftest import golden, set_knob
 from mfhip import _lib as L
 from mfhip import synth
@@ -16,33 +18,6 @@ from mfhip.context import Context
 
 pytestmark = pytest.mark.gpu
 
-MODES = [L.MODE_DETERMINISTIC_F64, L.MODE_FAST_F32]
-REGS = [L.ALS_REG_WEIGHTED, L.ALS_REG_PLAIN]
-
-
-def make_ctx(k, mode, **kw):
-    p = L.default_params()
-    p.num_factors = k
-    p.mode = mode
-    for a, b in kw.items():
-        setattr(p, a, b)
-    return Context(p)
-
-
-def shuffled_ids(rng, n, scale=3):
-    """n distinct ids, about half of them negative, in random order (row order is call order)."""
-    return (rng.permutation(n).astype(np.int32) - n // 2) * scale + 1
-
-
-def rows_of(side_index, n_rows):
-    """Per row the positions of its ratings, in input order (what the CSR must hold)."""
-    order = np.argsort(side_index, kind="stable")
-    cuts = np.searchsorted(side_index[order], np.arange(n_rows + 1))
-    return [order[cuts[a]:cuts[a + 1]] for a in range(n_rows)]
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float64).view(np.uint64)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -69,12 +44,6 @@ def int_problem(rng, k):
     P = rng.integers(-3, 4, (nu + 1, k)).astype(np.float64)
     Q = rng.integers(-3, 4, (ni + 1, k)).astype(np.float64)
     return pu, pi, r, uids, iids, P, Q
-
-
-def normal_eq_reference(F_other, other_index, r, pos, lam, reg, k):
-    Qm = F_other[other_index[pos]]
-    lam_row = lam * len(pos) if reg == L.ALS_REG_WEIGHTED else lam
-    return Qm.T @ Qm + lam_row * np.eye(k), Qm.T @ r[pos]
 
 
 @pytest.mark.parametrize("mode", MODES)
@@ -182,13 +151,6 @@ def test_solve_within_backward_error_bound(mode, k, rows, lo, hi):
 # ---------------------------------------------------------------------------------------------
 # 3. half-sweep order and the counter
 
-def small_problem(rng, nu=40, ni=25, n=400):
-    u = rng.integers(0, nu, n).astype(np.int32)
-    i = rng.integers(0, ni, n).astype(np.int32)
-    r = rng.integers(1, 11, n) / 2.0
-    return u, i, r
-
-
 @pytest.mark.parametrize("mode", MODES)
 def test_half_sweep_order_and_counter(mode):
     rng = np.random.default_rng(21)
@@ -238,19 +200,6 @@ def test_half_sweep_order_and_counter(mode):
 
 # ---------------------------------------------------------------------------------------------
 # 4. end to end against a numpy f64 ALS
-
-def numpy_half_sweep(X, Y, x_rows, y_index, r, lam):
-    for a, pos in enumerate(x_rows):
-        if len(pos):
-            Qm = Y[y_index[pos]]
-            X[a] = np.linalg.solve(Qm.T @ Qm + lam * len(pos) * np.eye(X.shape[1]), Qm.T @ r[pos])
-
-
-def objective(P, Q, pu, pi, r, lam):
-    err = r - np.einsum("nk,nk->n", P[pu], Q[pi])
-    nu, ni = np.bincount(pu, minlength=len(P)), np.bincount(pi, minlength=len(Q))
-    return err @ err + lam * (nu @ (P * P).sum(1) + ni @ (Q * Q).sum(1))
-
 
 @pytest.fixture(scope="module")
 def smoke_als():

@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 
 import mfhip
+from als_support import FILLERS, MODES, REGS, TINY, bits, dtype_of, frozen, make_ctx, rows_of, shuffled_ids
 from conftest import set_knob
 from mfhip import _lib as L
 from mfhip import synth
@@ -28,46 +29,10 @@ from mfhip.context import Context
 
 pytestmark = pytest.mark.gpu
 
-MODES = [L.MODE_DETERMINISTIC_F64, L.MODE_FAST_F32]
-REGS = [L.ALS_REG_WEIGHTED, L.ALS_REG_PLAIN]
 RANKS = [1, 3, 16, 31, 32, 33, 63, 64, 65, 100, 127, 128, 129, 192, 255, 256]
 REPLAY_RANKS = [3, 33, 64, 128, 160, 256]
 WAYS = (None, ("als_cg_stage", 0), ("als_chunk", 16))
-TINY = 1e-300       # the lambda that vanishes: 0 in f32, absorbed by any non-zero integer in f64
 EXACT = 1 << 24     # f32 holds every integer up to here
-FILLERS = 200       # zero-vector counterpart rows
-
-
-def make_ctx(k, mode):
-    p = L.default_params()
-    p.num_factors = k
-    p.mode = mode
-    return Context(p)
-
-
-def dtype_of(mode):
-    return np.float64 if mode == L.MODE_DETERMINISTIC_F64 else np.float32
-
-
-def shuffled_ids(rng, n, scale=3):
-    return (rng.permutation(n).astype(np.int32) - n // 2) * scale + 1
-
-
-def rows_of(side_index, n_rows):
-    order = np.argsort(side_index, kind="stable")
-    cuts = np.searchsorted(side_index[order], np.arange(n_rows + 1))
-    return [order[cuts[a]:cuts[a + 1]] for a in range(n_rows)]
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float64).view(np.uint64)
-
-
-def frozen(d):
-    for v in d.values():
-        if isinstance(v, np.ndarray):
-            v.setflags(write=False)
-    return d
 
 
 # ---------------------------------------------------------------------------------------------

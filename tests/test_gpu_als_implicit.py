@@ -8,40 +8,13 @@ import numpy as np
 import pytest
 
 import mfhip
+from als_support import MODES, REGS, bits, make_ctx, rows_of, shuffled_ids
 from conftest import set_knob
 from mfhip import _lib as L
 from mfhip import synth
-from mfhip.context import Context
 
 pytestmark = pytest.mark.gpu
 
-MODES = [L.MODE_DETERMINISTIC_F64, L.MODE_FAST_F32]
-REGS = [L.ALS_REG_WEIGHTED, L.ALS_REG_PLAIN]
-
-
-def make_ctx(k, mode, **kw):
-    p = L.default_params()
-    p.num_factors = k
-    p.mode = mode
-    for a, b in kw.items():
-        setattr(p, a, b)
-    return Context(p)
-
-
-def shuffled_ids(rng, n, scale=3):
-    """n distinct ids, about half of them negative, in random order (row order is call order)."""
-    return (rng.permutation(n).astype(np.int32) - n // 2) * scale + 1
-
-
-def rows_of(side_index, n_rows):
-    """Per row the positions of its ratings, in input order (what the CSR must hold)."""
-    order = np.argsort(side_index, kind="stable")
-    cuts = np.searchsorted(side_index[order], np.arange(n_rows + 1))
-    return [order[cuts[a]:cuts[a + 1]] for a in range(n_rows)]
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float64).view(np.uint64)
 
 
 def as_stored(F, mode):

@@ -15,13 +15,13 @@ WIDE puts a rank on each side of every 32-bucket edge (= every panel edge of fin
 Which test drives which instance (f32 and f64):
   test_explicit_solve_is_exact   k_als_wide whole rows (default; als_batch=5: three launches);
                                  als_chunk=16: chunks + k_als_reduce_wide
-  test_implicit_solve_is_exact   k_als_wide_implicit, k_als_gram_wide (als_gram_slice=8: many slices);
-                                 als_chunk=16: chunks + k_als_reduce_wide_implicit
+  test_implicit_solve_is_exact   k_als_wide<T, NB, true>, k_als_gram_wide (als_gram_slice=8: many slices);
+                                 als_chunk=16: chunks + k_als_reduce_wide<T, NB, true>
   test_hooks_*                   the dump path of finish_wide and k_als_gram_wide, whole rows and rows
                                  split by als_chunk=64; the half-sweep bitwise the same either way
   test_solve_within_backward_error_bound, test_end_to_end_against_numpy_als   real-valued data
-  test_strided_*                 the loop `for (wi = blockIdx.x; wi < n; wi += gridDim.x)` of wide_items
-                                 and wide_splits.  The grid is min(items, slabs) with 256 (f64) or 512
+  test_strided_*                 the loop `for (wi = blockIdx.x; wi < n; wi += gridDim.x)` of k_als_wide
+                                 and k_als_reduce_wide.  The grid is min(items, slabs) with 256 (f64) or 512
                                  (f32) slabs on an MI355X, so in every test above a workgroup meets one
                                  work item, als_batch=5 included; MFHIP_TEST als_slabs=N caps the grid
                                  at N workgroups, and with N = 1 and 3 each one meets several whole
@@ -34,16 +34,16 @@ import numpy as np
 import pytest
 
 import mfhip
-import test_gpu_als as A
 import test_gpu_als_ranks as R
+from als_support import (MODES, N_ITEMS, REGS, TINY, bits, explicit_problem, first_difference, implicit_problem,
+                         make_ctx, normal_eq_reference, numpy_half_sweep, objective, rows_of, shuffled_ids,
+                         small_problem)
 from conftest import set_knob
 from mfhip import _lib as L
 from mfhip import synth
 
 pytestmark = pytest.mark.gpu
 
-MODES = [L.MODE_DETERMINISTIC_F64, L.MODE_FAST_F32]
-REGS = [L.ALS_REG_WEIGHTED, L.ALS_REG_PLAIN]
 WIDE = [129, 144, 145, 160, 161, 192, 193, 224, 225, 255, 256]
 HOOK_RANKS = [129, 160, 161, 192, 224, 225, 256]
 
@@ -78,15 +78,15 @@ def run_exact(monkeypatch, d, k, mode, reg, knobs, implicit):
     with monkeypatch.context() as mp:
         for key, value in knobs.items():
             set_knob(mp, key, value)
-        with R.make_ctx(k, mode) as ctx:
+        with make_ctx(k, mode) as ctx:
             ctx.set_factors(L.SIDE_USER, d["uids"], d["P"])
             ctx.set_factors(L.SIDE_ITEM, d["iids"], d["Q0"])
             ctx.als_prepare(d["uids"][d["pu"]], d["iids"][d["pi"]], d["r"])
             if implicit:
-                ctx.als_run_implicit(1, R.TINY, 1.0, reg)
+                ctx.als_run_implicit(1, TINY, 1.0, reg)
             else:
-                ctx.als_run(1, R.TINY, reg)
-            assert np.array_equal(R.bits(ctx.lookup(L.SIDE_USER, d["uids"])[0]), R.bits(d["P"]))
+                ctx.als_run(1, TINY, reg)
+            assert np.array_equal(bits(ctx.lookup(L.SIDE_USER, d["uids"])[0]), bits(d["P"]))
             return ctx.lookup(L.SIDE_ITEM, d["iids"])[0]
 
 
@@ -99,17 +99,17 @@ def test_strided_exact_solve(monkeypatch, mode, k, implicit):
     problem) and als_chunk=16 (every row through k_als_reduce_wide, 12 or 4 split rows and some
     hundred chunks per workgroup): the planted solution exactly, and every row bitwise as with the
     uncapped grid; the unrated items stay as set."""
-    d = R.implicit_problem(k) if implicit else R.explicit_problem(k)
+    d = implicit_problem(k) if implicit else explicit_problem(k)
     want = d["X"] if implicit else d["X0"]
     for reg in REGS:
         for chunk in ({}, {"als_chunk": 16}):
             ref = run_exact(monkeypatch, d, k, mode, reg, chunk, implicit)
-            assert np.array_equal(ref[:R.N_ITEMS], want), (reg, chunk, R.first_difference(ref, want))
+            assert np.array_equal(ref[:N_ITEMS], want), (reg, chunk, first_difference(ref, want))
             for slabs in (1, 3):
                 X = run_exact(monkeypatch, d, k, mode, reg, dict(chunk, als_slabs=slabs), implicit)
-                assert np.array_equal(X[:R.N_ITEMS], want), (reg, chunk, slabs, R.first_difference(X, want))
-                assert np.array_equal(R.bits(X), R.bits(ref)), (reg, chunk, slabs)
-                assert np.array_equal(R.bits(X[R.N_ITEMS:]), R.bits(d["Q0"][R.N_ITEMS:]))
+                assert np.array_equal(X[:N_ITEMS], want), (reg, chunk, slabs, first_difference(X, want))
+                assert np.array_equal(bits(X), bits(ref)), (reg, chunk, slabs)
+                assert np.array_equal(bits(X[N_ITEMS:]), bits(d["Q0"][N_ITEMS:]))
 
 
 @pytest.mark.parametrize("mode", MODES)
@@ -125,7 +125,7 @@ def test_strided_real_valued_iteration(monkeypatch, smoke_als_160, mode):
         with monkeypatch.context() as mp:
             for key, value in knobs.items():
                 set_knob(mp, key, value)
-            with A.make_ctx(k, mode) as ctx:
+            with make_ctx(k, mode) as ctx:
                 ctx.set_factors(L.SIDE_USER, s["uids"], s["P0"])
                 ctx.set_factors(L.SIDE_ITEM, s["iids"], s["Q0"])
                 ctx.als_prepare(d.u, d.i, d.r - 3.0 if implicit else d.r)
@@ -133,7 +133,7 @@ def test_strided_real_valued_iteration(monkeypatch, smoke_als_160, mode):
                     ctx.als_run_implicit(2, lam, 1.0)
                 else:
                     ctx.als_run(2, lam)
-                return [A.bits(ctx.factors(side)[1]) for side in (L.SIDE_USER, L.SIDE_ITEM)]
+                return [bits(ctx.factors(side)[1]) for side in (L.SIDE_USER, L.SIDE_ITEM)]
 
     for implicit in (False, True):
         for chunk in ({}, {"als_chunk": 16}):
@@ -190,26 +190,26 @@ def test_solve_within_backward_error_bound(mode, k):
     perm = rng.permutation(len(pu))
     pu, pi = pu[perm], pi[perm]
     r = rng.integers(1, 11, len(pu)) / 2.0
-    uids, iids = A.shuffled_ids(rng, nu + 1), A.shuffled_ids(rng, rows + 2, 5)  # one user, two items unrated
+    uids, iids = shuffled_ids(rng, nu + 1), shuffled_ids(rng, rows + 2, 5)  # one user, two items unrated
     P, Q = rng.standard_normal((nu + 1, k)), rng.standard_normal((rows + 2, k))
     if f32:
         P, Q = P.astype(np.float32).astype(np.float64), Q.astype(np.float32).astype(np.float64)
-    irows = A.rows_of(pi, len(iids))
+    irows = rows_of(pi, len(iids))
     lam = 0.1
     worst = 0.0
     for reg in REGS:
-        with A.make_ctx(k, mode) as ctx:
+        with make_ctx(k, mode) as ctx:
             ctx.set_factors(L.SIDE_USER, uids, P)
             ctx.set_factors(L.SIDE_ITEM, iids, Q)
             ctx.als_prepare(uids[pu], iids[pi], r)
             ctx.als_run(1, lam, reg)
             X = ctx.lookup(L.SIDE_ITEM, iids)[0]
-            assert np.array_equal(A.bits(ctx.lookup(L.SIDE_USER, uids)[0]), A.bits(P))  # the side not solved
-            assert np.array_equal(A.bits(X[rows:]), A.bits(Q[rows:]))                    # rows with no rating
+            assert np.array_equal(bits(ctx.lookup(L.SIDE_USER, uids)[0]), bits(P))  # the side not solved
+            assert np.array_equal(bits(X[rows:]), bits(Q[rows:]))                    # rows with no rating
         for a in range(rows):
             pos = irows[a]
             n = len(pos)
-            M, b = A.normal_eq_reference(P, pu, r, pos, lam, reg, k)
+            M, b = normal_eq_reference(P, pu, r, pos, lam, reg, k)
             x = X[a]
             assert np.isfinite(x).all()
             c = k * (n + 2) + 4 * k * (3 * k + 1) + 2
@@ -232,15 +232,15 @@ def smoke_als_160():
     rng = np.random.default_rng(4)
     k, lam, T = 160, 0.1, 2
     P0, Q0 = rng.random((len(uids), k)), rng.random((len(iids), k))
-    urows, irows = A.rows_of(pu, len(uids)), A.rows_of(pi, len(iids))
+    urows, irows = rows_of(pu, len(uids)), rows_of(pi, len(iids))
     ref = {}
     for mode in MODES:
         P, Q = P0.copy(), Q0.copy()
         if mode == L.MODE_FAST_F32:
             P, Q = P.astype(np.float32).astype(np.float64), Q.astype(np.float32).astype(np.float64)
         for _ in range(T):
-            A.numpy_half_sweep(Q, P, irows, pu, d.r, lam)
-            A.numpy_half_sweep(P, Q, urows, pi, d.r, lam)
+            numpy_half_sweep(Q, P, irows, pu, d.r, lam)
+            numpy_half_sweep(P, Q, urows, pi, d.r, lam)
         err = d.r - np.einsum("nk,nk->n", P[pu], Q[pi])
         ref[mode] = float(np.sqrt(err @ err / len(err)))
     return dict(d=d, uids=uids, iids=iids, pu=pu, pi=pi, k=k, lam=lam, T=T, P0=P0, Q0=Q0, ref=ref)
@@ -256,7 +256,7 @@ def test_end_to_end_against_numpy_als(smoke_als_160, mode):
     d, k, lam, T = s["d"], s["k"], s["lam"], s["T"]
 
     def start():
-        ctx = A.make_ctx(k, mode)
+        ctx = make_ctx(k, mode)
         ctx.set_factors(L.SIDE_USER, s["uids"], s["P0"])
         ctx.set_factors(L.SIDE_ITEM, s["iids"], s["Q0"])
         ctx.als_prepare(d.u, d.i, d.r)
@@ -265,12 +265,12 @@ def test_end_to_end_against_numpy_als(smoke_als_160, mode):
     with start() as ctx, start() as twin:
         _, P = ctx.factors(L.SIDE_USER)
         _, Q = ctx.factors(L.SIDE_ITEM)
-        obj = [A.objective(P, Q, s["pu"], s["pi"], d.r, lam)]
+        obj = [objective(P, Q, s["pu"], s["pi"], d.r, lam)]
         for _ in range(2 * T):
             ctx.als_run(1, lam)
             _, P = ctx.factors(L.SIDE_USER)
             _, Q = ctx.factors(L.SIDE_ITEM)
-            obj.append(A.objective(P, Q, s["pu"], s["pi"], d.r, lam))
+            obj.append(objective(P, Q, s["pu"], s["pi"], d.r, lam))
         print("als wide objective per half-sweep:", " ".join(f"{x:.6f}" for x in obj))
         assert all(b < a for a, b in zip(obj, obj[1:])), obj
         rmse, matched = ctx.rmse(d.u, d.i, d.r)
@@ -281,7 +281,7 @@ def test_end_to_end_against_numpy_als(smoke_als_160, mode):
         for _ in range(2 * T):
             twin.als_run(1, lam)
         for side in (L.SIDE_USER, L.SIDE_ITEM):
-            assert np.array_equal(A.bits(twin.factors(side)[1]), A.bits(ctx.factors(side)[1]))
+            assert np.array_equal(bits(twin.factors(side)[1]), bits(ctx.factors(side)[1]))
 
 
 # ---------------------------------------------------------------------------------------------
@@ -292,7 +292,7 @@ def test_singular_system_gives_nan_and_returns(mode):
     """test_gpu_als.py's singular system at k = 130: a pivot that is not a positive finite number makes
     the row NaN, and the kernel finishes."""
     k = 130
-    with A.make_ctx(k, mode) as ctx:
+    with make_ctx(k, mode) as ctx:
         ctx.set_factors(L.SIDE_USER, [1, 2], np.full((2, k), np.inf))
         ctx.set_factors(L.SIDE_ITEM, [5, 6], np.ones((2, k)))
         ctx.als_prepare([1, 2, 1], [5, 5, 6], [1.0, 2.0, 3.0])
@@ -306,7 +306,7 @@ def test_k256_model_is_an_ordinary_one(mode, tmp_path):
     d = synth.generate(300, 120, 6000, seed=3)
     k, lam = 256, 0.1
     uids = np.unique(d.u)
-    with A.make_ctx(k, mode, seed=11) as ctx:
+    with make_ctx(k, mode, seed=11) as ctx:
         ctx.als_fit(d.u, d.i, d.r, 1, lam)
         rmse, matched = ctx.rmse(d.u, d.i, d.r)
         # against numpy on the factors read back: a prediction is a k-term chain in another order than
@@ -322,19 +322,19 @@ def test_k256_model_is_an_ordinary_one(mode, tmp_path):
         assert (cnt == 10).all() and np.isfinite(sc).all()
         path = os.path.join(tmp_path, "als256.mfsnap")
         ctx.save(path)
-        with A.make_ctx(k, mode, seed=11) as other:
+        with make_ctx(k, mode, seed=11) as other:
             other.load(path)
             for side in (L.SIDE_USER, L.SIDE_ITEM):
                 ia, va = ctx.factors(side)
                 ib, vb = other.factors(side)
-                assert np.array_equal(ia, ib) and np.array_equal(A.bits(va), A.bits(vb))
+                assert np.array_equal(ia, ib) and np.array_equal(bits(va), bits(vb))
 
 
 @pytest.mark.parametrize("mode", MODES)
 def test_rank_257_is_refused(mode):
     rng = np.random.default_rng(2)
-    u, i, r = A.small_problem(rng)
-    with A.make_ctx(257, mode) as ctx:
+    u, i, r = small_problem(rng)
+    with make_ctx(257, mode) as ctx:
         with pytest.raises(mfhip.MFError) as e:
             ctx.als_fit(u, i, r, 1, 0.1)
         assert e.value.code == L.MF_ERR_INVALID and "256" in str(e.value)
