@@ -437,6 +437,78 @@ int mf_als_fit_implicit_cg(mf_ctx* ctx, const int32_t* users, const int32_t* ite
                            int64_t n, int32_t iterations, double lambda, int32_t reg, double alpha,
                            int32_t cg_steps);
 
+/* Non-negative ALS (MLlib's ALS with nonnegative = true): the same half-sweeps with every row solved for
+   x >= 0 by a projected conjugate-gradient non-negative least squares (NNLS) in the family of MLlib's
+   NNLS.scala, on the row's k x k matrix where the Cholesky half-sweep keeps it (LDS up to rank 128,
+   global memory from 129 to 256).
+   Shared with the other six run calls: the data mf_als_prepare built, the half-sweep order (item side
+   first) and the half-sweep counter -- all eight kinds of run call may be mixed --, the state rules and
+   errors (ranks 1 to 256), the formation of the row's system (mf_als_run's, and with alpha
+   mf_als_run_implicit's: the sums, their order, the chunks, G, lambda' and n+), and that a row with no
+   rating is left untouched.  mf_als_fit_nonneg / mf_als_fit_implicit_nonneg are mf_als_prepare followed
+   by the run call with 2 * iterations half-sweeps (n == 0: a no-op).
+   The solve.  For a row with A (k x k, symmetric positive definite, lambda' already on the diagonal, G
+   added for implicit rows; the upper triangle is a copy of the lower) and b, in the context's precision
+   T, with proj(res, x) = res with entry i zeroed wherever res_i > 0 and x_i == 0:
+       x = 0;  bb = b.b;  lastWall = 0;  lastDir = 0;  lastNorm = 0
+       cap = max(400, 20 k);   tol2 = 1e-12 (rounded to T);   slack = 1 - 64 eps(T)
+       for it = 0 .. cap-1:
+           res = A x - b
+           g   = proj(res, x);   ng = g.g
+           dir = g;  step = (g.res) / (g.(A g));  nd = ng
+           if it > lastWall + 1:
+               d2 = fma(ng / lastNorm, lastDir, g);  s2 = (d2.res) / (d2.(A d2));  n2 = d2.d2
+               if not stop(s2, n2):  dir, step, nd = d2, s2, n2
+           if nd <= tol2 * bb: done, reason 0;  else if step is not finite: done, reason 3;
+           else if not step > 0: done, reason 2
+           for i ascending:  if step * dir_i > x_i:  step = x_i / dir_i            (do not cross a wall)
+           for i:  if step * dir_i > x_i * slack:  x_i = +0, lastWall = it
+                   else x_i = x_i - step * dir_i
+           lastDir = dir;  lastNorm = ng
+       stop(step, nd):  step is not finite,  or step <= 0,  or nd <= tol2 * bb
+   The stopping rule is relative to b.b, so the solve is scale-free: (A, b) times a power of two gives the
+   same x and the same iteration count bit for bit.  (MLlib's absolute thresholds step < 1e-7 and
+   |dir|^2 < 1e-12 |x|^2 are not; they never fire in f32.)  Every row ends with a reason code:
+       0  converged (nd <= tol2 * bb)            x
+       1  hit the iteration cap                  x as it stands
+       2  step <= 0                              x as it stands
+       3  a non-finite step or bb                the whole row is NaN (mf_als_run's rule for a bad pivot)
+   A bb that is not finite ends the row before it = 0 with reason 3.  The iteration count of a row is the
+   number of updates of x: `it` when the row is done, cap for reason 1.  A row with b <= 0 everywhere ends
+   at it = 0 with x = +0 and reason 0.  An implicit row with no positive rating is set to +0 without
+   iterating.  Every entry that leaves the solver is >= 0 and never -0 (x starts at +0, a wall
+   stores +0, and x_i - step * dir_i cannot round to -0).
+   Order, a function of k alone.  (A v)[i]: an fma chain from 0 over j = 0 .. k-1 of A[j][i] v[j].  Every
+   dot product u.v: 64 partial sums, partial l an fma chain from 0 over f = l, l + 64, l + 128, l + 192
+   (< k) of u[f] v[f], added pairwise: partial l with l ^ 32, then ^ 16, ^ 8, ^ 4, ^ 2, ^ 1.  res_i =
+   (A x)[i] - b_i; d2_i is one fma; step * dir_i is a product and x_i - step * dir_i a difference of it;
+   the wall clamp runs over i ascending with the step as the earlier entries left it.  Every other
+   operation is a single rounding.  Deterministic contexts compute in f64, fast contexts in f32
+   throughout.  No floating-point atomics: results are bitwise reproducible from run to run and do not
+   depend on the device or on how the rows are cut into launches; they depend on the chunk length only
+   through A and b, as mf_als_run's do.
+   Errors.  Exactly those of mf_als_run / mf_als_run_implicit / mf_als_fit / mf_als_fit_implicit. */
+int mf_als_run_nonneg(mf_ctx* ctx, int64_t half_sweeps, double lambda, int32_t reg);
+int mf_als_run_implicit_nonneg(mf_ctx* ctx, int64_t half_sweeps, double lambda, int32_t reg, double alpha);
+int mf_als_fit_nonneg(mf_ctx* ctx, const int32_t* users, const int32_t* items, const double* ratings, int64_t n,
+                      int32_t iterations, double lambda, int32_t reg);
+int mf_als_fit_implicit_nonneg(mf_ctx* ctx, const int32_t* users, const int32_t* items, const double* ratings,
+                               int64_t n, int32_t iterations, double lambda, int32_t reg, double alpha);
+/* What the non-negative half-sweeps did since mf_als_prepare, from integer counters on the device:
+   rows = rows solved (implicit rows set to zero without a solve included, with 0 iterations),
+   iterations = the sum of their iteration counts, max_iterations = the longest solve, capped / reason2 /
+   nan_rows = rows that ended with reason 1 / 2 / 3.  MF_ERR_STATE before mf_als_prepare. */
+struct mf_als_nonneg_stats {
+  int64_t rows, iterations, max_iterations, capped, reason2, nan_rows;
+};
+int mf_als_nonneg_stats(mf_ctx* ctx, struct mf_als_nonneg_stats* out);
+/* The solve above on the host (no GPU needed), in the stated order, in f32 (f64 == 0: A and b are rounded
+   to f32 first) or f64 arithmetic: the replay the kernels are checked against bit for bit.  A is k x k,
+   row-major; only its lower triangle is read.  x_out[k]; iters_out and reason_out may be NULL.
+   MF_ERR_INVALID: k outside 1 .. 256 or a null A, b or x_out. */
+int mf_nnls_solve(int32_t k, const double* A /* k*k symmetric */, const double* b, int f64, double* x_out,
+                  int32_t* iters_out, int32_t* reason_out);
+
 /* Exact updateLocalFactors replacement (DSGDforMF.scala:378-418) on caller buffers:
    users[nu x k], items[ni x k] are updated in place; omegas are per row.  Reentrant
    on disjoint buffers with distinct contexts, as Flink calls it per task slot. */

@@ -98,6 +98,15 @@ int mf_debug_als_normal_eq_implicit(mf_ctx* ctx, int side, int32_t id, double la
 int mf_debug_als_cg_matvec(mf_ctx* ctx, int side, int32_t id, double lambda, int32_t reg, double alpha,
                            const double* v, double* Av_out, double* b_out);
 int mf_debug_als_cg_capacity(mf_ctx* ctx, int32_t* ratings_out);
+/* mf_debug_als_nnls_row: after mf_als_prepare, the row mf_als_run_nonneg (alpha < 0) or
+   mf_als_run_implicit_nonneg (alpha >= 0) would store for `id` of `side` from the current factors, solved
+   through the half-sweep's own kernels -- the chunked path of a long row included -- and widened to f64:
+   x_out[k], *iters_out = the row's iteration count, *reason_out = its reason code (mfhip.h).  An implicit
+   row with no positive rating is solved here (b = 0: x = +0, 0 iterations, reason 0), which is what the
+   half-sweep stores for it unsolved.  Neither the factors nor mf_als_nonneg_stats change.
+   MF_ERR_INVALID as for mf_debug_als_normal_eq. */
+int mf_debug_als_nnls_row(mf_ctx* ctx, int side, int32_t id, double lambda, int32_t reg, double alpha,
+                          double* x_out, int32_t* iters_out, int32_t* reason_out);
 /* mf_debug_rank_csr: the pair table mf_rank_eval builds on the device for one pair list, copied back.
    The evaluated queries are the distinct ids of query[] the model holds on query_side, in ascending
    factor-row order: q_ids_out[*nq_out].  off_out[*nq_out + 1] and entries_out[*ne_out] are the table:

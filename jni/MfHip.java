@@ -52,6 +52,15 @@ public final class MfHip {
   public static native void alsRunCg(long ctx, long halfSweeps, double lambda, int reg, int cgSteps);
   public static native void alsRunImplicitCg(long ctx, long halfSweeps, double lambda, int reg, double alpha,
                                              int cgSteps);
+  // Non-negative ALS (MLlib's nonnegative = true; mf_als_fit_nonneg / mf_als_fit_implicit_nonneg): every row
+  // is solved for x >= 0 by a projected conjugate-gradient NNLS.  The run calls follow alsPrepare and share
+  // the half-sweep counter with every other kind of run call.
+  public static native void alsFitNonneg(long ctx, int[] users, int[] items, double[] ratings,
+                                         int iterations, double lambda, int reg);
+  public static native void alsFitImplicitNonneg(long ctx, int[] users, int[] items, double[] ratings,
+                                                 int iterations, double lambda, int reg, double alpha);
+  public static native void alsRunNonneg(long ctx, long halfSweeps, double lambda, int reg);
+  public static native void alsRunImplicitNonneg(long ctx, long halfSweeps, double lambda, int reg, double alpha);
   // unblock (DSGDforMF.scala:245-255) and checkpoint restore
   public static native long numFactors(long ctx, int side);
   public static native long getFactors(long ctx, int side, int[] idsOut, double[] vecsOut);

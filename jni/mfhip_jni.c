@@ -257,6 +257,50 @@ JNIEXPORT void JNICALL JFN(alsRunImplicitCg)(JNIEnv* env, jclass c, jlong h, jlo
   check(env, mf_als_run_implicit_cg(CTX(h), halfSweeps, lambda, reg, alpha, cgSteps));
 }
 
+/* The non-negative half-sweeps (MLlib's nonnegative = true): mf_als_fit_nonneg, or with alpha >= 0
+   mf_als_fit_implicit_nonneg. */
+static void als_nonneg_fit(JNIEnv* env, jlong h, jintArray u, jintArray i, jdoubleArray r, jint iterations,
+                           jdouble lambda, jint reg, int implicit, jdouble alpha) {
+  jsize n = 0;
+  if (rating_columns(env, u, i, r, &n)) return;
+  Elems eu = {0}, ei = {0}, er = {0};
+  if (acquire(env, &eu, u, kInt) || acquire(env, &ei, i, kInt) || acquire(env, &er, r, kDouble)) {
+    release(env, &eu, JNI_ABORT);
+    release(env, &ei, JNI_ABORT);
+    return;
+  }
+  const int32_t* pu = (const int32_t*)eu.p;
+  const int32_t* pi = (const int32_t*)ei.p;
+  const double* pr = (const double*)er.p;
+  int st;
+  if (implicit) st = mf_als_fit_implicit_nonneg(CTX(h), pu, pi, pr, n, iterations, lambda, reg, alpha);
+  else st = mf_als_fit_nonneg(CTX(h), pu, pi, pr, n, iterations, lambda, reg);
+  release(env, &er, JNI_ABORT);
+  release(env, &ei, JNI_ABORT);
+  release(env, &eu, JNI_ABORT);
+  check(env, st);
+}
+
+JNIEXPORT void JNICALL JFN(alsFitNonneg)(JNIEnv* env, jclass c, jlong h, jintArray u, jintArray i, jdoubleArray r,
+                                         jint iterations, jdouble lambda, jint reg) {
+  als_nonneg_fit(env, h, u, i, r, iterations, lambda, reg, 0, 0.0);
+}
+
+JNIEXPORT void JNICALL JFN(alsFitImplicitNonneg)(JNIEnv* env, jclass c, jlong h, jintArray u, jintArray i,
+                                                 jdoubleArray r, jint iterations, jdouble lambda, jint reg,
+                                                 jdouble alpha) {
+  als_nonneg_fit(env, h, u, i, r, iterations, lambda, reg, 1, alpha);
+}
+
+JNIEXPORT void JNICALL JFN(alsRunNonneg)(JNIEnv* env, jclass c, jlong h, jlong halfSweeps, jdouble lambda, jint reg) {
+  check(env, mf_als_run_nonneg(CTX(h), halfSweeps, lambda, reg));
+}
+
+JNIEXPORT void JNICALL JFN(alsRunImplicitNonneg)(JNIEnv* env, jclass c, jlong h, jlong halfSweeps, jdouble lambda,
+                                                 jint reg, jdouble alpha) {
+  check(env, mf_als_run_implicit_nonneg(CTX(h), halfSweeps, lambda, reg, alpha));
+}
+
 JNIEXPORT void JNICALL JFN(dsgdRun)(JNIEnv* env, jclass c, jlong h, jlong supersteps) {
   check(env, mf_dsgd_run(CTX(h), supersteps));
 }

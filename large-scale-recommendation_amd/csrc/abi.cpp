@@ -442,7 +442,46 @@ int mf_als_fit_implicit_cg(mf_ctx* ctx, const int32_t* u, const int32_t* i, cons
   return als_fit_entry(ctx, u, i, r, n, iterations, {lambda, reg, true, alpha, als_cg_entry_steps(cg_steps)});
 }
 
+int mf_als_run_nonneg(mf_ctx* ctx, int64_t half_sweeps, double lambda, int32_t reg) {
+  return als_run_entry(ctx, half_sweeps, {lambda, reg, false, 0.0, 0, true});
+}
+
+int mf_als_fit_nonneg(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n, int32_t iterations,
+                      double lambda, int32_t reg) {
+  return als_fit_entry(ctx, u, i, r, n, iterations, {lambda, reg, false, 0.0, 0, true});
+}
+
+int mf_als_run_implicit_nonneg(mf_ctx* ctx, int64_t half_sweeps, double lambda, int32_t reg, double alpha) {
+  return als_run_entry(ctx, half_sweeps, {lambda, reg, true, alpha, 0, true});
+}
+
+int mf_als_fit_implicit_nonneg(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n,
+                               int32_t iterations, double lambda, int32_t reg, double alpha) {
+  return als_fit_entry(ctx, u, i, r, n, iterations, {lambda, reg, true, alpha, 0, true});
+}
+
+int mf_als_nonneg_stats(mf_ctx* ctx, struct mf_als_nonneg_stats* out) {
+  return guarded([&] {
+    MF_REQUIRE(ctx && out, "null argument");
+    als_nonneg_stats(ctx, out);
+  });
+}
+
+int mf_nnls_solve(int32_t k, const double* A, const double* b, int f64, double* x_out, int32_t* iters_out,
+                  int32_t* reason_out) {
+  return guarded([&] { nnls_solve_host(k, A, b, f64 != 0, x_out, iters_out, reason_out); });
+}
+
 // (alpha < 0: the explicit system; any other alpha, NaN included, is the implicit one's and is checked as such)
+int mf_debug_als_nnls_row(mf_ctx* ctx, int side, int32_t id, double lambda, int32_t reg, double alpha, double* x_out,
+                          int32_t* iters_out, int32_t* reason_out) {
+  return guarded([&] {
+    MF_REQUIRE(ctx && x_out && iters_out && reason_out, "null argument");
+    MF_REQUIRE(side == MF_SIDE_USER || side == MF_SIDE_ITEM, "bad side");
+    als_nnls_row(ctx, side, id, {lambda, reg, !(alpha < 0.0), alpha, 0, true}, x_out, iters_out, reason_out);
+  });
+}
+
 int mf_debug_als_cg_matvec(mf_ctx* ctx, int side, int32_t id, double lambda, int32_t reg, double alpha, const double* v,
                            double* Av_out, double* b_out) {
   return guarded([&] {

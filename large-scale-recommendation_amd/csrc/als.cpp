@@ -1,5 +1,5 @@
-// als.cpp -- ALS training (mf_als_prepare / mf_als_run / mf_als_fit, their _implicit, _cg and
-// _implicit_cg variants) and its testing hooks.
+// als.cpp -- ALS training (mf_als_prepare / mf_als_run / mf_als_fit, their _implicit, _cg, _implicit_cg,
+// _nonneg and _implicit_nonneg variants) and its testing hooks.
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -178,6 +178,11 @@ void als_prepare(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* 
     als_build_side<float>(ctx, s, kSideU, ur, ir, r, n, ctx->U.rows(), chunk, batch);
     als_build_side<float>(ctx, s, MF_SIDE_ITEM, ir, ur, r, n, ctx->I.rows(), chunk, batch);
   }
+  {
+    DeviceGuard g(s.device);
+    s.als_nnls_stats.alloc(sizeof(struct mf_als_nonneg_stats));
+    MF_HIP(hipMemset(s.als_nnls_stats.get(), 0, sizeof(struct mf_als_nonneg_stats)));
+  }
   ctx->als_prepared = true;
   ctx->als_half_sweeps = 0;
 }
@@ -266,11 +271,12 @@ mf_ctx::AlsBatch als_row_span(const mf_ctx::AlsSide& A, int64_t row) {
   return {lo - A.items.begin(), hi - lo, sp - A.splits.begin(), sp != A.splits.end() && sp->row == row ? 1 : 0};
 }
 
-// One side solved from the other (P.implicit: after the counterpart's Gram matrix), by Cholesky or, with
-// P.cg_steps > 0, by conjugate gradients on the same work lists, batches and partial slots.
+// One side solved from the other (P.implicit: after the counterpart's Gram matrix), by Cholesky, with
+// P.nnls by the non-negative solve in its place or, with P.cg_steps > 0, by conjugate gradients on the
+// same work lists, batches and partial slots.
 // only_row >= 0 (the testing hooks): that row's work items alone, and s.als_dump takes the row's system
-// (Cholesky) or A v and b for the v in s.als_cg_v (conjugate gradients) instead of the row being solved;
-// false if the row has no rating.
+// (Cholesky), x with its iteration count and reason code (the non-negative solve) or A v and b for the v
+// in s.als_cg_v (conjugate gradients) instead of the row being solved; false if the row has no rating.
 bool als_half(mf_ctx* ctx, int side, const AlsParams& P, int64_t only_row = -1) {
   Shard& s = ctx->shards[0];
   DeviceGuard g(s.device);
@@ -305,6 +311,8 @@ bool als_half(mf_ctx* ctx, int side, const AlsParams& P, int64_t only_row = -1) 
     L.slabs = static_cast<int>(std::min<int64_t>(ctx->als_slabs, static_cast<int64_t>(A.items.size())));
     if (L.slabs > 0) s.als_slab.alloc(static_cast<size_t>(L.slabs) * als_gram_elems(k) * ctx->es);
     L.slab = s.als_slab.get();
+    L.nnls = P.nnls;
+    L.nnls_stats = s.als_nnls_stats.get();
   }
   auto gram = [&] {
     als_gram_launch(ctx, s, other);
@@ -329,7 +337,7 @@ bool als_half(mf_ctx* ctx, int side, const AlsParams& P, int64_t only_row = -1) 
       L.work = s.als_cg_hook_work.as<AlsCgWork>();
       L.n_work = static_cast<int>(row.items);
     }
-    s.als_dump.alloc(std::max<size_t>((static_cast<size_t>(k) * k + k) * ctx->es, 16));
+    s.als_dump.alloc(std::max<size_t>((static_cast<size_t>(k) * k + k + 2) * ctx->es, 16));
     L.dump = s.als_dump.get();
     L.hook_v = s.als_cg_v.get();
     if (P.implicit) gram();
@@ -368,7 +376,8 @@ void als_run(mf_ctx* ctx, int64_t half_sweeps, const AlsParams& P) {
   if (P.implicit) als_check_alpha(P.alpha);
   MF_REQUIRE(half_sweeps >= 0, "negative half-sweep count");
   als_check_run(P);
-  als_enter(ctx, std::string("mf_als_run") + (P.implicit ? "_implicit" : "") + (P.cg_steps ? "_cg" : ""));
+  als_enter(ctx, std::string("mf_als_run") + (P.implicit ? "_implicit" : "") + (P.cg_steps ? "_cg" : "") +
+                     (P.nnls ? "_nonneg" : ""));
   for (int64_t h = 0; h < half_sweeps; ++h) {
     // MLlib's order: the item side from the user factors first
     als_half(ctx, ctx->als_half_sweeps % 2 == 0 ? MF_SIDE_ITEM : kSideU, P);
@@ -405,6 +414,29 @@ void als_cg_matvec(mf_ctx* ctx, int side, int32_t id, const AlsParams& P, const 
   const std::vector<double> h = read_as_f64(ctx, s.als_dump, 2 * k);
   std::memcpy(Av_out, h.data(), k * 8);
   std::memcpy(b_out, h.data() + k, k * 8);
+}
+
+// One row through the non-negative half-sweep's own kernels (mf_debug_als_nnls_row): x, its iteration
+// count and its reason code.
+void als_nnls_row(mf_ctx* ctx, int side, int32_t id, const AlsParams& P, double* x_out, int32_t* iters_out,
+                  int32_t* reason_out) {
+  if (P.implicit) als_check_alpha(P.alpha);
+  als_check_run(P);
+  Shard& s = als_enter(ctx, "mf_debug_als_nnls_row");
+  als_hook_row(ctx, side, id, P);
+  DeviceGuard g(s.device);
+  const size_t k = static_cast<size_t>(ctx->P.num_factors);
+  const std::vector<double> h = read_as_f64(ctx, s.als_dump, k + 2);
+  std::memcpy(x_out, h.data(), k * 8);
+  *iters_out = static_cast<int32_t>(h[k]);
+  *reason_out = static_cast<int32_t>(h[k + 1]);
+}
+
+// The device counters of the non-negative half-sweeps since mf_als_prepare (mf_als_nonneg_stats).
+void als_nonneg_stats(mf_ctx* ctx, struct mf_als_nonneg_stats* out) {
+  Shard& s = als_enter(ctx, "mf_als_nonneg_stats");
+  DeviceGuard g(s.device);
+  MF_HIP(hipMemcpy(out, s.als_nnls_stats.get(), sizeof(struct mf_als_nonneg_stats), hipMemcpyDeviceToHost));
 }
 
 // G of one side's rated rows through the half-sweep's own launches (mf_debug_als_gram).

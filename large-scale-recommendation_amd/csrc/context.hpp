@@ -147,6 +147,8 @@ struct Shard {
   // ... the conjugate-gradient half-sweeps: per side the chunk items of its long rows, the state of one
   // launch's long rows, the testing hook's vector and chunk list
   DevBuf als_cg_work[2], als_cg_state, als_cg_v, als_cg_hook_work;
+  // ... the non-negative half-sweeps: the six 64-bit counters of mf_als_nonneg_stats (zeroed in mf_als_prepare)
+  DevBuf als_nnls_stats;
   // profiling
   std::vector<hipEvent_t> ev;
   size_t ev_used = 0;
@@ -402,6 +404,7 @@ struct AlsParams {
   bool implicit = false;  // the implicit-feedback system (mf_als_run_implicit), with confidence scale alpha
   double alpha = 0.0;
   int32_t cg_steps = 0;   // 0: Cholesky; 1 .. MF_ALS_CG_MAX_STEPS: that many conjugate-gradient steps
+  bool nnls = false;      // (with cg_steps == 0) the non-negative solve in the Cholesky solve's place
 };
 void als_check(const mf_ctx* ctx);
 void als_check_alpha(double alpha);
@@ -412,5 +415,11 @@ void als_normal_eq(mf_ctx* ctx, int side, int32_t id, const AlsParams& P, double
 void als_gram(mf_ctx* ctx, int side, double* G_out);
 void als_cg_matvec(mf_ctx* ctx, int side, int32_t id, const AlsParams& P, const double* v, double* Av_out,
                    double* b_out);
+void als_nnls_row(mf_ctx* ctx, int side, int32_t id, const AlsParams& P, double* x_out, int32_t* iters_out,
+                  int32_t* reason_out);
+void als_nonneg_stats(mf_ctx* ctx, struct mf_als_nonneg_stats* out);
+// nnls.cpp: mf_nnls_solve
+void nnls_solve_host(int32_t k, const double* A, const double* b, bool f64, double* x_out, int32_t* iters_out,
+                     int32_t* reason_out);
 
 }  // namespace mfhip

@@ -365,6 +365,12 @@ struct AlsLaunch {
   // rank the narrow kernels take).
   void* slab = nullptr;
   int slabs = 0;
+  // nnls (mf_als_run_nonneg, mf_als_run_implicit_nonneg): the same launches with the non-negative solve
+  // (als_nnls_device.hpp) in the Cholesky solve's place; nnls_stats are the six 64-bit device counters of
+  // mf_als_nonneg_stats.  With dump != null (the testing hook, one row) dump[0 .. k) = x, dump[k] = the
+  // iterations, dump[k + 1] = the reason code; X and the counters are not touched.
+  bool nnls = false;
+  void* nnls_stats = nullptr;
   // Conjugate gradients (kernels_als_cg.hip).  Whole rows (slot < 0) take `steps` CG steps from X[row]
   // in one launch; a row of at most als_cg_capacity(k, f64) ratings keeps its counterpart vectors in LDS
   // for all of them when `stage` is set, a longer one gathers them again in every pass (the same

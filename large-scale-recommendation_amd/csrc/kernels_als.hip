@@ -29,6 +29,11 @@
 // contiguous slice of the rated-row list through the same tiles and GramAcc and stores a KP x KP
 // partial; k_als_gram_reduce adds the partials in ascending slice order.
 //
+// The non-negative half-sweeps (mf_als_run_nonneg, mf_als_run_implicit_nonneg) are the same two kernels
+// with the template flag N set: the LDS matrix is symmetrised in place from its lower triangle and
+// nnls_row (als_nnls_device.hpp) takes the place of finish_row, its six vectors in LDS beside the matrix
+// (als_lds_bytes: at most 137 KiB, f64 at KP = 128).  The instances without N are untouched by it.
+//
 // These kernels take ranks 1..128 (rank buckets NB = 1..4).  Ranks 129..256, where the normal matrix no
 // longer fits in LDS, go to kernels_als_wide.hip: launch_als and launch_als_gram hand them on.
 #include <hip/hip_runtime.h>
@@ -37,6 +42,7 @@
 #include <string>
 
 #include "als_device.hpp"
+#include "als_nnls_device.hpp"
 #include "common.hpp"
 #include "kernels.hpp"
 
@@ -171,10 +177,23 @@ __device__ void finish_row(T* A, int ld, T* rhs, T* y, T* col, T* colraw, int k,
 }
 
 // LDS layout (elements of T): M[KP * (KP + 1)] (first the gather tile, then the normal matrix),
-// rhs[KP], y[KP], col[KP], colraw[KP], rv[kTile]
+// rhs[KP], y[KP], col[KP], colraw[KP], rv[kTile]; nnls: y, col and colraw are the first three of
+// nnls_row's six vectors, and rv follows the sixth.
 template <typename T>
-constexpr size_t als_lds_bytes(int kp) {
-  return (static_cast<size_t>(kp) * (kp + 1) + 4 * kp + kTile) * sizeof(T);
+constexpr size_t als_lds_bytes(int kp, bool nnls = false) {
+  return (static_cast<size_t>(kp) * (kp + 1) + (nnls ? 7 : 4) * kp + kTile) * sizeof(T);
+}
+
+// The row's system as finish_row takes it, solved for x >= 0: the upper triangle is filled from the lower
+// and nnls_row runs on the LDS matrix.  vec: 6 KP values in LDS.
+template <typename T, int NB>
+__device__ void finish_row_nnls(T* A, int ld, T* rhs, T* vec, int k, T* x_out, T* dump, unsigned long long* stats) {
+  const int tid = threadIdx.x;
+  for (int e = tid; e < k * k; e += kThreads) {
+    const int i = e / k, j = e % k;
+    if (j > i) A[i * ld + j] = A[j * ld + i];
+  }
+  nnls_row<T, kThreads>(A, ld, rhs, vec, 32 * NB, k, x_out, dump, stats);
 }
 
 
@@ -182,13 +201,14 @@ constexpr size_t als_lds_bytes(int kp) {
 // (rv) and right-hand-side coefficients 1 + w for r > 0, else 0 (cf, which borrows col: the
 // factorisation's scratch is idle while the tiles run); G is the counterpart's Gram matrix, KP x KP.  A
 // row with no positive rating has a zero right-hand side: its x is zero, and nothing is accumulated
-// for it.  The explicit instances ignore G and alpha.
-template <typename T, int NB, bool W>
+// for it.  The explicit instances ignore G and alpha.  N: the non-negative solve; nnls are its counters.
+template <typename T, int NB, bool W, bool N = false>
 __global__ __launch_bounds__(kThreads) void k_als(const AlsItem* __restrict__ items, const int32_t* __restrict__ cols,
                                                    const T* __restrict__ vals, const T* __restrict__ Q,
                                                    T* __restrict__ X, int k, T lambda, int weighted,
                                                    T* __restrict__ partial, T* __restrict__ dump,
-                                                   const T* __restrict__ G, T alpha) {
+                                                   const T* __restrict__ G, T alpha,
+                                                   unsigned long long* __restrict__ nnls) {
   constexpr int KP = 32 * NB;
   constexpr int LD = KP + 1;
   extern __shared__ __align__(16) unsigned char smem_raw[];
@@ -197,12 +217,15 @@ __global__ __launch_bounds__(kThreads) void k_als(const AlsItem* __restrict__ it
   T* y = rhs + KP;
   T* col = y + KP;
   T* colraw = col + KP;
-  T* rv = colraw + KP;
+  T* rv = colraw + KP + (N ? 3 * KP : 0);
   const AlsItem it = items[blockIdx.x];
   const int tid = threadIdx.x;
   if constexpr (W) {
     if (it.npos == 0 && !dump) {  // (a chunk of such a row stores no partial: k_als_reduce reads none)
       if (it.slot < 0 && tid < k) X[static_cast<size_t>(it.row) * k + tid] = T(0);
+      if constexpr (N) {
+        if (it.slot < 0 && tid == 0) nnls_count_zero_row(nnls);
+      }
       return;
     }
   }
@@ -257,15 +280,17 @@ __global__ __launch_bounds__(kThreads) void k_als(const AlsItem* __restrict__ it
   const T lam = weighted ? lambda * static_cast<T>(W ? it.npos : it.count) : lambda;
   if (tid < k) M[tid * LD + tid] += lam;
   __syncthreads();
-  finish_row<T, NB>(M, LD, rhs, y, col, colraw, k, X + static_cast<size_t>(it.row) * k, dump);
+  if constexpr (N) finish_row_nnls<T, NB>(M, LD, rhs, y, k, X + static_cast<size_t>(it.row) * k, dump, nnls);
+  else finish_row<T, NB>(M, LD, rhs, y, col, colraw, k, X + static_cast<size_t>(it.row) * k, dump);
 }
 
 // One workgroup per split row: partials [slot0, slot0 + chunks) added in ascending order.
 // W: plus G, once, after the partial sum; a row with no positive rating is set to zero.
-template <typename T, int NB, bool W>
+template <typename T, int NB, bool W, bool N = false>
 __global__ __launch_bounds__(kThreads) void k_als_reduce(const AlsSplit* __restrict__ rows, const T* __restrict__ partial,
                                                           T* __restrict__ X, int k, T lambda, int weighted,
-                                                          T* __restrict__ dump, const T* __restrict__ G) {
+                                                          T* __restrict__ dump, const T* __restrict__ G,
+                                                          unsigned long long* __restrict__ nnls) {
   constexpr int KP = 32 * NB;
   constexpr int LD = KP + 1;
   extern __shared__ __align__(16) unsigned char smem_raw[];
@@ -279,6 +304,9 @@ __global__ __launch_bounds__(kThreads) void k_als_reduce(const AlsSplit* __restr
   if constexpr (W) {
     if (sp.npos == 0 && !dump) {
       if (tid < k) X[static_cast<size_t>(sp.row) * k + tid] = T(0);
+      if constexpr (N) {
+        if (tid == 0) nnls_count_zero_row(nnls);
+      }
       return;
     }
   }
@@ -287,7 +315,8 @@ __global__ __launch_bounds__(kThreads) void k_als_reduce(const AlsSplit* __restr
   const T lam = weighted ? lambda * static_cast<T>(W ? sp.npos : sp.count) : lambda;
   if (tid < k) M[tid * LD + tid] += lam;
   __syncthreads();
-  finish_row<T, NB>(M, LD, rhs, y, col, colraw, k, X + static_cast<size_t>(sp.row) * k, dump);
+  if constexpr (N) finish_row_nnls<T, NB>(M, LD, rhs, y, k, X + static_cast<size_t>(sp.row) * k, dump, nnls);
+  else finish_row<T, NB>(M, LD, rhs, y, col, colraw, k, X + static_cast<size_t>(sp.row) * k, dump);
 }
 
 // G = sum over the rated rows of Y of y y^T.  Workgroup b takes rows [b * slice, (b + 1) * slice) of
@@ -331,12 +360,12 @@ __global__ __launch_bounds__(kThreads) void k_als_gram_reduce(const T* __restric
   G[e] = sum;
 }
 
-template <typename T, int NB, bool W>
+template <typename T, int NB, bool W, bool N>
 void launch_nb(const AlsLaunch& L) {
-  const size_t smem = als_lds_bytes<T>(32 * NB);
+  const size_t smem = als_lds_bytes<T>(32 * NB, N);
   if (smem > 64 * 1024)
-    for (const void* fn : {reinterpret_cast<const void*>(&k_als<T, NB, W>),
-                           reinterpret_cast<const void*>(&k_als_reduce<T, NB, W>)})
+    for (const void* fn : {reinterpret_cast<const void*>(&k_als<T, NB, W, N>),
+                           reinterpret_cast<const void*>(&k_als_reduce<T, NB, W, N>)})
       if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(smem)) != hipSuccess)
         fail(MF_ERR_HIP, "k_als: " + std::to_string(smem) + " bytes of LDS refused");
   T* X = static_cast<T*>(L.X);
@@ -345,13 +374,14 @@ void launch_nb(const AlsLaunch& L) {
   const T* G = static_cast<const T*>(L.gram);
   const T lambda = static_cast<T>(L.lambda);
   const int weighted = L.weighted ? 1 : 0;
+  unsigned long long* stats = static_cast<unsigned long long*>(L.nnls_stats);
   if (L.n_items > 0)
-    hipLaunchKernelGGL((k_als<T, NB, W>), dim3(static_cast<unsigned>(L.n_items)), dim3(kThreads), smem, L.st, L.items,
+    hipLaunchKernelGGL((k_als<T, NB, W, N>), dim3(static_cast<unsigned>(L.n_items)), dim3(kThreads), smem, L.st, L.items,
                        L.cols, static_cast<const T*>(L.vals), static_cast<const T*>(L.Q), X, L.k, lambda, weighted,
-                       partial, dump, G, static_cast<T>(L.alpha));
+                       partial, dump, G, static_cast<T>(L.alpha), stats);
   if (L.n_splits > 0)
-    hipLaunchKernelGGL((k_als_reduce<T, NB, W>), dim3(static_cast<unsigned>(L.n_splits)), dim3(kThreads), smem, L.st,
-                       L.splits, partial, X, L.k, lambda, weighted, dump, G);
+    hipLaunchKernelGGL((k_als_reduce<T, NB, W, N>), dim3(static_cast<unsigned>(L.n_splits)), dim3(kThreads), smem, L.st,
+                       L.splits, partial, X, L.k, lambda, weighted, dump, G, stats);
 }
 
 }  // namespace
@@ -371,9 +401,11 @@ size_t als_gram_elems(int k) {
 int als_gram_slices(int m, int slice) { return static_cast<int>((static_cast<int64_t>(m) + slice - 1) / slice); }
 
 void launch_als(const AlsLaunch& L) {
+  if (L.nnls && !L.nnls_stats) fail(MF_ERR_INVALID, "launch_als: the non-negative solve needs its counters");
   if (L.k > 128) return launch_als_wide(L);  // kernels_als_wide.hip
   als_dispatch<1>(L.f64, L.gram != nullptr, L.k, [&](auto t, auto w, auto nb) {
-    launch_nb<decltype(t), decltype(nb)::value, decltype(w)::value>(L);
+    if (L.nnls) launch_nb<decltype(t), decltype(nb)::value, decltype(w)::value, true>(L);
+    else launch_nb<decltype(t), decltype(nb)::value, decltype(w)::value, false>(L);
   });
 }
 

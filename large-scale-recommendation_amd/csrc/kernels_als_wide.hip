@@ -21,6 +21,9 @@
 //    instances of the routine in k_als_wide and k_als_reduce_wide round alike.
 // Chunks of long rows store partials exactly as the narrow path does; k_als_reduce_wide adds them
 // in ascending chunk order into the slab and runs the same finish_wide.
+// The template flag N (the non-negative half-sweeps) fills the slab's upper triangle from the lower and
+// runs nnls_row (als_nnls_device.hpp) over it instead of finish_wide; its six vectors take the stage
+// panel's place in LDS, so the LDS request is the same.  The instances without N are untouched by it.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -28,6 +31,7 @@
 #include <string>
 
 #include "als_device.hpp"
+#include "als_nnls_device.hpp"
 #include "common.hpp"
 #include "kernels.hpp"
 
@@ -186,6 +190,20 @@ __device__ __forceinline__ void finish_wide(T* S, T* P, T* stage, T* rhs, T* y, 
   if (tid < k) x_out[tid] = bad ? std::numeric_limits<T>::quiet_NaN() : rhs[tid];
 }
 
+// The row's system as finish_wide takes it, solved for x >= 0 by nnls_row over the slab.
+template <typename T, int NB>
+__device__ __forceinline__ void finish_wide_nnls(T* S, T* vec, T* rhs, int k, T* x_out, T* dump,
+                                                 unsigned long long* stats) {
+  constexpr int KP = 32 * NB;
+  static_assert(6 * KP <= KP * kPLd, "nnls_row's vectors fit in the stage panel");
+  const int tid = threadIdx.x;
+  for (int e = tid; e < k * k; e += kWThreads) {
+    const int i = e / k, j = e % k;
+    if (j > i) S[i * KP + j] = S[j * KP + i];
+  }
+  nnls_row<T, kWThreads>(S, KP, rhs, vec, KP, k, x_out, dump, stats);
+}
+
 // LDS layout (elements of T): P[KP * 33] (first the gather tile, then the backward solve's panel),
 // stage[KP * 33], rhs[KP], y[KP], col[KP], colraw[KP], rv[kTile], cf[kTile]
 template <typename T>
@@ -209,12 +227,13 @@ struct WideLds {
 };
 
 // The work items blockIdx.x, blockIdx.x + gridDim.x, ... of the launch; W, G and alpha as in kernels_als.hip.
-template <typename T, int NB, bool W>
+template <typename T, int NB, bool W, bool N = false>
 __global__ __launch_bounds__(kWThreads) void k_als_wide(const AlsItem* __restrict__ items, int n_items,
                                                          const int32_t* __restrict__ cols, const T* __restrict__ vals,
                                                          const T* __restrict__ Q, T* __restrict__ X, int k, T lambda,
                                                          int weighted, T* __restrict__ partial, T* __restrict__ dump,
-                                                         const T* __restrict__ G, T alpha, T* __restrict__ slab) {
+                                                         const T* __restrict__ G, T alpha, T* __restrict__ slab,
+                                                         unsigned long long* __restrict__ nnls) {
   constexpr int KP = 32 * NB;
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const WideLds<T, KP> L(smem_raw);
@@ -229,6 +248,9 @@ __global__ __launch_bounds__(kWThreads) void k_als_wide(const AlsItem* __restric
     if constexpr (W) {
       if (it.npos == 0 && !dump) {  // (a chunk of such a row stores no partial: the reduce reads none)
         if (it.slot < 0 && tid < k) X[static_cast<size_t>(it.row) * k + tid] = T(0);
+        if constexpr (N) {
+          if (it.slot < 0 && tid == 0) nnls_count_zero_row(nnls);
+        }
         continue;
       }
     }
@@ -295,18 +317,20 @@ __global__ __launch_bounds__(kWThreads) void k_als_wide(const AlsItem* __restric
     const T lam = weighted ? lambda * static_cast<T>(W ? it.npos : it.count) : lambda;
     if (tid < k) S[tid * KP + tid] += lam;
     __syncthreads();
-    finish_wide<T, NB>(S, L.P, L.stage, L.rhs, L.y, L.col, L.colraw, k, X + static_cast<size_t>(it.row) * k, dump);
+    if constexpr (N) finish_wide_nnls<T, NB>(S, L.stage, L.rhs, k, X + static_cast<size_t>(it.row) * k, dump, nnls);
+    else finish_wide<T, NB>(S, L.P, L.stage, L.rhs, L.y, L.col, L.colraw, k, X + static_cast<size_t>(it.row) * k, dump);
   }
 }
 
 // The split rows blockIdx.x, blockIdx.x + gridDim.x, ...: partials [slot0, slot0 + chunks) added in
 // ascending order into the slab.  W: plus G, once, after the partial sum; a row with no positive
 // rating is set to zero.
-template <typename T, int NB, bool W>
+template <typename T, int NB, bool W, bool N = false>
 __global__ __launch_bounds__(kWThreads) void k_als_reduce_wide(const AlsSplit* __restrict__ rows, int n_rows,
                                                                 const T* __restrict__ partial, T* __restrict__ X, int k,
                                                                 T lambda, int weighted, T* __restrict__ dump,
-                                                                const T* __restrict__ G, T* __restrict__ slab) {
+                                                                const T* __restrict__ G, T* __restrict__ slab,
+                                                                unsigned long long* __restrict__ nnls) {
   constexpr int KP = 32 * NB;
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const WideLds<T, KP> L(smem_raw);
@@ -318,6 +342,9 @@ __global__ __launch_bounds__(kWThreads) void k_als_reduce_wide(const AlsSplit* _
     if constexpr (W) {
       if (sp.npos == 0 && !dump) {
         if (tid < k) X[static_cast<size_t>(sp.row) * k + tid] = T(0);
+        if constexpr (N) {
+          if (tid == 0) nnls_count_zero_row(nnls);
+        }
         continue;
       }
     }
@@ -326,7 +353,8 @@ __global__ __launch_bounds__(kWThreads) void k_als_reduce_wide(const AlsSplit* _
     const T lam = weighted ? lambda * static_cast<T>(W ? sp.npos : sp.count) : lambda;
     if (tid < k) S[tid * KP + tid] += lam;
     __syncthreads();
-    finish_wide<T, NB>(S, L.P, L.stage, L.rhs, L.y, L.col, L.colraw, k, X + static_cast<size_t>(sp.row) * k, dump);
+    if constexpr (N) finish_wide_nnls<T, NB>(S, L.stage, L.rhs, k, X + static_cast<size_t>(sp.row) * k, dump, nnls);
+    else finish_wide<T, NB>(S, L.P, L.stage, L.rhs, L.y, L.col, L.colraw, k, X + static_cast<size_t>(sp.row) * k, dump);
   }
 }
 
@@ -382,12 +410,18 @@ void launch_als_wide(const AlsLaunch& L) {
     constexpr int NB = decltype(nb)::value;
     constexpr bool W = decltype(w)::value;
     const size_t smem = wide_lds_bytes<T>(32 * NB);
-    if (L.n_items > 0)
-      launch_wide_kernel(&k_als_wide<T, NB, W>, std::min(L.n_items, L.slabs), smem, L.st, L.items, L.n_items, L.cols,
-                         L.vals, L.Q, L.X, L.k, L.lambda, L.weighted, L.partial, L.dump, L.gram, L.alpha, L.slab);
-    if (L.n_splits > 0)
-      launch_wide_kernel(&k_als_reduce_wide<T, NB, W>, std::min(L.n_splits, L.slabs), smem, L.st, L.splits, L.n_splits,
-                         L.partial, L.X, L.k, L.lambda, L.weighted, L.dump, L.gram, L.slab);
+    unsigned long long* stats = static_cast<unsigned long long*>(L.nnls_stats);
+    auto run = [&](auto n) {
+      constexpr bool N = decltype(n)::value;
+      if (L.n_items > 0)
+        launch_wide_kernel(&k_als_wide<T, NB, W, N>, std::min(L.n_items, L.slabs), smem, L.st, L.items, L.n_items,
+                           L.cols, L.vals, L.Q, L.X, L.k, L.lambda, L.weighted, L.partial, L.dump, L.gram, L.alpha,
+                           L.slab, stats);
+      if (L.n_splits > 0)
+        launch_wide_kernel(&k_als_reduce_wide<T, NB, W, N>, std::min(L.n_splits, L.slabs), smem, L.st, L.splits,
+                           L.n_splits, L.partial, L.X, L.k, L.lambda, L.weighted, L.dump, L.gram, L.slab, stats);
+    };
+    L.nnls ? run(std::true_type()) : run(std::false_type());
   });
 }
 

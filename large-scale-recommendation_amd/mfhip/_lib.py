@@ -128,6 +128,10 @@ class mf_prequential(C.Structure):
     ]
 
 
+class mf_als_nonneg_stats(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("rows", "iterations", "max_iterations", "capped", "reason2", "nan_rows")]
+
+
 # Every symbol include/mfhip.h declares (tests check the library exports all of them).
 EXPORTS = [
     "mf_params_init", "mf_last_error", "mf_version", "mf_device_count", "mf_create",
@@ -141,6 +145,8 @@ EXPORTS = [
     "mf_als_run", "mf_als_run_implicit", "mf_als_fit_implicit", "mf_rank_eval", "mf_pair_ranks",
     "mf_online_prequential", "mf_online_update_sampled", "mf_negative_draws", "mf_online_prequential_sampled",
     "mf_als_run_cg", "mf_als_run_implicit_cg", "mf_als_fit_cg", "mf_als_fit_implicit_cg",
+    "mf_als_run_nonneg", "mf_als_run_implicit_nonneg", "mf_als_fit_nonneg", "mf_als_fit_implicit_nonneg",
+    "mf_als_nonneg_stats", "mf_nnls_solve",
 ]
 # The test hooks include/mfhip_testing.h declares (not product surface; same library).
 TESTING_EXPORTS = [
@@ -148,7 +154,7 @@ TESTING_EXPORTS = [
     "mf_debug_plan_digest", "mf_fast_plan_window", "mf_fast_kernel_name", "mf_debug_build_flags",
     "mf_debug_device_bytes", "mf_debug_als_normal_eq", "mf_debug_als_gram", "mf_debug_als_normal_eq_implicit",
     "mf_debug_det_slot_table", "mf_debug_sys_placement", "mf_debug_rank_csr", "mf_debug_als_cg_matvec",
-    "mf_debug_als_cg_capacity",
+    "mf_debug_als_cg_capacity", "mf_debug_als_nnls_row",
 ]
 
 _i32p = C.POINTER(C.c_int32)
@@ -252,6 +258,15 @@ def lib() -> C.CDLL:
         "mf_debug_als_cg_matvec": (C.c_int, [_ctxp, C.c_int, C.c_int32, C.c_double, C.c_int32, C.c_double, _f64p,
                                              _f64p, _f64p]),
         "mf_debug_als_cg_capacity": (C.c_int, [_ctxp, _i32p]),
+        "mf_als_run_nonneg": (C.c_int, [_ctxp, C.c_int64, C.c_double, C.c_int32]),
+        "mf_als_run_implicit_nonneg": (C.c_int, [_ctxp, C.c_int64, C.c_double, C.c_int32, C.c_double]),
+        "mf_als_fit_nonneg": (C.c_int, [_ctxp, _i32p, _i32p, _f64p, C.c_int64, C.c_int32, C.c_double, C.c_int32]),
+        "mf_als_fit_implicit_nonneg": (C.c_int, [_ctxp, _i32p, _i32p, _f64p, C.c_int64, C.c_int32, C.c_double,
+                                                 C.c_int32, C.c_double]),
+        "mf_als_nonneg_stats": (C.c_int, [_ctxp, C.POINTER(mf_als_nonneg_stats)]),
+        "mf_nnls_solve": (C.c_int, [C.c_int32, _f64p, _f64p, C.c_int, _f64p, _i32p, _i32p]),
+        "mf_debug_als_nnls_row": (C.c_int, [_ctxp, C.c_int, C.c_int32, C.c_double, C.c_int32, C.c_double, _f64p,
+                                            _i32p, _i32p]),
         "mf_debug_ring_schedule": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, _i32p, _i32p, _i32p, _i32p]),
         "mf_debug_det_slot_table": (C.c_int, [_i64p, _i32p, _i32p, C.c_int64, C.c_int64, C.c_int32, C.c_int64, _i64p,
                                               _i32p, _i32p, _i64p]),

@@ -15,6 +15,10 @@ factorisation.  ALS.train / ALS.trainImplicit themselves keep the Cholesky solve
 
     model = ALS.withSolver("cg", cg_steps=3).train(ratings, rank=128)
 
+ALS.withSolver("nnls") is MLlib's nonnegative = true: every row is solved for x >= 0 by a projected
+conjugate-gradient NNLS on the device (mf_als_fit_nonneg / mf_als_fit_implicit_nonneg); cg_steps is
+ignored for it.
+
 Weighted-lambda regularisation (ALS-WR), as ALS.train uses.  The initial factors are this library's
 (k x nextDouble of new Random(id ^ seed)), not MLlib's partition-dependent XORShift draws.
 """
@@ -119,7 +123,8 @@ class ALS:
 
     @staticmethod
     def withSolver(solver: str = "cholesky", cg_steps: int = 3) -> "_SolverALS":
-        """train / trainImplicit on the named solver: "cholesky" (ALS.train's own) or "cg"."""
+        """train / trainImplicit on the named solver: "cholesky" (ALS.train's own), "cg" or "nnls"
+        (non-negative factors; cg_steps is ignored for it)."""
         return _SolverALS(solver, cg_steps)
 
     @staticmethod
@@ -132,7 +137,7 @@ class ALS:
         return Context(p)
 
 
-SOLVERS = ("cholesky", "cg")
+SOLVERS = ("cholesky", "cg", "nnls")
 
 
 class _SolverALS:
@@ -153,7 +158,10 @@ class _SolverALS:
         u, i, r = _columns(ratings)
         ctx = ALS._context(rank, mode, seed)
         try:
-            ctx.als_fit_cg(u, i, r, int(iterations), float(lambda_), L.ALS_REG_WEIGHTED, self.cg_steps)
+            if self.solver == "nnls":
+                ctx.als_fit_nonneg(u, i, r, int(iterations), float(lambda_), L.ALS_REG_WEIGHTED)
+            else:
+                ctx.als_fit_cg(u, i, r, int(iterations), float(lambda_), L.ALS_REG_WEIGHTED, self.cg_steps)
         except Exception:
             ctx.close()
             raise
@@ -166,8 +174,12 @@ class _SolverALS:
         u, i, r = _columns(ratings)
         ctx = ALS._context(rank, mode, seed)
         try:
-            ctx.als_fit_implicit_cg(u, i, r, int(iterations), float(lambda_), float(alpha), L.ALS_REG_WEIGHTED,
-                                    self.cg_steps)
+            if self.solver == "nnls":
+                ctx.als_fit_implicit_nonneg(u, i, r, int(iterations), float(lambda_), float(alpha),
+                                            L.ALS_REG_WEIGHTED)
+            else:
+                ctx.als_fit_implicit_cg(u, i, r, int(iterations), float(lambda_), float(alpha), L.ALS_REG_WEIGHTED,
+                                        self.cg_steps)
         except Exception:
             ctx.close()
             raise

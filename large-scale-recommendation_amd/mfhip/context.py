@@ -11,6 +11,21 @@ from . import _lib as L
 from ._lib import as_f64, as_i32, check, ptr, same_length
 
 
+def nnls_solve(A, b, f64: bool = True):
+    """mf_nnls_solve: (x [k], iterations, reason) of the non-negative ALS solve on the host, in the kernels'
+    order of operations and in f32 or f64 arithmetic.  A is k x k symmetric.  No GPU needed."""
+    A = np.ascontiguousarray(A, np.float64)
+    b = np.ascontiguousarray(b, np.float64)
+    k = b.shape[0]
+    if b.ndim != 1 or A.shape != (k, k):
+        raise ValueError("A must be k x k and b must hold k values")
+    x = np.empty(k, np.float64)
+    it, why = C.c_int32(0), C.c_int32(0)
+    check(L.lib().mf_nnls_solve(k, ptr(A, C.c_double), ptr(b, C.c_double), 1 if f64 else 0, ptr(x, C.c_double),
+                                C.byref(it), C.byref(why)))
+    return x, int(it.value), int(why.value)
+
+
 @dataclass
 class RankMetrics:
     """What mf_rank_eval returns (include/mfhip.h): counts, the six means over `queries`, and with
@@ -224,6 +239,52 @@ class Context:
         n = C.c_int32(0)
         check(L.lib().mf_debug_als_cg_capacity(self._h, C.byref(n)))
         return int(n.value)
+
+    def als_run_nonneg(self, half_sweeps: int, lam: float, reg: int = L.ALS_REG_WEIGHTED) -> None:
+        """mf_als_run_nonneg: als_run's half-sweeps with every row solved for x >= 0 (projected
+        conjugate-gradient NNLS); the counter is als_run's."""
+        check(L.lib().mf_als_run_nonneg(self._h, int(half_sweeps), float(lam), int(reg)))
+
+    def als_run_implicit_nonneg(self, half_sweeps: int, lam: float, alpha: float,
+                                reg: int = L.ALS_REG_WEIGHTED) -> None:
+        """mf_als_run_implicit_nonneg: als_run_implicit's half-sweeps with the non-negative solve."""
+        check(L.lib().mf_als_run_implicit_nonneg(self._h, int(half_sweeps), float(lam), int(reg), float(alpha)))
+
+    def als_fit_nonneg(self, u, i, r, iterations: int, lam: float, reg: int = L.ALS_REG_WEIGHTED) -> None:
+        """mf_als_fit_nonneg: als_prepare + als_run_nonneg(2 * iterations)."""
+        u, i, r = as_i32(u), as_i32(i), as_f64(r)
+        same_length(u, i, r)
+        check(L.lib().mf_als_fit_nonneg(self._h, ptr(u, C.c_int32), ptr(i, C.c_int32), ptr(r, C.c_double), len(u),
+                                        int(iterations), float(lam), int(reg)))
+
+    def als_fit_implicit_nonneg(self, u, i, r, iterations: int, lam: float, alpha: float,
+                                reg: int = L.ALS_REG_WEIGHTED) -> None:
+        """mf_als_fit_implicit_nonneg: als_prepare + als_run_implicit_nonneg(2 * iterations)."""
+        u, i, r = as_i32(u), as_i32(i), as_f64(r)
+        same_length(u, i, r)
+        check(L.lib().mf_als_fit_implicit_nonneg(self._h, ptr(u, C.c_int32), ptr(i, C.c_int32), ptr(r, C.c_double),
+                                                 len(u), int(iterations), float(lam), int(reg), float(alpha)))
+
+    def als_nnls_row(self, side: int, id_: int, lam: float, alpha: float = -1.0, reg: int = L.ALS_REG_WEIGHTED):
+        """(x [k], iterations, reason) of one row through the non-negative half-sweep's kernels
+        (mf_debug_als_nnls_row); alpha < 0: the explicit system.  The model is not changed."""
+        x = np.empty(self.k, np.float64)
+        it, why = C.c_int32(0), C.c_int32(0)
+        check(L.lib().mf_debug_als_nnls_row(self._h, int(side), int(id_), float(lam), int(reg), float(alpha),
+                                            ptr(x, C.c_double), C.byref(it), C.byref(why)))
+        return x, int(it.value), int(why.value)
+
+    def als_nonneg_stats(self) -> dict:
+        """mf_als_nonneg_stats: what the non-negative half-sweeps did since als_prepare."""
+        st = L.mf_als_nonneg_stats()
+        check(L.lib().mf_als_nonneg_stats(self._h, C.byref(st)))
+        return {n: int(getattr(st, n)) for n, _ in st._fields_}
+
+    @staticmethod
+    def nnls_solve(A, b, f64: bool = True):
+        """mf_nnls_solve: (x [k], iterations, reason) of the non-negative solve on the host, in the kernels'
+        order and in f32 or f64 arithmetic.  No GPU needed."""
+        return nnls_solve(A, b, f64)
 
     # -- factors ---------------------------------------------------------------
     def num_factors(self, side: int) -> int:

@@ -31,6 +31,12 @@ reported); both then run on to 10 iterations and report the training RMSE (first
 --implicit the same for the implicit calls on the shifted ratings, with --det also in deterministic mode.
 The result goes under the key "cg" (of "k<K>" at another rank), beside what the file holds.
 
+--solver nnls compares the non-negative half-sweeps (mf_als_run_nonneg / mf_als_run_implicit_nonneg) with
+mf_als_run / mf_als_run_implicit in the same way (--implicit and --det as above; --total-iters is the
+iteration count both run on to).  Beside the times it prints the mf_als_nonneg_stats struct (mean and
+longest solve in iterations per row, rows at the cap, reason-2 and NaN rows), the share of zero entries in
+the fitted factors and both training RMSEs.  The result goes under the key "nnls".
+
 Writes profiles/als_bench.json.  At the default rank this run's fields replace the file's own and every
 other key of the file stays; at another rank the same fields go under the key "k<K>", beside what it
 holds.
@@ -127,8 +133,9 @@ def als_run(train, k, iters, lam, chunk, alpha=None, det=False):
     return res
 
 
-def cg_compare(train, k, rounds, lam, steps, alpha=None, det=False, total_iters=10):
-    """mf_als_run against mf_als_run_cg(steps), alternating in one process; alpha None: explicit."""
+def cg_compare(train, k, rounds, lam, steps, alpha=None, det=False, total_iters=10, solver="cg"):
+    """mf_als_run against mf_als_run_cg(steps) -- solver "nnls": against mf_als_run_nonneg --, alternating in
+    one process; alpha None: explicit."""
     from mfhip import _lib as L
     from mfhip.context import Context
 
@@ -137,25 +144,32 @@ def cg_compare(train, k, rounds, lam, steps, alpha=None, det=False, total_iters=
     p = L.default_params()
     p.num_factors = k
     p.mode = L.MODE_DETERMINISTIC_F64 if det else L.MODE_FAST_F32
-    res = {"k": k, "cg_steps": steps, "lambda": lam, "rounds": rounds, "deterministic": det, "nnz": len(u)}
+    nnls = solver == "nnls"
+    res = {"k": k, "lambda": lam, "rounds": rounds, "deterministic": det, "nnz": len(u)}
+    if not nnls:
+        res["cg_steps"] = steps
     if alpha is not None:
         res["alpha"] = alpha
     with Context(p) as chol, Context(p) as cg:
-        cap = cg.als_cg_capacity()
-        res["staged_capacity"] = cap
-        res["staged_share_of_rows"] = {
-            side: float((c[c > 0] <= cap).mean()) for side, c in (("item", np.bincount(i)), ("user", np.bincount(u)))}
+        if not nnls:
+            cap = cg.als_cg_capacity()
+            res["staged_capacity"] = cap
+            res["staged_share_of_rows"] = {
+                side: float((c[c > 0] <= cap).mean())
+                for side, c in (("item", np.bincount(i)), ("user", np.bincount(u)))}
         for ctx in (chol, cg):
             ctx.als_prepare(u, i, r)
 
         def run(ctx, n):
             if ctx is chol:
                 ctx.als_run(n, lam) if alpha is None else ctx.als_run_implicit(n, lam, alpha)
+            elif nnls:
+                ctx.als_run_nonneg(n, lam) if alpha is None else ctx.als_run_implicit_nonneg(n, lam, alpha)
             else:
                 ctx.als_run_cg(n, lam, cg_steps=steps) if alpha is None else \
                     ctx.als_run_implicit_cg(n, lam, alpha, cg_steps=steps)
 
-        names = {id(chol): "cholesky", id(cg): "cg"}
+        names = {id(chol): "cholesky", id(cg): solver}
         half = {n: {"item": [], "user": []} for n in names.values()}
         for ctx in (chol, cg):
             run(ctx, 2)  # warm-up
@@ -171,12 +185,26 @@ def cg_compare(train, k, rounds, lam, steps, alpha=None, det=False, total_iters=
             run(ctx, 2 * max(0, total_iters - 1 - rounds))
             res.setdefault("train_rmse_sample_after_%d" % max(total_iters, 1 + rounds), {})[names[id(ctx)]] = \
                 ctx.rmse(u[:2_000_000], i[:2_000_000], r[:2_000_000])[0]
+        if nnls:
+            st = cg.als_nonneg_stats()
+            res["nonneg_stats"] = st
+            res["mean_iterations_per_row"] = st["iterations"] / max(st["rows"], 1)
+            res["zero_share"] = {side: float((cg.factors(sd)[1] == 0).mean())
+                                 for side, sd in (("user", L.SIDE_USER), ("item", L.SIDE_ITEM))}
     res["half_sweep_ms"] = {n: {s: {"median": float(np.median(v)), "all": v} for s, v in half[n].items()} for n in half}
     it = {n: sum(res["half_sweep_ms"][n][s]["median"] for s in ("item", "user")) for n in half}
     res["iteration_ms_device"] = it
-    res["cg_speedup"] = it["cholesky"] / it["cg"]
+    res["cg_speedup" if not nnls else "nnls_speedup"] = it["cholesky"] / it[solver]
     kind = ("explicit" if alpha is None else f"implicit (alpha {alpha})") + (" deterministic" if det else " fast")
     h = res["half_sweep_ms"]
+    if nnls:
+        st = res["nonneg_stats"]
+        print(f"k {k} {kind}: Cholesky {it['cholesky']:.1f} ms / iteration (item {h['cholesky']['item']['median']:.1f}, "
+              f"user {h['cholesky']['user']['median']:.1f}), NNLS {it['nnls']:.1f} ms (item "
+              f"{h['nnls']['item']['median']:.1f}, user {h['nnls']['user']['median']:.1f}): x{res['nnls_speedup']:.3f}; "
+              f"stats {st}; mean {res['mean_iterations_per_row']:.1f} iterations per row; zero share "
+              f"{res['zero_share']}; rmse {[v for k_, v in res.items() if k_.startswith('train_rmse')][0]}", flush=True)
+        return res
     print(f"k {k} {kind}: Cholesky {it['cholesky']:.1f} ms / iteration (item {h['cholesky']['item']['median']:.1f}, user "
           f"{h['cholesky']['user']['median']:.1f}), CG S={steps} {it['cg']:.1f} ms (item {h['cg']['item']['median']:.1f}, "
           f"user {h['cg']['user']['median']:.1f}): x{res['cg_speedup']:.2f}; staged rows {res['staged_share_of_rows']}; "
@@ -218,8 +246,11 @@ def main():
     ap.add_argument("--alpha", type=float, default=1.0, help="the implicit runs' alpha")
     ap.add_argument("--k", type=int, default=128, help="the rank (default 128)")
     ap.add_argument("--det", action="store_true", help="also time one deterministic-mode iteration")
-    ap.add_argument("--solver", choices=("cholesky", "cg"), default="cholesky",
-                    help="cg: compare mf_als_run_cg with mf_als_run instead of the timings above")
+    ap.add_argument("--solver", choices=("cholesky", "cg", "nnls"), default="cholesky",
+                    help="cg / nnls: compare mf_als_run_cg / mf_als_run_nonneg with mf_als_run instead of the "
+                         "timings above")
+    ap.add_argument("--total-iters", type=int, default=10,
+                    help="iterations both solvers of a comparison run on to before the RMSE is taken")
     ap.add_argument("--cg-steps", type=int, default=3, help="CG steps per row (with --solver cg)")
     ap.add_argument("--scale", type=float, default=1.0, help="shrink the synthetic (rehearsal only)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "als_bench.json"))
@@ -234,19 +265,22 @@ def main():
     nu, ni, nr, k0, nb = synth.CONFIGS["NFLX"]
     k = a.k
     train, _ = synth.generate(max(1, int(nu * a.scale)), max(1, int(ni * a.scale)), max(1, int(nr * a.scale))).split()
-    if a.solver == "cg":
-        out = {"scale": a.scale, "runs": [cg_compare(train, k, a.iters, a.lam, a.cg_steps)]}
+    if a.solver != "cholesky":
+        kw = {"total_iters": a.total_iters, "solver": a.solver}
+        out = {"scale": a.scale, "runs": [cg_compare(train, k, a.iters, a.lam, a.cg_steps, **kw)]}
         if a.implicit:
             u, i, r = train
             shifted = (u, i, np.asarray(r, np.float64) - 3.0)
-            out["runs"].append(cg_compare(shifted, k, a.iters, a.lam, a.cg_steps, a.alpha))
+            out["runs"].append(cg_compare(shifted, k, a.iters, a.lam, a.cg_steps, a.alpha, **kw))
         if a.det:
-            out["runs"].append(cg_compare(train, k, a.iters, a.lam, a.cg_steps, det=True))
+            out["runs"].append(cg_compare(train, k, a.iters, a.lam, a.cg_steps, det=True, **kw))
+            if a.implicit and a.solver == "nnls":
+                out["runs"].append(cg_compare(shifted, k, a.iters, a.lam, a.cg_steps, a.alpha, det=True, **kw))
         old = {}
         if os.path.exists(a.out):
             with open(a.out) as f:
                 old = json.load(f)
-        (old if k == k0 else old.setdefault(f"k{k}", {}))["cg"] = out
+        (old if k == k0 else old.setdefault(f"k{k}", {}))[a.solver] = out
         os.makedirs(os.path.dirname(a.out), exist_ok=True)
         with open(a.out, "w") as f:
             json.dump(old, f, indent=1)
