@@ -509,6 +509,68 @@ int mf_als_nonneg_stats(mf_ctx* ctx, struct mf_als_nonneg_stats* out);
 int mf_nnls_solve(int32_t k, const double* A /* k*k symmetric */, const double* b, int f64, double* x_out,
                   int32_t* iters_out, int32_t* reason_out);
 
+/* Incremental ALS, the ALS side of "combination of online and offline MF" (sp/OnlineSpark.scala:26-162 with
+   offlineAlgorithm = "ALS"): new ratings join the CSRs mf_als_prepare left on the device, and only the rows
+   they touch are solved again.  Nothing is uploaded but the batch.
+   mf_als_solve names one of the eight kinds of half-sweep: {lambda, reg} as in mf_als_run; implicit != 0 with
+   alpha as in mf_als_run_implicit (alpha is read only then); solver = MF_ALS_SOLVER_CHOLESKY, _CG (cg_steps as
+   in mf_als_run_cg, read only then) or _NNLS (mf_als_run_nonneg).  Set reserved to 0.
+
+   mf_als_append.  Afterwards the prepared data is exactly what mf_als_prepare would have built from the
+   earlier arrays followed by these n ratings: per row, on each side, the old ratings in their old order, then
+   the new ones in the order of the caller's arrays, duplicate pairs kept.  Ids the model does not hold get
+   rows and initial values under mf_als_prepare's rules in every respect (first-touch order, the user looked
+   at before the item within one rating; k x nextDouble of new Random(id ^ seed); the same effect on a
+   prepared fast DSGD schedule).  Rows the model gained since the last prepare or append through any other
+   call (mf_online_update, mf_set_factors) have no ratings until some are appended.  The per-row count and
+   the per-row n+ are those of the whole row; n+ counts the ratings > 0 after rounding to the context's
+   precision.  The long-row chunks, the launches and the rated-row list that G is summed over are rebuilt as
+   mf_als_prepare builds them, with the chunk, batch, Gram-slice and slab values that prepare read.  The
+   half-sweep counter and mf_als_nonneg_stats are not reset.  n == 0 is a valid no-op.
+   Both CSRs are repacked on the device into fresh arrays (integer moves only, each old entry read once and
+   written once; the batch alone is sorted), so a call needs room for a second copy of the larger CSR.
+   Errors, all raised before anything changes.  MF_ERR_STATE: before mf_als_prepare, or after a later
+   mf_dsgd_prepare / mf_dsgd_fit (a prepare with n = 0 is the valid empty start).  MF_ERR_INVALID: n < 0,
+   n >= 2^31, a NULL array with n > 0, or a row that would pass 2^31 - 1 ratings.  Otherwise mf_als_prepare's.
+
+   mf_als_run_rows solves the rows of `side` named by ids[0 .. n_ids), each exactly as a full half-sweep of
+   that side with the same `how` would solve it now: the system, the order of every sum, the chunks, G over
+   the counterpart's rated rows, lambda' and n+, the NaN rules and the NNLS reason codes.  Every solved row
+   reads the counterpart's factors as they stand on entry; every other row keeps its bits.  Ids the model
+   does not hold and ids with no rating in the prepared data are skipped; duplicates are solved once;
+   *solved_out (may be NULL) is the number of rows solved.  Results do not depend on the order of ids[].
+   The half-sweep counter does not move.  NNLS rows count in mf_als_nonneg_stats as a half-sweep's do.
+   Errors.  What the mf_als_run* call of the same `how` raises (lambda <= 0, a bad reg, alpha < 0 or not
+   finite when implicit, cg_steps outside 1 .. MF_ALS_CG_MAX_STEPS for MF_ALS_SOLVER_CG, a rank above 256,
+   the state errors), and MF_ERR_INVALID for a bad side, an unknown solver, a NULL `how`, n_ids < 0, or NULL
+   ids with n_ids > 0.
+
+   mf_als_update is, by definition: every argument checked, then mf_als_append(users, items, ratings, n), then
+   `rounds` times { mf_als_run_rows(MF_SIDE_USER, the batch's users), mf_als_run_rows(MF_SIDE_ITEM, the
+   batch's items) }.  Users go first -- on purpose not MLlib's item-first order of a full sweep: a new user's
+   row is random until it is solved, and items solved from it first would be pulled towards noise.
+   rounds == 0 is an append; rounds < 0 is MF_ERR_INVALID.  *solved_users_out / *solved_items_out (may be
+   NULL) are the counts of the last round (0 with rounds == 0).  With the ratings of one new user and
+   rounds = 1 this is fold-in. */
+#define MF_ALS_SOLVER_CHOLESKY 0
+#define MF_ALS_SOLVER_CG 1
+#define MF_ALS_SOLVER_NNLS 2
+typedef struct mf_als_solve {
+  double lambda;
+  int32_t reg; /* MF_ALS_REG_* */
+  int32_t implicit;
+  double alpha;
+  int32_t solver; /* MF_ALS_SOLVER_* */
+  int32_t cg_steps;
+  int32_t reserved[4];
+} mf_als_solve;
+int mf_als_append(mf_ctx* ctx, const int32_t* users, const int32_t* items, const double* ratings, int64_t n);
+int mf_als_run_rows(mf_ctx* ctx, int side, const int32_t* ids, int64_t n_ids, const mf_als_solve* how,
+                    int64_t* solved_out /* may be NULL */);
+int mf_als_update(mf_ctx* ctx, const int32_t* users, const int32_t* items, const double* ratings, int64_t n,
+                  const mf_als_solve* how, int32_t rounds, int64_t* solved_users_out /* may be NULL */,
+                  int64_t* solved_items_out /* may be NULL */);
+
 /* Exact updateLocalFactors replacement (DSGDforMF.scala:378-418) on caller buffers:
    users[nu x k], items[ni x k] are updated in place; omegas are per row.  Reentrant
    on disjoint buffers with distinct contexts, as Flink calls it per task slot. */

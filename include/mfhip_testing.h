@@ -118,6 +118,22 @@ int mf_debug_als_nnls_row(mf_ctx* ctx, int side, int32_t id, double lambda, int3
 int mf_debug_rank_csr(mf_ctx* ctx, int query_side, int ground_truth, const int32_t* query, const int32_t* cand,
                       int64_t n, int32_t* q_ids_out, int64_t* off_out, int32_t* entries_out, int64_t cap_q,
                       int64_t cap_e, int64_t* nq_out, int64_t* ne_out);
+/* mf_debug_als_csr: after mf_als_prepare, the resident CSR of `side` copied back in row order.  *rows_out =
+   the rows it covers (those the side had at the last mf_als_prepare / mf_als_append), *nnz_out = its entries;
+   off_out[*rows_out + 1], cols_out[*nnz_out] = the counterpart's factor rows, vals_out[*nnz_out] = the ratings
+   widened to f64, npos_out[*rows_out] = per row its ratings > 0 (the n+ of its work items).  *rows_out and
+   *nnz_out are always set; MF_ERR_CAPACITY when cap_rows < *rows_out or cap_nnz < *nnz_out (nothing else is
+   written then). */
+int mf_debug_als_csr(mf_ctx* ctx, int side, int64_t* off_out, int32_t* cols_out, double* vals_out,
+                     int32_t* npos_out, int64_t cap_rows, int64_t cap_nnz, int64_t* rows_out, int64_t* nnz_out);
+/* mf_debug_als_append_placement: the rule mf_als_append's kernels follow, on the host (no GPU needed).  For
+   a side with offsets old_off[old_rows + 1] and a batch whose entry j belongs to row batch_row[j] < new_rows
+   (new_rows >= old_rows): new_off_out[new_rows + 1], and batch_pos_out[j] = where entry j lands in the new
+   arrays.  An old entry p of row x lands at p + new_off_out[x] - old_off[x].  mf_als_append itself uses only
+   the new_off half of this routine; its kernels place the batch entries from the sorted batch, and that is
+   checked through mf_debug_als_csr on the device. */
+int mf_debug_als_append_placement(const int64_t* old_off, int64_t old_rows, const int32_t* batch_row, int64_t n,
+                                  int64_t new_rows, int64_t* new_off_out, int64_t* batch_pos_out);
 
 #ifdef __cplusplus
 }

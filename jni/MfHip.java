@@ -61,6 +61,18 @@ public final class MfHip {
                                                  int iterations, double lambda, int reg, double alpha);
   public static native void alsRunNonneg(long ctx, long halfSweeps, double lambda, int reg);
   public static native void alsRunImplicitNonneg(long ctx, long halfSweeps, double lambda, int reg, double alpha);
+  // Incremental ALS (mf_als_append / mf_als_run_rows / mf_als_update), after alsPrepare or an alsFit*: the
+  // ratings join the CSRs on the device, and only named rows are solved.  The half-sweep is named by lambda,
+  // reg, implicit (0 / 1, alpha read only then), solver (0 Cholesky, 1 CG with cgSteps, 2 NNLS).
+  // alsRunRows returns the rows solved.  alsUpdate appends, then `rounds` times solves the batch's users and
+  // then its items -- users first, unlike a full sweep: a new user's row is random until it is solved;
+  // solvedOut (may be null, length >= 2) receives the last round's user and item counts.
+  public static native void alsAppend(long ctx, int[] users, int[] items, double[] ratings);
+  public static native long alsRunRows(long ctx, int side, int[] ids, double lambda, int reg, int implicit,
+                                       double alpha, int solver, int cgSteps);
+  public static native void alsUpdate(long ctx, int[] users, int[] items, double[] ratings, double lambda,
+                                      int reg, int implicit, double alpha, int solver, int cgSteps, int rounds,
+                                      int[] solvedOut);
   // unblock (DSGDforMF.scala:245-255) and checkpoint restore
   public static native long numFactors(long ctx, int side);
   public static native long getFactors(long ctx, int side, int[] idsOut, double[] vecsOut);

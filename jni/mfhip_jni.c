@@ -301,6 +301,62 @@ JNIEXPORT void JNICALL JFN(alsRunImplicitNonneg)(JNIEnv* env, jclass c, jlong h,
   check(env, mf_als_run_implicit_nonneg(CTX(h), halfSweeps, lambda, reg, alpha));
 }
 
+/* Incremental ALS: mf_als_append, mf_als_run_rows, mf_als_update (users first, then items). */
+static mf_als_solve als_how(jdouble lambda, jint reg, jint implicit, jdouble alpha, jint solver, jint cgSteps) {
+  mf_als_solve how = {0};
+  how.lambda = lambda;
+  how.reg = reg;
+  how.implicit = implicit;
+  how.alpha = alpha;
+  how.solver = solver;
+  how.cg_steps = cgSteps;
+  return how;
+}
+
+JNIEXPORT void JNICALL JFN(alsAppend)(JNIEnv* env, jclass c, jlong h, jintArray u, jintArray i, jdoubleArray r) {
+  with_ratings(env, h, u, i, r, mf_als_append);
+}
+
+JNIEXPORT jlong JNICALL JFN(alsRunRows)(JNIEnv* env, jclass c, jlong h, jint side, jintArray ids, jdouble lambda,
+                                        jint reg, jint implicit, jdouble alpha, jint solver, jint cgSteps) {
+  if (require(env, ids != NULL, "ids must not be null")) return 0;
+  const mf_als_solve how = als_how(lambda, reg, implicit, alpha, solver, cgSteps);
+  Elems e = {0};
+  if (acquire(env, &e, ids, kInt)) return 0;
+  int64_t solved = 0;
+  int st = mf_als_run_rows(CTX(h), side, (const int32_t*)e.p, len(env, ids), &how, &solved);
+  release(env, &e, JNI_ABORT);
+  check(env, st);
+  return (jlong)solved;
+}
+
+JNIEXPORT void JNICALL JFN(alsUpdate)(JNIEnv* env, jclass c, jlong h, jintArray u, jintArray i, jdoubleArray r,
+                                      jdouble lambda, jint reg, jint implicit, jdouble alpha, jint solver,
+                                      jint cgSteps, jint rounds, jintArray solvedOut) {
+  jsize n = 0;
+  if (rating_columns(env, u, i, r, &n)) return;
+  if (require(env, !solvedOut || len(env, solvedOut) >= 2, "solvedOut must hold 2 entries")) return;
+  const mf_als_solve how = als_how(lambda, reg, implicit, alpha, solver, cgSteps);
+  Elems eu = {0}, ei = {0}, er = {0};
+  if (acquire(env, &eu, u, kInt) || acquire(env, &ei, i, kInt) || acquire(env, &er, r, kDouble)) {
+    release(env, &eu, JNI_ABORT);
+    release(env, &ei, JNI_ABORT);
+    return;
+  }
+  int64_t su = 0, si = 0;
+  int st = mf_als_update(CTX(h), (const int32_t*)eu.p, (const int32_t*)ei.p, (const double*)er.p, n, &how, rounds,
+                         &su, &si);
+  release(env, &er, JNI_ABORT);
+  release(env, &ei, JNI_ABORT);
+  release(env, &eu, JNI_ABORT);
+  if (check(env, st) != MF_OK || !solvedOut) return;
+  Elems eo = {0};
+  if (acquire(env, &eo, solvedOut, kInt)) return;
+  ((jint*)eo.p)[0] = (jint)su;
+  ((jint*)eo.p)[1] = (jint)si;
+  release(env, &eo, 0);
+}
+
 JNIEXPORT void JNICALL JFN(dsgdRun)(JNIEnv* env, jclass c, jlong h, jlong supersteps) {
   check(env, mf_dsgd_run(CTX(h), supersteps));
 }

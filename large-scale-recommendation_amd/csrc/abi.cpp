@@ -460,6 +460,71 @@ int mf_als_fit_implicit_nonneg(mf_ctx* ctx, const int32_t* u, const int32_t* i, 
   return als_fit_entry(ctx, u, i, r, n, iterations, {lambda, reg, true, alpha, 0, true});
 }
 
+extern "C++" {
+namespace {
+
+// mf_als_solve as the AlsParams of the run call it names.
+AlsParams als_params_of(const mf_als_solve* how) {
+  MF_REQUIRE(how, "null mf_als_solve");
+  MF_REQUIRE(how->solver == MF_ALS_SOLVER_CHOLESKY || how->solver == MF_ALS_SOLVER_CG ||
+                 how->solver == MF_ALS_SOLVER_NNLS,
+             "unknown ALS solver");
+  AlsParams P{how->lambda, how->reg, how->implicit != 0, how->implicit != 0 ? how->alpha : 0.0};
+  if (how->solver == MF_ALS_SOLVER_CG) P.cg_steps = als_cg_entry_steps(how->cg_steps);
+  P.nnls = how->solver == MF_ALS_SOLVER_NNLS;
+  return P;
+}
+
+}  // namespace
+}  // extern "C++"
+
+int mf_als_append(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n) {
+  return guarded([&] {
+    MF_REQUIRE(ctx, "null context");
+    als_append(ctx, u, i, r, n);
+  });
+}
+
+int mf_als_run_rows(mf_ctx* ctx, int side, const int32_t* ids, int64_t n_ids, const mf_als_solve* how,
+                    int64_t* solved_out) {
+  return guarded([&] {
+    MF_REQUIRE(ctx, "null context");
+    const int64_t solved = als_run_rows(ctx, side, ids, n_ids, als_params_of(how));
+    if (solved_out) *solved_out = solved;
+  });
+}
+
+int mf_als_update(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n, const mf_als_solve* how,
+                  int32_t rounds, int64_t* solved_users_out, int64_t* solved_items_out) {
+  return guarded([&] {
+    MF_REQUIRE(ctx, "null context");
+    als_update(ctx, u, i, r, n, als_params_of(how), rounds, solved_users_out, solved_items_out);
+  });
+}
+
+int mf_debug_als_csr(mf_ctx* ctx, int side, int64_t* off_out, int32_t* cols_out, double* vals_out, int32_t* npos_out,
+                     int64_t cap_rows, int64_t cap_nnz, int64_t* rows_out, int64_t* nnz_out) {
+  return guarded([&] {
+    MF_REQUIRE(ctx && off_out && cols_out && vals_out && npos_out && rows_out && nnz_out, "null argument");
+    MF_REQUIRE(side == MF_SIDE_USER || side == MF_SIDE_ITEM, "bad side");
+    MF_REQUIRE(cap_rows >= 0 && cap_nnz >= 0, "negative count");
+    als_debug_csr(ctx, side, off_out, cols_out, vals_out, npos_out, cap_rows, cap_nnz, rows_out, nnz_out);
+  });
+}
+
+int mf_debug_als_append_placement(const int64_t* old_off, int64_t old_rows, const int32_t* batch_row, int64_t n,
+                                  int64_t new_rows, int64_t* new_off_out, int64_t* batch_pos_out) {
+  return guarded([&] {
+    MF_REQUIRE(old_off && new_off_out && batch_pos_out && (n == 0 || batch_row), "null argument");
+    MF_REQUIRE(old_rows >= 0 && n >= 0 && new_rows >= old_rows, "bad counts");
+    MF_REQUIRE(old_off[0] == 0, "old_off[0] must be 0");
+    for (int64_t x = 0; x < old_rows; ++x) MF_REQUIRE(old_off[x + 1] >= old_off[x], "old_off must not descend");
+    for (int64_t j = 0; j < n; ++j) MF_REQUIRE(batch_row[j] >= 0 && batch_row[j] < new_rows, "a batch row is out of range");
+    als_append_placement(old_off, old_rows, reinterpret_cast<const uint32_t*>(batch_row), n, new_rows, new_off_out,
+                         batch_pos_out);
+  });
+}
+
 int mf_als_nonneg_stats(mf_ctx* ctx, struct mf_als_nonneg_stats* out) {
   return guarded([&] {
     MF_REQUIRE(ctx && out, "null argument");

@@ -1,5 +1,6 @@
 // als.cpp -- ALS training (mf_als_prepare / mf_als_run / mf_als_fit, their _implicit, _cg, _implicit_cg,
-// _nonneg and _implicit_nonneg variants) and its testing hooks.
+// _nonneg and _implicit_nonneg variants), incremental ALS (mf_als_append / mf_als_run_rows / mf_als_update)
+// and their testing hooks.
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -52,9 +53,78 @@ void als_check_run(const AlsParams& P) {
 
 namespace {
 
+// Cuts rows into work items, long-row splits and launches: what mf_als_prepare and mf_als_append do for
+// every rated row of a side and mf_als_run_rows for the rows of one call.  Rows are added in ascending order.
+struct AlsCutter {
+  std::vector<AlsItem>& items;
+  std::vector<AlsSplit>& splits;
+  std::vector<mf_ctx::AlsBatch>& batches;
+  int64_t& max_slots;
+  int64_t chunk, batch;
+  mf_ctx::AlsBatch cur{0, 0, 0, 0};
+  int64_t cur_rows = 0, cur_slots = 0;
+  void close() {
+    if (cur.items > 0) batches.push_back(cur);
+    max_slots = std::max(max_slots, cur_slots);
+    cur = {static_cast<int64_t>(items.size()), 0, static_cast<int64_t>(splits.size()), 0};
+    cur_rows = cur_slots = 0;
+  }
+  // row's c >= 1 ratings at [begin, begin + c) of the CSR, npos of them > 0
+  void add(int64_t row, int64_t begin, int64_t c, int32_t npos) {
+    MF_REQUIRE(c <= INT32_MAX, "ALS: a row has more than 2^31 - 1 ratings");
+    const int64_t nch = c <= chunk ? 1 : (c + chunk - 1) / chunk;
+    if (cur_rows >= batch || (nch > 1 && cur_slots > 0 && cur_slots + nch > kAlsBatchSlots)) close();
+    if (nch == 1) {
+      items.push_back({begin, static_cast<int32_t>(row), static_cast<int32_t>(c), -1, npos});
+      cur.items += 1;
+    } else {
+      for (int64_t ch = 0; ch < nch; ++ch)
+        items.push_back({begin + ch * chunk, static_cast<int32_t>(row),
+                         static_cast<int32_t>(std::min(chunk, c - ch * chunk)), static_cast<int32_t>(cur_slots + ch), npos});
+      splits.push_back({static_cast<int32_t>(row), static_cast<int32_t>(cur_slots), static_cast<int32_t>(nch),
+                        static_cast<int32_t>(c), npos});
+      cur.items += nch;
+      cur.splits += 1;
+      cur_slots += nch;
+    }
+    ++cur_rows;
+  }
+};
+
+void als_upload(DevBuf& d, const void* src, size_t bytes) {
+  d.alloc(std::max<size_t>(bytes, 16));
+  if (bytes) MF_HIP(hipMemcpy(d.get(), src, bytes, hipMemcpyHostToDevice));
+}
+
+// A side's work lists from the shape of its CSR -- off[rows + 1] and per row its ratings > 0 -- with the
+// chunk and batch lengths mf_als_prepare read: the long-row chunking, the launch batches and the rated-row
+// list that G is summed over, on the host and on the device.  The one routine behind mf_als_prepare and
+// mf_als_append; the conjugate-gradient work lists are rebuilt on their next use.
+void als_work_lists(mf_ctx* ctx, Shard& s, int side, std::vector<int64_t> off, std::vector<int32_t> npos) {
+  mf_ctx::AlsSide& A = ctx->als[side];
+  A = mf_ctx::AlsSide();
+  const int64_t rows = static_cast<int64_t>(off.size()) - 1;
+  AlsCutter cut{A.items, A.splits, A.batches, A.max_slots, ctx->als_chunk, ctx->als_batch};
+  std::vector<int32_t> rated;
+  for (int64_t row = 0; row < rows; ++row) {
+    const int64_t c = off[row + 1] - off[row];
+    if (c == 0) continue;
+    rated.push_back(static_cast<int32_t>(row));
+    cut.add(row, off[row], c, npos[row]);
+  }
+  cut.close();
+  A.rated = static_cast<int64_t>(rated.size());
+  A.off = std::move(off);
+  A.npos = std::move(npos);
+  DeviceGuard g(s.device);
+  als_upload(s.als_items[side], A.items.data(), A.items.size() * sizeof(AlsItem));
+  als_upload(s.als_splits[side], A.splits.data(), A.splits.size() * sizeof(AlsSplit));
+  als_upload(s.als_rated[side], rated.data(), rated.size() * 4);
+}
+
 template <typename T>
 void als_build_side(mf_ctx* ctx, Shard& s, int side, const std::vector<uint32_t>& xr, const std::vector<uint32_t>& yr,
-                    const double* r, int64_t n, int64_t rows, int64_t chunk, int64_t batch) {
+                    const double* r, int64_t n, int64_t rows) {
   std::vector<int64_t> off(static_cast<size_t>(rows) + 1, 0);
   for (int64_t j = 0; j < n; ++j) ++off[xr[j] + 1];
   for (int64_t x = 0; x < rows; ++x) off[x + 1] += off[x];
@@ -68,78 +138,29 @@ void als_build_side(mf_ctx* ctx, Shard& s, int side, const std::vector<uint32_t>
       vals[p] = static_cast<T>(r[j]);
     }
   }
-  mf_ctx::AlsSide& A = ctx->als[side];
-  A = mf_ctx::AlsSide();
-  mf_ctx::AlsBatch cur{0, 0, 0, 0};
-  int64_t cur_rows = 0, cur_slots = 0;
-  auto close = [&]() {
-    if (cur.items > 0) A.batches.push_back(cur);
-    A.max_slots = std::max(A.max_slots, cur_slots);
-    cur = {static_cast<int64_t>(A.items.size()), 0, static_cast<int64_t>(A.splits.size()), 0};
-    cur_rows = cur_slots = 0;
-  };
-  std::vector<int32_t> rated;
+  std::vector<int32_t> npos(static_cast<size_t>(rows), 0);  // MLlib's numExplicits: the implicit half-sweep's n+
   for (int64_t row = 0; row < rows; ++row) {
-    const int64_t c = off[row + 1] - off[row];
-    if (c == 0) continue;
-    MF_REQUIRE(c <= INT32_MAX, "ALS: a row has more than 2^31 - 1 ratings");
-    rated.push_back(static_cast<int32_t>(row));
-    int32_t npos = 0;  // MLlib's numExplicits: the implicit half-sweep's n+
-    for (int64_t p = off[row]; p < off[row + 1]; ++p) npos += vals[p] > T(0);
-    const int64_t nch = c <= chunk ? 1 : (c + chunk - 1) / chunk;
-    if (cur_rows >= batch || (nch > 1 && cur_slots > 0 && cur_slots + nch > kAlsBatchSlots)) close();
-    if (nch == 1) {
-      A.items.push_back({off[row], static_cast<int32_t>(row), static_cast<int32_t>(c), -1, npos});
-      cur.items += 1;
-    } else {
-      for (int64_t ch = 0; ch < nch; ++ch)
-        A.items.push_back({off[row] + ch * chunk, static_cast<int32_t>(row),
-                           static_cast<int32_t>(std::min(chunk, c - ch * chunk)), static_cast<int32_t>(cur_slots + ch), npos});
-      A.splits.push_back({static_cast<int32_t>(row), static_cast<int32_t>(cur_slots), static_cast<int32_t>(nch),
-                          static_cast<int32_t>(c), npos});
-      cur.items += nch;
-      cur.splits += 1;
-      cur_slots += nch;
-    }
-    ++cur_rows;
+    int32_t np = 0;
+    for (int64_t p = off[row]; p < off[row + 1]; ++p) np += vals[p] > T(0);
+    npos[row] = np;
   }
-  close();
-  A.rated = static_cast<int64_t>(rated.size());
-  DeviceGuard g(s.device);
-  auto up = [&](DevBuf& d, const void* src, size_t bytes) {
-    d.alloc(std::max<size_t>(bytes, 16));
-    if (bytes) MF_HIP(hipMemcpy(d.get(), src, bytes, hipMemcpyHostToDevice));
-  };
-  up(s.als_cols[side], cols.data(), cols.size() * 4);
-  up(s.als_vals[side], vals.data(), vals.size() * sizeof(T));
-  up(s.als_items[side], A.items.data(), A.items.size() * sizeof(AlsItem));
-  up(s.als_splits[side], A.splits.data(), A.splits.size() * sizeof(AlsSplit));
-  up(s.als_rated[side], rated.data(), rated.size() * 4);
+  {
+    DeviceGuard g(s.device);
+    als_upload(s.als_cols[side], cols.data(), cols.size() * 4);
+    als_upload(s.als_vals[side], vals.data(), vals.size() * sizeof(T));
+    als_upload(s.als_off[side], off.data(), off.size() * 8);
+  }
+  als_work_lists(ctx, s, side, std::move(off), std::move(npos));
 }
 
-}  // namespace
-
-void als_prepare(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n) {
-  MF_REQUIRE(n >= 0, "negative rating count");
-  MF_REQUIRE(n == 0 || (u && i && r), "null rating arrays");
-  als_check(ctx);
-  require_healthy(ctx);
-  det_spec_wait(ctx, true);  // new ids change the layouts the builds read
-  sync_all(ctx);
-  Shard& s = ctx->shards[0];
-  ctx->als_prepared = false;
-  if (!ctx->have_model) {
-    ctx->U = SideLayout();
-    ctx->I = SideLayout();
-    ctx->have_model = true;
-    ++ctx->layout_gen;
-  }
+// The factor rows of a rating list for mf_als_prepare and mf_als_append.  ur / ir hold the rows of the ids
+// the model has (lookup_rows); ids it does not have take new rows in order of appearance, the user looked
+// at before the item within one rating, with the initial values a DSGD fit gives them.
+void als_insert_rows(mf_ctx* ctx, Shard& s, const int32_t* u, const int32_t* i, int64_t n, std::vector<uint32_t>& ur,
+                     std::vector<uint32_t>& ir) {
   const int k = ctx->P.num_factors;
   const int64_t u0 = ctx->U.rows(), i0 = ctx->I.rows();
   constexpr uint32_t kMiss = 0xFFFFFFFFu;
-  std::vector<uint32_t> ur, ir;
-  lookup_rows(ctx->U, u, n, ur);
-  lookup_rows(ctx->I, i, n, ir);
   std::vector<int32_t> fu, fi;
   for (int64_t j = 0; j < n; ++j) {  // unseen ids take new rows in order of appearance
     if (ur[j] == kMiss) ur[j] = static_cast<uint32_t>(online_row(ctx, ctx->U, u[j], fu));
@@ -162,9 +183,34 @@ void als_prepare(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* 
     init_vectors(fresh.data(), static_cast<int64_t>(fresh.size()), k, true, ctx->init_seed, vec);
     upload_rows(ctx, s, side, side == kSideU ? u0 : i0, vec.data(), static_cast<int64_t>(fresh.size()));
   }
-  int64_t chunk = kAlsChunk, batch = kAlsBatch;
-  if (const std::string v = test_knob("als_chunk"); !v.empty()) chunk = std::max<int64_t>(1, std::atoll(v.c_str()));
-  if (const std::string v = test_knob("als_batch"); !v.empty()) batch = std::max<int64_t>(1, std::atoll(v.c_str()));
+}
+
+}  // namespace
+
+void als_prepare(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n) {
+  MF_REQUIRE(n >= 0, "negative rating count");
+  MF_REQUIRE(n == 0 || (u && i && r), "null rating arrays");
+  als_check(ctx);
+  require_healthy(ctx);
+  det_spec_wait(ctx, true);  // new ids change the layouts the builds read
+  sync_all(ctx);
+  Shard& s = ctx->shards[0];
+  ctx->als_prepared = false;
+  if (!ctx->have_model) {
+    ctx->U = SideLayout();
+    ctx->I = SideLayout();
+    ctx->have_model = true;
+    ++ctx->layout_gen;
+  }
+  const int k = ctx->P.num_factors;
+  std::vector<uint32_t> ur, ir;
+  lookup_rows(ctx->U, u, n, ur);
+  lookup_rows(ctx->I, i, n, ir);
+  als_insert_rows(ctx, s, u, i, n, ur, ir);
+  ctx->als_chunk = kAlsChunk;
+  ctx->als_batch = kAlsBatch;
+  if (const std::string v = test_knob("als_chunk"); !v.empty()) ctx->als_chunk = std::max<int64_t>(1, std::atoll(v.c_str()));
+  if (const std::string v = test_knob("als_batch"); !v.empty()) ctx->als_batch = std::max<int64_t>(1, std::atoll(v.c_str()));
   ctx->als_gram_slice = kAlsGramSlice;
   if (const std::string v = test_knob("als_gram_slice"); !v.empty())
     ctx->als_gram_slice = std::min<int64_t>(std::max<int64_t>(1, std::atoll(v.c_str())), 1 << 30);
@@ -172,11 +218,11 @@ void als_prepare(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* 
   if (const std::string v = test_knob("als_slabs"); !v.empty())
     ctx->als_slabs = std::min<int64_t>(ctx->als_slabs, std::max<int64_t>(1, std::atoll(v.c_str())));
   if (ctx->f64) {
-    als_build_side<double>(ctx, s, kSideU, ur, ir, r, n, ctx->U.rows(), chunk, batch);
-    als_build_side<double>(ctx, s, MF_SIDE_ITEM, ir, ur, r, n, ctx->I.rows(), chunk, batch);
+    als_build_side<double>(ctx, s, kSideU, ur, ir, r, n, ctx->U.rows());
+    als_build_side<double>(ctx, s, MF_SIDE_ITEM, ir, ur, r, n, ctx->I.rows());
   } else {
-    als_build_side<float>(ctx, s, kSideU, ur, ir, r, n, ctx->U.rows(), chunk, batch);
-    als_build_side<float>(ctx, s, MF_SIDE_ITEM, ir, ur, r, n, ctx->I.rows(), chunk, batch);
+    als_build_side<float>(ctx, s, kSideU, ur, ir, r, n, ctx->U.rows());
+    als_build_side<float>(ctx, s, MF_SIDE_ITEM, ir, ur, r, n, ctx->I.rows());
   }
   {
     DeviceGuard g(s.device);
@@ -235,27 +281,30 @@ void als_gram_launch(mf_ctx* ctx, Shard& s, int side) {
 }
 
 // The chunk items of `side`'s long rows, per batch, with the index of each one's row among the batch's splits.
+void als_cg_work(const std::vector<AlsItem>& items, const std::vector<AlsSplit>& splits,
+                 const std::vector<mf_ctx::AlsBatch>& batches, std::vector<AlsCgWork>& work, std::vector<int64_t>& work0,
+                 int64_t& max_splits) {
+  work.clear();
+  work0.assign(1, 0);
+  max_splits = 0;
+  for (const mf_ctx::AlsBatch& b : batches) {
+    int64_t sp = b.split0;
+    for (int64_t x = b.item0; x < b.item0 + b.items; ++x) {
+      const AlsItem& it = items[static_cast<size_t>(x)];
+      if (it.slot < 0) continue;
+      while (splits[static_cast<size_t>(sp)].row != it.row) ++sp;  // both lists are in row order
+      work.push_back({static_cast<int32_t>(x - b.item0), static_cast<int32_t>(sp - b.split0)});
+    }
+    work0.push_back(static_cast<int64_t>(work.size()));
+    max_splits = std::max(max_splits, b.splits);
+  }
+}
+
 void als_cg_lists(mf_ctx* ctx, Shard& s, int side) {
   mf_ctx::AlsSide& A = ctx->als[side];
   if (A.cg_ready) return;
-  A.cg_work.clear();
-  A.cg_work0.assign(1, 0);
-  A.cg_max_splits = 0;
-  for (const mf_ctx::AlsBatch& b : A.batches) {
-    int64_t sp = b.split0;
-    for (int64_t x = b.item0; x < b.item0 + b.items; ++x) {
-      const AlsItem& it = A.items[static_cast<size_t>(x)];
-      if (it.slot < 0) continue;
-      while (A.splits[static_cast<size_t>(sp)].row != it.row) ++sp;  // both lists are in row order
-      A.cg_work.push_back({static_cast<int32_t>(x - b.item0), static_cast<int32_t>(sp - b.split0)});
-    }
-    A.cg_work0.push_back(static_cast<int64_t>(A.cg_work.size()));
-    A.cg_max_splits = std::max(A.cg_max_splits, b.splits);
-  }
-  s.als_cg_work[side].alloc(std::max<size_t>(A.cg_work.size() * sizeof(AlsCgWork), 16));
-  if (!A.cg_work.empty())
-    MF_HIP(hipMemcpy(s.als_cg_work[side].get(), A.cg_work.data(), A.cg_work.size() * sizeof(AlsCgWork),
-                     hipMemcpyHostToDevice));
+  als_cg_work(A.items, A.splits, A.batches, A.cg_work, A.cg_work0, A.cg_max_splits);
+  als_upload(s.als_cg_work[side], A.cg_work.data(), A.cg_work.size() * sizeof(AlsCgWork));
   A.cg_ready = true;
 }
 
@@ -277,16 +326,36 @@ mf_ctx::AlsBatch als_row_span(const mf_ctx::AlsSide& A, int64_t row) {
 // only_row >= 0 (the testing hooks): that row's work items alone, and s.als_dump takes the row's system
 // (Cholesky), x with its iteration count and reason code (the non-negative solve) or A v and b for the v
 // in s.als_cg_v (conjugate gradients) instead of the row being solved; false if the row has no rating.
-bool als_half(mf_ctx* ctx, int side, const AlsParams& P, int64_t only_row = -1) {
+// rows != null (mf_als_run_rows): those rows alone -- ascending, distinct, each with a rating -- from work
+// lists of their own, cut as the side's are (fresh slot numbers for the long rows, launches by the same
+// batch and slot limits); the kernels, the CSR and G are the full half-sweep's.
+bool als_half(mf_ctx* ctx, int side, const AlsParams& P, int64_t only_row = -1,
+              const std::vector<int32_t>* rows = nullptr) {
   Shard& s = ctx->shards[0];
   DeviceGuard g(s.device);
   mf_ctx::AlsSide& A = ctx->als[side];
   const int k = ctx->P.num_factors;
   const bool cg = P.cg_steps > 0;
   const int other = side == kSideU ? MF_SIDE_ITEM : kSideU;
-  const AlsItem* d_items = s.als_items[side].as<AlsItem>();
-  const AlsSplit* d_splits = s.als_splits[side].as<AlsSplit>();
-  s.als_part.alloc(std::max<size_t>(static_cast<size_t>(A.max_slots) * als_partial_elems(k) * ctx->es, 16));
+  mf_ctx::AlsSide sub;
+  if (rows) {
+    AlsCutter cut{sub.items, sub.splits, sub.batches, sub.max_slots, ctx->als_chunk, ctx->als_batch};
+    for (const int32_t row : *rows) cut.add(row, A.off[row], A.off[row + 1] - A.off[row], A.npos[row]);
+    cut.close();
+    als_upload(s.als_sub_items, sub.items.data(), sub.items.size() * sizeof(AlsItem));
+    als_upload(s.als_sub_splits, sub.splits.data(), sub.splits.size() * sizeof(AlsSplit));
+    if (cg) {
+      als_cg_work(sub.items, sub.splits, sub.batches, sub.cg_work, sub.cg_work0, sub.cg_max_splits);
+      als_upload(s.als_sub_work, sub.cg_work.data(), sub.cg_work.size() * sizeof(AlsCgWork));
+    }
+  } else if (cg) {
+    als_cg_lists(ctx, s, side);
+  }
+  const mf_ctx::AlsSide& W = rows ? sub : A;  // the work of this call
+  const AlsItem* d_items = rows ? s.als_sub_items.as<AlsItem>() : s.als_items[side].as<AlsItem>();
+  const AlsSplit* d_splits = rows ? s.als_sub_splits.as<AlsSplit>() : s.als_splits[side].as<AlsSplit>();
+  const AlsCgWork* d_work = rows ? s.als_sub_work.as<AlsCgWork>() : s.als_cg_work[side].as<AlsCgWork>();
+  s.als_part.alloc(std::max<size_t>(static_cast<size_t>(W.max_slots) * als_partial_elems(k) * ctx->es, 16));
   AlsLaunch L;
   L.st = s.stream;
   L.cols = s.als_cols[side].as<int32_t>();
@@ -300,15 +369,14 @@ bool als_half(mf_ctx* ctx, int side, const AlsParams& P, int64_t only_row = -1) 
   L.partial = s.als_part.get();
   L.alpha = P.alpha;
   if (cg) {
-    als_cg_lists(ctx, s, side);
-    s.als_cg_state.alloc(std::max<size_t>(static_cast<size_t>(std::max<int64_t>(A.cg_max_splits, 1)) *
+    s.als_cg_state.alloc(std::max<size_t>(static_cast<size_t>(std::max<int64_t>(W.cg_max_splits, 1)) *
                                               als_cg_state_elems(k) * ctx->es, 16));
     L.steps = P.cg_steps;
     L.stage = test_knob("als_cg_stage") != "0";
     L.state = s.als_cg_state.get();
   } else {
     // k > 128: one normal matrix in global memory per workgroup of the grid, however many rows there are
-    L.slabs = static_cast<int>(std::min<int64_t>(ctx->als_slabs, static_cast<int64_t>(A.items.size())));
+    L.slabs = static_cast<int>(std::min<int64_t>(ctx->als_slabs, static_cast<int64_t>(W.items.size())));
     if (L.slabs > 0) s.als_slab.alloc(static_cast<size_t>(L.slabs) * als_gram_elems(k) * ctx->es);
     L.slab = s.als_slab.get();
     L.nnls = P.nnls;
@@ -345,15 +413,15 @@ bool als_half(mf_ctx* ctx, int side, const AlsParams& P, int64_t only_row = -1) 
     return true;
   }
   LaunchTimer t(s, ctx->profiling);
-  if (P.implicit && !A.batches.empty()) {
+  if (P.implicit && !W.batches.empty()) {
     gram();
     ctx->stats.kernel_launches += 2;
   }
-  for (size_t b = 0; b < A.batches.size(); ++b) {
-    const mf_ctx::AlsBatch& B = A.batches[b];
+  for (size_t b = 0; b < W.batches.size(); ++b) {
+    const mf_ctx::AlsBatch& B = W.batches[b];
     if (cg) {
-      L.work = s.als_cg_work[side].as<AlsCgWork>() + A.cg_work0[b];
-      L.n_work = static_cast<int>(A.cg_work0[b + 1] - A.cg_work0[b]);
+      L.work = d_work + W.cg_work0[b];
+      L.n_work = static_cast<int>(W.cg_work0[b + 1] - W.cg_work0[b]);
     }
     launch(B);
     ctx->stats.kernel_launches += 1 + (B.splits > 0 ? (cg ? 2 * (P.cg_steps + 1) : 1) : 0);
@@ -451,6 +519,170 @@ void als_gram(mf_ctx* ctx, int side, double* G_out) {
   const size_t k = static_cast<size_t>(ctx->P.num_factors), kp = (k + 31) / 32 * 32;
   const std::vector<double> h = read_as_f64(ctx, s.als_gram, kp * kp);
   for (size_t a = 0; a < k; ++a) std::memcpy(G_out + a * k, h.data() + a * kp, k * 8);
+}
+
+// ---------------------------------------------------------------------------------------
+// Incremental ALS: mf_als_append repacks both CSRs on the device with the batch in (kernels_als_append.hip),
+// mf_als_run_rows solves named rows through als_half, mf_als_update is the two in sequence.
+
+void als_append_placement(const int64_t* old_off, int64_t old_rows, const uint32_t* batch_row, int64_t n,
+                          int64_t new_rows, int64_t* new_off, int64_t* batch_pos) {
+  std::vector<int64_t> add(static_cast<size_t>(new_rows), 0);
+  for (int64_t j = 0; j < n; ++j) ++add[batch_row[j]];
+  new_off[0] = 0;
+  for (int64_t x = 0; x < new_rows; ++x)
+    new_off[x + 1] = new_off[x] + (x < old_rows ? old_off[x + 1] - old_off[x] : 0) + add[x];
+  if (!batch_pos) return;
+  for (int64_t x = 0; x < new_rows; ++x) add[x] = new_off[x + 1] - add[x];  // where the row's new entries begin
+  for (int64_t j = 0; j < n; ++j) batch_pos[j] = add[batch_row[j]]++;
+}
+
+namespace {
+
+// One side of mf_als_append: its new offsets and n+ on the host, its entries moved on the device into fresh
+// arrays (the old ones go to `retired`, to be freed once the stream is done), its work lists rebuilt.
+template <typename T>
+void als_append_side(mf_ctx* ctx, Shard& s, int side, const std::vector<uint32_t>& xr, const T* vals, int64_t n,
+                     const uint32_t* d_xr, const uint32_t* d_yr, std::vector<DevBuf>& retired) {
+  mf_ctx::AlsSide& A = ctx->als[side];
+  const int64_t old_rows = static_cast<int64_t>(A.off.size()) - 1, new_rows = side_of(ctx, side).rows();
+  std::vector<int64_t> off(static_cast<size_t>(new_rows) + 1);
+  als_append_placement(A.off.data(), old_rows, xr.data(), n, new_rows, off.data(), nullptr);
+  std::vector<int32_t> npos(A.npos);
+  npos.resize(static_cast<size_t>(new_rows), 0);
+  for (int64_t j = 0; j < n; ++j) npos[xr[j]] += vals[j] > T(0);
+  DevBuf d_off, d_cols, d_vals;
+  als_upload(d_off, off.data(), off.size() * 8);
+  d_cols.alloc(std::max<size_t>(static_cast<size_t>(off.back()) * 4, 16));
+  d_vals.alloc(std::max<size_t>(static_cast<size_t>(off.back()) * sizeof(T), 16));
+  launch_als_append({s.stream, s.als_off[side].as<int64_t>(), old_rows, A.off.back(), d_off.as<int64_t>(), new_rows,
+                     s.als_cols[side].as<int32_t>(), s.als_vals[side].get(), d_cols.as<int32_t>(), d_vals.get(),
+                     static_cast<int>(sizeof(T)), d_xr, d_yr, s.als_app.val.get(), n},
+                    s.als_app);
+  std::swap(s.als_off[side], d_off);
+  std::swap(s.als_cols[side], d_cols);
+  std::swap(s.als_vals[side], d_vals);
+  retired.push_back(std::move(d_off));
+  retired.push_back(std::move(d_cols));
+  retired.push_back(std::move(d_vals));
+  // (the lists this uploads are read by no queued kernel: the moves do not touch them and als_enter drained
+  // the half-sweeps)
+  als_work_lists(ctx, s, side, std::move(off), std::move(npos));
+}
+
+template <typename T>
+void als_append_both(mf_ctx* ctx, Shard& s, const std::vector<uint32_t>& ur, const std::vector<uint32_t>& ir,
+                     const double* r, int64_t n) {
+  std::vector<T> vals(static_cast<size_t>(n));
+  for (int64_t j = 0; j < n; ++j) vals[static_cast<size_t>(j)] = static_cast<T>(r[j]);  // the context's precision
+  DeviceGuard g(s.device);
+  als_upload(s.als_app.urow, ur.data(), static_cast<size_t>(n) * 4);
+  als_upload(s.als_app.irow, ir.data(), static_cast<size_t>(n) * 4);
+  als_upload(s.als_app.val, vals.data(), static_cast<size_t>(n) * sizeof(T));
+  const uint32_t* d_ur = s.als_app.urow.as<uint32_t>();
+  const uint32_t* d_ir = s.als_app.irow.as<uint32_t>();
+  // One side at a time, the stream drained between them: the side's old arrays are freed before the other
+  // side's new ones are allocated (the transient is a second copy of one side, not of both), and the sort's
+  // scratch in s.als_app, which the second side may reallocate, is idle by then.
+  for (int side = 0; side < 2; ++side) {
+    std::vector<DevBuf> retired;
+    if (side == kSideU) als_append_side<T>(ctx, s, kSideU, ur, vals.data(), n, d_ur, d_ir, retired);
+    else als_append_side<T>(ctx, s, MF_SIDE_ITEM, ir, vals.data(), n, d_ir, d_ur, retired);
+    MF_HIP(hipStreamSynchronize(s.stream));  // `retired` is freed behind the moves
+  }
+}
+
+}  // namespace
+
+void als_append(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n) {
+  MF_REQUIRE(n >= 0, "negative rating count");
+  MF_REQUIRE(n < (int64_t{1} << 31), "mf_als_append takes fewer than 2^31 ratings in one call");
+  MF_REQUIRE(n == 0 || (u && i && r), "null rating arrays");
+  Shard& s = als_enter(ctx, "mf_als_append");
+  if (n == 0) return;
+  constexpr uint32_t kMiss = 0xFFFFFFFFu;
+  std::vector<uint32_t> ur, ir;
+  lookup_rows(ctx->U, u, n, ur);
+  lookup_rows(ctx->I, i, n, ir);
+  bool fresh = false;
+  for (int side = 0; side < 2; ++side) {  // nothing has changed yet: no row may pass 2^31 - 1 ratings
+    const mf_ctx::AlsSide& A = ctx->als[side];
+    const std::vector<uint32_t>& xr = side == kSideU ? ur : ir;
+    const int64_t have = static_cast<int64_t>(A.off.size()) - 1;
+    std::vector<int64_t> cnt(static_cast<size_t>(side_of(ctx, side).rows()), 0);
+    for (int64_t j = 0; j < n; ++j) {
+      if (xr[j] == kMiss) {  // (a new row holds at most the n < 2^31 ratings of this call)
+        fresh = true;
+        continue;
+      }
+      const int64_t x = xr[j];
+      if (cnt[x] == 0 && x < have) cnt[x] = A.off[x + 1] - A.off[x];
+      MF_REQUIRE(++cnt[x] <= INT32_MAX, "ALS: a row has more than 2^31 - 1 ratings");
+    }
+  }
+  if (fresh) det_spec_wait(ctx, true);  // new ids change the layouts the builds read
+  als_insert_rows(ctx, s, u, i, n, ur, ir);
+  ctx->f64 ? als_append_both<double>(ctx, s, ur, ir, r, n) : als_append_both<float>(ctx, s, ur, ir, r, n);
+}
+
+int64_t als_run_rows(mf_ctx* ctx, int side, const int32_t* ids, int64_t n_ids, const AlsParams& P) {
+  if (P.implicit) als_check_alpha(P.alpha);
+  als_check_run(P);
+  MF_REQUIRE(side == MF_SIDE_USER || side == MF_SIDE_ITEM, "bad side");
+  MF_REQUIRE(n_ids >= 0, "negative id count");
+  MF_REQUIRE(n_ids == 0 || ids, "null id array");
+  Shard& s = als_enter(ctx, "mf_als_run_rows");
+  const mf_ctx::AlsSide& A = ctx->als[side];
+  const SideLayout& S = side_of(ctx, side);
+  const int64_t have = static_cast<int64_t>(A.off.size()) - 1;
+  std::vector<uint8_t> named(static_cast<size_t>(have), 0);
+  for (int64_t j = 0; j < n_ids; ++j) {  // ids the model does not hold and rows without a rating are skipped
+    const int32_t row = S.index.find(ids[j]);
+    if (row >= 0 && row < have && A.off[row + 1] > A.off[row]) named[row] = 1;
+  }
+  std::vector<int32_t> rows;  // ascending row order, each row once: no trace of the order of ids[]
+  for (int64_t row = 0; row < have; ++row)
+    if (named[row]) rows.push_back(static_cast<int32_t>(row));
+  if (rows.empty()) return 0;
+  als_half(ctx, side, P, -1, &rows);
+  DeviceGuard g(s.device);
+  MF_HIP(hipStreamSynchronize(s.stream));
+  return static_cast<int64_t>(rows.size());
+}
+
+void als_update(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n, const AlsParams& P,
+                int32_t rounds, int64_t* solved_users, int64_t* solved_items) {
+  MF_REQUIRE(rounds >= 0, "negative round count");
+  if (P.implicit) als_check_alpha(P.alpha);
+  als_check_run(P);
+  als_append(ctx, u, i, r, n);  // (checks the rest before it changes anything)
+  int64_t su = 0, si = 0;
+  for (int32_t t = 0; t < rounds; ++t) {
+    // users first: a new user's row is random until solved, and items solved from it would be pulled to noise
+    su = als_run_rows(ctx, kSideU, u, n, P);
+    si = als_run_rows(ctx, MF_SIDE_ITEM, i, n, P);
+  }
+  if (solved_users) *solved_users = su;
+  if (solved_items) *solved_items = si;
+}
+
+// The resident CSR of a side copied back (mf_debug_als_csr): the offsets and entries from the device, the
+// per-row n+ from the host list the work items are cut from.
+void als_debug_csr(mf_ctx* ctx, int side, int64_t* off_out, int32_t* cols_out, double* vals_out, int32_t* npos_out,
+                   int64_t cap_rows, int64_t cap_nnz, int64_t* rows_out, int64_t* nnz_out) {
+  Shard& s = als_enter(ctx, "mf_debug_als_csr");
+  const mf_ctx::AlsSide& A = ctx->als[side];
+  const int64_t rows = static_cast<int64_t>(A.off.size()) - 1, nnz = A.off.back();
+  *rows_out = rows;
+  *nnz_out = nnz;
+  if (cap_rows < rows || cap_nnz < nnz) fail(MF_ERR_CAPACITY, "mf_debug_als_csr: the output arrays are too short");
+  DeviceGuard g(s.device);
+  MF_HIP(hipMemcpy(off_out, s.als_off[side].get(), static_cast<size_t>(rows + 1) * 8, hipMemcpyDeviceToHost));
+  std::copy(A.npos.begin(), A.npos.end(), npos_out);
+  if (nnz == 0) return;
+  MF_HIP(hipMemcpy(cols_out, s.als_cols[side].get(), static_cast<size_t>(nnz) * 4, hipMemcpyDeviceToHost));
+  const std::vector<double> v = read_as_f64(ctx, s.als_vals[side], static_cast<size_t>(nnz));
+  std::memcpy(vals_out, v.data(), static_cast<size_t>(nnz) * 8);
 }
 
 }  // namespace mfhip

@@ -159,6 +159,12 @@ struct RankScratch {
   DevBuf flag, pos, key, key2, head, wp, tmp;
 };
 
+// Device scratch of mf_als_append (kernels_als_append.hip): the batch as uploaded (user rows, item rows,
+// rating bits), and one side's sort of it (rows ascending, stable; positions in the batch).
+struct AlsAppendScratch {
+  DevBuf urow, irow, val, key, iota, idx, tmp;
+};
+
 // Pinned host staging buffer.
 class PinnedBuf {
  public:

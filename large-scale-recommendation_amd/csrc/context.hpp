@@ -149,6 +149,11 @@ struct Shard {
   DevBuf als_cg_work[2], als_cg_state, als_cg_v, als_cg_hook_work;
   // ... the non-negative half-sweeps: the six 64-bit counters of mf_als_nonneg_stats (zeroed in mf_als_prepare)
   DevBuf als_nnls_stats;
+  // ... mf_als_append: per side the CSR's 64-bit row offsets, the batch and its sort (kernels_als_append.hip)
+  DevBuf als_off[2];
+  AlsAppendScratch als_app;
+  // ... mf_als_run_rows: the item, split and chunk lists of one call
+  DevBuf als_sub_items, als_sub_splits, als_sub_work;
   // profiling
   std::vector<hipEvent_t> ev;
   size_t ev_used = 0;
@@ -217,6 +222,10 @@ struct mf_ctx {
     std::vector<AlsBatch> batches;
     int64_t max_slots = 0;
     int64_t rated = 0;  // rows with at least one rating (the length of Shard::als_rated)
+    // the CSR's shape as of the last mf_als_prepare / mf_als_append (the entries live on the device only):
+    // off[rows + 1], and per row its ratings > 0; rows the model gained since have no entry here
+    std::vector<int64_t> off;
+    std::vector<int32_t> npos;
     // the conjugate-gradient half-sweeps (built on first use): the chunk items of every batch, batch b's
     // at [cg_work0[b], cg_work0[b + 1]), and the most long rows of one batch
     std::vector<mfhip::AlsCgWork> cg_work;
@@ -224,6 +233,9 @@ struct mf_ctx {
     int64_t cg_max_splits = 0;
     bool cg_ready = false;
   } als[2];
+  // ratings per work item of a long row and rows per launch, as mf_als_prepare read them (mf_als_append
+  // rebuilds the work lists with the same values)
+  int64_t als_chunk = 0, als_batch = 0;
   int64_t als_gram_slice = 0;  // rated rows per workgroup of k_als_gram (fixed in mf_als_prepare)
   // k > 128: normal-matrix slabs = workgroups per launch of the wide kernels (fixed in mf_als_prepare
   // from the device's CU count; MFHIP_TEST als_slabs=N caps it, results do not depend on it)
@@ -418,6 +430,21 @@ void als_cg_matvec(mf_ctx* ctx, int side, int32_t id, const AlsParams& P, const 
 void als_nnls_row(mf_ctx* ctx, int side, int32_t id, const AlsParams& P, double* x_out, int32_t* iters_out,
                   int32_t* reason_out);
 void als_nonneg_stats(mf_ctx* ctx, struct mf_als_nonneg_stats* out);
+// mf_als_append / mf_als_run_rows / mf_als_update (which checks everything mf_als_run_rows would refuse
+// before it appends)
+void als_append(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n);
+int64_t als_run_rows(mf_ctx* ctx, int side, const int32_t* ids, int64_t n_ids, const AlsParams& P);
+void als_update(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n, const AlsParams& P,
+                int32_t rounds, int64_t* solved_users, int64_t* solved_items);
+void als_debug_csr(mf_ctx* ctx, int side, int64_t* off_out, int32_t* cols_out, double* vals_out, int32_t* npos_out,
+                   int64_t cap_rows, int64_t cap_nnz, int64_t* rows_out, int64_t* nnz_out);
+// Where the entries of a side land when a batch is appended (the rule the append kernels follow): new_off
+// [new_rows + 1] from old_off[old_rows + 1] and the batch's rows (each < new_rows), and per batch entry j its
+// position in the new arrays; an old entry p of row x moves to p + new_off[x] - old_off[x].  mf_als_append
+// itself takes only new_off from here (batch_pos == null): k_als_place derives a batch entry's position from
+// the sorted keys; batch_pos states the same rule for mf_debug_als_append_placement.
+void als_append_placement(const int64_t* old_off, int64_t old_rows, const uint32_t* batch_row, int64_t n,
+                          int64_t new_rows, int64_t* new_off, int64_t* batch_pos);
 // nnls.cpp: mf_nnls_solve
 void nnls_solve_host(int32_t k, const double* A, const double* b, bool f64, double* x_out, int32_t* iters_out,
                      int32_t* reason_out);

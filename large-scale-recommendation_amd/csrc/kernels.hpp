@@ -439,4 +439,32 @@ size_t als_cg_state_elems(int k);
 int als_cg_capacity(int k, bool f64);
 void launch_als_cg(const AlsLaunch& L);
 
+// ---- kernels_als_append.hip: mf_als_append ------------------------------------------------------
+// One side's packed CSR (counterpart rows, rating bits of 4 or 8 bytes) with a batch appended, into fresh
+// arrays: row x keeps its old entries in their order, then takes the batch's in batch order.  Integer
+// moves only.  old_off[old_rows + 1] and new_off[new_rows + 1] are device arrays, new_rows >= old_rows;
+// brow / bcol / bval are the batch in the caller's order (every brow < new_rows), n < 2^31; new_off must be
+// old_off's counts plus the batch's (als_append_placement).  The batch alone is sorted (stable radix sort
+// by row, rocprim); every old entry is read once and written once, a workgroup per 2048 consecutive old
+// entries, whatever rows they belong to.  The launch may reallocate `sc`: drain the stream between two
+// launches that share it.
+struct AlsAppendScratch;
+struct AlsAppendLaunch {
+  hipStream_t st;
+  const int64_t* old_off;
+  int64_t old_rows, old_nnz;
+  const int64_t* new_off;
+  int64_t new_rows;
+  const int32_t* old_cols;
+  const void* old_vals;
+  int32_t* new_cols;
+  void* new_vals;
+  int elem_bytes;  // 4 or 8
+  const uint32_t* brow;
+  const uint32_t* bcol;
+  const void* bval;
+  int64_t n;
+};
+void launch_als_append(const AlsAppendLaunch& L, AlsAppendScratch& sc);
+
 }  // namespace mfhip

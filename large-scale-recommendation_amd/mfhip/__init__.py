@@ -5,7 +5,7 @@ this package is the Python equivalent of the Scala entry points that bind it.
 """
 from . import _lib, jvm, negsample, synth
 from ._lib import MFError, MFNoDeviceError, device_count, version
-from .als import ALS, MatrixFactorizationModel
+from .als import ALS, MatrixFactorizationModel, StreamingALS
 from .context import Context, Prequential, RankMetrics, block_update
 from .core import (FactorInitializer, FactorInitializerDescriptor, Factors, FactorUpdater, FactorVector,
                    ItemUpdate, MockFactorUpdater, PseudoRandomFactorInitializer,
@@ -22,6 +22,6 @@ __all__ = [
     "LearningRateMethod", "OnlineMF", "Rating", "FactorVector", "Factors", "FactorUpdater", "SGDUpdater",
     "MockFactorUpdater", "FactorInitializer", "FactorInitializerDescriptor", "PseudoRandomFactorInitializer",
     "PseudoRandomFactorInitializerDescriptor", "RandomFactorInitializer", "RandomFactorInitializerDescriptor",
-    "UserUpdate", "ItemUpdate", "read_ratings", "ALS", "MatrixFactorizationModel",
+    "UserUpdate", "ItemUpdate", "read_ratings", "ALS", "MatrixFactorizationModel", "StreamingALS",
     "RankMetrics", "RankingMetrics", "Prequential", "PrequentialEvaluator", "host_prequential",
 ]

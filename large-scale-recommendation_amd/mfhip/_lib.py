@@ -41,6 +41,9 @@ ALS_REG_WEIGHTED = 0
 ALS_REG_PLAIN = 1
 ALS_CG_MAX_STEPS = 256
 ALS_MAX_RANK = 256
+ALS_SOLVER_CHOLESKY = 0
+ALS_SOLVER_CG = 1
+ALS_SOLVER_NNLS = 2
 RANK_NMETRICS = 6  # precision, recall, ap, ndcg, rr, hit: a per-query row of mf_rank_eval
 PAIR_RANK_COLD = -1      # mf_pair_ranks: the model does not hold the query id or the candidate id
 PAIR_RANK_EXCLUDED = -2  # ... the pair itself is in the exclusion list
@@ -132,6 +135,19 @@ class mf_als_nonneg_stats(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("rows", "iterations", "max_iterations", "capped", "reason2", "nan_rows")]
 
 
+class mf_als_solve(C.Structure):
+    """One of the eight kinds of half-sweep, for mf_als_run_rows / mf_als_update."""
+    _fields_ = [
+        ("lambda_", C.c_double),
+        ("reg", C.c_int32),
+        ("implicit", C.c_int32),
+        ("alpha", C.c_double),
+        ("solver", C.c_int32),
+        ("cg_steps", C.c_int32),
+        ("reserved", C.c_int32 * 4),
+    ]
+
+
 # Every symbol include/mfhip.h declares (tests check the library exports all of them).
 EXPORTS = [
     "mf_params_init", "mf_last_error", "mf_version", "mf_device_count", "mf_create",
@@ -146,7 +162,7 @@ EXPORTS = [
     "mf_online_prequential", "mf_online_update_sampled", "mf_negative_draws", "mf_online_prequential_sampled",
     "mf_als_run_cg", "mf_als_run_implicit_cg", "mf_als_fit_cg", "mf_als_fit_implicit_cg",
     "mf_als_run_nonneg", "mf_als_run_implicit_nonneg", "mf_als_fit_nonneg", "mf_als_fit_implicit_nonneg",
-    "mf_als_nonneg_stats", "mf_nnls_solve",
+    "mf_als_nonneg_stats", "mf_nnls_solve", "mf_als_append", "mf_als_run_rows", "mf_als_update",
 ]
 # The test hooks include/mfhip_testing.h declares (not product surface; same library).
 TESTING_EXPORTS = [
@@ -154,7 +170,7 @@ TESTING_EXPORTS = [
     "mf_debug_plan_digest", "mf_fast_plan_window", "mf_fast_kernel_name", "mf_debug_build_flags",
     "mf_debug_device_bytes", "mf_debug_als_normal_eq", "mf_debug_als_gram", "mf_debug_als_normal_eq_implicit",
     "mf_debug_det_slot_table", "mf_debug_sys_placement", "mf_debug_rank_csr", "mf_debug_als_cg_matvec",
-    "mf_debug_als_cg_capacity", "mf_debug_als_nnls_row",
+    "mf_debug_als_cg_capacity", "mf_debug_als_nnls_row", "mf_debug_als_csr", "mf_debug_als_append_placement",
 ]
 
 _i32p = C.POINTER(C.c_int32)
@@ -267,6 +283,13 @@ def lib() -> C.CDLL:
         "mf_nnls_solve": (C.c_int, [C.c_int32, _f64p, _f64p, C.c_int, _f64p, _i32p, _i32p]),
         "mf_debug_als_nnls_row": (C.c_int, [_ctxp, C.c_int, C.c_int32, C.c_double, C.c_int32, C.c_double, _f64p,
                                             _i32p, _i32p]),
+        "mf_als_append": (C.c_int, [_ctxp, _i32p, _i32p, _f64p, C.c_int64]),
+        "mf_als_run_rows": (C.c_int, [_ctxp, C.c_int, _i32p, C.c_int64, C.POINTER(mf_als_solve), _i64p]),
+        "mf_als_update": (C.c_int, [_ctxp, _i32p, _i32p, _f64p, C.c_int64, C.POINTER(mf_als_solve), C.c_int32, _i64p,
+                                    _i64p]),
+        "mf_debug_als_csr": (C.c_int, [_ctxp, C.c_int, _i64p, _i32p, _f64p, _i32p, C.c_int64, C.c_int64, _i64p,
+                                       _i64p]),
+        "mf_debug_als_append_placement": (C.c_int, [_i64p, C.c_int64, _i32p, C.c_int64, C.c_int64, _i64p, _i64p]),
         "mf_debug_ring_schedule": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, _i32p, _i32p, _i32p, _i32p]),
         "mf_debug_det_slot_table": (C.c_int, [_i64p, _i32p, _i32p, C.c_int64, C.c_int64, C.c_int32, C.c_int64, _i64p,
                                               _i32p, _i32p, _i64p]),

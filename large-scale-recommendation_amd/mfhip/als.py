@@ -29,7 +29,7 @@ from typing import List, Tuple
 import numpy as np
 
 from . import _lib as L
-from .context import Context
+from .context import Context, als_solve
 from .dsgd import _columns, _pairs
 from .ranking import RankingMetrics
 
@@ -138,6 +138,95 @@ class ALS:
 
 
 SOLVERS = ("cholesky", "cg", "nnls")
+
+
+class StreamingALS:
+    """An ALS model that takes in new ratings (mf_als_append / mf_als_run_rows / mf_als_update): the rating
+    history stays on the device, a micro-batch is appended to it there and only the rows it touches are
+    solved again -- its users first, then its items.
+
+        s = StreamingALS(rank=32, lambda_=0.05, mode="fast")
+        s.fit(history, iterations=10)
+        s.update(batch)              # (users solved, items solved); a new user's ratings: fold-in
+        s.refit(2)                   # full half-sweeps over everything so far, nothing uploaded
+        s.model.recommendProducts(user, 10)
+    """
+
+    def __init__(self, rank: int, lambda_: float = 0.01, implicit: bool = False, alpha: float = 0.01,
+                 solver: str = "cholesky", cg_steps: int = 3, mode: str = "deterministic", seed: int = 0):
+        if int(rank) < 1 or int(rank) > L.ALS_MAX_RANK:
+            raise ValueError(f"rank must lie in 1 .. {L.ALS_MAX_RANK}")
+        if not float(lambda_) > 0:
+            raise ValueError("lambda_ must be > 0")
+        if solver not in SOLVERS:
+            raise ValueError(f"unknown ALS solver {solver!r}: one of {SOLVERS}")
+        if not 1 <= int(cg_steps) <= L.ALS_CG_MAX_STEPS:
+            raise ValueError(f"cg_steps must lie in 1 .. {L.ALS_CG_MAX_STEPS}")
+        if implicit and not (float(alpha) >= 0 and np.isfinite(alpha)):
+            raise ValueError("alpha must be finite and >= 0")
+        if mode not in ("deterministic", "fast"):
+            raise ValueError(f"unknown mode {mode!r}: 'deterministic' or 'fast'")
+        self.how = als_solve(lambda_, L.ALS_REG_WEIGHTED, implicit, alpha, solver, cg_steps)
+        self._rank, self._mode, self._seed = int(rank), mode, int(seed)
+        self._ctx = None
+
+    def _run(self, half_sweeps: int) -> None:
+        h, c = self.how, self._ctx
+        if h.solver == L.ALS_SOLVER_CG:
+            if h.implicit:
+                c.als_run_implicit_cg(half_sweeps, h.lambda_, h.alpha, h.reg, h.cg_steps)
+            else:
+                c.als_run_cg(half_sweeps, h.lambda_, h.reg, h.cg_steps)
+        elif h.solver == L.ALS_SOLVER_NNLS:
+            if h.implicit:
+                c.als_run_implicit_nonneg(half_sweeps, h.lambda_, h.alpha, h.reg)
+            else:
+                c.als_run_nonneg(half_sweeps, h.lambda_, h.reg)
+        elif h.implicit:
+            c.als_run_implicit(half_sweeps, h.lambda_, h.alpha, h.reg)
+        else:
+            c.als_run(half_sweeps, h.lambda_, h.reg)
+
+    def _fitted(self) -> Context:
+        if self._ctx is None:
+            raise RuntimeError("StreamingALS: call fit() first (an empty rating list is a valid start)")
+        return self._ctx
+
+    def fit(self, ratings, iterations: int = 10) -> "StreamingALS":
+        """The history so far: upload it (als_prepare) and run `iterations` full iterations."""
+        if int(iterations) < 0:
+            raise ValueError("iterations must be >= 0")
+        u, i, r = _columns(ratings)
+        if self._ctx is None:
+            self._ctx = ALS._context(self._rank, self._mode, self._seed)
+        self._ctx.als_prepare(u, i, r)
+        self._run(2 * int(iterations))
+        return self
+
+    def update(self, ratings, rounds: int = 1) -> Tuple[int, int]:
+        """A micro-batch: appended on the device, then `rounds` times its users and its items solved.
+        Returns the rows solved in the last round as (users, items)."""
+        if int(rounds) < 0:
+            raise ValueError("rounds must be >= 0")
+        u, i, r = _columns(ratings)
+        return self._fitted().als_update(u, i, r, self.how, int(rounds))
+
+    def refit(self, half_sweeps: int = 2) -> "StreamingALS":
+        """Full half-sweeps over the resident data (the item side first, as a fit's); nothing is uploaded."""
+        if int(half_sweeps) < 0:
+            raise ValueError("half_sweeps must be >= 0")
+        self._fitted()
+        self._run(int(half_sweeps))
+        return self
+
+    @property
+    def model(self) -> MatrixFactorizationModel:
+        return MatrixFactorizationModel(self._fitted())
+
+    def close(self) -> None:
+        if self._ctx is not None:
+            self._ctx.close()
+            self._ctx = None
 
 
 class _SolverALS:

@@ -26,6 +26,21 @@ def nnls_solve(A, b, f64: bool = True):
     return x, int(it.value), int(why.value)
 
 
+ALS_SOLVERS = {"cholesky": L.ALS_SOLVER_CHOLESKY, "cg": L.ALS_SOLVER_CG, "nnls": L.ALS_SOLVER_NNLS}
+
+
+def als_solve(lam: float, reg: int = L.ALS_REG_WEIGHTED, implicit: bool = False, alpha: float = 0.0,
+              solver: str = "cholesky", cg_steps: int = 3) -> L.mf_als_solve:
+    """The mf_als_solve of als_run_rows / als_update: which of the eight kinds of half-sweep solves the rows."""
+    if solver not in ALS_SOLVERS:
+        raise ValueError(f"unknown ALS solver {solver!r}: one of {tuple(ALS_SOLVERS)}")
+    how = L.mf_als_solve()
+    how.lambda_, how.reg = float(lam), int(reg)
+    how.implicit, how.alpha = int(bool(implicit)), float(alpha)
+    how.solver, how.cg_steps = ALS_SOLVERS[solver], int(cg_steps)
+    return how
+
+
 @dataclass
 class RankMetrics:
     """What mf_rank_eval returns (include/mfhip.h): counts, the six means over `queries`, and with
@@ -285,6 +300,51 @@ class Context:
         """mf_nnls_solve: (x [k], iterations, reason) of the non-negative solve on the host, in the kernels'
         order and in f32 or f64 arithmetic.  No GPU needed."""
         return nnls_solve(A, b, f64)
+
+    def als_append(self, u, i, r) -> None:
+        """mf_als_append: the ratings join the resident CSRs, which are then what als_prepare would have
+        built from everything so far; unseen ids are inserted as als_prepare inserts them."""
+        u, i, r = as_i32(u), as_i32(i), as_f64(r)
+        same_length(u, i, r)
+        check(L.lib().mf_als_append(self._h, ptr(u, C.c_int32), ptr(i, C.c_int32), ptr(r, C.c_double), len(u)))
+
+    def als_run_rows(self, side: int, ids, how: L.mf_als_solve) -> int:
+        """mf_als_run_rows: the named rows of `side` solved as a full half-sweep with `how` (als_solve) would
+        solve them now; returns the number of rows solved (unknown and unrated ids are skipped)."""
+        ids = as_i32(ids)
+        solved = C.c_int64(0)
+        check(L.lib().mf_als_run_rows(self._h, int(side), ptr(ids, C.c_int32), len(ids), C.byref(how),
+                                      C.byref(solved)))
+        return int(solved.value)
+
+    def als_update(self, u, i, r, how: L.mf_als_solve, rounds: int = 1) -> Tuple[int, int]:
+        """mf_als_update: als_append, then `rounds` times the batch's users and then its items solved
+        (users first: a new user's row is random until solved); returns the last round's (users, items)."""
+        u, i, r = as_i32(u), as_i32(i), as_f64(r)
+        same_length(u, i, r)
+        su, si = C.c_int64(0), C.c_int64(0)
+        check(L.lib().mf_als_update(self._h, ptr(u, C.c_int32), ptr(i, C.c_int32), ptr(r, C.c_double), len(u),
+                                    C.byref(how), int(rounds), C.byref(su), C.byref(si)))
+        return int(su.value), int(si.value)
+
+    def als_csr(self, side: int):
+        """(off [rows + 1], cols [nnz], vals [nnz] as f64, npos [rows]) of the resident CSR of `side`
+        (mf_debug_als_csr)."""
+        rows, nnz = C.c_int64(0), C.c_int64(0)
+        one64, one32, onef = np.zeros(1, np.int64), np.zeros(1, np.int32), np.zeros(1, np.float64)
+        st = L.lib().mf_debug_als_csr(self._h, int(side), ptr(one64, C.c_int64), ptr(one32, C.c_int32),
+                                      ptr(onef, C.c_double), ptr(one32, C.c_int32), 0, 0,
+                                      C.byref(rows), C.byref(nnz))
+        if st not in (L.MF_OK, L.MF_ERR_CAPACITY):
+            check(st)
+        off = np.zeros(rows.value + 1, np.int64)
+        cols = np.zeros(max(nnz.value, 1), np.int32)
+        vals = np.zeros(max(nnz.value, 1), np.float64)
+        npos = np.zeros(max(rows.value, 1), np.int32)
+        check(L.lib().mf_debug_als_csr(self._h, int(side), ptr(off, C.c_int64), ptr(cols, C.c_int32),
+                                       ptr(vals, C.c_double), ptr(npos, C.c_int32), rows.value, nnz.value,
+                                       C.byref(rows), C.byref(nnz)))
+        return off, cols[:nnz.value], vals[:nnz.value], npos[:rows.value]
 
     # -- factors ---------------------------------------------------------------
     def num_factors(self, side: int) -> int:
