@@ -645,6 +645,59 @@ int mf_online_prequential_sampled(mf_ctx* ctx, const int32_t* users, const int32
                                   int64_t* touched_users, int64_t* touched_items,
                                   int32_t negatives, double negative_rating, int64_t seed, int64_t first_event,
                                   int32_t* sampled_items_out /* [n * negatives] or NULL */);
+/* The resident seen set: the distinct (user, item) pairs the model's readers hide ("filter already seen"),
+   built once and kept on the device keyed by factor row, so that the four calls below name it instead of
+   passing -- and resolving, uploading and sorting -- the same exclusion arrays in every call.
+   mf_seen_set replaces the set with the distinct pairs given; n == 0 leaves an empty set.  mf_seen_add forms
+   the union with what is held (only the batch is sorted; on a context with no set it is mf_seen_set).  A
+   pair naming a user or item id the model does not hold at the time of the call is dropped, mf_recommend's
+   rule for exclusion pairs, and counted in *ignored_out (may be NULL); duplicates count once.
+   mf_seen_from_als replaces the set with the distinct (user, item) pairs of the data mf_als_prepare /
+   mf_als_append left on the device: nothing is uploaded, ratings of every sign count (a rated pair is a seen
+   pair).  It is a snapshot: a later mf_als_append does not change the set, the caller follows it with
+   mf_seen_add of the same batch.  mf_seen_clear leaves no set; mf_seen_count gives the distinct pairs held
+   (64-bit; 0 with no set).
+   Lifetime.  The set survives everything that only adds rows -- mf_online_update*, mf_set_factors,
+   mf_load_model, mf_als_append, every run call -- and a row gained after the set was built has no seen pairs
+   until some are added.  mf_dsgd_prepare / mf_dsgd_fit rebuild the rows and leave no set, as they invalidate
+   the ALS data.  The set is not part of mf_save_model.
+   Readers.  mf_recommend_seen, mf_rank_eval_seen and mf_pair_ranks_seen return, bit for bit, what
+   mf_recommend, mf_rank_eval and mf_pair_ranks return when given every pair of the set as excl_* arrays: ids,
+   scores, counts, ranks, codes, valid_out, every metric and sum, under all of their rules ("a pair both
+   excluded and in the ground truth stays in G and is never hit" among them).  Both query sides work: user
+   queries exclude items, item queries users (that orientation of the table is made from the other on first
+   use and kept until the set changes; it needs a set of fewer than 2^31 - 1 pairs).  No set, or an empty one,
+   is n_excl == 0.  mf_online_prequential_seen is mf_online_prequential_sampled with the set as its
+   exclusions (negatives == 0: mf_online_prequential for the two arrival-order flavours;
+   MF_ONLINE_SPARK_SWEEP is refused as there); with add_events != 0 it ends with mf_seen_add(users, items,
+   n), when every id of the batch is known, so that the next batch's events find these seen: the prequential
+   loop a caller would otherwise write by hand.
+   Errors.  MF_ERR_INVALID: a NULL context, a negative count, a NULL array with a positive count, n >= 2^31 -
+   1 pairs in one call (mf_seen_from_als: as many ratings in the prepared data), and whatever the namesake
+   refuses.  MF_ERR_STATE: every call here on a rank-mode context; mf_seen_from_als wherever mf_als_run would
+   fail for want of prepared data.  MF_ERR_NOT_FITTED from the three readers as from their namesakes.  All
+   validation runs before anything changes.  A context on several devices keeps the set on its first. */
+int mf_seen_set(mf_ctx* ctx, const int32_t* users, const int32_t* items, int64_t n, int64_t* ignored_out);
+int mf_seen_add(mf_ctx* ctx, const int32_t* users, const int32_t* items, int64_t n, int64_t* ignored_out);
+int mf_seen_from_als(mf_ctx* ctx);
+int mf_seen_clear(mf_ctx* ctx);
+int mf_seen_count(mf_ctx* ctx, int64_t* pairs);
+int mf_recommend_seen(mf_ctx* ctx, int query_side, const int32_t* queries, int64_t n_queries, int32_t top_n,
+                      int32_t* ids_out, double* scores_out, int32_t* counts_out);
+int mf_rank_eval_seen(mf_ctx* ctx, int query_side,
+                      const int32_t* gt_query, const int32_t* gt_cand, int64_t n_gt,
+                      int32_t top_n, mf_rank_metrics* out,
+                      int32_t* q_ids_out, int32_t* q_counts_out, double* q_metrics_out, int64_t cap);
+int mf_pair_ranks_seen(mf_ctx* ctx, int query_side,
+                       const int32_t* queries, const int32_t* cands, int64_t n,
+                       int32_t* rank_out, int32_t* valid_out /* or NULL */, double* score_out /* or NULL */);
+int mf_online_prequential_seen(mf_ctx* ctx, const int32_t* users, const int32_t* items, const double* ratings,
+                               int64_t n, int flavour, int32_t top_n,
+                               mf_prequential* out, int32_t* rank_out /* [n] or NULL */,
+                               int64_t* touched_users, int64_t* touched_items,
+                               int32_t negatives, double negative_rating, int64_t seed, int64_t first_event,
+                               int32_t* sampled_items_out /* [n * negatives] or NULL */,
+                               int add_events);
 /* Vectors for specific ids (found[j] = 0 for unknown ids). */
 int mf_lookup(mf_ctx* ctx, int side, const int32_t* ids, int64_t n, double* vecs_out,
               uint8_t* found);

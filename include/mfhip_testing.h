@@ -134,6 +134,22 @@ int mf_debug_als_csr(mf_ctx* ctx, int side, int64_t* off_out, int32_t* cols_out,
    checked through mf_debug_als_csr on the device. */
 int mf_debug_als_append_placement(const int64_t* old_off, int64_t old_rows, const int32_t* batch_row, int64_t n,
                                   int64_t new_rows, int64_t* new_off_out, int64_t* batch_pos_out);
+/* mf_debug_seen_csr: the resident seen set's table of `side` copied back (MF_SIDE_ITEM: the item-major table,
+   built here if it is not there, as an item query would).  *rows_out = the rows `side` holds now, *nnz_out =
+   the distinct pairs held; row_ids_out[*rows_out] = the id of every factor row, off_out[*rows_out + 1] and
+   entries_out[*nnz_out] = the table as the readers see it, padded to the present rows: per factor row its
+   distinct counterpart factor rows, ascending; entry_ids_out (may be NULL) = the ids of those counterpart
+   rows.  No set reads as an empty one.  *rows_out and *nnz_out are always set; MF_ERR_CAPACITY when cap_rows <
+   *rows_out or cap_nnz < *nnz_out (nothing else is written then). */
+int mf_debug_seen_csr(mf_ctx* ctx, int side, int32_t* row_ids_out, int64_t* off_out, int32_t* entries_out,
+                      int32_t* entry_ids_out, int64_t cap_rows, int64_t cap_nnz, int64_t* rows_out, int64_t* nnz_out);
+/* mf_debug_seen_merge_placement: the rule mf_seen_add's kernels follow, on the host (no GPU needed).  Keys are
+   (row << 32) | counterpart row.  old_keys[n_old]: the table's keys, distinct and ascending; batch_keys[n_batch]:
+   a batch in any order, duplicates allowed.  With `novel` the distinct batch keys the table does not hold, in
+   ascending order (*n_novel_out of them): old_pos_out[p] = p + #(novel keys < old_keys[p]) and novel_pos_out[i]
+   = i + #(old keys < novel[i]), the positions in the merged arrays; novel_pos_out has room for n_batch. */
+int mf_debug_seen_merge_placement(const uint64_t* old_keys, int64_t n_old, const uint64_t* batch_keys, int64_t n_batch,
+                                  int64_t* old_pos_out, int64_t* novel_pos_out, int64_t* n_novel_out);
 
 #ifdef __cplusplus
 }

@@ -117,6 +117,26 @@ public final class MfHip {
                                                      double[] metricsOut, int[] ranksOut, int negatives,
                                                      double negRating, long seed, long firstEvent,
                                                      int[] sampledOut);
+  // the resident seen set (mf_seen_*): the distinct (user, item) pairs the readers hide, kept on the device.
+  // seenSet replaces it, seenAdd forms the union (both return the pairs ignored for an unknown id),
+  // seenFromAls takes the pairs of the prepared ALS data without an upload.  The four *Seen readers are
+  // recommend / rankEval / pairRanks / onlinePrequentialSampled with the set as their exclusions, bit for
+  // bit; addEvents: the batch joins the set after the update
+  public static native long seenSet(long ctx, int[] users, int[] items);
+  public static native long seenAdd(long ctx, int[] users, int[] items);
+  public static native void seenFromAls(long ctx);
+  public static native void seenClear(long ctx);
+  public static native long seenCount(long ctx);
+  public static native void recommendSeen(long ctx, int querySide, int[] queries, int topN,
+                                          int[] idsOut, double[] scoresOut, int[] countsOut);
+  public static native void rankEvalSeen(long ctx, int querySide, int[] gtQuery, int[] gtCand, int topN,
+                                         double[] metricsOut);
+  public static native void pairRanksSeen(long ctx, int querySide, int[] queries, int[] cands,
+                                          int[] ranksOut, int[] validOut, double[] scoresOut);
+  public static native void onlinePrequentialSeen(long ctx, int[] users, int[] items, double[] r,
+                                                  int flavour, int topN, double[] metricsOut, int[] ranksOut,
+                                                  int negatives, double negRating, long seed, long firstEvent,
+                                                  int[] sampledOut, boolean addEvents);
   public static native void blockUpdate(long ctx, double[] r, int[] uidx, int[] iidx,
                                         double[] users, int[] uomega, double[] items, int[] iomega,
                                         int k, int iteration, int ratingBlockId, long seed,

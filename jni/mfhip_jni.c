@@ -652,6 +652,135 @@ JNIEXPORT void JNICALL JFN(onlinePrequentialSampled)(JNIEnv* env, jclass c, jlon
   check(env, st);
 }
 
+/* ---- the resident seen set (mf_seen_*) and the four readers that take it ---- */
+static jlong seen_put(JNIEnv* env, jlong h, jintArray u, jintArray i, int add) {
+  if (require(env, u && i && len(env, u) == len(env, i), "users and items must match in length")) return 0;
+  const jsize n = len(env, u);
+  Elems e[2];
+  const jarray arr[2] = {u, i};
+  const int kind[2] = {kInt, kInt};
+  if (acquire_all(env, e, arr, kind, 2)) return 0;
+  int64_t ignored = 0;
+  const int32_t* pu = n ? (const int32_t*)e[0].p : NULL;
+  const int32_t* pi = n ? (const int32_t*)e[1].p : NULL;
+  int st = add ? mf_seen_add(CTX(h), pu, pi, n, &ignored) : mf_seen_set(CTX(h), pu, pi, n, &ignored);
+  for (int x = 1; x >= 0; --x) release(env, &e[x], JNI_ABORT);
+  check(env, st);
+  return (jlong)ignored;
+}
+
+JNIEXPORT jlong JNICALL JFN(seenSet)(JNIEnv* env, jclass c, jlong h, jintArray u, jintArray i) {
+  return seen_put(env, h, u, i, 0);
+}
+
+JNIEXPORT jlong JNICALL JFN(seenAdd)(JNIEnv* env, jclass c, jlong h, jintArray u, jintArray i) {
+  return seen_put(env, h, u, i, 1);
+}
+
+JNIEXPORT void JNICALL JFN(seenFromAls)(JNIEnv* env, jclass c, jlong h) { check(env, mf_seen_from_als(CTX(h))); }
+
+JNIEXPORT void JNICALL JFN(seenClear)(JNIEnv* env, jclass c, jlong h) { check(env, mf_seen_clear(CTX(h))); }
+
+JNIEXPORT jlong JNICALL JFN(seenCount)(JNIEnv* env, jclass c, jlong h) {
+  int64_t pairs = 0;
+  check(env, mf_seen_count(CTX(h), &pairs));
+  return (jlong)pairs;
+}
+
+JNIEXPORT void JNICALL JFN(recommendSeen)(JNIEnv* env, jclass c, jlong h, jint side, jintArray q, jint top,
+                                          jintArray ids, jdoubleArray scores, jintArray counts) {
+  if (require(env, q && ids && counts, "queries, idsOut and countsOut must not be null")) return;
+  if (require(env, top >= 1 && top <= MF_RECOMMEND_MAX_TOP, "topN out of range")) return;
+  const jsize n = len(env, q);
+  if (require(env, (jlong)len(env, ids) >= (jlong)n * top && (!scores || (jlong)len(env, scores) >= (jlong)n * top) &&
+                       len(env, counts) >= n,
+              "idsOut / scoresOut must hold queries.length * topN entries and countsOut queries.length"))
+    return;
+  Elems e[4];
+  const jarray arr[4] = {q, ids, scores, counts};
+  const int kind[4] = {kInt, kInt, kDouble, kInt};
+  if (acquire_all(env, e, arr, kind, 4)) return;
+  int st = mf_recommend_seen(CTX(h), side, (const int32_t*)e[0].p, n, top, (int32_t*)e[1].p, (double*)e[2].p,
+                             (int32_t*)e[3].p);
+  for (int x = 3; x >= 1; --x) release(env, &e[x], st == MF_OK ? 0 : JNI_ABORT);
+  release(env, &e[0], JNI_ABORT);
+  check(env, st);
+}
+
+JNIEXPORT void JNICALL JFN(rankEvalSeen)(JNIEnv* env, jclass c, jlong h, jint side, jintArray gq, jintArray gc, jint top,
+                                         jdoubleArray metrics) {
+  if (require(env, gq && gc && len(env, gq) == len(env, gc), "gtQuery and gtCand must match in length")) return;
+  if (require(env, metrics && len(env, metrics) >= 8, "metricsOut must hold 8 entries")) return;
+  if (require(env, top >= 1 && top <= MF_RECOMMEND_MAX_TOP, "topN out of range")) return;
+  const jsize ng = len(env, gq);
+  Elems e[3];
+  const jarray arr[3] = {gq, gc, metrics};
+  const int kind[3] = {kInt, kInt, kDouble};
+  if (acquire_all(env, e, arr, kind, 3)) return;
+  mf_rank_metrics m;
+  int st = mf_rank_eval_seen(CTX(h), side, ng ? (const int32_t*)e[0].p : NULL, ng ? (const int32_t*)e[1].p : NULL, ng,
+                             top, &m, NULL, NULL, NULL, 0);
+  if (st == MF_OK) {
+    double* o = (double*)e[2].p;
+    o[0] = (double)m.queries;
+    o[1] = (double)m.hits;
+    o[2] = m.precision;
+    o[3] = m.recall;
+    o[4] = m.map;
+    o[5] = m.ndcg;
+    o[6] = m.mrr;
+    o[7] = m.hit_rate;
+  }
+  release(env, &e[2], st == MF_OK ? 0 : JNI_ABORT);
+  for (int x = 1; x >= 0; --x) release(env, &e[x], JNI_ABORT);
+  check(env, st);
+}
+
+JNIEXPORT void JNICALL JFN(pairRanksSeen)(JNIEnv* env, jclass c, jlong h, jint side, jintArray q, jintArray cd,
+                                          jintArray ranks, jintArray valid, jdoubleArray scores) {
+  if (require(env, q && cd && len(env, q) == len(env, cd), "queries and cands must match in length")) return;
+  const jsize n = len(env, q);
+  if (require(env, ranks && len(env, ranks) >= n, "ranksOut must hold one entry per pair")) return;
+  if (require(env, (!valid || len(env, valid) >= n) && (!scores || len(env, scores) >= n),
+              "validOut / scoresOut must be null or hold one entry per pair"))
+    return;
+  Elems e[5];
+  const jarray arr[5] = {q, cd, ranks, valid, scores};
+  const int kind[5] = {kInt, kInt, kInt, kInt, kDouble};
+  if (acquire_all(env, e, arr, kind, 5)) return;
+  int st = mf_pair_ranks_seen(CTX(h), side, n ? (const int32_t*)e[0].p : NULL, n ? (const int32_t*)e[1].p : NULL, n,
+                              (int32_t*)e[2].p, (int32_t*)e[3].p, (double*)e[4].p);
+  for (int x = 4; x >= 2; --x) release(env, &e[x], st == MF_OK ? 0 : JNI_ABORT);
+  for (int x = 1; x >= 0; --x) release(env, &e[x], JNI_ABORT);
+  check(env, st);
+}
+
+JNIEXPORT void JNICALL JFN(onlinePrequentialSeen)(JNIEnv* env, jclass c, jlong h, jintArray u, jintArray i,
+                                                  jdoubleArray r, jint flavour, jint top, jdoubleArray metrics,
+                                                  jintArray ranks, jint negatives, jdouble negRating, jlong seed,
+                                                  jlong firstEvent, jintArray sampled, jboolean addEvents) {
+  if (require(env, u && i && r && len(env, u) == len(env, i) && len(env, u) == len(env, r),
+              "users, items and ratings must match in length"))
+    return;
+  const jsize n = len(env, u);
+  if (require(env, metrics && len(env, metrics) >= 12, "metricsOut must hold 12 entries")) return;
+  if (require(env, !ranks || len(env, ranks) >= n, "ranksOut must be null or hold one entry per event")) return;
+  if (sampled_shape(env, n, negatives, sampled)) return;
+  Elems e[6];
+  const jarray arr[6] = {u, i, r, metrics, ranks, sampled};
+  const int kind[6] = {kInt, kInt, kDouble, kDouble, kInt, kInt};
+  if (acquire_all(env, e, arr, kind, 6)) return;
+  mf_prequential m;
+  int st = mf_online_prequential_seen(CTX(h), n ? (const int32_t*)e[0].p : NULL, n ? (const int32_t*)e[1].p : NULL,
+                                      n ? (const double*)e[2].p : NULL, n, flavour, top, &m, (int32_t*)e[4].p, NULL,
+                                      NULL, negatives, negRating, seed, firstEvent, (int32_t*)e[5].p,
+                                      addEvents ? 1 : 0);
+  if (st == MF_OK) store_prequential((double*)e[3].p, &m);
+  for (int x = 5; x >= 3; --x) release(env, &e[x], st == MF_OK ? 0 : JNI_ABORT);
+  for (int x = 2; x >= 0; --x) release(env, &e[x], JNI_ABORT);
+  check(env, st);
+}
+
 typedef int (*eval_fn)(JNIEnv*, jlong, const int32_t*, const int32_t*, const double*, jsize, jdouble, double*);
 
 static int call_rmse(JNIEnv* env, jlong h, const int32_t* u, const int32_t* i, const double* r, jsize n, jdouble unused,

@@ -368,6 +368,156 @@ int mf_debug_rank_csr(mf_ctx* ctx, int query_side, int ground_truth, const int32
   });
 }
 
+// ---- the resident seen set and its four readers ----------------------------------------------------------
+namespace {
+// what the set calls share: a single-process context whose first shard holds the table
+void seen_check(mf_ctx* ctx, const char* who) {
+  MF_REQUIRE(ctx, "null context");
+  if (ctx->rank_mode)
+    fail(MF_ERR_STATE, std::string(who) + " runs on a single-process context; a rank-mode context (mf_create_rank) "
+                                          "holds only its own users' rows");
+}
+int seen_put_entry(mf_ctx* ctx, const int32_t* u, const int32_t* i, int64_t n, bool add, int64_t* ignored_out,
+                   const char* who) {
+  return guarded([&] {
+    MF_REQUIRE(ctx, "null context");
+    MF_REQUIRE(n >= 0, "negative count");
+    MF_REQUIRE(n == 0 || (u && i), "null pair list");
+    MF_REQUIRE(n < (int64_t{1} << 31) - 1, "fewer than 2^31 - 1 pairs per call");
+    seen_check(ctx, who);
+    require_healthy(ctx);
+    seen_put(ctx, u, i, n, add, ignored_out);
+  });
+}
+}  // namespace
+
+int mf_seen_set(mf_ctx* ctx, const int32_t* users, const int32_t* items, int64_t n, int64_t* ignored_out) {
+  return seen_put_entry(ctx, users, items, n, false, ignored_out, "mf_seen_set");
+}
+
+int mf_seen_add(mf_ctx* ctx, const int32_t* users, const int32_t* items, int64_t n, int64_t* ignored_out) {
+  return seen_put_entry(ctx, users, items, n, true, ignored_out, "mf_seen_add");
+}
+
+int mf_seen_from_als(mf_ctx* ctx) {
+  return guarded([&] {
+    seen_check(ctx, "mf_seen_from_als");
+    seen_from_als(ctx);
+  });
+}
+
+int mf_seen_clear(mf_ctx* ctx) {
+  return guarded([&] {
+    seen_check(ctx, "mf_seen_clear");
+    seen_clear(ctx);
+  });
+}
+
+int mf_seen_count(mf_ctx* ctx, int64_t* pairs) {
+  return guarded([&] {
+    MF_REQUIRE(ctx && pairs, "null argument");
+    seen_check(ctx, "mf_seen_count");
+    *pairs = seen_count(ctx);
+  });
+}
+
+int mf_recommend_seen(mf_ctx* ctx, int query_side, const int32_t* queries, int64_t n_queries, int32_t top_n,
+                      int32_t* ids_out, double* scores_out, int32_t* counts_out) {
+  return guarded([&] {
+    MF_REQUIRE(ctx, "null context");
+    MF_REQUIRE(query_side == MF_SIDE_USER || query_side == MF_SIDE_ITEM, "bad side");
+    MF_REQUIRE(top_n >= 1 && top_n <= MF_RECOMMEND_MAX_TOP,
+               "top_n must be in [1, " + std::to_string(MF_RECOMMEND_MAX_TOP) + "]");
+    MF_REQUIRE(n_queries >= 0, "negative count");
+    MF_REQUIRE(n_queries == 0 || (queries && ids_out && counts_out), "null argument");
+    rank_check(ctx, query_side, "mf_recommend_seen");
+    if (n_queries == 0) return;
+    recommend(ctx, query_side, queries, n_queries, top_n, nullptr, nullptr, 0, ids_out, scores_out, counts_out, true);
+  });
+}
+
+int mf_rank_eval_seen(mf_ctx* ctx, int query_side, const int32_t* gt_query, const int32_t* gt_cand, int64_t n_gt,
+                      int32_t top_n, mf_rank_metrics* out, int32_t* q_ids_out, int32_t* q_counts_out,
+                      double* q_metrics_out, int64_t cap) {
+  return guarded([&] {
+    MF_REQUIRE(ctx, "null context");
+    MF_REQUIRE(out, "out is null");
+    MF_REQUIRE(query_side == MF_SIDE_USER || query_side == MF_SIDE_ITEM, "bad side");
+    MF_REQUIRE(top_n >= 1 && top_n <= MF_RECOMMEND_MAX_TOP,
+               "top_n must be in [1, " + std::to_string(MF_RECOMMEND_MAX_TOP) + "]");
+    MF_REQUIRE(n_gt >= 0, "negative count");
+    MF_REQUIRE(n_gt == 0 || (gt_query && gt_cand), "null ground-truth list");
+    const int given = (q_ids_out != nullptr) + (q_counts_out != nullptr) + (q_metrics_out != nullptr);
+    MF_REQUIRE(given == 0 || given == 3, "per-query outputs: give all three arrays or none");
+    MF_REQUIRE(given == 0 || cap >= 0, "negative count");
+    rank_check(ctx, query_side, "mf_rank_eval_seen");
+    rank_eval(ctx, query_side, gt_query, gt_cand, n_gt, top_n, nullptr, nullptr, 0, out, q_ids_out, q_counts_out,
+              q_metrics_out, cap, true);
+  });
+}
+
+int mf_pair_ranks_seen(mf_ctx* ctx, int query_side, const int32_t* queries, const int32_t* cands, int64_t n,
+                       int32_t* rank_out, int32_t* valid_out, double* score_out) {
+  return guarded([&] {
+    MF_REQUIRE(ctx, "null context");
+    MF_REQUIRE(query_side == MF_SIDE_USER || query_side == MF_SIDE_ITEM, "bad side");
+    MF_REQUIRE(n >= 0, "negative count");
+    MF_REQUIRE(n == 0 || (queries && cands && rank_out), "null argument");
+    rank_check(ctx, query_side, "mf_pair_ranks_seen");
+    pair_ranks(ctx, query_side, queries, cands, n, nullptr, nullptr, 0, rank_out, valid_out, score_out, true);
+  });
+}
+
+int mf_online_prequential_seen(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n, int flavour,
+                               int32_t top_n, mf_prequential* out, int32_t* rank_out, int64_t* touched_users,
+                               int64_t* touched_items, int32_t negatives, double negative_rating, int64_t seed,
+                               int64_t first_event, int32_t* sampled_items_out, int add_events) {
+  return guarded([&] {
+    // everything mf_online_prequential_sampled would refuse is refused here, before anything changes
+    const NegSampling neg{negatives, negative_rating, seed, first_event};
+    check_negative_sampling(neg);
+    MF_REQUIRE(ctx, "null context");
+    MF_REQUIRE(out, "out is null");
+    MF_REQUIRE(top_n >= 1 && top_n <= MF_RECOMMEND_MAX_TOP,
+               "top_n must be in [1, " + std::to_string(MF_RECOMMEND_MAX_TOP) + "]");
+    MF_REQUIRE(n >= 0, "negative count");
+    MF_REQUIRE(n == 0 || (u && i && r), "bad rating arrays");
+    if (ctx->rank_mode)
+      fail(MF_ERR_STATE, "mf_online_prequential_seen runs on a single-process context; a rank-mode context "
+                         "(mf_create_rank) holds only its own users' rows");
+    MF_REQUIRE(ctx->shards.size() == 1, "online updates run on a single-device context");
+    MF_REQUIRE(flavour >= MF_ONLINE_NEXT_FACTORS && flavour < MF_ONLINE_SPARK_SWEEP,
+               "MF_ONLINE_NEXT_FACTORS or MF_ONLINE_DELTA: MF_ONLINE_SPARK_SWEEP has no sampled form");
+    MF_REQUIRE(n < (int64_t{1} << 31) - 1 && n * (1 + negatives) < (int64_t{1} << 31),
+               "a sampled batch holds fewer than 2^31 updates");
+    require_healthy(ctx);
+    det_spec_wait(ctx, true);  // new ids change the layouts the builds read
+    online_prequential_seen(ctx, u, i, r, n, flavour, top_n, neg, sampled_items_out, out, rank_out, touched_users,
+                            touched_items, add_events != 0);
+  });
+}
+
+int mf_debug_seen_csr(mf_ctx* ctx, int side, int32_t* row_ids_out, int64_t* off_out, int32_t* entries_out,
+                      int32_t* entry_ids_out, int64_t cap_rows, int64_t cap_nnz, int64_t* rows_out, int64_t* nnz_out) {
+  return guarded([&] {
+    MF_REQUIRE(ctx && row_ids_out && off_out && entries_out && rows_out && nnz_out, "null argument");
+    MF_REQUIRE(side == MF_SIDE_USER || side == MF_SIDE_ITEM, "bad side");
+    MF_REQUIRE(cap_rows >= 0 && cap_nnz >= 0, "negative count");
+    seen_check(ctx, "mf_debug_seen_csr");
+    seen_debug_csr(ctx, side, row_ids_out, off_out, entries_out, entry_ids_out, cap_rows, cap_nnz, rows_out, nnz_out);
+  });
+}
+
+int mf_debug_seen_merge_placement(const uint64_t* old_keys, int64_t n_old, const uint64_t* batch_keys, int64_t n_batch,
+                                  int64_t* old_pos_out, int64_t* novel_pos_out, int64_t* n_novel_out) {
+  return guarded([&] {
+    MF_REQUIRE(n_old >= 0 && n_batch >= 0, "negative count");
+    MF_REQUIRE(n_novel_out && (n_old == 0 || (old_keys && old_pos_out)) && (n_batch == 0 || (batch_keys && novel_pos_out)),
+               "null argument");
+    seen_merge_placement(old_keys, n_old, batch_keys, n_batch, old_pos_out, novel_pos_out, n_novel_out);
+  });
+}
+
 int mf_als_prepare(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n) {
   return guarded([&] {
     MF_REQUIRE(ctx, "null context");

@@ -165,6 +165,21 @@ struct AlsAppendScratch {
   DevBuf urow, irow, val, key, iota, idx, tmp;
 };
 
+// The resident seen set (seen.cpp, kernels_seen.hip): per orientation [user-major, item-major] one CSR over
+// that side's factor rows, off (int64, rows[side] + 1) and ent (int32, the row's distinct counterpart rows,
+// ascending).  The user-major table is the set; the item-major one is made from it on first use and dropped
+// (item_valid) whenever the set changes.  in / lb: a batch's rows as uploaded and, per sorted key, the old
+// keys below it; iota: the identity the pair-rank kernels take as qpos; qbeg / qend: one recommend batch's
+// exclusion ranges.
+struct SeenTable {
+  DevBuf off[2], ent[2];
+  int64_t rows[2] = {0, 0};
+  int64_t nnz = 0;  // distinct pairs held
+  bool have = false, item_valid = false;
+  DevBuf in, lb, nov_off, nov_ent, iota, qbeg, qend;
+  int64_t iota_n = 0;
+};
+
 // Pinned host staging buffer.
 class PinnedBuf {
  public:

@@ -1,7 +1,7 @@
 // context.hpp -- the context (mf_ctx), its shards, and the helpers more than one host translation
 // unit uses.  Private to the host side: included by the .cpp files only (mfhip.cpp, dsgd_det.cpp,
-// dsgd_fast.cpp, ring.cpp, abi.cpp, online.cpp, eval.cpp, rank_eval.cpp, pair_rank.cpp, als.cpp), never by a .hip file or by
-// kernels.hpp / plan.hpp; placement.cpp, which knows no context, does without it.
+// dsgd_fast.cpp, ring.cpp, abi.cpp, online.cpp, eval.cpp, rank_eval.cpp, pair_rank.cpp, als.cpp, seen.cpp),
+// never by a .hip file or by kernels.hpp / plan.hpp; placement.cpp, which knows no context, does without it.
 #pragma once
 
 #include <array>
@@ -137,6 +137,8 @@ struct Shard {
   // rk_* sums): the pairs' factor rows (query rows, then candidate rows), the two parts of their keys,
   // and the per-pair rank / list length / score
   DevBuf pr_in, pr_ord, pr_tid, pr_rank, pr_valid, pr_score;
+  // the resident seen set (mf_seen_*; on the context's first shard, like the evaluation it serves)
+  SeenTable seen;
   // ALS (mf_als_prepare): per solved side [user, item] the CSR (counterpart rows, ratings) and the
   // work lists; the long rows' partial systems of one launch; the testing hook's output
   DevBuf als_cols[2], als_vals[2], als_items[2], als_splits[2], als_part, als_dump;
@@ -381,7 +383,8 @@ void allgather_items(mf_ctx* ctx);
 EvalOut evaluate(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n,
                  const int32_t* mult, double lambda, double* pred_out, uint8_t* found_out);
 void recommend(mf_ctx* ctx, int qside, const int32_t* queries, int64_t nq, int32_t top_n, const int32_t* eq,
-               const int32_t* ec, int64_t ne, int32_t* ids_out, double* scores_out, int32_t* counts_out);
+               const int32_t* ec, int64_t ne, int32_t* ids_out, double* scores_out, int32_t* counts_out,
+               bool seen = false);
 void get_factors(mf_ctx* ctx, int side, int32_t* ids, double* vecs, int64_t cap, int64_t* written);
 void lookup_factors(mf_ctx* ctx, int side, const int32_t* ids, int64_t n, double* vecs_out, uint8_t* found);
 
@@ -389,7 +392,7 @@ void lookup_factors(mf_ctx* ctx, int side, const int32_t* ids, int64_t n, double
 const std::vector<double>& gain_table();  // 128 gains 1 / log(i + 2), then their 129 prefix sums
 void rank_eval(mf_ctx* ctx, int qside, const int32_t* gq, const int32_t* gc, int64_t ng, int32_t top_n,
                const int32_t* eq, const int32_t* ec, int64_t ne, mf_rank_metrics* out, int32_t* q_ids_out,
-               int32_t* q_counts_out, double* q_metrics_out, int64_t cap);
+               int32_t* q_counts_out, double* q_metrics_out, int64_t cap, bool seen = false);
 void debug_rank_csr(mf_ctx* ctx, int qside, bool gt, const int32_t* q, const int32_t* c, int64_t n, int32_t* q_ids_out,
                     int64_t* off_out, int32_t* entries_out, int64_t cap_q, int64_t cap_e, int64_t* nq_out,
                     int64_t* ne_out);
@@ -398,7 +401,8 @@ void debug_rank_csr(mf_ctx* ctx, int qside, bool gt, const int32_t* q, const int
 // The ranks of n pairs, left on the device in the shard's pr_rank / pr_valid / pr_score and copied to the
 // non-null outputs; returns the number of cold pairs.
 int64_t pair_ranks(mf_ctx* ctx, int qside, const int32_t* q, const int32_t* c, int64_t n, const int32_t* eq,
-                   const int32_t* ec, int64_t ne, int32_t* rank_out, int32_t* valid_out, double* score_out);
+                   const int32_t* ec, int64_t ne, int32_t* rank_out, int32_t* valid_out, double* score_out,
+                   bool seen = false);
 void online_prequential(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n, int flavour,
                         int num_partitions, int32_t top_n, const int32_t* eu, const int32_t* ei, int64_t ne,
                         mf_prequential* out, int32_t* rank_out, int64_t* tu, int64_t* ti);
@@ -407,6 +411,36 @@ void online_prequential_sampled(mf_ctx* ctx, const int32_t* u, const int32_t* i,
                                 int flavour, int32_t top_n, const int32_t* eu, const int32_t* ei, int64_t ne,
                                 const NegSampling& neg, int32_t* sampled_out, mf_prequential* out, int32_t* rank_out,
                                 int64_t* tu, int64_t* ti);
+// mf_online_prequential_seen: ... with the resident seen set as the exclusions, and (add_events) the batch
+// added to the set after the update
+void online_prequential_seen(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n, int flavour,
+                             int32_t top_n, const NegSampling& neg, int32_t* sampled_out, mf_prequential* out,
+                             int32_t* rank_out, int64_t* tu, int64_t* ti, bool add_events);
+
+// seen.cpp: the resident seen set (mf_seen_*), on the context's first shard.  In each of the four readers
+// above `seen` = true takes the set for the exclusions (eq / ec / ne are not read).
+// seen_put: mf_seen_set (add = false) / mf_seen_add; *ignored (may be null) = pairs naming an unknown id.
+void seen_put(mf_ctx* ctx, const int32_t* u, const int32_t* i, int64_t n, bool add, int64_t* ignored);
+void seen_from_als(mf_ctx* ctx);
+void seen_clear(mf_ctx* ctx);  // no set (mf_seen_clear; mf_dsgd_prepare, which rebuilds the rows)
+int64_t seen_count(const mf_ctx* ctx);
+// What a reader takes: the table of query side qside, its offsets padded to the side's present rows (a row
+// gained since holds nothing), and the identity as qpos.  any = false: no pair is held (n_excl == 0).  Made
+// on the shard's stream, under the caller's DeviceGuard; the item-major table is built here on first use.
+struct SeenView {
+  const int64_t* off = nullptr;
+  const int32_t* ent = nullptr;
+  const int32_t* iota = nullptr;
+  bool any = false;
+};
+SeenView seen_view(mf_ctx* ctx, Shard& s, int qside);
+void seen_debug_csr(mf_ctx* ctx, int side, int32_t* row_ids_out, int64_t* off_out, int32_t* ent_out, int32_t* ent_ids_out,
+                    int64_t cap_rows, int64_t cap_nnz, int64_t* rows_out, int64_t* nnz_out);
+// Where the keys land when a batch is merged into a sorted table of distinct keys (the rule the merge kernels
+// follow): with `novel` the distinct batch keys the table does not hold, ascending, old key p moves to
+// p + #(novel < it) and novel key i to i + #(old < it).
+void seen_merge_placement(const uint64_t* old_keys, int64_t n_old, const uint64_t* batch_keys, int64_t n_batch,
+                          int64_t* old_pos, int64_t* novel_pos, int64_t* n_novel);
 
 // als.cpp
 // How a half-sweep solves its rows.

@@ -132,8 +132,10 @@ EvalOut evaluate(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* 
 // that a small batch against a large catalogue still fills the device); every position of
 // queries[] then takes its row's result.  MFHIP_TEST rec_batch=B / rec_split=S override both.
 void recommend(mf_ctx* ctx, int qside, const int32_t* queries, int64_t nq, int32_t top_n, const int32_t* eq,
-               const int32_t* ec, int64_t ne, int32_t* ids_out, double* scores_out, int32_t* counts_out) {
+               const int32_t* ec, int64_t ne, int32_t* ids_out, double* scores_out, int32_t* counts_out,
+               bool seen) {
   Shard& s = ctx->shards[0];
+  if (seen) ne = 0;  // the resident set stands in for the call's own CSR (below)
   consolidate(ctx, s);
   sync_all(ctx);  // a run may still be sweeping (mf_dsgd_run returns early)
   const int cside = 1 - qside;
@@ -216,12 +218,27 @@ void recommend(mf_ctx* ctx, int qside, const int32_t* queries, int64_t nq, int32
     s.rec_counts.alloc(static_cast<size_t>(batch) * 4);
     const void* Q = qside == kSideU ? s.uf.get() : s.itf.get();
     const void* Cf = cside == kSideU ? s.uf.get() : s.itf.get();
+    // the seen set: a batch's exclusion ranges are gathered from the resident offsets through its rows
+    const SeenView sv = seen ? seen_view(ctx, s, qside) : SeenView{};
+    if (sv.any) {
+      s.seen.qbeg.alloc(static_cast<size_t>(batch) * 8);
+      s.seen.qend.alloc(static_cast<size_t>(batch) * 8);
+    }
     for (int64_t b0 = 0; b0 < nu; b0 += batch) {
       const int64_t nb = std::min(batch, nu - b0);
+      const int64_t *ebeg = s.rec_eoff.as<int64_t>() + b0, *eend = ebeg + 1;
+      const int32_t* erows_d = s.rec_erows.as<int32_t>();
+      if (sv.any) {
+        launch_seen_gather(s.stream, sv.off, s.rec_q.as<int32_t>() + b0, static_cast<int>(nb), s.seen.qbeg.as<int64_t>(),
+                           s.seen.qend.as<int64_t>());
+        ebeg = s.seen.qbeg.as<int64_t>();
+        eend = s.seen.qend.as<int64_t>();
+        erows_d = sv.ent;
+      }
       launch_recommend(s.stream, Q, Cf, s.rec_q.as<int32_t>() + b0, static_cast<int>(nb), static_cast<int32_t>(C),
-                       static_cast<int>(S), k, top_n, ctx->f64, s.rec_id[cside].as<int32_t>(),
-                       s.rec_eoff.as<int64_t>() + b0, s.rec_erows.as<int32_t>(), s.rec_part.get(),
-                       s.rec_ids.as<int32_t>(), s.rec_scores.as<double>(), s.rec_counts.as<int32_t>());
+                       static_cast<int>(S), k, top_n, ctx->f64, s.rec_id[cside].as<int32_t>(), ebeg, eend, erows_d,
+                       s.rec_part.get(), s.rec_ids.as<int32_t>(), s.rec_scores.as<double>(),
+                       s.rec_counts.as<int32_t>());
       MF_HIP(hipGetLastError());
       MF_HIP(hipStreamSynchronize(s.stream));
       MF_HIP(hipMemcpy(uid.data() + static_cast<size_t>(b0) * N, s.rec_ids.get(), static_cast<size_t>(nb) * N * 4,

@@ -247,15 +247,18 @@ void device_fast_schedule(hipStream_t st, const DevRatingBlocks& dr, const Ratin
 // valid rows) the top_n best of candidate rows [0, C) of slab Cf by p.q, as ids / scores / counts
 // ([nq][top_n], [nq]; device).  f64: the sequential pq = pq + a*b chain (k_predict's value); f32:
 // the fmaf chain over f = 0..k-1 on the f32-input MFMA.  cand_id: row -> id of the candidate side.
-// excl_off (nq + 1) / excl_rows: per query the sorted candidate rows never returned.  The candidate
+// excl_beg / excl_end (nq each) / excl_rows: per query the sorted candidate rows never returned,
+// excl_rows[excl_beg[q], excl_end[q]).  A call's own CSR passes (off, off + 1); the resident seen set passes
+// two arrays gathered from its offsets through qrows (launch_seen_gather).  The candidate
 // rows are walked in S <= 64 splits; part: nq * S * top_n keys of recommend_key_bytes(f64) scratch.
 // recommend_query_tile: the queries one workgroup owns (the host sizes S by it).  scores may be null
 // (mf_rank_eval reads only ids and counts).
 size_t recommend_key_bytes(bool f64);
 int recommend_query_tile(int top_n, bool f64);
 void launch_recommend(hipStream_t st, const void* Q, const void* Cf, const int32_t* qrows, int nq, int32_t C, int S,
-                      int k, int top_n, bool f64, const int32_t* cand_id, const int64_t* excl_off,
-                      const int32_t* excl_rows, void* part, int32_t* ids, double* scores, int32_t* counts);
+                      int k, int top_n, bool f64, const int32_t* cand_id, const int64_t* excl_beg,
+                      const int64_t* excl_end, const int32_t* excl_rows, void* part, int32_t* ids, double* scores,
+                      int32_t* counts);
 
 // ---- kernels_rank.hip: ranking metrics ----------------------------------------------------------
 // The pair tables of mf_rank_eval on the device.  qrow[n]: the query-side row of every pair
@@ -271,6 +274,16 @@ struct RankScratch;
 int64_t rank_query_set(hipStream_t st, RankScratch& sc, const uint32_t* qrow, int64_t n, uint32_t rows, DevBuf& qrows);
 void rank_pair_csr(hipStream_t st, RankScratch& sc, const uint32_t* qrow, const uint32_t* cand, int64_t n, uint32_t rows,
                    int64_t nq, bool gt, DevBuf& off, DevBuf& ent);
+// rank_pair_csr's three steps after its keys, for a caller that forms the keys itself (the resident seen
+// set, kernels_seen.hip).  A key is (position << 32) | low with position in [0, nq), or nq << 32 for a
+// pair that is dropped.  rank_keys_reserve sizes sc.key / key2 / head / wp for n keys (n < 2^31 - 1); the
+// caller writes sc.key[0, n).  rank_keys_sort: sc.key2 = the keys sorted over the bits in use, sc.head[p]
+// = 1 where a kept key differs from its predecessor (n + 1 entries, the last 0); a caller may clear
+// heads before the next step.  rank_keys_csr: ent = the low part of every head in order, off[q] = the
+// heads before position q's first key, q = 0 .. nq; sc.wp is left as the exclusive scan of the heads.
+void rank_keys_reserve(RankScratch& sc, int64_t n);
+void rank_keys_sort(hipStream_t st, RankScratch& sc, int64_t n, int64_t nq);
+void rank_keys_csr(hipStream_t st, RankScratch& sc, int64_t n, int64_t nq, bool gt, int64_t* off, int32_t* ent);
 // Per-query metrics of a batch of nb lists (ids [nb][top_n] / counts [nb] as launch_recommend wrote
 // them) against the ground-truth rows gt_off[0 .. nb] / gt_ent: met[q][MF_RANK_NMETRICS] and cnt[q][2] =
 // (hits, g).  gt_off / met / cnt point at the batch's first query.  tab: 128 gains 1 / log(i + 2), then
@@ -283,6 +296,41 @@ void launch_rank_metrics(hipStream_t st, const int32_t* ids, const int32_t* coun
 int64_t rank_reduce_slices(int64_t nq);
 void launch_rank_reduce(hipStream_t st, const double* met, const int64_t* cnt, int64_t nq, double* part, int64_t* ipart,
                         double* sums, int64_t* isums);
+
+// ---- kernels_seen.hip: the resident seen set ----------------------------------------------------
+// The set's tables are CSRs over a side's factor rows: off (int64, rows + 1) and ent (int32, the distinct
+// counterpart rows of a row, ascending) -- per row the shape launch_recommend's excl_rows and the pair-rank
+// kernels' exclusion table have.  Keys are (row << 32) | counterpart row; a dropped pair takes rows << 32
+// (rank_keys_sort's convention).  All of it is integer work: sort, scan, search and move.
+// launch_seen_pair_keys: key[j] of the pair (qrow[j], crow[j]); dropped when qrow[j] >= rows or crow[j] is
+// 0xFFFFFFFF (an unknown id).
+void launch_seen_pair_keys(hipStream_t st, const uint32_t* qrow, const uint32_t* crow, int64_t n, uint32_t rows,
+                           uint64_t* key);
+// launch_seen_csr_keys: key[e] of every entry e of a CSR (off[rows + 1], cols[nnz]), walked by entries in
+// tiles of 2048 (two searches of off per workgroup, then a lane narrows inside that span; a long row is
+// handled by as many workgroups as it has tiles).  swap: the key of the other orientation, (col << 32) | row.
+void launch_seen_csr_keys(hipStream_t st, const int64_t* off, int64_t rows, int64_t nnz, const int32_t* cols,
+                          bool swap, uint64_t* key);
+// The merge of a sorted batch into a table (mf_seen_add; the rule mf_debug_seen_merge_placement states).
+// launch_seen_novel, after rank_keys_sort of the batch: clears head[p] where the table (old_off[old_rows + 1],
+// old_ent) already holds key2[p], and lb[p] = the table's keys below key2[p] for every remaining head.
+// launch_seen_merge, after rank_keys_csr of those heads gave the novel keys as a CSR (nov_off[new_rows + 1],
+// nov_ent) and wp: new_off[r] = old_off[min(r, old_rows)] + nov_off[r]; an old entry e with key K moves to
+// e + #(novel keys < K) (tiles of 2048 old entries; the novel range of a tile's first and last key found
+// once per workgroup); the novel key at sorted position p lands at wp[p] + lb[p].  No atomics: every
+// position follows from the sorted keys alone.
+void launch_seen_novel(hipStream_t st, const uint64_t* key2, int32_t* head, int64_t n, const int64_t* old_off,
+                       int64_t old_rows, const int32_t* old_ent, int64_t* lb);
+void launch_seen_merge(hipStream_t st, const int64_t* old_off, int64_t old_rows, int64_t old_nnz, const int32_t* old_ent,
+                       const int64_t* nov_off, const int32_t* nov_ent, int64_t new_rows, const uint64_t* key2,
+                       const int32_t* head, const int32_t* wp, const int64_t* lb, int64_t n, int64_t* new_off,
+                       int32_t* new_ent);
+// off[r] = off[have] for r in (have, want]: rows gained since the table was built hold nothing.
+void launch_seen_pad(hipStream_t st, int64_t* off, int64_t have, int64_t want);
+// beg[q] = off[qrows[q]], end[q] = off[qrows[q] + 1]: a batch's exclusion ranges for launch_recommend.
+void launch_seen_gather(hipStream_t st, const int64_t* off, const int32_t* qrows, int n, int64_t* beg, int64_t* end);
+// out[x] = x, x in [0, n): the identity the pair-rank kernels take as qpos with a table keyed by row.
+void launch_seen_iota(hipStream_t st, int32_t* out, int64_t n);
 
 // ---- kernels_pairrank.hip: ranks of given pairs -------------------------------------------------
 // The position of pairs (query row, candidate row) in the query's complete ranked list (mf_pair_ranks,

@@ -248,13 +248,23 @@ void rank_pair_csr(hipStream_t st, RankScratch& sc, const uint32_t* qrow, const 
     MF_HIP(hipMemsetAsync(off.get(), 0, static_cast<size_t>(nq + 1) * 8, st));
     return;
   }
-  const int N = static_cast<int>(n);
-  sc.key.alloc(static_cast<size_t>(n) * 8);
-  sc.key2.alloc(static_cast<size_t>(n) * 8);
-  sc.head.alloc(static_cast<size_t>(n + 1) * 4);
-  sc.wp.alloc(static_cast<size_t>(n + 1) * 4);
+  rank_keys_reserve(sc, n);
   hipLaunchKernelGGL(k_rank_keys, dim3(grid_for(n)), dim3(kThreads), 0, st, qrow, cand, n, rows, sc.flag.as<int32_t>(),
                      sc.pos.as<int32_t>(), nq, gt, sc.key.as<uint64_t>());
+  rank_keys_sort(st, sc, n, nq);
+  rank_keys_csr(st, sc, n, nq, gt, off.as<int64_t>(), ent.as<int32_t>());
+}
+
+void rank_keys_reserve(RankScratch& sc, int64_t n) {
+  MF_REQUIRE(n >= 0 && n < (int64_t{1} << 31) - 1, "rank tables: too many pairs");
+  sc.key.alloc(static_cast<size_t>(std::max<int64_t>(n, 1)) * 8);
+  sc.key2.alloc(static_cast<size_t>(std::max<int64_t>(n, 1)) * 8);
+  sc.head.alloc(static_cast<size_t>(n + 1) * 4);
+  sc.wp.alloc(static_cast<size_t>(n + 1) * 4);
+}
+
+void rank_keys_sort(hipStream_t st, RankScratch& sc, int64_t n, int64_t nq) {
+  const int N = static_cast<int>(n);
   const int end_bit = 32 + bits_for(static_cast<uint64_t>(nq) + 1);  // positions 0 .. nq (nq: dropped)
   size_t tb = 0;
   MF_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, tb, sc.key.as<uint64_t>(), sc.key2.as<uint64_t>(), N, 0, end_bit, st));
@@ -263,14 +273,19 @@ void rank_pair_csr(hipStream_t st, RankScratch& sc, const uint32_t* qrow, const 
                                            st));
   hipLaunchKernelGGL(k_rank_heads, dim3(grid_for(n + 1)), dim3(kThreads), 0, st, sc.key2.as<uint64_t>(), n, nq,
                      sc.head.as<int32_t>());
-  tb = 0;
+  MF_HIP(hipGetLastError());
+}
+
+void rank_keys_csr(hipStream_t st, RankScratch& sc, int64_t n, int64_t nq, bool gt, int64_t* off, int32_t* ent) {
+  const int N = static_cast<int>(n);
+  size_t tb = 0;
   MF_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, sc.head.as<int32_t>(), sc.wp.as<int32_t>(), N + 1, st));
   sc.tmp.alloc(std::max<size_t>(tb, 256));
   MF_HIP(hipcub::DeviceScan::ExclusiveSum(sc.tmp.get(), tb, sc.head.as<int32_t>(), sc.wp.as<int32_t>(), N + 1, st));
   hipLaunchKernelGGL(k_rank_entries, dim3(grid_for(n)), dim3(kThreads), 0, st, sc.key2.as<uint64_t>(),
-                     sc.head.as<int32_t>(), sc.wp.as<int32_t>(), n, gt, ent.as<int32_t>());
+                     sc.head.as<int32_t>(), sc.wp.as<int32_t>(), n, gt, ent);
   hipLaunchKernelGGL(k_rank_offsets, dim3(grid_for(nq + 1)), dim3(kThreads), 0, st, sc.key2.as<uint64_t>(),
-                     sc.wp.as<int32_t>(), n, nq, off.as<int64_t>());
+                     sc.wp.as<int32_t>(), n, nq, off);
   MF_HIP(hipGetLastError());
 }
 

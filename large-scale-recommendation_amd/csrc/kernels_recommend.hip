@@ -133,7 +133,8 @@ template <int NW, bool VEC>
 __global__ __launch_bounds__(NW * 64) void k_rec_f32(const float* __restrict__ Qf, const float* __restrict__ Cf,
                                                      const int32_t* __restrict__ qrows, int nq, int32_t C, int32_t per,
                                                      int k, int N, const int32_t* __restrict__ cand_id,
-                                                     const int64_t* __restrict__ excl_off,
+                                                     const int64_t* __restrict__ excl_beg,
+                                                     const int64_t* __restrict__ excl_end,
                                                      const int32_t* __restrict__ excl_rows, Key32* __restrict__ part) {
   constexpr int NT = NW * 64, QT = NW * 32, BSTR = rec_bstr(NW);
   constexpr int A_PER = kCT * 4 / NT;  // float4 slots of the candidate stage per thread
@@ -209,7 +210,7 @@ __global__ __launch_bounds__(NW * 64) void k_rec_f32(const float* __restrict__ Q
   const bool qok = qme < nq;
   Key32* mylist = lists + jq * N;
   int64_t eb = 0, ee = 0;
-  if (qok) { eb = excl_off[qme]; ee = excl_off[qme + 1]; }
+  if (qok) { eb = excl_beg[qme]; ee = excl_end[qme]; }
 
   f32x16 acc[4];
 #pragma unroll
@@ -301,7 +302,8 @@ constexpr int kQW = 4;  // queries per wave
 __global__ __launch_bounds__(256) void k_rec_f64(const double* __restrict__ Qf, const double* __restrict__ Cf,
                                                  const int32_t* __restrict__ qrows, int nq, int32_t C, int32_t per,
                                                  int k, int N, const int32_t* __restrict__ cand_id,
-                                                 const int64_t* __restrict__ excl_off,
+                                                 const int64_t* __restrict__ excl_beg,
+                                                 const int64_t* __restrict__ excl_end,
                                                  const int32_t* __restrict__ excl_rows, Key64* __restrict__ part) {
   __shared__ Key64 lists[4][kQW * MF_RECOMMEND_MAX_TOP];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -337,7 +339,7 @@ __global__ __launch_bounds__(256) void k_rec_f64(const double* __restrict__ Qf, 
       Key64* list = wl + i * N;
       const Key64 key = make_key(pq[i], cid);
       bool want = cok && key_gt(key, list[N - 1]);
-      if (want) want = !excluded(excl_rows, excl_off[q], excl_off[q + 1], crow);
+      if (want) want = !excluded(excl_rows, excl_beg[q], excl_end[q], crow);
       // one lane at a time inserts into the query's list
       for (;;) {
         want = want && key_gt(key, list[N - 1]);
@@ -392,8 +394,8 @@ __global__ __launch_bounds__(256) void k_rec_merge(const K* __restrict__ part, i
 
 template <int NW>
 void rec_f32_dispatch(hipStream_t st, const float* Q, const float* Cf, const int32_t* qrows, int nq, int32_t C, int S,
-                      int32_t per, int k, int N, const int32_t* cand_id, const int64_t* eo, const int32_t* er,
-                      void* part) {
+                      int32_t per, int k, int N, const int32_t* cand_id, const int64_t* eb, const int64_t* ee,
+                      const int32_t* er, void* part) {
   const dim3 grid(static_cast<unsigned>((nq + NW * 32 - 1) / (NW * 32)), static_cast<unsigned>(S)), block(NW * 64);
   const size_t smem = sizeof(Key32) * NW * 32 * N + 8 * kPend * NW * 64 + sizeof(float) * 2 * rec_stage_floats(NW);
   // up to 72 KB (NW = 4, top 16): above the 64 KB a kernel gets without asking
@@ -402,10 +404,10 @@ void rec_f32_dispatch(hipStream_t st, const float* Q, const float* Cf, const int
   if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(smem)) != hipSuccess)
     fail(MF_ERR_HIP, "k_rec_f32: " + std::to_string(smem) + " bytes of LDS refused");
   if (k % 4 == 0)
-    hipLaunchKernelGGL((k_rec_f32<NW, true>), grid, block, smem, st, Q, Cf, qrows, nq, C, per, k, N, cand_id, eo, er,
+    hipLaunchKernelGGL((k_rec_f32<NW, true>), grid, block, smem, st, Q, Cf, qrows, nq, C, per, k, N, cand_id, eb, ee, er,
                        static_cast<Key32*>(part));
   else
-    hipLaunchKernelGGL((k_rec_f32<NW, false>), grid, block, smem, st, Q, Cf, qrows, nq, C, per, k, N, cand_id, eo, er,
+    hipLaunchKernelGGL((k_rec_f32<NW, false>), grid, block, smem, st, Q, Cf, qrows, nq, C, per, k, N, cand_id, eb, ee, er,
                        static_cast<Key32*>(part));
 }
 
@@ -419,21 +421,23 @@ int recommend_query_tile(int top_n, bool f64) {
 }
 
 void launch_recommend(hipStream_t st, const void* Q, const void* Cf, const int32_t* qrows, int nq, int32_t C, int S,
-                      int k, int top_n, bool f64, const int32_t* cand_id, const int64_t* excl_off,
-                      const int32_t* excl_rows, void* part, int32_t* ids, double* scores, int32_t* counts) {
+                      int k, int top_n, bool f64, const int32_t* cand_id, const int64_t* excl_beg,
+                      const int64_t* excl_end, const int32_t* excl_rows, void* part, int32_t* ids, double* scores,
+                      int32_t* counts) {
   if (nq <= 0) return;
   const int32_t per = (C + S - 1) / S;
   if (f64) {
     const dim3 grid(static_cast<unsigned>((nq + 4 * kQW - 1) / (4 * kQW)), static_cast<unsigned>(S)), block(256);
     hipLaunchKernelGGL(k_rec_f64, grid, block, 0, st, static_cast<const double*>(Q), static_cast<const double*>(Cf),
-                       qrows, nq, C, per, k, top_n, cand_id, excl_off, excl_rows, static_cast<Key64*>(part));
+                       qrows, nq, C, per, k, top_n, cand_id, excl_beg, excl_end, excl_rows, static_cast<Key64*>(part));
   } else {
     const float* q = static_cast<const float*>(Q);
     const float* c = static_cast<const float*>(Cf);
     // the lists of a block stay within 32 KB of LDS: 128 queries per block up to top 16, 64 up to 48, else 32
-    if (top_n <= 16) rec_f32_dispatch<4>(st, q, c, qrows, nq, C, S, per, k, top_n, cand_id, excl_off, excl_rows, part);
-    else if (top_n <= 48) rec_f32_dispatch<2>(st, q, c, qrows, nq, C, S, per, k, top_n, cand_id, excl_off, excl_rows, part);
-    else rec_f32_dispatch<1>(st, q, c, qrows, nq, C, S, per, k, top_n, cand_id, excl_off, excl_rows, part);
+    const int64_t *eb = excl_beg, *ee = excl_end;
+    if (top_n <= 16) rec_f32_dispatch<4>(st, q, c, qrows, nq, C, S, per, k, top_n, cand_id, eb, ee, excl_rows, part);
+    else if (top_n <= 48) rec_f32_dispatch<2>(st, q, c, qrows, nq, C, S, per, k, top_n, cand_id, eb, ee, excl_rows, part);
+    else rec_f32_dispatch<1>(st, q, c, qrows, nq, C, S, per, k, top_n, cand_id, eb, ee, excl_rows, part);
   }
   const dim3 mgrid(static_cast<unsigned>((nq + 3) / 4)), mblock(256);
   if (f64)

@@ -358,6 +358,7 @@ void prepare(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, i
   det_spec_wait(ctx, true);
   ctx->failed.clear();
   ctx->als_prepared = false;  // the layouts are rebuilt: an ALS CSR names rows of the old ones
+  seen_clear(ctx);            // ... and so does the seen set
   sync_all(ctx);
   PhaseClock clk;
   ctx->item_split = 0;

@@ -30,8 +30,10 @@ constexpr uint32_t kMiss = 0xFFFFFFFFu;
 }
 
 int64_t pair_ranks(mf_ctx* ctx, int qside, const int32_t* q, const int32_t* c, int64_t n, const int32_t* eq,
-                   const int32_t* ec, int64_t ne, int32_t* rank_out, int32_t* valid_out, double* score_out) {
+                   const int32_t* ec, int64_t ne, int32_t* rank_out, int32_t* valid_out, double* score_out,
+                   bool seen) {
   if (n == 0) return 0;
+  if (seen) ne = 0;  // the resident set stands in for the call's own table (below)
   MF_REQUIRE(n < (int64_t{1} << 31) - 1, "mf_pair_ranks: fewer than 2^31 - 1 pairs per call");
   Shard& s = ctx->shards[0];
   consolidate(ctx, s);
@@ -68,22 +70,26 @@ int64_t pair_ranks(mf_ctx* ctx, int qside, const int32_t* q, const int32_t* c, i
   MF_HIP(hipMemcpy(d_q, qr.data(), static_cast<size_t>(n) * 4, hipMemcpyHostToDevice));
   MF_HIP(hipMemcpy(d_c, cr.data(), static_cast<size_t>(n) * 4, hipMemcpyHostToDevice));
 
+  // the seen set is keyed by factor row: a row's position in it is the row itself, and nothing is built
+  const SeenView sv = seen ? seen_view(ctx, s, qside) : SeenView{};
   // the exclusion table over the distinct query rows of the pairs
   const uint32_t rows = static_cast<uint32_t>(QS.rows());
-  const int64_t nq = rank_query_set(s.stream, s.rank_sc, d_q, n, rows, s.rec_q);
-  if (ne > 0) {
-    std::vector<uint32_t> er_q, er_c;
-    lookup_rows(QS, eq, ne, er_q);
-    lookup_rows(CS, ec, ne, er_c);
-    MF_HIP(hipStreamSynchronize(s.stream));
-    s.rk_in.alloc(static_cast<size_t>(ne) * 8);
-    MF_HIP(hipMemcpy(s.rk_in.get(), er_q.data(), static_cast<size_t>(ne) * 4, hipMemcpyHostToDevice));
-    MF_HIP(hipMemcpy(s.rk_in.as<uint32_t>() + ne, er_c.data(), static_cast<size_t>(ne) * 4, hipMemcpyHostToDevice));
-  } else {
-    s.rk_in.alloc(8);
+  if (!sv.any) {
+    const int64_t nq = rank_query_set(s.stream, s.rank_sc, d_q, n, rows, s.rec_q);
+    if (ne > 0) {
+      std::vector<uint32_t> er_q, er_c;
+      lookup_rows(QS, eq, ne, er_q);
+      lookup_rows(CS, ec, ne, er_c);
+      MF_HIP(hipStreamSynchronize(s.stream));
+      s.rk_in.alloc(static_cast<size_t>(ne) * 8);
+      MF_HIP(hipMemcpy(s.rk_in.get(), er_q.data(), static_cast<size_t>(ne) * 4, hipMemcpyHostToDevice));
+      MF_HIP(hipMemcpy(s.rk_in.as<uint32_t>() + ne, er_c.data(), static_cast<size_t>(ne) * 4, hipMemcpyHostToDevice));
+    } else {
+      s.rk_in.alloc(8);
+    }
+    const uint32_t* ein = s.rk_in.as<uint32_t>();
+    rank_pair_csr(s.stream, s.rank_sc, ein, ein + ne, ne, rows, nq, false, s.rec_eoff, s.rec_erows);
   }
-  const uint32_t* ein = s.rk_in.as<uint32_t>();
-  rank_pair_csr(s.stream, s.rank_sc, ein, ein + ne, ne, rows, nq, false, s.rec_eoff, s.rec_erows);
   if (clk.on) MF_HIP(hipStreamSynchronize(s.stream));
   clk.lap("pair_ranks: tables");
 
@@ -101,10 +107,12 @@ int64_t pair_ranks(mf_ctx* ctx, int qside, const int32_t* q, const int32_t* c, i
   const void* Q = qside == kSideU ? s.uf.get() : s.itf.get();
   const void* Cf = cside == kSideU ? s.uf.get() : s.itf.get();
   const int32_t* cand_id = s.rec_id[cside].as<int32_t>();
-  const int32_t* qpos = s.rank_sc.pos.as<int32_t>();
-  launch_pair_targets(s.stream, Q, Cf, d_q, d_c, n, static_cast<int32_t>(C), k, ctx->f64, cand_id, qpos,
-                      s.rec_eoff.as<int64_t>(), s.rec_erows.as<int32_t>(), s.pr_ord.get(), s.pr_tid.as<uint32_t>(),
-                      s.pr_rank.as<int32_t>(), s.pr_valid.as<int32_t>(), s.pr_score.as<double>());
+  const int32_t* qpos = sv.any ? sv.iota : s.rank_sc.pos.as<int32_t>();
+  const int64_t* eoff = sv.any ? sv.off : s.rec_eoff.as<int64_t>();
+  const int32_t* erows = sv.any ? sv.ent : s.rec_erows.as<int32_t>();
+  launch_pair_targets(s.stream, Q, Cf, d_q, d_c, n, static_cast<int32_t>(C), k, ctx->f64, cand_id, qpos, eoff, erows,
+                      s.pr_ord.get(), s.pr_tid.as<uint32_t>(), s.pr_rank.as<int32_t>(), s.pr_valid.as<int32_t>(),
+                      s.pr_score.as<double>());
 
   // batches, and candidate splits as recommend() chooses them: enough workgroups for two per CU, each
   // split at least one candidate tile of 128 rows
@@ -123,7 +131,7 @@ int64_t pair_ranks(mf_ctx* ctx, int qside, const int32_t* q, const int32_t* c, i
   for (int64_t b0 = 0; b0 < n; b0 += batch) {
     const int64_t nb = std::min(batch, n - b0);
     launch_pair_count(s.stream, Q, Cf, d_q + b0, static_cast<int>(nb), static_cast<int32_t>(C), static_cast<int>(S), k,
-                      ctx->f64, nw, cand_id, qpos, s.rec_eoff.as<int64_t>(), s.rec_erows.as<int32_t>(), ne > 0,
+                      ctx->f64, nw, cand_id, qpos, eoff, erows, sv.any || ne > 0,
                       s.pr_ord.as<char>() + static_cast<size_t>(b0) * ob, s.pr_tid.as<uint32_t>() + b0,
                       s.pr_rank.as<int32_t>() + b0);
   }
@@ -140,14 +148,14 @@ int64_t pair_ranks(mf_ctx* ctx, int qside, const int32_t* q, const int32_t* c, i
 // step 2, the online update, queues its first kernel.
 namespace {
 void prequential_ranks(mf_ctx* ctx, const int32_t* u, const int32_t* i, int64_t n, int32_t top_n, const int32_t* eu,
-                       const int32_t* ei, int64_t ne, mf_prequential* out, int32_t* rank_out) {
+                       const int32_t* ei, int64_t ne, mf_prequential* out, int32_t* rank_out, bool seen = false) {
   *out = mf_prequential{};
   out->events = n;
   out->cold = n;
   if (n > 0 && !ctx->have_model) {
     if (rank_out) std::fill(rank_out, rank_out + n, MF_PAIR_RANK_COLD);
   } else if (n > 0) {
-    out->cold = pair_ranks(ctx, kSideU, u, i, n, eu, ei, ne, rank_out, nullptr, nullptr);
+    out->cold = pair_ranks(ctx, kSideU, u, i, n, eu, ei, ne, rank_out, nullptr, nullptr, seen);
     if (out->cold < n) {  // the ranks are on the device
       Shard& s = ctx->shards[0];
       DeviceGuard g(s.device);
@@ -203,6 +211,15 @@ void online_prequential_sampled(mf_ctx* ctx, const int32_t* u, const int32_t* i,
                                 int64_t* tu, int64_t* ti) {
   prequential_ranks(ctx, u, i, n, top_n, eu, ei, ne, out, rank_out);
   online_update_sampled(ctx, u, i, r, n, flavour, neg, sampled_out, tu, ti);
+}
+
+void online_prequential_seen(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n, int flavour,
+                             int32_t top_n, const NegSampling& neg, int32_t* sampled_out, mf_prequential* out,
+                             int32_t* rank_out, int64_t* tu, int64_t* ti, bool add_events) {
+  prequential_ranks(ctx, u, i, n, top_n, nullptr, nullptr, 0, out, rank_out, true);
+  online_update_sampled(ctx, u, i, r, n, flavour, neg, sampled_out, tu, ti);
+  // every id of the batch has a row now: its events are seen from the next batch on
+  if (add_events) seen_put(ctx, u, i, n, true, nullptr);
 }
 
 }  // namespace mfhip

@@ -74,7 +74,7 @@ const std::vector<double>& gain_table() {
 
 void rank_eval(mf_ctx* ctx, int qside, const int32_t* gq, const int32_t* gc, int64_t ng, int32_t top_n,
                const int32_t* eq, const int32_t* ec, int64_t ne, mf_rank_metrics* out, int32_t* q_ids_out,
-               int32_t* q_counts_out, double* q_metrics_out, int64_t cap) {
+               int32_t* q_counts_out, double* q_metrics_out, int64_t cap, bool seen) {
   *out = mf_rank_metrics{};
   if (ng == 0) return;
   Shard& s = ctx->shards[0];
@@ -89,6 +89,10 @@ void rank_eval(mf_ctx* ctx, int qside, const int32_t* gq, const int32_t* gc, int
   const size_t N = static_cast<size_t>(top_n);
   DeviceGuard g(s.device);
 
+  // the seen set stands in for the exclusion table of the call (taken first: it may build its item-major
+  // table with the scratch build_truth uses)
+  const SeenView sv = seen ? seen_view(ctx, s, qside) : SeenView{};
+  if (seen) ne = 0;
   std::vector<uint32_t> qr;
   const int64_t nq = build_truth(s, QS, gq, gc, ng, qr);
   {
@@ -113,7 +117,7 @@ void rank_eval(mf_ctx* ctx, int qside, const int32_t* gq, const int32_t* gc, int
     MF_HIP(hipStreamSynchronize(s.stream));
     return;
   }
-  build_exclusions(s, QS, CS, eq, ec, ne, nq);
+  if (!sv.any) build_exclusions(s, QS, CS, eq, ec, ne, nq);
   if (clk.on) MF_HIP(hipStreamSynchronize(s.stream));
   clk.lap("rank_eval: pair tables");
 
@@ -151,14 +155,27 @@ void rank_eval(mf_ctx* ctx, int qside, const int32_t* gq, const int32_t* gc, int
   if (C == 0) MF_HIP(hipMemsetAsync(s.rec_counts.get(), 0, static_cast<size_t>(batch) * 4, s.stream));  // empty lists
   const void* Q = qside == kSideU ? s.uf.get() : s.itf.get();
   const void* Cf = cside == kSideU ? s.uf.get() : s.itf.get();
+  if (sv.any) {
+    s.seen.qbeg.alloc(static_cast<size_t>(batch) * 8);
+    s.seen.qend.alloc(static_cast<size_t>(batch) * 8);
+  }
   // no copy and no wait inside the loop: stream order makes the reuse of a batch's scratch safe
   for (int64_t b0 = 0; b0 < nq; b0 += batch) {
     const int64_t nb = std::min(batch, nq - b0);
-    if (C > 0)
+    if (C > 0) {
+      const int64_t *ebeg = s.rec_eoff.as<int64_t>() + b0, *eend = ebeg + 1;
+      const int32_t* erows_d = s.rec_erows.as<int32_t>();
+      if (sv.any) {  // the batch's ranges, gathered from the resident offsets through its rows
+        launch_seen_gather(s.stream, sv.off, s.rec_q.as<int32_t>() + b0, static_cast<int>(nb), s.seen.qbeg.as<int64_t>(),
+                           s.seen.qend.as<int64_t>());
+        ebeg = s.seen.qbeg.as<int64_t>();
+        eend = s.seen.qend.as<int64_t>();
+        erows_d = sv.ent;
+      }
       launch_recommend(s.stream, Q, Cf, s.rec_q.as<int32_t>() + b0, static_cast<int>(nb), static_cast<int32_t>(C),
-                       static_cast<int>(S), k, top_n, ctx->f64, s.rec_id[cside].as<int32_t>(),
-                       s.rec_eoff.as<int64_t>() + b0, s.rec_erows.as<int32_t>(), s.rec_part.get(),
-                       s.rec_ids.as<int32_t>(), nullptr, s.rec_counts.as<int32_t>());
+                       static_cast<int>(S), k, top_n, ctx->f64, s.rec_id[cside].as<int32_t>(), ebeg, eend, erows_d,
+                       s.rec_part.get(), s.rec_ids.as<int32_t>(), nullptr, s.rec_counts.as<int32_t>());
+    }
     launch_rank_metrics(s.stream, s.rec_ids.as<int32_t>(), s.rec_counts.as<int32_t>(), static_cast<int>(nb), top_n,
                         s.rk_goff.as<int64_t>() + b0, s.rk_gent.as<int32_t>(), s.rk_tab.as<double>(),
                         s.rk_met.as<double>() + b0 * MF_RANK_NMETRICS, s.rk_cnt.as<int64_t>() + b0 * 2);

@@ -4,7 +4,7 @@ The compute path is libmfhip.so (hand-written HIP for gfx950 behind a C ABI, inc
 this package is the Python equivalent of the Scala entry points that bind it.
 """
 from . import _lib, jvm, negsample, synth
-from ._lib import MFError, MFNoDeviceError, device_count, version
+from ._lib import SEEN, MFError, MFNoDeviceError, device_count, version
 from .als import ALS, MatrixFactorizationModel, StreamingALS
 from .context import Context, Prequential, RankMetrics, block_update
 from .core import (FactorInitializer, FactorInitializerDescriptor, Factors, FactorUpdater, FactorVector,
@@ -24,4 +24,5 @@ __all__ = [
     "PseudoRandomFactorInitializerDescriptor", "RandomFactorInitializer", "RandomFactorInitializerDescriptor",
     "UserUpdate", "ItemUpdate", "read_ratings", "ALS", "MatrixFactorizationModel", "StreamingALS",
     "RankMetrics", "RankingMetrics", "Prequential", "PrequentialEvaluator", "host_prequential",
+    "SEEN",
 ]

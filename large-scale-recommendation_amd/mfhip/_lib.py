@@ -50,6 +50,17 @@ PAIR_RANK_EXCLUDED = -2  # ... the pair itself is in the exclusion list
 NEG_MAX = 64             # mf_online_update_sampled: negatives per event at most
 
 
+class _Seen:
+    """exclude=SEEN: the context's resident seen set (Context.seen_set / seen_add / seen_from_als) stands in
+    for the exclusion arrays of recommend, rank_eval, pair_ranks and the prequential calls."""
+
+    def __repr__(self):
+        return "mfhip.SEEN"
+
+
+SEEN = _Seen()
+
+
 class MFError(RuntimeError):
     """Non-zero status from libmfhip (the JNI shim raises RuntimeException, like the reference)."""
 
@@ -163,6 +174,8 @@ EXPORTS = [
     "mf_als_run_cg", "mf_als_run_implicit_cg", "mf_als_fit_cg", "mf_als_fit_implicit_cg",
     "mf_als_run_nonneg", "mf_als_run_implicit_nonneg", "mf_als_fit_nonneg", "mf_als_fit_implicit_nonneg",
     "mf_als_nonneg_stats", "mf_nnls_solve", "mf_als_append", "mf_als_run_rows", "mf_als_update",
+    "mf_seen_set", "mf_seen_add", "mf_seen_from_als", "mf_seen_clear", "mf_seen_count", "mf_recommend_seen",
+    "mf_rank_eval_seen", "mf_pair_ranks_seen", "mf_online_prequential_seen",
 ]
 # The test hooks include/mfhip_testing.h declares (not product surface; same library).
 TESTING_EXPORTS = [
@@ -171,6 +184,7 @@ TESTING_EXPORTS = [
     "mf_debug_device_bytes", "mf_debug_als_normal_eq", "mf_debug_als_gram", "mf_debug_als_normal_eq_implicit",
     "mf_debug_det_slot_table", "mf_debug_sys_placement", "mf_debug_rank_csr", "mf_debug_als_cg_matvec",
     "mf_debug_als_cg_capacity", "mf_debug_als_nnls_row", "mf_debug_als_csr", "mf_debug_als_append_placement",
+    "mf_debug_seen_csr", "mf_debug_seen_merge_placement",
 ]
 
 _i32p = C.POINTER(C.c_int32)
@@ -290,6 +304,22 @@ def lib() -> C.CDLL:
         "mf_debug_als_csr": (C.c_int, [_ctxp, C.c_int, _i64p, _i32p, _f64p, _i32p, C.c_int64, C.c_int64, _i64p,
                                        _i64p]),
         "mf_debug_als_append_placement": (C.c_int, [_i64p, C.c_int64, _i32p, C.c_int64, C.c_int64, _i64p, _i64p]),
+        "mf_seen_set": (C.c_int, [_ctxp, _i32p, _i32p, C.c_int64, _i64p]),
+        "mf_seen_add": (C.c_int, [_ctxp, _i32p, _i32p, C.c_int64, _i64p]),
+        "mf_seen_from_als": (C.c_int, [_ctxp]),
+        "mf_seen_clear": (C.c_int, [_ctxp]),
+        "mf_seen_count": (C.c_int, [_ctxp, _i64p]),
+        "mf_recommend_seen": (C.c_int, [_ctxp, C.c_int, _i32p, C.c_int64, C.c_int32, _i32p, _f64p, _i32p]),
+        "mf_rank_eval_seen": (C.c_int, [_ctxp, C.c_int, _i32p, _i32p, C.c_int64, C.c_int32, C.POINTER(mf_rank_metrics),
+                                        _i32p, _i32p, _f64p, C.c_int64]),
+        "mf_pair_ranks_seen": (C.c_int, [_ctxp, C.c_int, _i32p, _i32p, C.c_int64, _i32p, _i32p, _f64p]),
+        "mf_online_prequential_seen": (C.c_int, [_ctxp, _i32p, _i32p, _f64p, C.c_int64, C.c_int, C.c_int32,
+                                                 C.POINTER(mf_prequential), _i32p, _i64p, _i64p, C.c_int32, C.c_double,
+                                                 C.c_int64, C.c_int64, _i32p, C.c_int]),
+        "mf_debug_seen_csr": (C.c_int, [_ctxp, C.c_int, _i32p, _i64p, _i32p, _i32p, C.c_int64, C.c_int64, _i64p,
+                                        _i64p]),
+        "mf_debug_seen_merge_placement": (C.c_int, [C.POINTER(C.c_uint64), C.c_int64, C.POINTER(C.c_uint64), C.c_int64,
+                                                    _i64p, _i64p, _i64p]),
         "mf_debug_ring_schedule": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, _i32p, _i32p, _i32p, _i32p]),
         "mf_debug_det_slot_table": (C.c_int, [_i64p, _i32p, _i32p, C.c_int64, C.c_int64, C.c_int32, C.c_int64, _i64p,
                                               _i32p, _i32p, _i64p]),
@@ -299,8 +329,8 @@ def lib() -> C.CDLL:
         "mf_debug_device_bytes": (C.c_int, [_i64p]),
     }
     for name, (res, args) in sig.items():
-        if name in TESTING_EXPORTS and not hasattr(L, name):
-            continue  # an older build (A/B runs): its test hooks may predate this binding
+        if (name in TESTING_EXPORTS or "MFHIP_LIB" in os.environ) and not hasattr(L, name):
+            continue  # an older build (A/B runs, named through MFHIP_LIB): it may predate this binding
         fn = getattr(L, name)
         fn.restype = res
         fn.argtypes = args

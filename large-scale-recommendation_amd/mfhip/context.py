@@ -414,6 +414,12 @@ class Context:
         ids = np.zeros(rows, np.int32)
         sc = np.zeros(rows, np.float64) if scores else None
         counts = np.zeros(max(n, 1), np.int32)
+        if exclude is L.SEEN:
+            check(L.lib().mf_recommend_seen(self._h, int(side), ptr(q, C.c_int32), n, top_n, ptr(ids, C.c_int32),
+                                            ptr(sc, C.c_double) if scores else None, ptr(counts, C.c_int32)))
+            shape = (n, max(top_n, 1))
+            return (ids[:n * shape[1]].reshape(shape), sc[:n * shape[1]].reshape(shape) if scores else None,
+                    counts[:n])
         eq = ec = None
         ne = 0
         if exclude is not None:
@@ -436,7 +442,7 @@ class Context:
         ng = same_length(gq, gc)
         eq = ec = None
         ne = 0
-        if exclude is not None:
+        if exclude is not None and exclude is not L.SEEN:
             eq, ec = as_i32(exclude[0]), as_i32(exclude[1])
             ne = same_length(eq, ec)
         out = L.mf_rank_metrics()
@@ -444,12 +450,15 @@ class Context:
         ids = np.zeros(max(cap, 1), np.int32)
         counts = np.zeros((max(cap, 1), 2), np.int32)
         values = np.zeros((max(cap, 1), L.RANK_NMETRICS), np.float64)
-        check(L.lib().mf_rank_eval(self._h, int(side), ptr(gq, C.c_int32) if ng else None,
-                                   ptr(gc, C.c_int32) if ng else None, ng, int(top_n),
-                                   ptr(eq, C.c_int32) if ne else None, ptr(ec, C.c_int32) if ne else None, ne,
-                                   C.byref(out), ptr(ids, C.c_int32) if per_query else None,
-                                   ptr(counts, C.c_int32) if per_query else None,
-                                   ptr(values, C.c_double) if per_query else None, cap))
+        head = (self._h, int(side), ptr(gq, C.c_int32) if ng else None, ptr(gc, C.c_int32) if ng else None, ng,
+                int(top_n))
+        tail = (C.byref(out), ptr(ids, C.c_int32) if per_query else None,
+                ptr(counts, C.c_int32) if per_query else None, ptr(values, C.c_double) if per_query else None, cap)
+        if exclude is L.SEEN:
+            check(L.lib().mf_rank_eval_seen(*head, *tail))
+        else:
+            check(L.lib().mf_rank_eval(*head, ptr(eq, C.c_int32) if ne else None, ptr(ec, C.c_int32) if ne else None,
+                                       ne, *tail))
         m = RankMetrics(queries=out.queries, unknown_queries=out.unknown_queries, gt_pairs=out.gt_pairs, hits=out.hits,
                         precision=out.precision, recall=out.recall, map=out.map, ndcg=out.ndcg, mrr=out.mrr,
                         hit_rate=out.hit_rate)
@@ -468,12 +477,17 @@ class Context:
         n = same_length(q, c)
         eq = ec = None
         ne = 0
-        if exclude is not None:
+        if exclude is not None and exclude is not L.SEEN:
             eq, ec = as_i32(exclude[0]), as_i32(exclude[1])
             ne = same_length(eq, ec)
         ranks = np.zeros(max(n, 1), np.int32)
         valid = np.zeros(max(n, 1), np.int32)
         sc = np.zeros(max(n, 1), np.float64) if scores else None
+        if exclude is L.SEEN:
+            check(L.lib().mf_pair_ranks_seen(self._h, int(side), ptr(q, C.c_int32) if n else None,
+                                             ptr(c, C.c_int32) if n else None, n, ptr(ranks, C.c_int32),
+                                             ptr(valid, C.c_int32), ptr(sc, C.c_double) if scores else None))
+            return ranks[:n], valid[:n], (sc[:n] if scores else None)
         check(L.lib().mf_pair_ranks(self._h, int(side), ptr(q, C.c_int32) if n else None,
                                     ptr(c, C.c_int32) if n else None, n,
                                     ptr(eq, C.c_int32) if ne else None, ptr(ec, C.c_int32) if ne else None, ne,
@@ -496,6 +510,49 @@ class Context:
                                         ptr(ent, C.c_int32), max(n, 1), max(n, 1), C.byref(nq), C.byref(ne)))
         return qids[:nq.value], off[:nq.value + 1], ent[:ne.value]
 
+    # -- the resident seen set ---------------------------------------------------
+    def _seen_put(self, fn, u, i) -> int:
+        u, i = as_i32(u), as_i32(i)
+        n = same_length(u, i)
+        ignored = C.c_int64(0)
+        check(fn(self._h, ptr(u, C.c_int32) if n else None, ptr(i, C.c_int32) if n else None, n, C.byref(ignored)))
+        return ignored.value
+
+    def seen_set(self, u, i) -> int:
+        """mf_seen_set: the resident seen set := the distinct pairs (u[j], i[j]) whose ids the model holds; the
+        readers take it with exclude=SEEN.  Returns the pairs ignored for an unknown id."""
+        return self._seen_put(L.lib().mf_seen_set, u, i)
+
+    def seen_add(self, u, i) -> int:
+        """mf_seen_add: the set's union with the pairs given (only the batch is sorted)."""
+        return self._seen_put(L.lib().mf_seen_add, u, i)
+
+    def seen_from_als(self) -> None:
+        """mf_seen_from_als: the set := the distinct pairs of the prepared ALS data; nothing is uploaded."""
+        check(L.lib().mf_seen_from_als(self._h))
+
+    def seen_clear(self) -> None:
+        check(L.lib().mf_seen_clear(self._h))
+
+    def seen_count(self) -> int:
+        v = C.c_int64(0)
+        check(L.lib().mf_seen_count(self._h, C.byref(v)))
+        return v.value
+
+    def debug_seen_csr(self, side: int = L.SIDE_USER):
+        """mf_debug_seen_csr: the set's table of `side` as the readers see it: (row ids [rows], offsets
+        [rows + 1], entries = counterpart factor rows, the ids of those rows)."""
+        rows = max(self.num_factors(side), 1)
+        nnz = max(self.seen_count(), 1)
+        rid = np.zeros(rows, np.int32)
+        off = np.zeros(rows + 1, np.int64)
+        ent = np.zeros(nnz, np.int32)
+        eid = np.zeros(nnz, np.int32)
+        r, m = C.c_int64(0), C.c_int64(0)
+        check(L.lib().mf_debug_seen_csr(self._h, int(side), ptr(rid, C.c_int32), ptr(off, C.c_int64),
+                                        ptr(ent, C.c_int32), ptr(eid, C.c_int32), rows, nnz, C.byref(r), C.byref(m)))
+        return rid[:r.value], off[:r.value + 1], ent[:m.value], eid[:m.value]
+
     # -- online ----------------------------------------------------------------
     def online_update(self, u, i, r, flavour: int = L.ONLINE_NEXT_FACTORS, num_partitions: int = 0):
         u, i, r = as_i32(u), as_i32(i), as_f64(r)
@@ -506,11 +563,16 @@ class Context:
         return tu.value, ti.value
 
     def online_prequential(self, u, i, r, top_n: int, flavour: int = L.ONLINE_NEXT_FACTORS, num_partitions: int = 0,
-                           exclude=None, ranks: bool = False) -> "Prequential":
+                           exclude=None, ranks: bool = False, add_events: bool = False) -> "Prequential":
         """mf_online_prequential: test-then-train on one micro-batch.  Every event (u[j], i[j]) is ranked
         among all items for its user with the model as it stands (pair_ranks; exclude = (user ids, item
         ids) never ranked above it), its ndcg / rr / hit at top_n and its percentile rank summed on the
-        device in a fixed order, and only then online_update(u, i, r, flavour, num_partitions) runs."""
+        device in a fixed order, and only then online_update(u, i, r, flavour, num_partitions) runs.
+        exclude=SEEN (mf_online_prequential_seen, arrival-order flavours): the resident seen set is the
+        exclusions, and with add_events the batch joins it after the update."""
+        if exclude is L.SEEN:
+            return self.online_prequential_sampled(u, i, r, top_n, 0, flavour=flavour, exclude=L.SEEN, ranks=ranks,
+                                                   add_events=add_events)
         u, i, r = as_i32(u), as_i32(i), as_f64(r)
         n = same_length(u, i, r)
         eq = ec = None
@@ -559,27 +621,34 @@ class Context:
 
     def online_prequential_sampled(self, u, i, r, top_n: int, negatives: int, negative_rating: float = 0.0,
                                    seed: int = 0, first_event: int = 0, flavour: int = L.ONLINE_NEXT_FACTORS,
-                                   exclude=None, ranks: bool = False, sampled: bool = False):
+                                   exclude=None, ranks: bool = False, sampled: bool = False,
+                                   add_events: bool = False):
         """mf_online_prequential_sampled: online_prequential's step 1 unchanged (the events ranked against
         the model as it stands), then online_update_sampled.  Returns the Prequential record, and with
-        sampled=True (record, drawn item ids [n, negatives])."""
+        sampled=True (record, drawn item ids [n, negatives]).  exclude=SEEN (mf_online_prequential_seen):
+        the resident seen set is the exclusions, and with add_events the batch joins it after the update."""
         u, i, r = as_i32(u), as_i32(i), as_f64(r)
         n = same_length(u, i, r)
         negatives = int(negatives)
         eq = ec = None
         ne = 0
-        if exclude is not None:
+        if exclude is not None and exclude is not L.SEEN:
             eq, ec = as_i32(exclude[0]), as_i32(exclude[1])
             ne = same_length(eq, ec)
         out = L.mf_prequential()
         rk = np.zeros(max(n, 1), np.int32) if ranks else None
         ids = np.zeros(max(n * max(negatives, 0), 1), np.int32) if sampled else None
         tu, ti = C.c_int64(0), C.c_int64(0)
-        check(L.lib().mf_online_prequential_sampled(
-            self._h, ptr(u, C.c_int32), ptr(i, C.c_int32), ptr(r, C.c_double), n, int(flavour), int(top_n),
-            ptr(eq, C.c_int32) if ne else None, ptr(ec, C.c_int32) if ne else None, ne, C.byref(out),
-            ptr(rk, C.c_int32) if ranks else None, C.byref(tu), C.byref(ti), negatives, float(negative_rating),
-            int(seed), int(first_event), ptr(ids, C.c_int32) if sampled else None))
+        head = (self._h, ptr(u, C.c_int32), ptr(i, C.c_int32), ptr(r, C.c_double), n, int(flavour), int(top_n))
+        tail = (C.byref(out), ptr(rk, C.c_int32) if ranks else None, C.byref(tu), C.byref(ti), negatives,
+                float(negative_rating), int(seed), int(first_event), ptr(ids, C.c_int32) if sampled else None)
+        if exclude is L.SEEN:
+            check(L.lib().mf_online_prequential_seen(*head, *tail, 1 if add_events else 0))
+        else:
+            if add_events:
+                raise ValueError("add_events needs exclude=SEEN")
+            check(L.lib().mf_online_prequential_sampled(
+                *head, ptr(eq, C.c_int32) if ne else None, ptr(ec, C.c_int32) if ne else None, ne, *tail))
         rec = Prequential(events=out.events, evaluated=out.evaluated, cold=out.cold, excluded=out.excluded,
                           hits=out.hits, sum_ndcg=out.sum_ndcg, sum_rr=out.sum_rr, sum_pr=out.sum_pr, ndcg=out.ndcg,
                           mrr=out.mrr, hit_rate=out.hit_rate, mpr=out.mpr, touched_users=tu.value,
