@@ -206,6 +206,53 @@ int mf_recommend(mf_ctx* ctx, int query_side, const int32_t* queries, int64_t n_
                  const int32_t* excl_query, const int32_t* excl_cand, int64_t n_excl,
                  int32_t* ids_out, double* scores_out, int32_t* counts_out);
 
+/* Nearest neighbours in factor space, scored and selected on the device like mf_recommend and never
+   forming a score matrix.
+   mf_similar: "items like this item" / "users like this user".  For each queries[j] (an id of `side`) the
+   top_n ids of the SAME side.  Candidates are every row of `side`; with include_self == 0 the query's own
+   row is left out, so counts_out[j] = min(top_n, rows - 1 - distinct known exclusions of the query) and a
+   side with one row gives count 0; with include_self == 1 the query is a candidate like any other (naming
+   the (query, query) pair in the exclusions removes it again, and naming it with include_self == 0 changes
+   nothing).  An unknown query id gives count 0; duplicate query ids each take their row's result.
+   mf_recommend_vectors: top_n rows of cand_side for query vectors the model does not hold (an anonymous
+   session, a row folded in elsewhere, an average of item vectors).  vecs: n_queries x k, row-major,
+   k = num_factors, converted to the context's precision exactly as mf_set_factors converts rows (f64 kept,
+   f32 by one rounding).  NaN and infinite entries are allowed and follow the ordering rules below.
+   excl_query_index[e] names position j of vecs; indices outside [0, n_queries) are ignored.
+   Shared with mf_recommend: the output layout (ids_out / scores_out (may be NULL): n_queries x top_n,
+   row-major), counts_out as the only validity signal with slots past it holding id 0 and score 0.0; the
+   order (score descending, ties by candidate id ascending (signed), NaN below every number, -0 as +0); the
+   exclusion rules (pairs naming an unknown id or a query not asked are ignored, duplicates allowed,
+   n_excl == 0 takes NULL pointers); top_n in 1 .. MF_RECOMMEND_MAX_TOP; n_queries == 0 is valid; a context
+   on several devices uses its first.
+   Scores, metric = MF_METRIC_DOT: the value mf_recommend would report if the query row sat on the
+   opposite side, the same arithmetic bit for bit -- MF_MODE_DETERMINISTIC_F64 the chain pq = pq + a*b over
+   f = 0..k-1, MF_MODE_FAST_F32 the f32 fmaf chain over f = 0..k-1 from 0, widened.
+   Scores, metric = MF_METRIC_COSINE, for rows x in the context's precision T (f32 or f64):
+     nn(x)  = the sum over ascending f from 0 of x_f * x_f in T: f32 the chain nn = fmaf(x_f, x_f, nn), f64
+              nn = nn + x_f * x_f (product rounded, then the sum: not fused)
+     inv(x) = 1.0 / sqrt((double)nn), square root and division in f64; f32 then rounds it once to f32
+     score  = dot * (inv(query) * inv(candidate)) in T: the product of the two inverses first, each multiply
+              rounded once, the result widened to f64; dot is the MF_METRIC_DOT value above (in T)
+   This is symmetric bit for bit: score(a, b) == score(b, a).  A zero row has inv = +inf and dot = 0, so its
+   score is NaN and it sorts last; whatever IEEE arithmetic gives on overflow or underflow is the answer,
+   there is no special casing.  Results are reproducible bit for bit and depend neither on how the queries
+   are batched nor on how the candidates are split.  Norms are computed per call and never kept: a row
+   changed by mf_set_factors, an online batch or a fit is reflected by the next call.
+   Errors.  MF_ERR_INVALID: NULL ctx, a bad side, an unknown metric, an include_self other than 0 or 1,
+   top_n outside 1 .. MF_RECOMMEND_MAX_TOP, a negative count, a NULL array with a positive count.
+   MF_ERR_NOT_FITTED before a model exists; MF_ERR_STATE on a rank-mode context, as mf_recommend. */
+#define MF_METRIC_DOT    0
+#define MF_METRIC_COSINE 1
+int mf_similar(mf_ctx* ctx, int side, const int32_t* queries, int64_t n_queries, int32_t top_n,
+               int32_t metric, int32_t include_self,
+               const int32_t* excl_query, const int32_t* excl_cand, int64_t n_excl,
+               int32_t* ids_out, double* scores_out /* may be NULL */, int32_t* counts_out);
+int mf_recommend_vectors(mf_ctx* ctx, int cand_side, const double* vecs, int64_t n_queries, int32_t top_n,
+                         int32_t metric,
+                         const int64_t* excl_query_index, const int32_t* excl_cand, int64_t n_excl,
+                         int32_t* ids_out, double* scores_out /* may be NULL */, int32_t* counts_out);
+
 /* RankingMetrics (precisionAt, meanAveragePrecision, ndcgAt) of MLlib, for the models ALS.train builds
    (sp/OnlineSpark.scala:125-131), plus recall, reciprocal rank and hit rate: held-out (query,
    candidate) pairs against the model's top-N lists, on the device.  The pair tables are built, the

@@ -87,6 +87,18 @@ public final class MfHip {
   public static native void recommend(long ctx, int querySide, int[] queries, int topN,
                                       int[] exclQuery, int[] exclCand,
                                       int[] idsOut, double[] scoresOut, int[] countsOut);
+  // nearest neighbours in factor space (mf_similar, mf_recommend_vectors); outputs as for recommend
+  public static final int METRIC_DOT = 0, METRIC_COSINE = 1;
+  // for every queries[j] (an id of `side`) the topN nearest ids of the same side; the query's own row is
+  // left out unless includeSelf
+  public static native void similar(long ctx, int side, int[] queries, int topN, int metric, boolean includeSelf,
+                                    int[] exclQuery, int[] exclCand,
+                                    int[] idsOut, double[] scoresOut, int[] countsOut);
+  // the topN rows of candSide for numQueries vectors the model need not hold (vecs: numQueries * k doubles,
+  // row-major); exclQueryIndex[e] names a position in vecs
+  public static native void recommendVectors(long ctx, int candSide, double[] vecs, int numQueries, int topN,
+                                             int metric, int[] exclQueryIndex, int[] exclCand,
+                                             int[] idsOut, double[] scoresOut, int[] countsOut);
   // RankingMetrics of held-out (query, candidate) pairs against the model's topN lists (mf_rank_eval),
   // taken on the device.  metricsOut (length >= 8) receives queries, hits, precision, recall, MAP, NDCG,
   // MRR, hit rate; exclQuery / exclCand as for recommend

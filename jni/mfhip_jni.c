@@ -707,6 +707,68 @@ JNIEXPORT void JNICALL JFN(recommendSeen)(JNIEnv* env, jclass c, jlong h, jint s
   check(env, st);
 }
 
+/* the output-array checks recommend, similar and recommendVectors share; 0 when ok */
+static int top_lists_fit(JNIEnv* env, jsize n, jint top, jintArray ids, jdoubleArray scores, jintArray counts) {
+  if (require(env, ids && counts, "idsOut and countsOut must not be null")) return -1;
+  if (require(env, top >= 1 && top <= MF_RECOMMEND_MAX_TOP, "topN out of range")) return -1;
+  return require(env, (jlong)len(env, ids) >= (jlong)n * top && (!scores || (jlong)len(env, scores) >= (jlong)n * top) &&
+                          len(env, counts) >= n,
+                 "idsOut / scoresOut must hold one row of topN entries per query and countsOut one entry");
+}
+
+JNIEXPORT void JNICALL JFN(similar)(JNIEnv* env, jclass c, jlong h, jint side, jintArray q, jint top, jint metric,
+                                    jboolean self, jintArray xq, jintArray xc, jintArray ids, jdoubleArray scores,
+                                    jintArray counts) {
+  if (require(env, q != NULL, "queries must not be null")) return;
+  const jsize n = len(env, q), ne = xq ? len(env, xq) : 0;
+  if (top_lists_fit(env, n, top, ids, scores, counts)) return;
+  if (require(env, (!xq && !xc) || (xq && xc && len(env, xq) == len(env, xc)),
+              "exclQuery and exclCand must both be null or match in length"))
+    return;
+  Elems e[6];
+  const jarray arr[6] = {q, xq, xc, ids, scores, counts};
+  const int kind[6] = {kInt, kInt, kInt, kInt, kDouble, kInt};
+  if (acquire_all(env, e, arr, kind, 6)) return;
+  int st = mf_similar(CTX(h), side, (const int32_t*)e[0].p, n, top, metric, self ? 1 : 0,
+                      ne ? (const int32_t*)e[1].p : NULL, ne ? (const int32_t*)e[2].p : NULL, ne, (int32_t*)e[3].p,
+                      (double*)e[4].p, (int32_t*)e[5].p);
+  for (int x = 5; x >= 3; --x) release(env, &e[x], st == MF_OK ? 0 : JNI_ABORT);
+  for (int x = 2; x >= 0; --x) release(env, &e[x], JNI_ABORT);
+  check(env, st);
+}
+
+JNIEXPORT void JNICALL JFN(recommendVectors)(JNIEnv* env, jclass c, jlong h, jint side, jdoubleArray vecs, jint n,
+                                             jint top, jint metric, jintArray xq, jintArray xc, jintArray ids,
+                                             jdoubleArray scores, jintArray counts) {
+  const jlong k = rank_of(env, h);
+  if (k < 0) return;
+  if (require(env, n >= 0 && vecs && (jlong)len(env, vecs) >= (jlong)n * k, "vecs must hold numQueries * k doubles"))
+    return;
+  if (top_lists_fit(env, n, top, ids, scores, counts)) return;
+  if (require(env, (!xq && !xc) || (xq && xc && len(env, xq) == len(env, xc)),
+              "exclQueryIndex and exclCand must both be null or match in length"))
+    return;
+  const jsize ne = xq ? len(env, xq) : 0;
+  /* a Java array index is an int; the C call takes 64-bit positions */
+  int64_t* xq64 = ne ? (int64_t*)malloc(sizeof(int64_t) * (size_t)ne) : NULL;
+  if (require(env, ne == 0 || xq64 != NULL, "out of memory")) return;
+  Elems e[6];
+  const jarray arr[6] = {vecs, xq, xc, ids, scores, counts};
+  const int kind[6] = {kDouble, kInt, kInt, kInt, kDouble, kInt};
+  if (acquire_all(env, e, arr, kind, 6)) {
+    free(xq64);
+    return;
+  }
+  for (jsize x = 0; x < ne; ++x) xq64[x] = ((const int32_t*)e[1].p)[x];
+  int st = mf_recommend_vectors(CTX(h), side, (const double*)e[0].p, n, top, metric, xq64,
+                                ne ? (const int32_t*)e[2].p : NULL, ne, (int32_t*)e[3].p, (double*)e[4].p,
+                                (int32_t*)e[5].p);
+  free(xq64);
+  for (int x = 5; x >= 3; --x) release(env, &e[x], st == MF_OK ? 0 : JNI_ABORT);
+  for (int x = 2; x >= 0; --x) release(env, &e[x], JNI_ABORT);
+  check(env, st);
+}
+
 JNIEXPORT void JNICALL JFN(rankEvalSeen)(JNIEnv* env, jclass c, jlong h, jint side, jintArray gq, jintArray gc, jint top,
                                          jdoubleArray metrics) {
   if (require(env, gq && gc && len(env, gq) == len(env, gc), "gtQuery and gtCand must match in length")) return;

@@ -244,6 +244,54 @@ int mf_recommend(mf_ctx* ctx, int query_side, const int32_t* queries, int64_t n_
 }
 
 namespace {
+// the checks mf_similar and mf_recommend_vectors share with mf_recommend
+void top_list_check(mf_ctx* ctx, int side, int32_t top_n, int32_t metric, int64_t n_queries, int64_t n_excl,
+                    const char* who) {
+  MF_REQUIRE(ctx, "null context");
+  MF_REQUIRE(side == MF_SIDE_USER || side == MF_SIDE_ITEM, "bad side");
+  MF_REQUIRE(metric == MF_METRIC_DOT || metric == MF_METRIC_COSINE, "bad metric");
+  MF_REQUIRE(top_n >= 1 && top_n <= MF_RECOMMEND_MAX_TOP,
+             "top_n must be in [1, " + std::to_string(MF_RECOMMEND_MAX_TOP) + "]");
+  MF_REQUIRE(n_queries >= 0 && n_excl >= 0, "negative count");
+  if (ctx->rank_mode)
+    fail(MF_ERR_STATE, std::string(who) + " runs on a single-process context; a rank-mode context (mf_create_rank) "
+                                          "holds only its own users' rows");
+  if (!ctx->have_model)
+    fail(MF_ERR_NOT_FITTED, "The MatrixFactorization model has not been fitted to data. "
+                            "Prior to predicting values, it has to be trained on data.");
+  require_healthy(ctx);
+}
+}  // namespace
+
+int mf_similar(mf_ctx* ctx, int side, const int32_t* queries, int64_t n_queries, int32_t top_n, int32_t metric,
+               int32_t include_self, const int32_t* excl_query, const int32_t* excl_cand, int64_t n_excl,
+               int32_t* ids_out, double* scores_out, int32_t* counts_out) {
+  return guarded([&] {
+    MF_REQUIRE(ctx, "null context");
+    MF_REQUIRE(include_self == 0 || include_self == 1, "include_self must be 0 or 1");
+    top_list_check(ctx, side, top_n, metric, n_queries, n_excl, "mf_similar");
+    MF_REQUIRE(n_excl == 0 || (excl_query && excl_cand), "null exclusion list");
+    if (n_queries == 0) return;
+    MF_REQUIRE(queries && ids_out && counts_out, "null argument");
+    similar(ctx, side, queries, n_queries, top_n, metric, include_self != 0, excl_query, excl_cand, n_excl, ids_out,
+            scores_out, counts_out);
+  });
+}
+
+int mf_recommend_vectors(mf_ctx* ctx, int cand_side, const double* vecs, int64_t n_queries, int32_t top_n,
+                         int32_t metric, const int64_t* excl_query_index, const int32_t* excl_cand, int64_t n_excl,
+                         int32_t* ids_out, double* scores_out, int32_t* counts_out) {
+  return guarded([&] {
+    top_list_check(ctx, cand_side, top_n, metric, n_queries, n_excl, "mf_recommend_vectors");
+    MF_REQUIRE(n_excl == 0 || (excl_query_index && excl_cand), "null exclusion list");
+    if (n_queries == 0) return;
+    MF_REQUIRE(vecs && ids_out && counts_out, "null argument");
+    recommend_vectors(ctx, cand_side, vecs, n_queries, top_n, metric, excl_query_index, excl_cand, n_excl, ids_out,
+                      scores_out, counts_out);
+  });
+}
+
+namespace {
 // the checks mf_rank_eval and its testing hook share with mf_recommend
 void rank_check(mf_ctx* ctx, int query_side, const char* who) {
   MF_REQUIRE(ctx, "null context");

@@ -128,6 +128,11 @@ struct Shard {
   DevBuf rec_id[2];
   uint64_t rec_id_gen[2] = {0, 0};
   DevBuf rec_q, rec_eoff, rec_erows, rec_part, rec_ids, rec_scores, rec_counts;
+  // ... the cosine metric (mf_similar, mf_recommend_vectors): one call's inverse norms of the candidate rows
+  // and of the staged queries, and one batch of the caller's vectors in the context's precision with its
+  // pinned host stage (mf_recommend_vectors)
+  DevBuf rec_cinv, rec_qinv, rec_qvec;
+  PinnedBuf rec_pin;
   // ranking metrics (mf_rank_eval, which also uses the rec_* buffers): the table build's scratch, a pair
   // list as uploaded (query rows, then candidate rows or ids), the ground-truth CSR, the per-query
   // metrics and (hits, g), the slice sums, the gain table and the call's totals
@@ -385,6 +390,12 @@ EvalOut evaluate(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* 
 void recommend(mf_ctx* ctx, int qside, const int32_t* queries, int64_t nq, int32_t top_n, const int32_t* eq,
                const int32_t* ec, int64_t ne, int32_t* ids_out, double* scores_out, int32_t* counts_out,
                bool seen = false);
+void similar(mf_ctx* ctx, int side, const int32_t* queries, int64_t nq, int32_t top_n, int metric, bool include_self,
+             const int32_t* eq, const int32_t* ec, int64_t ne, int32_t* ids_out, double* scores_out,
+             int32_t* counts_out);
+void recommend_vectors(mf_ctx* ctx, int cside, const double* vecs, int64_t nq, int32_t top_n, int metric,
+                       const int64_t* eqi, const int32_t* ec, int64_t ne, int32_t* ids_out, double* scores_out,
+                       int32_t* counts_out);
 void get_factors(mf_ctx* ctx, int side, int32_t* ids, double* vecs, int64_t cap, int64_t* written);
 void lookup_factors(mf_ctx* ctx, int side, const int32_t* ids, int64_t n, double* vecs_out, uint8_t* found);
 

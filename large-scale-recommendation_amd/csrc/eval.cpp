@@ -1,5 +1,6 @@
 // eval.cpp -- reading the model out: evaluation (mf_predict / mf_rmse / mf_empirical_risk),
-// top-N recommendation (mf_recommend) and the factor read-outs (mf_get_factors, mf_lookup).
+// top-N lists (mf_recommend, mf_similar, mf_recommend_vectors) and the factor read-outs (mf_get_factors,
+// mf_lookup).
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -126,25 +127,168 @@ EvalOut evaluate(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* 
 }
 
 // ---------------------------------------------------------------------------------------
-// Top-N recommendation (mf_recommend): ids resolved on the host, score + select on the device
-// (kernels_recommend.hip), on shard 0 like evaluate.  Distinct known query rows are scored once, in
-// batches that bound the device scratch at batch x S x top_n keys (S = candidate splits, chosen so
-// that a small batch against a large catalogue still fills the device); every position of
-// queries[] then takes its row's result.  MFHIP_TEST rec_batch=B / rec_split=S override both.
-void recommend(mf_ctx* ctx, int qside, const int32_t* queries, int64_t nq, int32_t top_n, const int32_t* eq,
-               const int32_t* ec, int64_t ne, int32_t* ids_out, double* scores_out, int32_t* counts_out,
-               bool seen) {
+// Top-N lists (mf_recommend, mf_recommend_seen, mf_similar, mf_recommend_vectors): a front resolves the
+// call's queries and exclusions to rows, one core scores and selects on the device
+// (kernels_recommend.hip), on shard 0 like evaluate.  The query rows are scored in batches that bound the
+// device scratch at batch x S x top_n keys (S = candidate splits, chosen so that a small batch against a
+// large catalogue still fills the device).  MFHIP_TEST rec_batch=B / rec_split=S override both.
+namespace {
+
+constexpr uint32_t kMiss = 0xFFFFFFFFu;
+
+// (query position << 32 | candidate row) pairs -> the exclusion CSR of nu queries: sorted distinct rows
+void exclusion_csr(std::vector<uint64_t>& pairs, int64_t nu, std::vector<int64_t>& eoff, std::vector<int32_t>& erows) {
+  eoff.assign(static_cast<size_t>(nu) + 1, 0);
+  std::sort(pairs.begin(), pairs.end());
+  pairs.erase(std::unique(pairs.begin(), pairs.end()), pairs.end());
+  erows.resize(pairs.size());
+  for (size_t x = 0; x < pairs.size(); ++x) {
+    ++eoff[(pairs[x] >> 32) + 1];
+    erows[x] = static_cast<int32_t>(pairs[x] & 0xFFFFFFFFu);
+  }
+  for (int64_t u = 0; u < nu; ++u) eoff[u + 1] += eoff[u];
+}
+
+// The core.  nu queries against every row of side cside, minus each query's exclusions (eoff / erows, or
+// with seen_qside >= 0 the resident seen set of that query side): ids [nu][top_n], scores (may be null),
+// counts [nu] on the host.  The queries are either rows qrows[0 .. nu) of a resident factor slab Q of q_rows
+// rows (which may be the candidate slab itself: mf_similar), or, with Q null, the caller's nu x k f64 vectors
+// hvecs (qrows = 0 .. nu-1): those are converted as upload_rows converts factor rows and staged one batch
+// ahead, so the conversion of batch b + 1 runs on the host while the device scores batch b.
+void recommend_core(mf_ctx* ctx, Shard& s, const void* Q, int64_t q_rows, const double* hvecs,
+                    const std::vector<int32_t>& qrows, int cside, int32_t top_n, int metric,
+                    const std::vector<int64_t>& eoff, const std::vector<int32_t>& erows, int seen_qside, int32_t* uid,
+                    double* usc, int32_t* ucnt) {
+  const SideLayout& CS = side_of(ctx, cside);
+  const int64_t C = CS.rows(), nu = static_cast<int64_t>(qrows.size());
+  const int k = ctx->P.num_factors;
+  const size_t N = static_cast<size_t>(top_n);
+  if (nu == 0) return;
+  if (C == 0) {
+    std::fill(uid, uid + static_cast<size_t>(nu) * N, 0);
+    if (usc) std::fill(usc, usc + static_cast<size_t>(nu) * N, 0.0);
+    std::fill(ucnt, ucnt + nu, 0);
+    return;
+  }
+  DeviceGuard g(s.device);
+  if (s.rec_id_gen[cside] != ctx->layout_gen || s.rec_id[cside].bytes() < static_cast<size_t>(C) * 4) {
+    s.rec_id[cside].alloc(static_cast<size_t>(C) * 4);
+    MF_HIP(hipMemcpy(s.rec_id[cside].get(), CS.row_id.data(), static_cast<size_t>(C) * 4, hipMemcpyHostToDevice));
+    s.rec_id_gen[cside] = ctx->layout_gen;
+  }
+  s.rec_q.alloc(static_cast<size_t>(nu) * 4);
+  s.rec_eoff.alloc(eoff.size() * 8);
+  s.rec_erows.alloc(std::max<size_t>(erows.size(), 1) * 4);
+  MF_HIP(hipMemcpy(s.rec_q.get(), qrows.data(), static_cast<size_t>(nu) * 4, hipMemcpyHostToDevice));
+  MF_HIP(hipMemcpy(s.rec_eoff.get(), eoff.data(), eoff.size() * 8, hipMemcpyHostToDevice));
+  if (!erows.empty()) MF_HIP(hipMemcpy(s.rec_erows.get(), erows.data(), erows.size() * 4, hipMemcpyHostToDevice));
+
+  int64_t batch = 8192;
+  if (const std::string v = test_knob("rec_batch"); !v.empty()) batch = std::max<int64_t>(1, std::atoll(v.c_str()));
+  batch = std::min(batch, nu);
+  // S: enough workgroups for two per CU, each split at least one candidate tile of 128 rows
+  const int qt = recommend_query_tile(top_n, ctx->f64);
+  const int64_t qtiles = (batch + qt - 1) / qt;
+  int64_t S = std::min<int64_t>((512 + qtiles - 1) / qtiles, (C + 127) / 128);
+  if (const std::string v = test_knob("rec_split"); !v.empty()) S = std::atoll(v.c_str());
+  S = std::max<int64_t>(1, std::min<int64_t>({S, 64, C}));
+
+  s.rec_part.alloc(static_cast<size_t>(batch) * S * N * recommend_key_bytes(ctx->f64));
+  s.rec_ids.alloc(static_cast<size_t>(batch) * N * 4);
+  s.rec_scores.alloc(static_cast<size_t>(batch) * N * 8);
+  s.rec_counts.alloc(static_cast<size_t>(batch) * 4);
+  const void* Cf = cside == kSideU ? s.uf.get() : s.itf.get();
+  // cosine: the inverse norms of this call (never kept: the rows may change before the next one)
+  const bool cosine = metric == MF_METRIC_COSINE;
+  const void *q_inv = nullptr, *c_inv = nullptr;
+  if (cosine) {
+    s.rec_cinv.alloc(static_cast<size_t>(C) * ctx->es);
+    launch_row_inv_norm(s.stream, Cf, C, k, ctx->f64, s.rec_cinv.get());
+    q_inv = c_inv = s.rec_cinv.get();
+    if (Q != Cf) {
+      s.rec_qinv.alloc(static_cast<size_t>(Q ? q_rows : batch) * ctx->es);
+      if (Q) launch_row_inv_norm(s.stream, Q, q_rows, k, ctx->f64, s.rec_qinv.get());
+      q_inv = s.rec_qinv.get();
+    }
+    MF_HIP(hipGetLastError());
+  }
+  // host vectors: batch [b0, b0 + nb) -> the pinned stage in the context's precision -> rec_qvec, queued
+  // behind whatever the stream holds (the previous batch's kernels still read rec_qvec)
+  const size_t kk = static_cast<size_t>(k);
+  auto stage_vectors = [&](int64_t b0, int64_t nb) {
+    const double* src = hvecs + static_cast<size_t>(b0) * kk;
+    const int64_t n = nb * k;
+    if (ctx->f64) {
+      std::memcpy(s.rec_pin.as<double>(), src, static_cast<size_t>(n) * 8);
+    } else {
+      float* dst = s.rec_pin.as<float>();
+      parallel_for(n, [&](int64_t b, int64_t e, int) {
+        for (int64_t x = b; x < e; ++x) dst[x] = static_cast<float>(src[x]);
+      });
+    }
+    MF_HIP(hipMemcpyAsync(s.rec_qvec.get(), s.rec_pin.as<char>(), static_cast<size_t>(n) * ctx->es,
+                          hipMemcpyHostToDevice, s.stream));
+  };
+  if (!Q) {
+    s.rec_qvec.alloc(static_cast<size_t>(batch) * kk * ctx->es);
+    s.rec_pin.alloc(static_cast<size_t>(batch) * kk * ctx->es);
+    stage_vectors(0, batch);
+    MF_HIP(hipStreamSynchronize(s.stream));  // the stage is rewritten while batch 0 runs
+  }
+  // the seen set: a batch's exclusion ranges are gathered from the resident offsets through its rows
+  const SeenView sv = seen_qside >= 0 ? seen_view(ctx, s, seen_qside) : SeenView{};
+  if (sv.any) {
+    s.seen.qbeg.alloc(static_cast<size_t>(batch) * 8);
+    s.seen.qend.alloc(static_cast<size_t>(batch) * 8);
+  }
+  for (int64_t b0 = 0; b0 < nu; b0 += batch) {
+    const int64_t nb = std::min(batch, nu - b0);
+    const int64_t *ebeg = s.rec_eoff.as<int64_t>() + b0, *eend = ebeg + 1;
+    const int32_t* erows_d = s.rec_erows.as<int32_t>();
+    if (sv.any) {
+      launch_seen_gather(s.stream, sv.off, s.rec_q.as<int32_t>() + b0, static_cast<int>(nb), s.seen.qbeg.as<int64_t>(),
+                         s.seen.qend.as<int64_t>());
+      ebeg = s.seen.qbeg.as<int64_t>();
+      eend = s.seen.qend.as<int64_t>();
+      erows_d = sv.ent;
+    }
+    // a staged batch is rows 0 .. nb-1 of rec_qvec: the head of the identity list in rec_q names them
+    const int32_t* rows_d = s.rec_q.as<int32_t>() + (Q ? b0 : 0);
+    if (!Q && cosine) launch_row_inv_norm(s.stream, s.rec_qvec.get(), nb, k, ctx->f64, s.rec_qinv.get());
+    launch_recommend(s.stream, Q ? Q : s.rec_qvec.get(), Cf, rows_d, static_cast<int>(nb), static_cast<int32_t>(C),
+                     static_cast<int>(S), k, top_n, ctx->f64, s.rec_id[cside].as<int32_t>(), ebeg, eend, erows_d,
+                     s.rec_part.get(), s.rec_ids.as<int32_t>(), s.rec_scores.as<double>(),
+                     s.rec_counts.as<int32_t>(), q_inv, c_inv);
+    MF_HIP(hipGetLastError());
+    if (!Q && b0 + batch < nu) {
+      // the stage is free: its last copy finished with the previous batch's synchronisation
+      stage_vectors(b0 + batch, std::min(batch, nu - b0 - batch));
+    }
+    MF_HIP(hipStreamSynchronize(s.stream));
+    MF_HIP(hipMemcpy(uid + static_cast<size_t>(b0) * N, s.rec_ids.get(), static_cast<size_t>(nb) * N * 4,
+                     hipMemcpyDeviceToHost));
+    if (usc)
+      MF_HIP(hipMemcpy(usc + static_cast<size_t>(b0) * N, s.rec_scores.get(), static_cast<size_t>(nb) * N * 8,
+                       hipMemcpyDeviceToHost));
+    MF_HIP(hipMemcpy(ucnt + b0, s.rec_counts.get(), static_cast<size_t>(nb) * 4, hipMemcpyDeviceToHost));
+  }
+}
+
+// The front of the calls whose queries are ids of side qside, candidates the rows of side cside (the other
+// side: mf_recommend; the same side: mf_similar).  Distinct known query rows are scored once; every position
+// of queries[] then takes its row's result.  no_self: each query's own row joins its exclusions (it is a
+// candidate only when qside == cside) -- no kernel knows about "self".
+void recommend_ids(mf_ctx* ctx, int qside, int cside, const int32_t* queries, int64_t nq, int32_t top_n, int metric,
+                   bool no_self, const int32_t* eq, const int32_t* ec, int64_t ne, int32_t* ids_out, double* scores_out,
+                   int32_t* counts_out, bool seen) {
   Shard& s = ctx->shards[0];
-  if (seen) ne = 0;  // the resident set stands in for the call's own CSR (below)
+  if (seen) ne = 0;  // the resident set stands in for the call's own CSR
   consolidate(ctx, s);
   sync_all(ctx);  // a run may still be sweeping (mf_dsgd_run returns early)
-  const int cside = 1 - qside;
   const SideLayout& QS = side_of(ctx, qside);
   const SideLayout& CS = side_of(ctx, cside);
   const int64_t C = CS.rows();
-  const int k = ctx->P.num_factors;
   const size_t N = static_cast<size_t>(top_n);
-  constexpr uint32_t kMiss = 0xFFFFFFFFu;
 
   // distinct known query rows, ascending; pos[j] = queries[j]'s index among them (-1: unknown id)
   std::vector<uint32_t> qr;
@@ -165,90 +309,28 @@ void recommend(mf_ctx* ctx, int qside, const int32_t* queries, int64_t nq, int32
   // exclusion CSR: one row per distinct query, sorted candidate rows inside it
   std::vector<int64_t> eoff(static_cast<size_t>(nu) + 1, 0);
   std::vector<int32_t> erows;
-  if (ne > 0 && nu > 0 && C > 0) {
-    std::vector<uint32_t> er_q, er_c;
-    lookup_rows(QS, eq, ne, er_q);
-    lookup_rows(CS, ec, ne, er_c);
+  if ((ne > 0 || no_self) && nu > 0 && C > 0) {
     std::vector<uint64_t> pairs;
-    pairs.reserve(static_cast<size_t>(ne));
-    for (int64_t e = 0; e < ne; ++e) {
-      const int64_t u = upos(er_q[e]);
-      if (u < 0 || er_c[e] == kMiss) continue;
-      pairs.push_back((static_cast<uint64_t>(u) << 32) | er_c[e]);
+    pairs.reserve(static_cast<size_t>(ne) + (no_self ? static_cast<size_t>(nu) : 0));
+    if (ne > 0) {
+      std::vector<uint32_t> er_q, er_c;
+      lookup_rows(QS, eq, ne, er_q);
+      lookup_rows(CS, ec, ne, er_c);
+      for (int64_t e = 0; e < ne; ++e) {
+        const int64_t u = upos(er_q[e]);
+        if (u < 0 || er_c[e] == kMiss) continue;
+        pairs.push_back((static_cast<uint64_t>(u) << 32) | er_c[e]);
+      }
     }
-    std::sort(pairs.begin(), pairs.end());
-    pairs.erase(std::unique(pairs.begin(), pairs.end()), pairs.end());
-    erows.resize(pairs.size());
-    for (size_t x = 0; x < pairs.size(); ++x) {
-      ++eoff[(pairs[x] >> 32) + 1];
-      erows[x] = static_cast<int32_t>(pairs[x] & 0xFFFFFFFFu);
-    }
-    for (int64_t u = 0; u < nu; ++u) eoff[u + 1] += eoff[u];
+    if (no_self)
+      for (int64_t u = 0; u < nu; ++u) pairs.push_back((static_cast<uint64_t>(u) << 32) | static_cast<uint32_t>(uniq[u]));
+    exclusion_csr(pairs, nu, eoff, erows);
   }
 
   std::vector<int32_t> uid(static_cast<size_t>(nu) * N, 0), ucnt(static_cast<size_t>(nu), 0);
   std::vector<double> usc(scores_out ? static_cast<size_t>(nu) * N : 0, 0.0);
-  if (nu > 0 && C > 0) {
-    DeviceGuard g(s.device);
-    if (s.rec_id_gen[cside] != ctx->layout_gen || s.rec_id[cside].bytes() < static_cast<size_t>(C) * 4) {
-      s.rec_id[cside].alloc(static_cast<size_t>(C) * 4);
-      MF_HIP(hipMemcpy(s.rec_id[cside].get(), CS.row_id.data(), static_cast<size_t>(C) * 4, hipMemcpyHostToDevice));
-      s.rec_id_gen[cside] = ctx->layout_gen;
-    }
-    s.rec_q.alloc(static_cast<size_t>(nu) * 4);
-    s.rec_eoff.alloc(eoff.size() * 8);
-    s.rec_erows.alloc(std::max<size_t>(erows.size(), 1) * 4);
-    MF_HIP(hipMemcpy(s.rec_q.get(), uniq.data(), static_cast<size_t>(nu) * 4, hipMemcpyHostToDevice));
-    MF_HIP(hipMemcpy(s.rec_eoff.get(), eoff.data(), eoff.size() * 8, hipMemcpyHostToDevice));
-    if (!erows.empty()) MF_HIP(hipMemcpy(s.rec_erows.get(), erows.data(), erows.size() * 4, hipMemcpyHostToDevice));
-
-    int64_t batch = 8192;
-    if (const std::string v = test_knob("rec_batch"); !v.empty()) batch = std::max<int64_t>(1, std::atoll(v.c_str()));
-    batch = std::min(batch, nu);
-    // S: enough workgroups for two per CU, each split at least one candidate tile of 128 rows
-    const int qt = recommend_query_tile(top_n, ctx->f64);
-    const int64_t qtiles = (batch + qt - 1) / qt;
-    int64_t S = std::min<int64_t>((512 + qtiles - 1) / qtiles, (C + 127) / 128);
-    if (const std::string v = test_knob("rec_split"); !v.empty()) S = std::atoll(v.c_str());
-    S = std::max<int64_t>(1, std::min<int64_t>({S, 64, C}));
-
-    s.rec_part.alloc(static_cast<size_t>(batch) * S * N * recommend_key_bytes(ctx->f64));
-    s.rec_ids.alloc(static_cast<size_t>(batch) * N * 4);
-    s.rec_scores.alloc(static_cast<size_t>(batch) * N * 8);
-    s.rec_counts.alloc(static_cast<size_t>(batch) * 4);
-    const void* Q = qside == kSideU ? s.uf.get() : s.itf.get();
-    const void* Cf = cside == kSideU ? s.uf.get() : s.itf.get();
-    // the seen set: a batch's exclusion ranges are gathered from the resident offsets through its rows
-    const SeenView sv = seen ? seen_view(ctx, s, qside) : SeenView{};
-    if (sv.any) {
-      s.seen.qbeg.alloc(static_cast<size_t>(batch) * 8);
-      s.seen.qend.alloc(static_cast<size_t>(batch) * 8);
-    }
-    for (int64_t b0 = 0; b0 < nu; b0 += batch) {
-      const int64_t nb = std::min(batch, nu - b0);
-      const int64_t *ebeg = s.rec_eoff.as<int64_t>() + b0, *eend = ebeg + 1;
-      const int32_t* erows_d = s.rec_erows.as<int32_t>();
-      if (sv.any) {
-        launch_seen_gather(s.stream, sv.off, s.rec_q.as<int32_t>() + b0, static_cast<int>(nb), s.seen.qbeg.as<int64_t>(),
-                           s.seen.qend.as<int64_t>());
-        ebeg = s.seen.qbeg.as<int64_t>();
-        eend = s.seen.qend.as<int64_t>();
-        erows_d = sv.ent;
-      }
-      launch_recommend(s.stream, Q, Cf, s.rec_q.as<int32_t>() + b0, static_cast<int>(nb), static_cast<int32_t>(C),
-                       static_cast<int>(S), k, top_n, ctx->f64, s.rec_id[cside].as<int32_t>(), ebeg, eend, erows_d,
-                       s.rec_part.get(), s.rec_ids.as<int32_t>(), s.rec_scores.as<double>(),
-                       s.rec_counts.as<int32_t>());
-      MF_HIP(hipGetLastError());
-      MF_HIP(hipStreamSynchronize(s.stream));
-      MF_HIP(hipMemcpy(uid.data() + static_cast<size_t>(b0) * N, s.rec_ids.get(), static_cast<size_t>(nb) * N * 4,
-                       hipMemcpyDeviceToHost));
-      if (scores_out)
-        MF_HIP(hipMemcpy(usc.data() + static_cast<size_t>(b0) * N, s.rec_scores.get(), static_cast<size_t>(nb) * N * 8,
-                         hipMemcpyDeviceToHost));
-      MF_HIP(hipMemcpy(ucnt.data() + b0, s.rec_counts.get(), static_cast<size_t>(nb) * 4, hipMemcpyDeviceToHost));
-    }
-  }
+  recommend_core(ctx, s, qside == kSideU ? s.uf.get() : s.itf.get(), QS.rows(), nullptr, uniq, cside, top_n, metric,
+                 eoff, erows, seen ? qside : -1, uid.data(), scores_out ? usc.data() : nullptr, ucnt.data());
   parallel_for(nq, [&](int64_t b, int64_t e, int) {
     for (int64_t j = b; j < e; ++j) {
       const int64_t u = upos(qr[j]);
@@ -264,6 +346,51 @@ void recommend(mf_ctx* ctx, int qside, const int32_t* queries, int64_t nq, int32
       if (scores_out) std::memcpy(scores_out + static_cast<size_t>(j) * N, usc.data() + static_cast<size_t>(u) * N, N * 8);
     }
   });
+}
+
+}  // namespace
+
+void recommend(mf_ctx* ctx, int qside, const int32_t* queries, int64_t nq, int32_t top_n, const int32_t* eq,
+               const int32_t* ec, int64_t ne, int32_t* ids_out, double* scores_out, int32_t* counts_out,
+               bool seen) {
+  recommend_ids(ctx, qside, 1 - qside, queries, nq, top_n, MF_METRIC_DOT, false, eq, ec, ne, ids_out, scores_out,
+                counts_out, seen);
+}
+
+// mf_similar: the nearest rows of the queries' own side.
+void similar(mf_ctx* ctx, int side, const int32_t* queries, int64_t nq, int32_t top_n, int metric, bool include_self,
+             const int32_t* eq, const int32_t* ec, int64_t ne, int32_t* ids_out, double* scores_out,
+             int32_t* counts_out) {
+  recommend_ids(ctx, side, side, queries, nq, top_n, metric, !include_self, eq, ec, ne, ids_out, scores_out, counts_out,
+                false);
+}
+
+// mf_recommend_vectors: the queries are the caller's vectors; query j is row j of vecs, exclusions name j.
+void recommend_vectors(mf_ctx* ctx, int cside, const double* vecs, int64_t nq, int32_t top_n, int metric,
+                       const int64_t* eqi, const int32_t* ec, int64_t ne, int32_t* ids_out, double* scores_out,
+                       int32_t* counts_out) {
+  Shard& s = ctx->shards[0];
+  consolidate(ctx, s);
+  sync_all(ctx);
+  const SideLayout& CS = side_of(ctx, cside);
+  MF_REQUIRE(nq < (int64_t{1} << 31), "too many query vectors for one call");
+  std::vector<int32_t> rows(static_cast<size_t>(nq));
+  std::iota(rows.begin(), rows.end(), 0);
+  std::vector<int64_t> eoff(static_cast<size_t>(nq) + 1, 0);
+  std::vector<int32_t> erows;
+  if (ne > 0 && CS.rows() > 0) {
+    std::vector<uint32_t> er_c;
+    lookup_rows(CS, ec, ne, er_c);
+    std::vector<uint64_t> pairs;
+    pairs.reserve(static_cast<size_t>(ne));
+    for (int64_t e = 0; e < ne; ++e) {
+      if (eqi[e] < 0 || eqi[e] >= nq || er_c[e] == kMiss) continue;
+      pairs.push_back((static_cast<uint64_t>(eqi[e]) << 32) | er_c[e]);
+    }
+    exclusion_csr(pairs, nq, eoff, erows);
+  }
+  recommend_core(ctx, s, nullptr, 0, vecs, rows, cside, top_n, metric, eoff, erows, -1, ids_out, scores_out,
+                 counts_out);
 }
 
 // Every row of a side (rank mode: the rank's own users), ascending by id (mf_get_factors).

@@ -253,12 +253,17 @@ void device_fast_schedule(hipStream_t st, const DevRatingBlocks& dr, const Ratin
 // rows are walked in S <= 64 splits; part: nq * S * top_n keys of recommend_key_bytes(f64) scratch.
 // recommend_query_tile: the queries one workgroup owns (the host sizes S by it).  scores may be null
 // (mf_rank_eval reads only ids and counts).
+// Cosine (mf_similar, mf_recommend_vectors): c_inv given -- one inverse norm per candidate row, q_inv one per
+// row of Q (indexed through qrows like Q), both in the context's precision, as launch_row_inv_norm writes
+// them; a score is then dot * (q_inv * c_inv), scaled before it is selected.  Null: the dot kernels.
+// launch_row_inv_norm: inv[r] = 1 / sqrt(sum over ascending f of X[r][f]^2) for rows [0, rows) of X.
 size_t recommend_key_bytes(bool f64);
 int recommend_query_tile(int top_n, bool f64);
 void launch_recommend(hipStream_t st, const void* Q, const void* Cf, const int32_t* qrows, int nq, int32_t C, int S,
                       int k, int top_n, bool f64, const int32_t* cand_id, const int64_t* excl_beg,
                       const int64_t* excl_end, const int32_t* excl_rows, void* part, int32_t* ids, double* scores,
-                      int32_t* counts);
+                      int32_t* counts, const void* q_inv = nullptr, const void* c_inv = nullptr);
+void launch_row_inv_norm(hipStream_t st, const void* X, int64_t rows, int k, bool f64, void* inv);
 
 // ---- kernels_rank.hip: ranking metrics ----------------------------------------------------------
 // The pair tables of mf_rank_eval on the device.  qrow[n]: the query-side row of every pair

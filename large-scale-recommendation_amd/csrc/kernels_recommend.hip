@@ -15,6 +15,11 @@
 //               pq = pq + a * b over f = 0..k-1 (this file is compiled with -ffp-contract=off), the
 //               value k_predict gives for the pair, against QW query rows of its wave.
 //  k_rec_merge  the S partial lists of a query (one per candidate split) -> its final top N.
+//  k_row_inv_norm  one inverse norm per row, 1 / sqrt(sum x_f^2), for the cosine metric (mf_similar,
+//               mf_recommend_vectors).  Both score kernels take the metric as a template parameter COS:
+//               with it, a score is dot * (inv(query) * inv(candidate)) before it meets the selection,
+//               so thresholds, parked values, keys and the merge all carry the scaled score; without it
+//               they are the kernels mf_recommend always ran, instruction for instruction.
 //
 // Selection (shared): a query's list is N keys in LDS, sorted descending; a key orders by score
 // descending, then candidate id ascending, NaN below every number -- one unsigned compare.  A score
@@ -128,21 +133,27 @@ __host__ __device__ constexpr int rec_stage_floats(int nw) { return kKC * (kAStr
 
 // Grid: (query tiles, S).  qrows: the batch's query rows (all valid), nq of them.  Candidates:
 // rows [0, C) of slab Cf, split s takes [s * per, min(C, (s + 1) * per)).  part: [nq][S][N] keys.
-// VEC: k % 4 == 0, rows are loaded as float4.
-template <int NW, bool VEC>
+// VEC: k % 4 == 0, rows are loaded as float4.  COS: scores are scaled by qinv[query row] * cinv[candidate
+// row]; a tile's 128 candidate inverses ride through LDS with it, one buffer per tile parity (a wave may
+// stage tile T + 1 while another still selects from tile T).
+template <int NW, bool VEC, bool COS>
 __global__ __launch_bounds__(NW * 64) void k_rec_f32(const float* __restrict__ Qf, const float* __restrict__ Cf,
                                                      const int32_t* __restrict__ qrows, int nq, int32_t C, int32_t per,
                                                      int k, int N, const int32_t* __restrict__ cand_id,
                                                      const int64_t* __restrict__ excl_beg,
                                                      const int64_t* __restrict__ excl_end,
-                                                     const int32_t* __restrict__ excl_rows, Key32* __restrict__ part) {
+                                                     const int32_t* __restrict__ excl_rows, Key32* __restrict__ part,
+                                                     const float* __restrict__ qinv,
+                                                     const float* __restrict__ cinv) {
   constexpr int NT = NW * 64, QT = NW * 32, BSTR = rec_bstr(NW);
+  constexpr int CI_PER = (kCT + NT - 1) / NT;  // candidate inverses of a tile per thread (COS)
   constexpr int A_PER = kCT * 4 / NT;  // float4 slots of the candidate stage per thread
   constexpr int B_PER = QT * 4 / NT;   // ... of the query stage (= 2)
   extern __shared__ __align__(16) unsigned char rec_smem[];
   Key32* lists = reinterpret_cast<Key32*>(rec_smem);                         // [QT][N]
   uint64_t* pend = reinterpret_cast<uint64_t*>(rec_smem + sizeof(Key32) * QT * N);  // [kPend][NT]
   float* stage = reinterpret_cast<float*>(pend + kPend * NT);                      // [2][kKC][kAStr + BSTR]
+  float* cinv_s = stage + 2 * rec_stage_floats(NW);                                // [2][kCT], COS only
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int q0 = blockIdx.x * QT, S = gridDim.y, s = blockIdx.y;
   const int32_t cbeg = static_cast<int32_t>(min(static_cast<int64_t>(C), static_cast<int64_t>(s) * per));
@@ -158,6 +169,7 @@ __global__ __launch_bounds__(NW * 64) void k_rec_f32(const float* __restrict__ Q
     bsrc[i] = q < nq ? Qf + static_cast<int64_t>(qrows[q]) * k : nullptr;
   }
   float4 ra[A_PER], rb[B_PER];
+  float rci[CI_PER];
   auto load4 = [&](const float* row, int f) -> float4 {
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
     if (row == nullptr) return v;
@@ -180,8 +192,18 @@ __global__ __launch_bounds__(NW * 64) void k_rec_f32(const float* __restrict__ Q
     }
 #pragma unroll
     for (int i = 0; i < B_PER; ++i) rb[i] = load4(bsrc[i], f0 + 4 * ((tid + i * NT) & 3));
+    if constexpr (COS) {
+      if (f0 == 0) {  // a new tile: its inverses
+#pragma unroll
+        for (int i = 0; i < CI_PER; ++i) {
+          const int x = tid + i * NT;
+          rci[i] = (x < kCT && c0 + x < cend) ? cinv[c0 + x] : 0.f;
+        }
+      }
+    }
   };
-  auto put = [&](float* buf) {
+  // ci: where a new tile's inverses go (null inside a tile)
+  auto put = [&](float* buf, float* ci) {
 #pragma unroll
     for (int i = 0; i < A_PER; ++i) {
       const int x = tid + i * NT, row = x / 4, kf = 4 * (x & 3);
@@ -199,6 +221,15 @@ __global__ __launch_bounds__(NW * 64) void k_rec_f32(const float* __restrict__ Q
       bb[(kf + 2) * BSTR + row] = rb[i].z;
       bb[(kf + 3) * BSTR + row] = rb[i].w;
     }
+    if constexpr (COS) {
+      if (ci != nullptr) {
+#pragma unroll
+        for (int i = 0; i < CI_PER; ++i) {
+          const int x = tid + i * NT;
+          if (x < kCT) ci[x] = rci[i];
+        }
+      }
+    }
   };
 
   const int nkc = (k + kKC - 1) / kKC;
@@ -211,6 +242,10 @@ __global__ __launch_bounds__(NW * 64) void k_rec_f32(const float* __restrict__ Q
   Key32* mylist = lists + jq * N;
   int64_t eb = 0, ee = 0;
   if (qok) { eb = excl_beg[qme]; ee = excl_end[qme]; }
+  float qi = 0.f;
+  if constexpr (COS) {
+    if (qok) qi = qinv[qrows[qme]];
+  }
 
   f32x16 acc[4];
 #pragma unroll
@@ -220,7 +255,7 @@ __global__ __launch_bounds__(NW * 64) void k_rec_f32(const float* __restrict__ Q
 
   if (total > 0) {
     fetch(cbeg, 0);
-    put(stage);
+    put(stage, cinv_s);
   }
   __syncthreads();
   int tile = 0, kc = 0;
@@ -246,6 +281,7 @@ __global__ __launch_bounds__(NW * 64) void k_rec_f32(const float* __restrict__ Q
       const int32_t c0 = cbeg + tile * kCT;
       uint32_t thr_hi = static_cast<uint32_t>(mylist[N - 1].v >> 32);
       int cnt = 0;
+      [[maybe_unused]] float4 ci4 = make_float4(0.f, 0.f, 0.f, 0.f);
       auto drain = [&]() {
         for (int i = 0; __any(i < cnt); ++i) {
           bool have = i < cnt;
@@ -271,7 +307,13 @@ __global__ __launch_bounds__(NW * 64) void k_rec_f32(const float* __restrict__ Q
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int32_t local = 32 * t + (r & 3) + 8 * (r >> 2) + 4 * h;
-          const uint32_t o = ord32(acc[t][r]);
+          float sc = acc[t][r];
+          if constexpr (COS) {
+            if ((r & 3) == 0) ci4 = *reinterpret_cast<const float4*>(cinv_s + (tile & 1) * kCT + local);
+            const float ci = (r & 3) == 0 ? ci4.x : (r & 3) == 1 ? ci4.y : (r & 3) == 2 ? ci4.z : ci4.w;
+            sc = sc * (qi * ci);
+          }
+          const uint32_t o = ord32(sc);
           if (qok && c0 + local < cend && o >= thr_hi) {
             pend[cnt * NT + tid] = (static_cast<uint64_t>(o) << 32) | static_cast<uint32_t>(local);
             ++cnt;
@@ -282,7 +324,8 @@ __global__ __launch_bounds__(NW * 64) void k_rec_f32(const float* __restrict__ Q
       }
       drain();
     }
-    if (it + 1 < total) put(stage + ((it + 1) & 1) * rec_stage_floats(NW));
+    if (it + 1 < total)
+      put(stage + ((it + 1) & 1) * rec_stage_floats(NW), nkc_i == 0 ? cinv_s + (ntile_i & 1) * kCT : nullptr);
     __syncthreads();
     tile = ntile_i;
     kc = nkc_i;
@@ -298,13 +341,16 @@ __global__ __launch_bounds__(NW * 64) void k_rec_f32(const float* __restrict__ Q
 constexpr int kQW = 4;  // queries per wave
 
 // Grid: (ceil(nq / (4 * kQW)), S), 4 waves per block.  Lane = candidate; the wave's kQW query rows
-// are wave-uniform reads.
+// are wave-uniform reads.  COS: as k_rec_f32, one inverse per candidate lane, the queries' wave-uniform.
+template <bool COS>
 __global__ __launch_bounds__(256) void k_rec_f64(const double* __restrict__ Qf, const double* __restrict__ Cf,
                                                  const int32_t* __restrict__ qrows, int nq, int32_t C, int32_t per,
                                                  int k, int N, const int32_t* __restrict__ cand_id,
                                                  const int64_t* __restrict__ excl_beg,
                                                  const int64_t* __restrict__ excl_end,
-                                                 const int32_t* __restrict__ excl_rows, Key64* __restrict__ part) {
+                                                 const int32_t* __restrict__ excl_rows, Key64* __restrict__ part,
+                                                 const double* __restrict__ qinv,
+                                                 const double* __restrict__ cinv) {
   __shared__ Key64 lists[4][kQW * MF_RECOMMEND_MAX_TOP];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int S = gridDim.y, s = blockIdx.y;
@@ -314,10 +360,12 @@ __global__ __launch_bounds__(256) void k_rec_f64(const double* __restrict__ Qf, 
   Key64* wl = lists[wave];
   for (int x = lane; x < kQW * N; x += 64) wl[x] = Key64{0, 0};
   const double* qp[kQW];
+  [[maybe_unused]] double qi[kQW];
 #pragma unroll
   for (int i = 0; i < kQW; ++i) {
     const int q = min(q0 + i, nq - 1);
     qp[i] = Qf + static_cast<int64_t>(qrows[max(q, 0)]) * k;
+    if constexpr (COS) qi[i] = qinv[qrows[max(q, 0)]];
   }
   for (int32_t c0 = cbeg; c0 < cend; c0 += 64) {
     const int32_t crow = c0 + lane;
@@ -332,6 +380,11 @@ __global__ __launch_bounds__(256) void k_rec_f64(const double* __restrict__ Qf, 
       for (int i = 0; i < kQW; ++i) pq[i] = pq[i] + qp[i][f] * c;
     }
     const int32_t cid = cok ? cand_id[crow] : 0;
+    if constexpr (COS) {
+      const double ci = cok ? cinv[crow] : 0.0;
+#pragma unroll
+      for (int i = 0; i < kQW; ++i) pq[i] = pq[i] * (qi[i] * ci);
+    }
 #pragma unroll
     for (int i = 0; i < kQW; ++i) {
       const int q = q0 + i;
@@ -357,6 +410,48 @@ __global__ __launch_bounds__(256) void k_rec_f64(const double* __restrict__ Qf, 
     const int i = x / N, q = q0 + i;
     if (q < nq) part[(static_cast<int64_t>(q) * S + s) * N + (x - i * N)] = wl[x];
   }
+}
+
+// ---- row norms (cosine) -------------------------------------------------------------------------
+// inv[row] = 1 / sqrt(nn), nn the sum over ascending f from 0 of x_f * x_f in T (f32: an fmaf chain; f64:
+// nn = nn + x * x, not fused), the square root and the division in f64, rounded once to T.  A zero row
+// gives +inf.  One lane per row, the chain is sequential in f; a wave moves its 64 rows through LDS in
+// chunks of 128 bytes per row, so that the loads are whole cache lines (a lane walking its own row would
+// touch 64 lines per load), all of a chunk's loads in flight at once.  The row stride of the tile is odd in
+// elements: the lanes' reads of their own rows fall on distinct banks.  One wave per block: a batch of a
+// few thousand query vectors still spreads over as many CUs.
+constexpr int kNormRows = 64;  // rows per block
+
+template <typename T>
+__global__ __launch_bounds__(kNormRows) void k_row_inv_norm(const T* __restrict__ X, int64_t rows, int k,
+                                                            T* __restrict__ inv) {
+  constexpr int KC = 128 / sizeof(T);
+  __shared__ T tile[kNormRows][KC + 1];
+  const int lane = threadIdx.x;
+  const int64_t r0 = static_cast<int64_t>(blockIdx.x) * kNormRows;
+  T nn = 0;
+  for (int f0 = 0; f0 < k; f0 += KC) {  // k is uniform
+    const int kc = min(KC, k - f0);
+    T ld[KC];
+#pragma unroll
+    for (int i = 0; i < KC; ++i) {
+      const int e = i * 64 + lane, r = e / KC, c = e % KC;
+      ld[i] = (r0 + r < rows && c < kc) ? X[(r0 + r) * k + f0 + c] : T(0);
+    }
+#pragma unroll
+    for (int i = 0; i < KC; ++i) {
+      const int e = i * 64 + lane;
+      tile[e / KC][e % KC] = ld[i];
+    }
+    __syncthreads();
+    for (int c = 0; c < kc; ++c) {
+      const T v = tile[lane][c];
+      if constexpr (sizeof(T) == 4) nn = fmaf(v, v, nn);
+      else nn = nn + v * v;
+    }
+    __syncthreads();
+  }
+  if (r0 + lane < rows) inv[r0 + lane] = static_cast<T>(1.0 / sqrt(static_cast<double>(nn)));
 }
 
 // ---- merge ------------------------------------------------------------------------------------
@@ -392,23 +487,25 @@ __global__ __launch_bounds__(256) void k_rec_merge(const K* __restrict__ part, i
   if (lane == 0) counts[q] = cnt;
 }
 
-template <int NW>
-void rec_f32_dispatch(hipStream_t st, const float* Q, const float* Cf, const int32_t* qrows, int nq, int32_t C, int S,
-                      int32_t per, int k, int N, const int32_t* cand_id, const int64_t* eb, const int64_t* ee,
-                      const int32_t* er, void* part) {
+template <int NW, bool VEC, bool COS>
+void rec_f32_launch(hipStream_t st, const float* Q, const float* Cf, const int32_t* qrows, int nq, int32_t C, int S,
+                    int32_t per, int k, int N, const int32_t* cand_id, const int64_t* eb, const int64_t* ee,
+                    const int32_t* er, void* part, const float* qinv, const float* cinv) {
   const dim3 grid(static_cast<unsigned>((nq + NW * 32 - 1) / (NW * 32)), static_cast<unsigned>(S)), block(NW * 64);
-  const size_t smem = sizeof(Key32) * NW * 32 * N + 8 * kPend * NW * 64 + sizeof(float) * 2 * rec_stage_floats(NW);
-  // up to 72 KB (NW = 4, top 16): above the 64 KB a kernel gets without asking
-  const void* fn = k % 4 == 0 ? reinterpret_cast<const void*>(&k_rec_f32<NW, true>)
-                              : reinterpret_cast<const void*>(&k_rec_f32<NW, false>);
+  const size_t smem = sizeof(Key32) * NW * 32 * N + 8 * kPend * NW * 64 + sizeof(float) * 2 * rec_stage_floats(NW) +
+                      (COS ? sizeof(float) * 2 * kCT : 0);
+  // up to 72 KB (NW = 4, top 16; 1 KB more with COS): above the 64 KB a kernel gets without asking
+  const void* fn = reinterpret_cast<const void*>(&k_rec_f32<NW, VEC, COS>);
   if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(smem)) != hipSuccess)
     fail(MF_ERR_HIP, "k_rec_f32: " + std::to_string(smem) + " bytes of LDS refused");
-  if (k % 4 == 0)
-    hipLaunchKernelGGL((k_rec_f32<NW, true>), grid, block, smem, st, Q, Cf, qrows, nq, C, per, k, N, cand_id, eb, ee, er,
-                       static_cast<Key32*>(part));
-  else
-    hipLaunchKernelGGL((k_rec_f32<NW, false>), grid, block, smem, st, Q, Cf, qrows, nq, C, per, k, N, cand_id, eb, ee, er,
-                       static_cast<Key32*>(part));
+  hipLaunchKernelGGL((k_rec_f32<NW, VEC, COS>), grid, block, smem, st, Q, Cf, qrows, nq, C, per, k, N, cand_id, eb, ee,
+                     er, static_cast<Key32*>(part), qinv, cinv);
+}
+
+template <int NW, typename... A>
+void rec_f32_dispatch(bool vec, bool cos, A... a) {
+  if (cos) vec ? rec_f32_launch<NW, true, true>(a...) : rec_f32_launch<NW, false, true>(a...);
+  else vec ? rec_f32_launch<NW, true, false>(a...) : rec_f32_launch<NW, false, false>(a...);
 }
 
 }  // namespace
@@ -420,24 +517,48 @@ int recommend_query_tile(int top_n, bool f64) {
   return top_n <= 16 ? 128 : top_n <= 48 ? 64 : 32;
 }
 
+void launch_row_inv_norm(hipStream_t st, const void* X, int64_t rows, int k, bool f64, void* inv) {
+  if (rows <= 0) return;
+  const dim3 grid(static_cast<unsigned>((rows + kNormRows - 1) / kNormRows)), block(kNormRows);
+  if (f64)
+    hipLaunchKernelGGL((k_row_inv_norm<double>), grid, block, 0, st, static_cast<const double*>(X), rows, k,
+                       static_cast<double*>(inv));
+  else
+    hipLaunchKernelGGL((k_row_inv_norm<float>), grid, block, 0, st, static_cast<const float*>(X), rows, k,
+                       static_cast<float*>(inv));
+}
+
 void launch_recommend(hipStream_t st, const void* Q, const void* Cf, const int32_t* qrows, int nq, int32_t C, int S,
                       int k, int top_n, bool f64, const int32_t* cand_id, const int64_t* excl_beg,
                       const int64_t* excl_end, const int32_t* excl_rows, void* part, int32_t* ids, double* scores,
-                      int32_t* counts) {
+                      int32_t* counts, const void* q_inv, const void* c_inv) {
   if (nq <= 0) return;
   const int32_t per = (C + S - 1) / S;
+  const bool cos = c_inv != nullptr;
   if (f64) {
     const dim3 grid(static_cast<unsigned>((nq + 4 * kQW - 1) / (4 * kQW)), static_cast<unsigned>(S)), block(256);
-    hipLaunchKernelGGL(k_rec_f64, grid, block, 0, st, static_cast<const double*>(Q), static_cast<const double*>(Cf),
-                       qrows, nq, C, per, k, top_n, cand_id, excl_beg, excl_end, excl_rows, static_cast<Key64*>(part));
+    const double *qi = static_cast<const double*>(q_inv), *ci = static_cast<const double*>(c_inv);
+    if (cos)
+      hipLaunchKernelGGL((k_rec_f64<true>), grid, block, 0, st, static_cast<const double*>(Q),
+                         static_cast<const double*>(Cf), qrows, nq, C, per, k, top_n, cand_id, excl_beg, excl_end,
+                         excl_rows, static_cast<Key64*>(part), qi, ci);
+    else
+      hipLaunchKernelGGL((k_rec_f64<false>), grid, block, 0, st, static_cast<const double*>(Q),
+                         static_cast<const double*>(Cf), qrows, nq, C, per, k, top_n, cand_id, excl_beg, excl_end,
+                         excl_rows, static_cast<Key64*>(part), qi, ci);
   } else {
     const float* q = static_cast<const float*>(Q);
     const float* c = static_cast<const float*>(Cf);
+    const float *qi = static_cast<const float*>(q_inv), *ci = static_cast<const float*>(c_inv);
     // the lists of a block stay within 32 KB of LDS: 128 queries per block up to top 16, 64 up to 48, else 32
     const int64_t *eb = excl_beg, *ee = excl_end;
-    if (top_n <= 16) rec_f32_dispatch<4>(st, q, c, qrows, nq, C, S, per, k, top_n, cand_id, eb, ee, excl_rows, part);
-    else if (top_n <= 48) rec_f32_dispatch<2>(st, q, c, qrows, nq, C, S, per, k, top_n, cand_id, eb, ee, excl_rows, part);
-    else rec_f32_dispatch<1>(st, q, c, qrows, nq, C, S, per, k, top_n, cand_id, eb, ee, excl_rows, part);
+    const bool vec = k % 4 == 0;
+    if (top_n <= 16)
+      rec_f32_dispatch<4>(vec, cos, st, q, c, qrows, nq, C, S, per, k, top_n, cand_id, eb, ee, excl_rows, part, qi, ci);
+    else if (top_n <= 48)
+      rec_f32_dispatch<2>(vec, cos, st, q, c, qrows, nq, C, S, per, k, top_n, cand_id, eb, ee, excl_rows, part, qi, ci);
+    else
+      rec_f32_dispatch<1>(vec, cos, st, q, c, qrows, nq, C, S, per, k, top_n, cand_id, eb, ee, excl_rows, part, qi, ci);
   }
   const dim3 mgrid(static_cast<unsigned>((nq + 3) / 4)), mblock(256);
   if (f64)

@@ -37,6 +37,8 @@ INIT_PSEUDO_RANDOM = 0
 INIT_SEEDED = 1
 UID_BYTES = 128
 RECOMMEND_MAX_TOP = 128
+METRIC_DOT = 0     # mf_similar / mf_recommend_vectors: the score mf_recommend reports
+METRIC_COSINE = 1  # ... scaled by both rows' inverse norms
 ALS_REG_WEIGHTED = 0
 ALS_REG_PLAIN = 1
 ALS_CG_MAX_STEPS = 256
@@ -175,7 +177,7 @@ EXPORTS = [
     "mf_als_run_nonneg", "mf_als_run_implicit_nonneg", "mf_als_fit_nonneg", "mf_als_fit_implicit_nonneg",
     "mf_als_nonneg_stats", "mf_nnls_solve", "mf_als_append", "mf_als_run_rows", "mf_als_update",
     "mf_seen_set", "mf_seen_add", "mf_seen_from_als", "mf_seen_clear", "mf_seen_count", "mf_recommend_seen",
-    "mf_rank_eval_seen", "mf_pair_ranks_seen", "mf_online_prequential_seen",
+    "mf_rank_eval_seen", "mf_pair_ranks_seen", "mf_online_prequential_seen", "mf_similar", "mf_recommend_vectors",
 ]
 # The test hooks include/mfhip_testing.h declares (not product surface; same library).
 TESTING_EXPORTS = [
@@ -255,6 +257,10 @@ def lib() -> C.CDLL:
                                            _f64p, _f64p]),
         "mf_recommend": (C.c_int, [_ctxp, C.c_int, _i32p, C.c_int64, C.c_int32, _i32p, _i32p, C.c_int64, _i32p, _f64p,
                                    _i32p]),
+        "mf_similar": (C.c_int, [_ctxp, C.c_int, _i32p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _i32p, _i32p,
+                                 C.c_int64, _i32p, _f64p, _i32p]),
+        "mf_recommend_vectors": (C.c_int, [_ctxp, C.c_int, _f64p, C.c_int64, C.c_int32, C.c_int32, _i64p, _i32p,
+                                           C.c_int64, _i32p, _f64p, _i32p]),
         "mf_rank_eval": (C.c_int, [_ctxp, C.c_int, _i32p, _i32p, C.c_int64, C.c_int32, _i32p, _i32p, C.c_int64,
                                    C.POINTER(mf_rank_metrics), _i32p, _i32p, _f64p, C.c_int64]),
         "mf_pair_ranks": (C.c_int, [_ctxp, C.c_int, _i32p, _i32p, C.c_int64, _i32p, _i32p, C.c_int64, _i32p, _i32p,

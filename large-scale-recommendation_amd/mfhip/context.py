@@ -432,6 +432,55 @@ class Context:
         shape = (n, max(top_n, 1))
         return (ids[:n * shape[1]].reshape(shape), sc[:n * shape[1]].reshape(shape) if scores else None, counts[:n])
 
+    def similar(self, queries, top_n: int, side: int = L.SIDE_ITEM, metric: int = L.METRIC_COSINE,
+                include_self: bool = False, exclude=None, scores: bool = True):
+        """mf_similar: for every query id of `side` the top_n nearest ids of the same side, by cosine
+        (METRIC_COSINE) or by dot product (METRIC_DOT), scored and selected on the device.  The query's own
+        row is left out unless include_self.  exclude: (query ids, candidate ids) pairs never returned.
+        Returns (ids, scores or None, counts) laid out as recommend() lays them out."""
+        q = as_i32(queries)
+        n, top_n = len(q), int(top_n)
+        rows = max(n, 1) * max(top_n, 1)
+        ids = np.zeros(rows, np.int32)
+        sc = np.zeros(rows, np.float64) if scores else None
+        counts = np.zeros(max(n, 1), np.int32)
+        eq = ec = None
+        ne = 0
+        if exclude is not None:
+            eq, ec = as_i32(exclude[0]), as_i32(exclude[1])
+            ne = same_length(eq, ec)
+        check(L.lib().mf_similar(self._h, int(side), ptr(q, C.c_int32), n, top_n, int(metric), int(include_self),
+                                 ptr(eq, C.c_int32) if ne else None, ptr(ec, C.c_int32) if ne else None, ne,
+                                 ptr(ids, C.c_int32), ptr(sc, C.c_double) if scores else None, ptr(counts, C.c_int32)))
+        shape = (n, max(top_n, 1))
+        return (ids[:n * shape[1]].reshape(shape), sc[:n * shape[1]].reshape(shape) if scores else None, counts[:n])
+
+    def recommend_vectors(self, vecs, top_n: int, side: int = L.SIDE_ITEM, metric: int = L.METRIC_DOT, exclude=None,
+                          scores: bool = True):
+        """mf_recommend_vectors: for every row of vecs ([n, k] f64, vectors the model need not hold) the top_n
+        ids of `side`, by dot product or cosine.  exclude: (positions in vecs, candidate ids) pairs never
+        returned; positions outside [0, n) are ignored.  Returns (ids, scores or None, counts) laid out as
+        recommend() lays them out."""
+        v = np.ascontiguousarray(vecs, np.float64)
+        if v.ndim != 2 or v.shape[1] != self.k:
+            raise ValueError(f"vecs must be [n, {self.k}], got {v.shape}")
+        n, top_n = v.shape[0], int(top_n)
+        rows = max(n, 1) * max(top_n, 1)
+        ids = np.zeros(rows, np.int32)
+        sc = np.zeros(rows, np.float64) if scores else None
+        counts = np.zeros(max(n, 1), np.int32)
+        eq = ec = None
+        ne = 0
+        if exclude is not None:
+            eq, ec = np.ascontiguousarray(exclude[0], np.int64), as_i32(exclude[1])
+            ne = same_length(eq, ec)
+        check(L.lib().mf_recommend_vectors(self._h, int(side), ptr(v, C.c_double) if n else None, n, top_n, int(metric),
+                                           ptr(eq, C.c_int64) if ne else None, ptr(ec, C.c_int32) if ne else None, ne,
+                                           ptr(ids, C.c_int32), ptr(sc, C.c_double) if scores else None,
+                                           ptr(counts, C.c_int32)))
+        shape = (n, max(top_n, 1))
+        return (ids[:n * shape[1]].reshape(shape), sc[:n * shape[1]].reshape(shape) if scores else None, counts[:n])
+
     def rank_eval(self, gt_queries, gt_cands, top_n: int, side: int = L.SIDE_USER, exclude=None,
                   per_query: bool = False) -> "RankMetrics":
         """mf_rank_eval: ranking metrics of the held-out pairs (gt_queries[j], gt_cands[j]) against the

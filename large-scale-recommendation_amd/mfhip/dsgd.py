@@ -204,6 +204,18 @@ class DSGDforMF:
         ids, sc, cnt = self._ctx.recommend([int(item)], num, side=L.SIDE_ITEM)
         return [(int(ids[0, x]), int(item), float(sc[0, x])) for x in range(int(cnt[0]))]
 
+    def similarProducts(self, product: int, num: int, metric: int = L.METRIC_COSINE) -> List[Tuple[int, float]]:
+        """The num items nearest to `product` in factor space, the item itself left out: (id, score)."""
+        self._require_fit()
+        ids, sc, cnt = self._ctx.similar([int(product)], num, side=L.SIDE_ITEM, metric=metric)
+        return [(int(ids[0, x]), float(sc[0, x])) for x in range(int(cnt[0]))]
+
+    def similarUsers(self, user: int, num: int, metric: int = L.METRIC_COSINE) -> List[Tuple[int, float]]:
+        """The num users nearest to `user` in factor space, the user left out: (id, score)."""
+        self._require_fit()
+        ids, sc, cnt = self._ctx.similar([int(user)], num, side=L.SIDE_USER, metric=metric)
+        return [(int(ids[0, x]), float(sc[0, x])) for x in range(int(cnt[0]))]
+
     def recommendProductsForUsers(self, num: int, users=None, exclude=None) -> dict:
         """users=None: every user of the model.  exclude: (user ids, item ids) pairs never recommended."""
         self._require_fit()
