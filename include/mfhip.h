@@ -618,6 +618,59 @@ int mf_als_update(mf_ctx* ctx, const int32_t* users, const int32_t* items, const
                   const mf_als_solve* how, int32_t rounds, int64_t* solved_users_out /* may be NULL */,
                   int64_t* solved_items_out /* may be NULL */);
 
+/* Removal, the mirror image of mf_als_append: ratings leave the CSRs on the device, so that a sliding window,
+   a retraction (an un-rated item, a returned purchase, a deleted account, a withdrawn item) needs no
+   mf_als_prepare of the surviving history.  The reference's ratingsHistory (sp/OnlineSpark.scala:47,70) is an
+   unbounded union; that limitation is not reproduced.  Nothing is uploaded but the batch.
+
+   mf_als_remove.  The rule: the entries are processed in ascending j, and entry j removes the OLDEST remaining
+   rating of the pair (users[j], items[j]) -- the first one in the row's CSR order.  CSR order is arrival order
+   on both sides, so the user-side and the item-side CSR lose the same instance.  found_out[j] (n bytes, may be
+   NULL) = 1 if there was such a rating.  An entry is a miss, and a miss changes nothing, when it names an id
+   the model does not hold (no row is ever inserted), a pair that was never rated, or a pair whose instances
+   are all gone already; m entries naming one pair remove its m oldest instances.  *removed_out (may be NULL)
+   is the number of hits.  The rating values play no part in the choice.
+   Resulting state.  The prepared data is exactly what mf_als_prepare would have built from the earlier arrays
+   with the removed instances deleted: per row and per side the surviving ratings keep their order; the per-row
+   count and n+ are those of what survives (n+ counts the stored values > 0, a comparison on the stored bits
+   and the only floating-point operation of the call); the long-row chunks, the launches and the rated-row
+   list that G is summed over are rebuilt as mf_als_prepare builds them, with the chunk, batch, Gram-slice and
+   slab values that prepare read.  Sliding window: after prepare(A), append(B), append(C), a remove of A's
+   (user, item) arrays leaves exactly prepare(B ++ C) on the same rows, even where A and B rate the same pair.
+   Emptied rows.  A row that loses its last rating stays in the model and keeps its factor bits; every later
+   half-sweep and mf_als_run_rows skip it, and it leaves the rated-row list, so implicit G no longer sums it:
+   the rule for rows the data does not name.
+   Untouched: factor rows, row numbering, the half-sweep counter, mf_als_nonneg_stats, a prepared fast DSGD
+   schedule and the seen set (below: mf_seen_remove, mf_seen_from_als).  The conjugate-gradient work lists are
+   rebuilt on their next use, as after an append.
+   Each CSR is repacked on the device into fresh arrays, one side at a time (integer work only: the batch is
+   sorted, every stored entry searches it, the few that match are ranked by age; every survivor is read once
+   and written once), so a call needs room for a second copy of the larger CSR.
+   Errors, all raised before anything changes.  MF_ERR_STATE as mf_als_append: before mf_als_prepare, after a
+   later mf_dsgd_prepare / mf_dsgd_fit, on a rank-mode context or one with more than one device.
+   MF_ERR_INVALID: a NULL ctx, n < 0, n >= 2^31, NULL users / items with n > 0, a rank above 256.  n == 0 is
+   a valid no-op with NULL arrays.
+
+   mf_als_remove_rows.  Every rating of the rows of `side` named by ids[0 .. n_ids) leaves both CSRs: an
+   account deletion, a withdrawn item.  Ids the model does not hold and ids without ratings are skipped,
+   duplicates are allowed; *removed_out (may be NULL) counts the ratings removed, each once.  The resulting
+   state and the errors are mf_als_remove's, and MF_ERR_INVALID for a bad side, n_ids < 0 or NULL ids with
+   n_ids > 0.  The factor row stays: mf_recommend and every other reader still return it.  Deleting a factor
+   row (or renumbering rows) is out of scope.
+
+   mf_als_retract is, by definition: every argument checked as mf_als_update checks them, then
+   mf_als_remove(users, items, n, found_out, removed_out), then `rounds` times { mf_als_run_rows(MF_SIDE_USER,
+   users), mf_als_run_rows(MF_SIDE_ITEM, items) }.  Users go first for symmetry with mf_als_update (no row is
+   new here, so the order carries no hazard).  Rows the removal emptied fall out of mf_als_run_rows by its own
+   rule.  rounds == 0 is a remove; rounds < 0 is MF_ERR_INVALID.  *solved_users_out / *solved_items_out (may be
+   NULL) are the counts of the last round (0 with rounds == 0). */
+int mf_als_remove(mf_ctx* ctx, const int32_t* users, const int32_t* items, int64_t n,
+                  uint8_t* found_out /* [n] or NULL */, int64_t* removed_out /* may be NULL */);
+int mf_als_remove_rows(mf_ctx* ctx, int side, const int32_t* ids, int64_t n_ids, int64_t* removed_out /* may be NULL */);
+int mf_als_retract(mf_ctx* ctx, const int32_t* users, const int32_t* items, int64_t n, const mf_als_solve* how,
+                   int32_t rounds, uint8_t* found_out /* [n] or NULL */, int64_t* removed_out /* may be NULL */,
+                   int64_t* solved_users_out /* may be NULL */, int64_t* solved_items_out /* may be NULL */);
+
 /* Exact updateLocalFactors replacement (DSGDforMF.scala:378-418) on caller buffers:
    users[nu x k], items[ni x k] are updated in place; omegas are per row.  Reentrant
    on disjoint buffers with distinct contexts, as Flink calls it per task slot. */
@@ -704,6 +757,12 @@ int mf_online_prequential_sampled(mf_ctx* ctx, const int32_t* users, const int32
    pair).  It is a snapshot: a later mf_als_append does not change the set, the caller follows it with
    mf_seen_add of the same batch.  mf_seen_clear leaves no set; mf_seen_count gives the distinct pairs held
    (64-bit; 0 with no set).
+   mf_seen_remove is the set difference: the set becomes the held set minus the pairs given.  *removed_out
+   (may be NULL) is the number of distinct pairs that were held and are gone, *ignored_out (may be NULL) the
+   pairs naming an unknown id, mf_seen_add's rule.  Pairs that are not held are no error.  With no set the call
+   changes nothing and still writes both outputs (*removed_out = 0).  Errors and state rules are mf_seen_add's.
+   The set has no multiplicity: after mf_als_remove on a window in which a pair may recur, the exact seen set
+   is mf_seen_from_als again, not mf_seen_remove of the expired batch.
    Lifetime.  The set survives everything that only adds rows -- mf_online_update*, mf_set_factors,
    mf_load_model, mf_als_append, every run call -- and a row gained after the set was built has no seen pairs
    until some are added.  mf_dsgd_prepare / mf_dsgd_fit rebuild the rows and leave no set, as they invalidate
@@ -726,6 +785,8 @@ int mf_online_prequential_sampled(mf_ctx* ctx, const int32_t* users, const int32
    validation runs before anything changes.  A context on several devices keeps the set on its first. */
 int mf_seen_set(mf_ctx* ctx, const int32_t* users, const int32_t* items, int64_t n, int64_t* ignored_out);
 int mf_seen_add(mf_ctx* ctx, const int32_t* users, const int32_t* items, int64_t n, int64_t* ignored_out);
+int mf_seen_remove(mf_ctx* ctx, const int32_t* users, const int32_t* items, int64_t n, int64_t* removed_out,
+                   int64_t* ignored_out);
 int mf_seen_from_als(mf_ctx* ctx);
 int mf_seen_clear(mf_ctx* ctx);
 int mf_seen_count(mf_ctx* ctx, int64_t* pairs);

@@ -134,6 +134,14 @@ int mf_debug_als_csr(mf_ctx* ctx, int side, int64_t* off_out, int32_t* cols_out,
    checked through mf_debug_als_csr on the device. */
 int mf_debug_als_append_placement(const int64_t* old_off, int64_t old_rows, const int32_t* batch_row, int64_t n,
                                   int64_t new_rows, int64_t* new_off_out, int64_t* batch_pos_out);
+/* mf_debug_als_remove_select: the rule mf_als_remove's kernels follow, on the host in plain C++ (no GPU
+   needed).  For one side's CSR off[rows + 1] / cols[off[rows]] and a batch whose entry j names the pair
+   (batch_row[j] < rows, batch_col[j]): in ascending j, entry j takes the oldest remaining instance of its pair,
+   the first position of the row that holds batch_col[j] and that no earlier entry took.  pos_out[j] = that
+   position in cols[], or -1 for a miss.  MF_ERR_INVALID: off[0] != 0, descending offsets, a batch row outside
+   [0, rows), a negative count or a NULL array that would be read. */
+int mf_debug_als_remove_select(const int64_t* off, int64_t rows, const int32_t* cols, const int32_t* batch_row,
+                               const int32_t* batch_col, int64_t n, int64_t* pos_out);
 /* mf_debug_seen_csr: the resident seen set's table of `side` copied back (MF_SIDE_ITEM: the item-major table,
    built here if it is not there, as an item query would).  *rows_out = the rows `side` holds now, *nnz_out =
    the distinct pairs held; row_ids_out[*rows_out] = the id of every factor row, off_out[*rows_out + 1] and

@@ -73,6 +73,16 @@ public final class MfHip {
   public static native void alsUpdate(long ctx, int[] users, int[] items, double[] ratings, double lambda,
                                       int reg, int implicit, double alpha, int solver, int cgSteps, int rounds,
                                       int[] solvedOut);
+  // Removal (mf_als_remove / mf_als_remove_rows / mf_als_retract): entry j removes the oldest rating of the
+  // pair (users[j], items[j]) still held; alsRemoveRows removes every rating of the named users or items (the
+  // factor rows stay); alsRetract removes, then `rounds` times solves the batch's users and then its items.
+  // Each returns the ratings removed; foundOut (may be null, length >= n) receives 0 / 1 per entry, solvedOut
+  // (may be null, length >= 2) the last round's user and item counts.
+  public static native long alsRemove(long ctx, int[] users, int[] items, byte[] foundOut);
+  public static native long alsRemoveRows(long ctx, int side, int[] ids);
+  public static native long alsRetract(long ctx, int[] users, int[] items, double lambda, int reg, int implicit,
+                                       double alpha, int solver, int cgSteps, int rounds, byte[] foundOut,
+                                       int[] solvedOut);
   // unblock (DSGDforMF.scala:245-255) and checkpoint restore
   public static native long numFactors(long ctx, int side);
   public static native long getFactors(long ctx, int side, int[] idsOut, double[] vecsOut);
@@ -136,6 +146,9 @@ public final class MfHip {
   // bit; addEvents: the batch joins the set after the update
   public static native long seenSet(long ctx, int[] users, int[] items);
   public static native long seenAdd(long ctx, int[] users, int[] items);
+  // seenRemove (mf_seen_remove): the set minus the pairs given; returns the distinct held pairs removed,
+  // ignoredOut (may be null, length >= 1) receives the pairs naming an unknown id
+  public static native long seenRemove(long ctx, int[] users, int[] items, int[] ignoredOut);
   public static native void seenFromAls(long ctx);
   public static native void seenClear(long ctx);
   public static native long seenCount(long ctx);

@@ -357,6 +357,65 @@ JNIEXPORT void JNICALL JFN(alsUpdate)(JNIEnv* env, jclass c, jlong h, jintArray 
   release(env, &eo, 0);
 }
 
+/* Removal: mf_als_remove, mf_als_remove_rows, mf_als_retract.  foundOut (may be null, length >= n) receives
+   0 / 1 per entry; the return value is the number of ratings removed. */
+static int acquire_all(JNIEnv* env, Elems* e, const jarray* a, const int* kind, int n);
+static jlong als_remove_or_retract(JNIEnv* env, jlong h, jintArray u, jintArray i, const mf_als_solve* how, jint rounds,
+                                   jbyteArray foundOut, jintArray solvedOut) {
+  if (require(env, u && i && len(env, u) == len(env, i), "users and items must match in length")) return 0;
+  const jsize n = len(env, u);
+  if (require(env, !foundOut || len(env, foundOut) >= n, "foundOut must hold an entry per pair")) return 0;
+  if (require(env, !solvedOut || len(env, solvedOut) >= 2, "solvedOut must hold 2 entries")) return 0;
+  uint8_t* found = foundOut && n ? (uint8_t*)malloc((size_t)n) : NULL;
+  if (require(env, !(foundOut && n) || found, "out of memory")) return 0;
+  Elems e[2];
+  const jarray arr[2] = {u, i};
+  const int kind[2] = {kInt, kInt};
+  if (acquire_all(env, e, arr, kind, 2)) {
+    free(found);
+    return 0;
+  }
+  const int32_t* pu = n ? (const int32_t*)e[0].p : NULL;
+  const int32_t* pi = n ? (const int32_t*)e[1].p : NULL;
+  int64_t removed = 0, su = 0, si = 0;
+  int st = how ? mf_als_retract(CTX(h), pu, pi, n, how, rounds, found, &removed, &su, &si)
+               : mf_als_remove(CTX(h), pu, pi, n, found, &removed);
+  for (int x = 1; x >= 0; --x) release(env, &e[x], JNI_ABORT);
+  if (check(env, st) == MF_OK) {
+    Elems eo = {0};
+    if (found) (*env)->SetByteArrayRegion(env, foundOut, 0, n, (const jbyte*)found);
+    if (solvedOut && !acquire(env, &eo, solvedOut, kInt)) {
+      ((jint*)eo.p)[0] = (jint)su;
+      ((jint*)eo.p)[1] = (jint)si;
+      release(env, &eo, 0);
+    }
+  }
+  free(found);
+  return (jlong)removed;
+}
+
+JNIEXPORT jlong JNICALL JFN(alsRemove)(JNIEnv* env, jclass c, jlong h, jintArray u, jintArray i, jbyteArray foundOut) {
+  return als_remove_or_retract(env, h, u, i, NULL, 0, foundOut, NULL);
+}
+
+JNIEXPORT jlong JNICALL JFN(alsRemoveRows)(JNIEnv* env, jclass c, jlong h, jint side, jintArray ids) {
+  if (require(env, ids != NULL, "ids must not be null")) return 0;
+  Elems e = {0};
+  if (acquire(env, &e, ids, kInt)) return 0;
+  int64_t removed = 0;
+  int st = mf_als_remove_rows(CTX(h), side, (const int32_t*)e.p, len(env, ids), &removed);
+  release(env, &e, JNI_ABORT);
+  check(env, st);
+  return (jlong)removed;
+}
+
+JNIEXPORT jlong JNICALL JFN(alsRetract)(JNIEnv* env, jclass c, jlong h, jintArray u, jintArray i, jdouble lambda,
+                                        jint reg, jint implicit, jdouble alpha, jint solver, jint cgSteps, jint rounds,
+                                        jbyteArray foundOut, jintArray solvedOut) {
+  const mf_als_solve how = als_how(lambda, reg, implicit, alpha, solver, cgSteps);
+  return als_remove_or_retract(env, h, u, i, &how, rounds, foundOut, solvedOut);
+}
+
 JNIEXPORT void JNICALL JFN(dsgdRun)(JNIEnv* env, jclass c, jlong h, jlong supersteps) {
   check(env, mf_dsgd_run(CTX(h), supersteps));
 }
@@ -675,6 +734,28 @@ JNIEXPORT jlong JNICALL JFN(seenSet)(JNIEnv* env, jclass c, jlong h, jintArray u
 
 JNIEXPORT jlong JNICALL JFN(seenAdd)(JNIEnv* env, jclass c, jlong h, jintArray u, jintArray i) {
   return seen_put(env, h, u, i, 1);
+}
+
+/* mf_seen_remove: returns the distinct held pairs removed; ignoredOut (may be null, length >= 1) the pairs
+   naming an unknown id. */
+JNIEXPORT jlong JNICALL JFN(seenRemove)(JNIEnv* env, jclass c, jlong h, jintArray u, jintArray i, jintArray ignoredOut) {
+  if (require(env, u && i && len(env, u) == len(env, i), "users and items must match in length")) return 0;
+  if (require(env, !ignoredOut || len(env, ignoredOut) >= 1, "ignoredOut must hold 1 entry")) return 0;
+  const jsize n = len(env, u);
+  Elems e[2];
+  const jarray arr[2] = {u, i};
+  const int kind[2] = {kInt, kInt};
+  if (acquire_all(env, e, arr, kind, 2)) return 0;
+  int64_t removed = 0, ignored = 0;
+  int st = mf_seen_remove(CTX(h), n ? (const int32_t*)e[0].p : NULL, n ? (const int32_t*)e[1].p : NULL, n, &removed,
+                          &ignored);
+  for (int x = 1; x >= 0; --x) release(env, &e[x], JNI_ABORT);
+  Elems eo = {0};
+  if (check(env, st) == MF_OK && ignoredOut && !acquire(env, &eo, ignoredOut, kInt)) {
+    ((jint*)eo.p)[0] = (jint)ignored; /* at most n < 2^31 */
+    release(env, &eo, 0);
+  }
+  return (jlong)removed;
 }
 
 JNIEXPORT void JNICALL JFN(seenFromAls)(JNIEnv* env, jclass c, jlong h) { check(env, mf_seen_from_als(CTX(h))); }

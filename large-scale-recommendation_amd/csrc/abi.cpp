@@ -447,6 +447,19 @@ int mf_seen_add(mf_ctx* ctx, const int32_t* users, const int32_t* items, int64_t
   return seen_put_entry(ctx, users, items, n, true, ignored_out, "mf_seen_add");
 }
 
+int mf_seen_remove(mf_ctx* ctx, const int32_t* users, const int32_t* items, int64_t n, int64_t* removed_out,
+                   int64_t* ignored_out) {
+  return guarded([&] {
+    MF_REQUIRE(ctx, "null context");
+    MF_REQUIRE(n >= 0, "negative count");
+    MF_REQUIRE(n == 0 || (users && items), "null pair list");
+    MF_REQUIRE(n < (int64_t{1} << 31) - 1, "fewer than 2^31 - 1 pairs per call");
+    seen_check(ctx, "mf_seen_remove");
+    require_healthy(ctx);
+    seen_remove(ctx, users, items, n, removed_out, ignored_out);
+  });
+}
+
 int mf_seen_from_als(mf_ctx* ctx) {
   return guarded([&] {
     seen_check(ctx, "mf_seen_from_als");
@@ -697,6 +710,44 @@ int mf_als_update(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double*
   return guarded([&] {
     MF_REQUIRE(ctx, "null context");
     als_update(ctx, u, i, r, n, als_params_of(how), rounds, solved_users_out, solved_items_out);
+  });
+}
+
+int mf_als_remove(mf_ctx* ctx, const int32_t* u, const int32_t* i, int64_t n, uint8_t* found_out, int64_t* removed_out) {
+  return guarded([&] {
+    MF_REQUIRE(ctx, "null context");
+    const int64_t removed = als_remove(ctx, u, i, n, found_out);
+    if (removed_out) *removed_out = removed;
+  });
+}
+
+int mf_als_remove_rows(mf_ctx* ctx, int side, const int32_t* ids, int64_t n_ids, int64_t* removed_out) {
+  return guarded([&] {
+    MF_REQUIRE(ctx, "null context");
+    const int64_t removed = als_remove_rows(ctx, side, ids, n_ids);
+    if (removed_out) *removed_out = removed;
+  });
+}
+
+int mf_als_retract(mf_ctx* ctx, const int32_t* u, const int32_t* i, int64_t n, const mf_als_solve* how, int32_t rounds,
+                   uint8_t* found_out, int64_t* removed_out, int64_t* solved_users_out, int64_t* solved_items_out) {
+  return guarded([&] {
+    MF_REQUIRE(ctx, "null context");
+    const int64_t removed =
+        als_retract(ctx, u, i, n, als_params_of(how), rounds, found_out, solved_users_out, solved_items_out);
+    if (removed_out) *removed_out = removed;
+  });
+}
+
+int mf_debug_als_remove_select(const int64_t* off, int64_t rows, const int32_t* cols, const int32_t* batch_row,
+                               const int32_t* batch_col, int64_t n, int64_t* pos_out) {
+  return guarded([&] {
+    MF_REQUIRE(off && rows >= 0 && n >= 0, "null offsets or a negative count");
+    MF_REQUIRE(off[0] == 0, "off[0] must be 0");
+    for (int64_t x = 0; x < rows; ++x) MF_REQUIRE(off[x + 1] >= off[x], "off must not descend");
+    MF_REQUIRE((off[rows] == 0 || cols) && (n == 0 || (batch_row && batch_col && pos_out)), "null argument");
+    for (int64_t j = 0; j < n; ++j) MF_REQUIRE(batch_row[j] >= 0 && batch_row[j] < rows, "a batch row is out of range");
+    als_remove_select(off, rows, cols, batch_row, batch_col, n, pos_out);
   });
 }
 

@@ -1,6 +1,6 @@
 // als.cpp -- ALS training (mf_als_prepare / mf_als_run / mf_als_fit, their _implicit, _cg, _implicit_cg,
-// _nonneg and _implicit_nonneg variants), incremental ALS (mf_als_append / mf_als_run_rows / mf_als_update)
-// and their testing hooks.
+// _nonneg and _implicit_nonneg variants), incremental ALS (mf_als_append / mf_als_run_rows / mf_als_update),
+// removal (mf_als_remove / mf_als_remove_rows / mf_als_retract) and their testing hooks.
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -664,6 +664,151 @@ void als_update(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r
   }
   if (solved_users) *solved_users = su;
   if (solved_items) *solved_items = si;
+}
+
+// ---------------------------------------------------------------------------------------
+// Removal: mf_als_remove / mf_als_remove_rows repack both CSRs on the device without the entries that go
+// (kernels_als_remove.hip), mf_als_retract is a remove followed by mf_als_run_rows of what it named.
+
+void als_remove_select(const int64_t* off, int64_t rows, const int32_t* cols, const int32_t* batch_row,
+                       const int32_t* batch_col, int64_t n, int64_t* pos_out) {
+  std::vector<uint8_t> gone(static_cast<size_t>(off[rows]), 0);
+  for (int64_t j = 0; j < n; ++j) {  // in ascending j: the oldest remaining instance of the pair
+    pos_out[j] = -1;
+    for (int64_t p = off[batch_row[j]]; p < off[batch_row[j] + 1]; ++p) {
+      if (cols[p] != batch_col[j] || gone[p]) continue;
+      gone[p] = 1;
+      pos_out[j] = p;
+      break;
+    }
+  }
+}
+
+namespace {
+
+// One side of a removal.  The selection runs first and changes nothing; when entries go, the survivors move
+// into fresh arrays on the device, the host takes the new offsets and the per-row removed ratings > 0 (it
+// holds the shape, never the entries), and the work lists are rebuilt.  Returns the entries that went.
+int64_t als_remove_side(mf_ctx* ctx, Shard& s, int side, const uint64_t* d_bkey, int64_t nb, const uint8_t* rowmark,
+                        const uint8_t* colmark, uint8_t* d_found) {
+  mf_ctx::AlsSide& A = ctx->als[side];
+  const int64_t rows = static_cast<int64_t>(A.off.size()) - 1, nnz = A.off.back();
+  AlsRemoveScratch& sc = s.als_rem;
+  sc.rempos.alloc(std::max<size_t>(static_cast<size_t>(rows) * 4, 16));
+  const AlsRemoveLaunch L{s.stream, s.als_off[side].as<int64_t>(), rows, nnz, s.als_cols[side].as<int32_t>(),
+                          s.als_vals[side].get(), static_cast<int>(ctx->es), d_bkey, nb, rowmark, colmark};
+  const int64_t gone = launch_als_remove_select(L, sc, d_found, sc.rempos.as<int32_t>());
+  if (gone == 0) return 0;
+  DevBuf d_off, d_cols, d_vals;
+  d_off.alloc(static_cast<size_t>(rows + 1) * 8);
+  d_cols.alloc(std::max<size_t>(static_cast<size_t>(nnz - gone) * 4, 16));
+  d_vals.alloc(std::max<size_t>(static_cast<size_t>(nnz - gone) * ctx->es, 16));
+  launch_als_remove_move(L, sc, d_off.as<int64_t>(), d_cols.as<int32_t>(), d_vals.get());
+  std::vector<int64_t> off(static_cast<size_t>(rows) + 1);
+  std::vector<int32_t> npos(A.npos), rempos(static_cast<size_t>(rows));
+  MF_HIP(hipMemcpyAsync(off.data(), d_off.get(), off.size() * 8, hipMemcpyDeviceToHost, s.stream));
+  MF_HIP(hipMemcpyAsync(rempos.data(), sc.rempos.get(), rempos.size() * 4, hipMemcpyDeviceToHost, s.stream));
+  MF_HIP(hipStreamSynchronize(s.stream));  // the old arrays are freed behind the move
+  for (int64_t x = 0; x < rows; ++x) npos[x] -= rempos[x];
+  std::swap(s.als_off[side], d_off);
+  std::swap(s.als_cols[side], d_cols);
+  std::swap(s.als_vals[side], d_vals);
+  als_work_lists(ctx, s, side, std::move(off), std::move(npos));
+  return gone;
+}
+
+void als_remove_args(const int32_t* u, const int32_t* i, int64_t n, const char* api) {
+  MF_REQUIRE(n >= 0, "negative rating count");
+  MF_REQUIRE(n < (int64_t{1} << 31), std::string(api) + " takes fewer than 2^31 entries in one call");
+  MF_REQUIRE(n == 0 || (u && i), "null rating arrays");
+}
+
+}  // namespace
+
+int64_t als_remove(mf_ctx* ctx, const int32_t* u, const int32_t* i, int64_t n, uint8_t* found) {
+  als_remove_args(u, i, n, "mf_als_remove");
+  Shard& s = als_enter(ctx, "mf_als_remove");
+  if (n == 0) return 0;
+  if (found) std::memset(found, 0, static_cast<size_t>(n));
+  constexpr uint32_t kMiss = 0xFFFFFFFFu;
+  std::vector<uint32_t> ur, ir;
+  lookup_rows(ctx->U, u, n, ur);
+  lookup_rows(ctx->I, i, n, ir);
+  // the entries that can name a stored rating: both ids known, both rows inside the CSRs
+  const int64_t have_u = static_cast<int64_t>(ctx->als[kSideU].off.size()) - 1;
+  const int64_t have_i = static_cast<int64_t>(ctx->als[MF_SIDE_ITEM].off.size()) - 1;
+  std::vector<int64_t> at;
+  std::vector<uint64_t> key;
+  for (int64_t j = 0; j < n; ++j) {
+    if (ur[j] == kMiss || ir[j] == kMiss || ur[j] >= have_u || ir[j] >= have_i) continue;
+    at.push_back(j);
+    key.push_back((static_cast<uint64_t>(ur[j]) << 32) | ir[j]);
+  }
+  const int64_t nb = static_cast<int64_t>(at.size());
+  if (nb == 0) return 0;
+  DeviceGuard g(s.device);
+  AlsRemoveScratch& sc = s.als_rem;
+  // One side at a time, as mf_als_append: the transient is a second copy of one side.  CSR order is arrival
+  // order on both sides, so the m oldest instances of a pair in its user row are the m oldest in its item row.
+  als_upload(sc.in, key.data(), key.size() * 8);
+  sc.found.alloc(static_cast<size_t>(nb));
+  const int64_t gone = als_remove_side(ctx, s, kSideU, sc.in.as<uint64_t>(), nb, nullptr, nullptr, sc.found.as<uint8_t>());
+  if (gone == 0) return 0;  // every entry a miss: nothing has changed
+  if (found) {
+    std::vector<uint8_t> f(static_cast<size_t>(nb));
+    MF_HIP(hipMemcpy(f.data(), sc.found.get(), f.size(), hipMemcpyDeviceToHost));
+    for (int64_t t = 0; t < nb; ++t) found[at[t]] = f[t];
+  }
+  for (int64_t t = 0; t < nb; ++t) key[t] = (key[t] << 32) | (key[t] >> 32);
+  als_upload(sc.in, key.data(), key.size() * 8);
+  const int64_t gone_i = als_remove_side(ctx, s, MF_SIDE_ITEM, sc.in.as<uint64_t>(), nb, nullptr, nullptr, nullptr);
+  if (gone_i != gone) fail(MF_ERR_STATE, "mf_als_remove: the two CSRs did not hold the same ratings");
+  return gone;
+}
+
+int64_t als_remove_rows(mf_ctx* ctx, int side, const int32_t* ids, int64_t n_ids) {
+  MF_REQUIRE(side == MF_SIDE_USER || side == MF_SIDE_ITEM, "bad side");
+  MF_REQUIRE(n_ids >= 0, "negative id count");
+  MF_REQUIRE(n_ids == 0 || ids, "null id array");
+  Shard& s = als_enter(ctx, "mf_als_remove_rows");
+  const mf_ctx::AlsSide& A = ctx->als[side];
+  const SideLayout& S = side_of(ctx, side);
+  const int64_t have = static_cast<int64_t>(A.off.size()) - 1;
+  std::vector<uint8_t> mark(static_cast<size_t>(have), 0);
+  int64_t want = 0;
+  for (int64_t j = 0; j < n_ids; ++j) {  // ids the model does not hold and rows without a rating are skipped
+    const int32_t row = S.index.find(ids[j]);
+    if (row < 0 || row >= have || mark[row]) continue;
+    const int64_t c = A.off[row + 1] - A.off[row];
+    if (c == 0) continue;
+    mark[row] = 1;
+    want += c;
+  }
+  if (want == 0) return 0;
+  MF_REQUIRE(want < (int64_t{1} << 31) - 1, "mf_als_remove_rows removes fewer than 2^31 - 1 ratings in one call");
+  DeviceGuard g(s.device);
+  AlsRemoveScratch& sc = s.als_rem;
+  als_upload(sc.mark, mark.data(), mark.size());
+  const int64_t gone = als_remove_side(ctx, s, side, nullptr, 0, sc.mark.as<uint8_t>(), nullptr, nullptr);
+  const int64_t gone_o = als_remove_side(ctx, s, 1 - side, nullptr, 0, nullptr, sc.mark.as<uint8_t>(), nullptr);
+  if (gone != want || gone_o != want) fail(MF_ERR_STATE, "mf_als_remove_rows: the two CSRs did not hold the same ratings");
+  return want;
+}
+
+int64_t als_retract(mf_ctx* ctx, const int32_t* u, const int32_t* i, int64_t n, const AlsParams& P, int32_t rounds,
+                    uint8_t* found, int64_t* solved_users, int64_t* solved_items) {
+  MF_REQUIRE(rounds >= 0, "negative round count");
+  if (P.implicit) als_check_alpha(P.alpha);
+  als_check_run(P);
+  const int64_t gone = als_remove(ctx, u, i, n, found);  // (checks the rest before it changes anything)
+  int64_t su = 0, si = 0;
+  for (int32_t t = 0; t < rounds; ++t) {  // rows that lost their last rating fall out by mf_als_run_rows' own rule
+    su = als_run_rows(ctx, kSideU, u, n, P);
+    si = als_run_rows(ctx, MF_SIDE_ITEM, i, n, P);
+  }
+  if (solved_users) *solved_users = su;
+  if (solved_items) *solved_items = si;
+  return gone;
 }
 
 // The resident CSR of a side copied back (mf_debug_als_csr): the offsets and entries from the device, the

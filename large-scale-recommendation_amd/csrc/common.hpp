@@ -165,6 +165,18 @@ struct AlsAppendScratch {
   DevBuf urow, irow, val, key, iota, idx, tmp;
 };
 
+// Device scratch of mf_als_remove / mf_als_remove_rows / mf_seen_remove (kernels_als_remove.hip).  From the
+// caller: the batch keys as uploaded (in), row marks (mark), and what comes back (found per batch entry,
+// rempos per row).  From the selection: the sorted batch (key, idx), per tile of 2048 entries its candidates
+// and their exclusive scan (tile_cnt, tile_base), the `cands` candidates by position (cand_e, cand_key) and
+// by key (skey, sidx), their kill flags and the scan of those (kill, before; read only when `batch`).
+struct AlsRemoveScratch {
+  DevBuf in, mark, found, rempos;
+  DevBuf key, idx, iota, tmp, tile_cnt, tile_base, cand_e, cand_key, skey, sidx, kill, before;
+  int64_t cands = 0;
+  bool batch = false;
+};
+
 // The resident seen set (seen.cpp, kernels_seen.hip): per orientation [user-major, item-major] one CSR over
 // that side's factor rows, off (int64, rows[side] + 1) and ent (int32, the row's distinct counterpart rows,
 // ascending).  The user-major table is the set; the item-major one is made from it on first use and dropped

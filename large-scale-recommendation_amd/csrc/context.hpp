@@ -159,6 +159,8 @@ struct Shard {
   // ... mf_als_append: per side the CSR's 64-bit row offsets, the batch and its sort (kernels_als_append.hip)
   DevBuf als_off[2];
   AlsAppendScratch als_app;
+  // ... mf_als_remove / mf_als_remove_rows / mf_seen_remove: the batch, the selection and what comes back
+  AlsRemoveScratch als_rem;
   // ... mf_als_run_rows: the item, split and chunk lists of one call
   DevBuf als_sub_items, als_sub_splits, als_sub_work;
   // profiling
@@ -432,6 +434,8 @@ void online_prequential_seen(mf_ctx* ctx, const int32_t* u, const int32_t* i, co
 // above `seen` = true takes the set for the exclusions (eq / ec / ne are not read).
 // seen_put: mf_seen_set (add = false) / mf_seen_add; *ignored (may be null) = pairs naming an unknown id.
 void seen_put(mf_ctx* ctx, const int32_t* u, const int32_t* i, int64_t n, bool add, int64_t* ignored);
+// seen_remove: mf_seen_remove; *removed = the distinct held pairs that went, *ignored as seen_put's (either may be null).
+void seen_remove(mf_ctx* ctx, const int32_t* u, const int32_t* i, int64_t n, int64_t* removed, int64_t* ignored);
 void seen_from_als(mf_ctx* ctx);
 void seen_clear(mf_ctx* ctx);  // no set (mf_seen_clear; mf_dsgd_prepare, which rebuilds the rows)
 int64_t seen_count(const mf_ctx* ctx);
@@ -481,6 +485,17 @@ void als_append(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r
 int64_t als_run_rows(mf_ctx* ctx, int side, const int32_t* ids, int64_t n_ids, const AlsParams& P);
 void als_update(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n, const AlsParams& P,
                 int32_t rounds, int64_t* solved_users, int64_t* solved_items);
+// mf_als_remove / mf_als_remove_rows / mf_als_retract (which checks everything mf_als_run_rows would refuse
+// before it removes); each returns the ratings removed.  found: n bytes or null.
+int64_t als_remove(mf_ctx* ctx, const int32_t* u, const int32_t* i, int64_t n, uint8_t* found);
+int64_t als_remove_rows(mf_ctx* ctx, int side, const int32_t* ids, int64_t n_ids);
+int64_t als_retract(mf_ctx* ctx, const int32_t* u, const int32_t* i, int64_t n, const AlsParams& P, int32_t rounds,
+                    uint8_t* found, int64_t* solved_users, int64_t* solved_items);
+// Which stored entry each batch entry removes (the rule the removal kernels follow, mf_debug_als_remove_select):
+// in ascending j, entry j takes the first position of row batch_row[j] that holds batch_col[j] and that no
+// earlier entry took; pos_out[j] = that position in cols[], or -1.
+void als_remove_select(const int64_t* off, int64_t rows, const int32_t* cols, const int32_t* batch_row,
+                       const int32_t* batch_col, int64_t n, int64_t* pos_out);
 void als_debug_csr(mf_ctx* ctx, int side, int64_t* off_out, int32_t* cols_out, double* vals_out, int32_t* npos_out,
                    int64_t cap_rows, int64_t cap_nnz, int64_t* rows_out, int64_t* nnz_out);
 // Where the entries of a side land when a batch is appended (the rule the append kernels follow): new_off

@@ -520,4 +520,36 @@ struct AlsAppendLaunch {
 };
 void launch_als_append(const AlsAppendLaunch& L, AlsAppendScratch& sc);
 
+// ---- kernels_als_remove.hip: mf_als_remove, mf_als_remove_rows, mf_seen_remove -------------------
+// Entries taken out of a packed CSR (off[rows + 1], cols, values of elem_bytes = 4 or 8, or 0 for a CSR
+// without values: the seen set's table), the survivors keeping their order.  Integer work only, but for the
+// `> 0` on the stored value behind rempos.  Two ways to name what goes:
+//   bkey != null: nb keys (row << 32) | col in the caller's order, every row < rows.  Key j takes the OLDEST
+//     entry of its pair that no earlier key of the batch took (the first in the row's order): m keys of one
+//     pair take its m oldest entries.  found[j] (device, nb bytes; may be null) = 1 where there was one.
+//   bkey == null: every entry whose row is marked in rowmark[rows] or whose column in colmark[] (either
+//     may be null).
+// launch_als_remove_select finds them and returns how many go (it drains the stream); rempos (device, rows
+// int32; may be null; needs values) receives per row the removed entries whose value is > 0.  Nothing has
+// moved yet.  When it returned > 0, launch_als_remove_move with the same L and scratch writes new_off[rows +
+// 1] and the surviving entries into fresh arrays of nnz - gone entries: every survivor is read once and
+// written once, a workgroup per 2048 consecutive entries whatever rows they belong to.  A select may
+// reallocate `sc`: drain the stream between a move and the next select.
+struct AlsRemoveScratch;
+struct AlsRemoveLaunch {
+  hipStream_t st;
+  const int64_t* off;
+  int64_t rows, nnz;
+  const int32_t* cols;
+  const void* vals;
+  int elem_bytes;  // 4, 8, or 0: no values
+  const uint64_t* bkey;
+  int64_t nb;
+  const uint8_t* rowmark;
+  const uint8_t* colmark;
+};
+int64_t launch_als_remove_select(const AlsRemoveLaunch& L, AlsRemoveScratch& sc, uint8_t* found, int32_t* rempos);
+void launch_als_remove_move(const AlsRemoveLaunch& L, const AlsRemoveScratch& sc, int64_t* new_off, int32_t* new_cols,
+                            void* new_vals);
+
 }  // namespace mfhip

@@ -1,5 +1,5 @@
-// seen.cpp -- the resident seen set (mf_seen_set / mf_seen_add / mf_seen_from_als / mf_seen_clear /
-// mf_seen_count): the distinct (user, item) pairs the model's readers hide, built once and kept on the
+// seen.cpp -- the resident seen set (mf_seen_set / mf_seen_add / mf_seen_remove / mf_seen_from_als /
+// mf_seen_clear / mf_seen_count): the distinct (user, item) pairs the model's readers hide, built once and kept on the
 // device keyed by factor row, so that mf_recommend_seen, mf_rank_eval_seen, mf_pair_ranks_seen and
 // mf_online_prequential_seen name it instead of resolving, uploading and sorting the same pairs in every
 // call.  Ids are resolved on the host (lookup_rows, as rank_eval.cpp does); everything after that is
@@ -135,6 +135,51 @@ void seen_put(mf_ctx* ctx, const int32_t* u, const int32_t* i, int64_t n, bool a
   } else {
     build_from_keys(s, n, rows);
   }
+}
+
+// mf_seen_remove: the user-major table without the pairs given, through the compaction mf_als_remove uses
+// (kernels_als_remove.hip, a CSR without values: every held pair a batch key names goes, however often it is
+// named).  Fresh arrays; the item-major table is made again on its next use.
+void seen_remove(mf_ctx* ctx, const int32_t* u, const int32_t* i, int64_t n, int64_t* removed, int64_t* ignored) {
+  Shard& s = ctx->shards[0];
+  SeenTable& T = s.seen;
+  std::vector<uint32_t> ur, ir;
+  if (n > 0) {
+    lookup_rows(ctx->U, u, n, ur);
+    lookup_rows(ctx->I, i, n, ir);
+  }
+  const bool held = T.have && T.nnz > 0;
+  int64_t dropped = 0;
+  std::vector<uint64_t> key;
+  for (int64_t j = 0; j < n; ++j) {
+    if (ur[j] == kMiss || ir[j] == kMiss) {
+      ++dropped;
+    } else if (held && static_cast<int64_t>(ur[j]) < T.rows[kSideU]) {  // (a row gained since holds nothing)
+      key.push_back((static_cast<uint64_t>(ur[j]) << 32) | ir[j]);
+    }
+  }
+  if (ignored) *ignored = dropped;
+  if (removed) *removed = 0;
+  if (key.empty()) return;
+  DeviceGuard g(s.device);
+  MF_HIP(hipStreamSynchronize(s.stream));  // a reader may still search the arrays
+  AlsRemoveScratch& sc = s.als_rem;
+  sc.in.alloc(key.size() * 8);
+  MF_HIP(hipMemcpy(sc.in.get(), key.data(), key.size() * 8, hipMemcpyHostToDevice));
+  const AlsRemoveLaunch L{s.stream, T.off[kSideU].as<int64_t>(), T.rows[kSideU], T.nnz, T.ent[kSideU].as<int32_t>(),
+                          nullptr, 0, sc.in.as<uint64_t>(), static_cast<int64_t>(key.size()), nullptr, nullptr};
+  const int64_t gone = launch_als_remove_select(L, sc, nullptr, nullptr);
+  if (gone == 0) return;  // none of the pairs is held: the tables stand
+  DevBuf off, ent;
+  off.alloc(off_bytes(T.rows[kSideU]));
+  ent.alloc(std::max<size_t>(static_cast<size_t>(T.nnz - gone) * 4, 16));
+  launch_als_remove_move(L, sc, off.as<int64_t>(), ent.as<int32_t>(), nullptr);
+  MF_HIP(hipStreamSynchronize(s.stream));
+  T.off[kSideU] = std::move(off);
+  T.ent[kSideU] = std::move(ent);
+  T.nnz -= gone;
+  T.item_valid = false;
+  if (removed) *removed = gone;
 }
 
 void seen_from_als(mf_ctx* ctx) {

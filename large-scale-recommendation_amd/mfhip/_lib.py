@@ -178,6 +178,7 @@ EXPORTS = [
     "mf_als_nonneg_stats", "mf_nnls_solve", "mf_als_append", "mf_als_run_rows", "mf_als_update",
     "mf_seen_set", "mf_seen_add", "mf_seen_from_als", "mf_seen_clear", "mf_seen_count", "mf_recommend_seen",
     "mf_rank_eval_seen", "mf_pair_ranks_seen", "mf_online_prequential_seen", "mf_similar", "mf_recommend_vectors",
+    "mf_als_remove", "mf_als_remove_rows", "mf_als_retract", "mf_seen_remove",
 ]
 # The test hooks include/mfhip_testing.h declares (not product surface; same library).
 TESTING_EXPORTS = [
@@ -186,7 +187,7 @@ TESTING_EXPORTS = [
     "mf_debug_device_bytes", "mf_debug_als_normal_eq", "mf_debug_als_gram", "mf_debug_als_normal_eq_implicit",
     "mf_debug_det_slot_table", "mf_debug_sys_placement", "mf_debug_rank_csr", "mf_debug_als_cg_matvec",
     "mf_debug_als_cg_capacity", "mf_debug_als_nnls_row", "mf_debug_als_csr", "mf_debug_als_append_placement",
-    "mf_debug_seen_csr", "mf_debug_seen_merge_placement",
+    "mf_debug_seen_csr", "mf_debug_seen_merge_placement", "mf_debug_als_remove_select",
 ]
 
 _i32p = C.POINTER(C.c_int32)
@@ -310,6 +311,12 @@ def lib() -> C.CDLL:
         "mf_debug_als_csr": (C.c_int, [_ctxp, C.c_int, _i64p, _i32p, _f64p, _i32p, C.c_int64, C.c_int64, _i64p,
                                        _i64p]),
         "mf_debug_als_append_placement": (C.c_int, [_i64p, C.c_int64, _i32p, C.c_int64, C.c_int64, _i64p, _i64p]),
+        "mf_als_remove": (C.c_int, [_ctxp, _i32p, _i32p, C.c_int64, _u8p, _i64p]),
+        "mf_als_remove_rows": (C.c_int, [_ctxp, C.c_int, _i32p, C.c_int64, _i64p]),
+        "mf_als_retract": (C.c_int, [_ctxp, _i32p, _i32p, C.c_int64, C.POINTER(mf_als_solve), C.c_int32, _u8p, _i64p,
+                                     _i64p, _i64p]),
+        "mf_debug_als_remove_select": (C.c_int, [_i64p, C.c_int64, _i32p, _i32p, _i32p, C.c_int64, _i64p]),
+        "mf_seen_remove": (C.c_int, [_ctxp, _i32p, _i32p, C.c_int64, _i64p, _i64p]),
         "mf_seen_set": (C.c_int, [_ctxp, _i32p, _i32p, C.c_int64, _i64p]),
         "mf_seen_add": (C.c_int, [_ctxp, _i32p, _i32p, C.c_int64, _i64p]),
         "mf_seen_from_als": (C.c_int, [_ctxp]),

@@ -221,6 +221,17 @@ class StreamingALS:
         u, i, r = _columns(ratings)
         return self._fitted().als_update(u, i, r, self.how, int(rounds))
 
+    def forget(self, pairs, rounds: int = 1) -> Tuple[int, int, int]:
+        """Retraction (mf_als_retract): each (user, item) pair given removes the oldest rating of that pair
+        still held, then `rounds` times the pairs' users and their items are solved again (rows left without
+        a rating are skipped and keep their factors).  Returns (ratings removed, users solved, items solved)."""
+        if int(rounds) < 0:
+            raise ValueError("rounds must be >= 0")
+        ctx = self._fitted()
+        u, i = _pairs(pairs)
+        _, removed, su, si = ctx.als_retract(u, i, self.how, int(rounds))
+        return removed, su, si
+
     def refit(self, half_sweeps: int = 2) -> "StreamingALS":
         """Full half-sweeps over the resident data (the item side first, as a fit's); nothing is uploaded."""
         if int(half_sweeps) < 0:

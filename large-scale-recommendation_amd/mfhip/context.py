@@ -327,6 +327,39 @@ class Context:
                                     C.byref(how), int(rounds), C.byref(su), C.byref(si)))
         return int(su.value), int(si.value)
 
+    def als_remove(self, u, i) -> Tuple[np.ndarray, int]:
+        """mf_als_remove: entry j removes the oldest rating of the pair (u[j], i[j]) still held; the resident
+        CSRs are then what als_prepare would have built without the removed ratings.  Returns (found [n] as
+        bool, ratings removed)."""
+        u, i = as_i32(u), as_i32(i)
+        n = same_length(u, i)
+        found = np.zeros(max(n, 1), np.uint8)
+        removed = C.c_int64(0)
+        check(L.lib().mf_als_remove(self._h, ptr(u, C.c_int32) if n else None, ptr(i, C.c_int32) if n else None, n,
+                                    ptr(found, C.c_uint8), C.byref(removed)))
+        return found[:n].astype(bool), int(removed.value)
+
+    def als_remove_rows(self, side: int, ids) -> int:
+        """mf_als_remove_rows: every rating of the named rows of `side` leaves the resident data (the factor
+        rows stay); returns the ratings removed."""
+        ids = as_i32(ids)
+        removed = C.c_int64(0)
+        check(L.lib().mf_als_remove_rows(self._h, int(side), ptr(ids, C.c_int32) if len(ids) else None, len(ids),
+                                         C.byref(removed)))
+        return int(removed.value)
+
+    def als_retract(self, u, i, how: L.mf_als_solve, rounds: int = 1) -> Tuple[np.ndarray, int, int, int]:
+        """mf_als_retract: als_remove, then `rounds` times the batch's users and then its items solved; returns
+        (found, ratings removed, users solved, items solved) with the last round's counts."""
+        u, i = as_i32(u), as_i32(i)
+        n = same_length(u, i)
+        found = np.zeros(max(n, 1), np.uint8)
+        removed, su, si = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        check(L.lib().mf_als_retract(self._h, ptr(u, C.c_int32) if n else None, ptr(i, C.c_int32) if n else None, n,
+                                     C.byref(how), int(rounds), ptr(found, C.c_uint8), C.byref(removed), C.byref(su),
+                                     C.byref(si)))
+        return found[:n].astype(bool), int(removed.value), int(su.value), int(si.value)
+
     def als_csr(self, side: int):
         """(off [rows + 1], cols [nnz], vals [nnz] as f64, npos [rows]) of the resident CSR of `side`
         (mf_debug_als_csr)."""
@@ -575,6 +608,16 @@ class Context:
     def seen_add(self, u, i) -> int:
         """mf_seen_add: the set's union with the pairs given (only the batch is sorted)."""
         return self._seen_put(L.lib().mf_seen_add, u, i)
+
+    def seen_remove(self, u, i) -> Tuple[int, int]:
+        """mf_seen_remove: the set minus the pairs given; returns (distinct held pairs removed, pairs ignored
+        for an unknown id).  With no set nothing changes."""
+        u, i = as_i32(u), as_i32(i)
+        n = same_length(u, i)
+        removed, ignored = C.c_int64(0), C.c_int64(0)
+        check(L.lib().mf_seen_remove(self._h, ptr(u, C.c_int32) if n else None, ptr(i, C.c_int32) if n else None, n,
+                                     C.byref(removed), C.byref(ignored)))
+        return int(removed.value), int(ignored.value)
 
     def seen_from_als(self) -> None:
         """mf_seen_from_als: the set := the distinct pairs of the prepared ALS data; nothing is uploaded."""
