@@ -122,6 +122,18 @@ void als_work_lists(mf_ctx* ctx, Shard& s, int side, std::vector<int64_t> off, s
   als_upload(s.als_rated[side], rated.data(), rated.size() * 4);
 }
 
+// The end of an append or a removal: the side takes the fresh arrays its entries were moved into and its work
+// lists are rebuilt from the new shape.  d_off / d_cols / d_vals come back holding the OLD arrays, which
+// queued moves may still read: the caller frees them only once the stream is done.  (The lists this uploads
+// are read by no queued kernel: the moves do not touch them and als_enter drained the half-sweeps.)
+void als_adopt_arrays(mf_ctx* ctx, Shard& s, int side, DevBuf& d_off, DevBuf& d_cols, DevBuf& d_vals,
+                      std::vector<int64_t> off, std::vector<int32_t> npos) {
+  std::swap(s.als_off[side], d_off);
+  std::swap(s.als_cols[side], d_cols);
+  std::swap(s.als_vals[side], d_vals);
+  als_work_lists(ctx, s, side, std::move(off), std::move(npos));
+}
+
 template <typename T>
 void als_build_side(mf_ctx* ctx, Shard& s, int side, const std::vector<uint32_t>& xr, const std::vector<uint32_t>& yr,
                     const double* r, int64_t n, int64_t rows) {
@@ -160,11 +172,10 @@ void als_insert_rows(mf_ctx* ctx, Shard& s, const int32_t* u, const int32_t* i, 
                      std::vector<uint32_t>& ir) {
   const int k = ctx->P.num_factors;
   const int64_t u0 = ctx->U.rows(), i0 = ctx->I.rows();
-  constexpr uint32_t kMiss = 0xFFFFFFFFu;
   std::vector<int32_t> fu, fi;
   for (int64_t j = 0; j < n; ++j) {  // unseen ids take new rows in order of appearance
-    if (ur[j] == kMiss) ur[j] = static_cast<uint32_t>(online_row(ctx, ctx->U, u[j], fu));
-    if (ir[j] == kMiss) ir[j] = static_cast<uint32_t>(online_row(ctx, ctx->I, i[j], fi));
+    if (ur[j] == kRowMiss) ur[j] = static_cast<uint32_t>(online_row(ctx, ctx->U, u[j], fu));
+    if (ir[j] == kRowMiss) ir[j] = static_cast<uint32_t>(online_row(ctx, ctx->I, i[j], fi));
   }
   // as in an online batch: new rows take the slab rows a fast DSGD schedule keeps zeroed
   if (ctx->prepared && !ctx->f64 && (!fu.empty() || !fi.empty())) ctx->prepared = false;
@@ -559,15 +570,10 @@ void als_append_side(mf_ctx* ctx, Shard& s, int side, const std::vector<uint32_t
                      s.als_cols[side].as<int32_t>(), s.als_vals[side].get(), d_cols.as<int32_t>(), d_vals.get(),
                      static_cast<int>(sizeof(T)), d_xr, d_yr, s.als_app.val.get(), n},
                     s.als_app);
-  std::swap(s.als_off[side], d_off);
-  std::swap(s.als_cols[side], d_cols);
-  std::swap(s.als_vals[side], d_vals);
+  als_adopt_arrays(ctx, s, side, d_off, d_cols, d_vals, std::move(off), std::move(npos));
   retired.push_back(std::move(d_off));
   retired.push_back(std::move(d_cols));
   retired.push_back(std::move(d_vals));
-  // (the lists this uploads are read by no queued kernel: the moves do not touch them and als_enter drained
-  // the half-sweeps)
-  als_work_lists(ctx, s, side, std::move(off), std::move(npos));
 }
 
 template <typename T>
@@ -600,7 +606,6 @@ void als_append(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r
   MF_REQUIRE(n == 0 || (u && i && r), "null rating arrays");
   Shard& s = als_enter(ctx, "mf_als_append");
   if (n == 0) return;
-  constexpr uint32_t kMiss = 0xFFFFFFFFu;
   std::vector<uint32_t> ur, ir;
   lookup_rows(ctx->U, u, n, ur);
   lookup_rows(ctx->I, i, n, ir);
@@ -611,7 +616,7 @@ void als_append(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r
     const int64_t have = static_cast<int64_t>(A.off.size()) - 1;
     std::vector<int64_t> cnt(static_cast<size_t>(side_of(ctx, side).rows()), 0);
     for (int64_t j = 0; j < n; ++j) {
-      if (xr[j] == kMiss) {  // (a new row holds at most the n < 2^31 ratings of this call)
+      if (xr[j] == kRowMiss) {  // (a new row holds at most the n < 2^31 ratings of this call)
         fresh = true;
         continue;
       }
@@ -710,10 +715,7 @@ int64_t als_remove_side(mf_ctx* ctx, Shard& s, int side, const uint64_t* d_bkey,
   MF_HIP(hipMemcpyAsync(rempos.data(), sc.rempos.get(), rempos.size() * 4, hipMemcpyDeviceToHost, s.stream));
   MF_HIP(hipStreamSynchronize(s.stream));  // the old arrays are freed behind the move
   for (int64_t x = 0; x < rows; ++x) npos[x] -= rempos[x];
-  std::swap(s.als_off[side], d_off);
-  std::swap(s.als_cols[side], d_cols);
-  std::swap(s.als_vals[side], d_vals);
-  als_work_lists(ctx, s, side, std::move(off), std::move(npos));
+  als_adopt_arrays(ctx, s, side, d_off, d_cols, d_vals, std::move(off), std::move(npos));
   return gone;
 }
 
@@ -730,7 +732,6 @@ int64_t als_remove(mf_ctx* ctx, const int32_t* u, const int32_t* i, int64_t n, u
   Shard& s = als_enter(ctx, "mf_als_remove");
   if (n == 0) return 0;
   if (found) std::memset(found, 0, static_cast<size_t>(n));
-  constexpr uint32_t kMiss = 0xFFFFFFFFu;
   std::vector<uint32_t> ur, ir;
   lookup_rows(ctx->U, u, n, ur);
   lookup_rows(ctx->I, i, n, ir);
@@ -740,7 +741,7 @@ int64_t als_remove(mf_ctx* ctx, const int32_t* u, const int32_t* i, int64_t n, u
   std::vector<int64_t> at;
   std::vector<uint64_t> key;
   for (int64_t j = 0; j < n; ++j) {
-    if (ur[j] == kMiss || ir[j] == kMiss || ur[j] >= have_u || ir[j] >= have_i) continue;
+    if (ur[j] == kRowMiss || ir[j] == kRowMiss || ur[j] >= have_u || ir[j] >= have_i) continue;
     at.push_back(j);
     key.push_back((static_cast<uint64_t>(ur[j]) << 32) | ir[j]);
   }

@@ -134,7 +134,6 @@ EvalOut evaluate(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* 
 // large catalogue still fills the device).  MFHIP_TEST rec_batch=B / rec_split=S override both.
 namespace {
 
-constexpr uint32_t kMiss = 0xFFFFFFFFu;
 
 // (query position << 32 | candidate row) pairs -> the exclusion CSR of nu queries: sorted distinct rows
 void exclusion_csr(std::vector<uint64_t>& pairs, int64_t nu, std::vector<int64_t>& eoff, std::vector<int32_t>& erows) {
@@ -296,12 +295,12 @@ void recommend_ids(mf_ctx* ctx, int qside, int cside, const int32_t* queries, in
   std::vector<int32_t> uniq;
   uniq.reserve(qr.size());
   for (uint32_t r : qr)
-    if (r != kMiss) uniq.push_back(static_cast<int32_t>(r));
+    if (r != kRowMiss) uniq.push_back(static_cast<int32_t>(r));
   std::sort(uniq.begin(), uniq.end());
   uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
   const int64_t nu = static_cast<int64_t>(uniq.size());
   auto upos = [&](uint32_t row) -> int64_t {
-    if (row == kMiss) return -1;
+    if (row == kRowMiss) return -1;
     auto it = std::lower_bound(uniq.begin(), uniq.end(), static_cast<int32_t>(row));
     return it != uniq.end() && *it == static_cast<int32_t>(row) ? it - uniq.begin() : -1;
   };
@@ -318,7 +317,7 @@ void recommend_ids(mf_ctx* ctx, int qside, int cside, const int32_t* queries, in
       lookup_rows(CS, ec, ne, er_c);
       for (int64_t e = 0; e < ne; ++e) {
         const int64_t u = upos(er_q[e]);
-        if (u < 0 || er_c[e] == kMiss) continue;
+        if (u < 0 || er_c[e] == kRowMiss) continue;
         pairs.push_back((static_cast<uint64_t>(u) << 32) | er_c[e]);
       }
     }
@@ -384,7 +383,7 @@ void recommend_vectors(mf_ctx* ctx, int cside, const double* vecs, int64_t nq, i
     std::vector<uint64_t> pairs;
     pairs.reserve(static_cast<size_t>(ne));
     for (int64_t e = 0; e < ne; ++e) {
-      if (eqi[e] < 0 || eqi[e] >= nq || er_c[e] == kMiss) continue;
+      if (eqi[e] < 0 || eqi[e] >= nq || er_c[e] == kRowMiss) continue;
       pairs.push_back((static_cast<uint64_t>(eqi[e]) << 32) | er_c[e]);
     }
     exclusion_csr(pairs, nq, eoff, erows);

@@ -10,6 +10,10 @@
 
 namespace mfhip {
 
+// "No row": what a lookup writes for an id the model does not hold (find_many, lookup_rows of plan.hpp,
+// the device lookup of kernels_online.hip), and what every consumer of looked-up rows tests for.
+constexpr uint32_t kRowMiss = 0xFFFFFFFFu;
+
 class IdIndex {
  public:
   // id and row side by side: a lookup touches one cache line, not two
@@ -62,12 +66,12 @@ class IdIndex {
     }
   }
 
-  // find() of n ids into rows (-1 as 0xFFFFFFFF), the slot of the id kPrefetch places ahead
+  // find() of n ids into rows (-1 as kRowMiss), the slot of the id kPrefetch places ahead
   // prefetched: the table is far larger than L2, so independent lookups overlap their misses.
   void find_many(const int32_t* ids, int64_t n, uint32_t* rows) const {
     constexpr int64_t kPrefetch = 16;
     if (slots_.empty()) {
-      for (int64_t j = 0; j < n; ++j) rows[j] = 0xFFFFFFFFu;
+      for (int64_t j = 0; j < n; ++j) rows[j] = kRowMiss;
       return;
     }
     for (int64_t j = 0; j < n && j < kPrefetch; ++j) __builtin_prefetch(&slots_[hash(ids[j]) & mask_]);

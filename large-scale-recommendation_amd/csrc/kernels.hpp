@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime_api.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <type_traits>
 
@@ -111,7 +112,7 @@ uint32_t online_sweep_plan(hipStream_t st, OnlineSweepScratch& sc, const uint32_
                            const float* erf = nullptr);
 // The online batch's id -> row lookup on the device, over a mirror of the host IdIndex (same
 // hash, same slots; id_index.hpp): in[0, n) user ids and in[n, 2n) item ids (the batch as
-// uploaded) are replaced by their rows, 0xFFFFFFFF where the table has no such id; *misses counts
+// uploaded) are replaced by their rows, kRowMiss where the table has no such id; *misses counts
 // those (the host then gives the unseen ids rows in first-touch order).  A null table: all misses.
 void launch_id_lookup(hipStream_t st, uint32_t* in, int64_t n, const void* uslots, uint64_t umask, const void* islots,
                       uint64_t imask, int32_t* misses);
@@ -265,14 +266,52 @@ void launch_recommend(hipStream_t st, const void* Q, const void* Cf, const int32
                       int32_t* counts, const void* q_inv = nullptr, const void* c_inv = nullptr);
 void launch_row_inv_norm(hipStream_t st, const void* X, int64_t rows, int k, bool f64, void* inv);
 
+// ---- table kernels: what they share (kernels_table.hip, csr_search.hpp, csr_device.hpp) --------
+// The table kernels build, merge, search or compact a packed CSR on the device: kernels_rank.hip,
+// kernels_seen.hip, kernels_als_append.hip, kernels_als_remove.hip, with readers in kernels_recommend.hip
+// and kernels_pairrank.hip.  A new one includes csr_search.hpp for its searches (row_of, lower, upper,
+// contains), csr_device.hpp when it walks a CSR's entries in tiles (csr_tile, kCsrThreads, kCsrTile), takes
+// kRowMiss (id_index.hpp) for "no row", and sizes, fills, sorts and scans with the functions below -- it
+// defines none of these again.
+//
+// grid_for: workgroups of kGridThreads threads for a grid-stride loop over n elements, at least 1, at most cap.
+constexpr int kGridThreads = 256;
+inline unsigned grid_for(int64_t n, int64_t cap = 1 << 16) {
+  return static_cast<unsigned>(std::max<int64_t>(1, std::min<int64_t>((n + kGridThreads - 1) / kGridThreads, cap)));
+}
+// The radix bits that hold every key < v (1 .. 32): the end bit of a sort over rows or waves.
+inline int radix_bits_for(uint64_t v) {
+  int b = 1;
+  while (b < 32 && (uint64_t{1} << b) < v) ++b;
+  return b;
+}
+// out[x] = x, x in [0, n): a sort's payload, and the identity the pair-rank kernels take as qpos with a
+// table keyed by row.
+void launch_iota(hipStream_t st, int32_t* out, int64_t n);
+// The temp storage of a rocprim / hipcub call of `bytes` bytes, kept in buf.  THE RULE: a block that work
+// queued on st may still use is never freed under it -- buf grows only after st has drained.  This adds no
+// wait to any path: hipFree waits for the device before it frees, and where a caller drains the stream
+// between two launches that share a scratch the wait finds nothing queued.  The size query / get storage /
+// run pairs of the table kernels take their storage here.
+void* temp_storage(hipStream_t st, DevBuf& buf, size_t bytes);
+// kout = kin[0, n) sorted over key bits [0, end_bit), stable (rocprim radix sort, SortCfg of
+// radix_sort_cfg.hpp), pos[s] = the position in kin of the key at sorted place s; 0 < n < 2^31.  tmp and
+// iota (the identity payload) are scratch, grown by the rule above.  K: uint32_t or uint64_t.
+template <typename K>
+void sort_positions(hipStream_t st, DevBuf& tmp, DevBuf& iota, const K* kin, K* kout, int32_t* pos, int64_t n,
+                    int end_bit);
+// out[x] = in[0] + .. + in[x - 1], x in [0, n) (rocprim); tmp as above.  T: int32_t or int64_t.
+template <typename T>
+void scan_exclusive(hipStream_t st, DevBuf& tmp, const T* in, T* out, int64_t n);
+
 // ---- kernels_rank.hip: ranking metrics ----------------------------------------------------------
 // The pair tables of mf_rank_eval on the device.  qrow[n]: the query-side row of every pair
-// (0xFFFFFFFF: unknown id), rows: the rows of that side.
+// (kRowMiss: unknown id), rows: the rows of that side.
 // rank_query_set: the distinct known rows, ascending, into qrows (the list launch_recommend takes);
 // returns their count nq (one small read-back) and leaves every row's flag / position in sc.
 // rank_pair_csr (after rank_query_set on the same scratch; the pairs may be another list): per
 // evaluated query its distinct entries, sorted: off (int64, nq + 1) and ent (room for n).  gt = false:
-// cand[] holds candidate rows, pairs with 0xFFFFFFFF are dropped, ent = rows ascending (launch_recommend's
+// cand[] holds candidate rows, pairs with kRowMiss are dropped, ent = rows ascending (launch_recommend's
 // excl_off / excl_rows).  gt = true: cand[] holds candidate ids, all kept, ent = ids ascending.
 // Pairs whose query is unknown or not in the query set are dropped.
 struct RankScratch;
@@ -308,12 +347,11 @@ void launch_rank_reduce(hipStream_t st, const double* met, const int64_t* cnt, i
 // kernels' exclusion table have.  Keys are (row << 32) | counterpart row; a dropped pair takes rows << 32
 // (rank_keys_sort's convention).  All of it is integer work: sort, scan, search and move.
 // launch_seen_pair_keys: key[j] of the pair (qrow[j], crow[j]); dropped when qrow[j] >= rows or crow[j] is
-// 0xFFFFFFFF (an unknown id).
+// kRowMiss (an unknown id).
 void launch_seen_pair_keys(hipStream_t st, const uint32_t* qrow, const uint32_t* crow, int64_t n, uint32_t rows,
                            uint64_t* key);
-// launch_seen_csr_keys: key[e] of every entry e of a CSR (off[rows + 1], cols[nnz]), walked by entries in
-// tiles of 2048 (two searches of off per workgroup, then a lane narrows inside that span; a long row is
-// handled by as many workgroups as it has tiles).  swap: the key of the other orientation, (col << 32) | row.
+// launch_seen_csr_keys: key[e] of every entry e of a CSR (off[rows + 1], cols[nnz]), by the tile walk of
+// csr_device.hpp.  swap: the key of the other orientation, (col << 32) | row.
 void launch_seen_csr_keys(hipStream_t st, const int64_t* off, int64_t rows, int64_t nnz, const int32_t* cols,
                           bool swap, uint64_t* key);
 // The merge of a sorted batch into a table (mf_seen_add; the rule mf_debug_seen_merge_placement states).
@@ -321,8 +359,8 @@ void launch_seen_csr_keys(hipStream_t st, const int64_t* off, int64_t rows, int6
 // old_ent) already holds key2[p], and lb[p] = the table's keys below key2[p] for every remaining head.
 // launch_seen_merge, after rank_keys_csr of those heads gave the novel keys as a CSR (nov_off[new_rows + 1],
 // nov_ent) and wp: new_off[r] = old_off[min(r, old_rows)] + nov_off[r]; an old entry e with key K moves to
-// e + #(novel keys < K) (tiles of 2048 old entries; the novel range of a tile's first and last key found
-// once per workgroup); the novel key at sorted position p lands at wp[p] + lb[p].  No atomics: every
+// e + #(novel keys < K) (the tile walk over the old entries; the novel range of a tile's first and last key
+// found once per workgroup); the novel key at sorted position p lands at wp[p] + lb[p].  No atomics: every
 // position follows from the sorted keys alone.
 void launch_seen_novel(hipStream_t st, const uint64_t* key2, int32_t* head, int64_t n, const int64_t* old_off,
                        int64_t old_rows, const int32_t* old_ent, int64_t* lb);
@@ -334,13 +372,11 @@ void launch_seen_merge(hipStream_t st, const int64_t* old_off, int64_t old_rows,
 void launch_seen_pad(hipStream_t st, int64_t* off, int64_t have, int64_t want);
 // beg[q] = off[qrows[q]], end[q] = off[qrows[q] + 1]: a batch's exclusion ranges for launch_recommend.
 void launch_seen_gather(hipStream_t st, const int64_t* off, const int32_t* qrows, int n, int64_t* beg, int64_t* end);
-// out[x] = x, x in [0, n): the identity the pair-rank kernels take as qpos with a table keyed by row.
-void launch_seen_iota(hipStream_t st, int32_t* out, int64_t n);
 
 // ---- kernels_pairrank.hip: ranks of given pairs -------------------------------------------------
 // The position of pairs (query row, candidate row) in the query's complete ranked list (mf_pair_ranks,
 // mf_online_prequential): rank = the candidates whose key (mf_recommend's order) beats the pair's.
-// qrow / crow: the factor rows of the n pairs (0xFFFFFFFF: unknown id).  qpos: per query-side row its
+// qrow / crow: the factor rows of the n pairs (kRowMiss: unknown id).  qpos: per query-side row its
 // position in the exclusion CSR excl_off / excl_rows (rank_query_set's positions, rank_pair_csr's
 // table).  Per pair: tord (pair_rank_ord_bytes(f64) each; 0 = not ranked) and tid, the two parts of its
 // key; rank (the count, or MF_PAIR_RANK_COLD / MF_PAIR_RANK_EXCLUDED), valid (the list's length) and

@@ -5,12 +5,12 @@
 // m OLDEST entries (the first m in the row's order; fewer when the row holds fewer), or marks: every entry
 // whose row, or whose column, is marked.
 //
-//  select   the batch is sorted (stable radix sort of the 64-bit keys, carrying the caller's position j).
-//           k_remove_scan walks the ENTRIES in tiles of 2048 as k_als_move does -- two searches of off per
-//           workgroup for the rows of its first and last entry, one search each for the batch keys of those
-//           rows -- and every entry looks its own key up in that span of the sorted batch.  The few that are
-//           named are the candidates.  One pass counts them per tile, a scan of the tile counts gives every
-//           tile its base, a second pass writes them: cand_e / cand_key, ascending by position.
+//  select   the batch is sorted (sort_positions: stable, the 64-bit keys carrying the caller's position j).
+//           k_remove_scan takes the entries by the tile walk of csr_device.hpp, with one more search per end
+//           of the tile for the batch keys of its first and last row, and every entry looks its own key up
+//           in that span of the sorted batch.  The few that are named are the candidates.  One pass counts
+//           them per tile, a scan of the tile counts gives every tile its base, a second pass writes them:
+//           cand_e / cand_key, ascending by position.
 //  age      the candidates are sorted by key (stable, so inside a pair's run they stay in position order,
 //           which is their age).  The candidate at place t of its run goes when t < the pair's multiplicity in
 //           the batch; the batch key at place t of its run is a hit when t < the run of candidates.  Both are
@@ -28,34 +28,19 @@
 
 #include <hip/hip_runtime.h>
 
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-
-#include <algorithm>
-
 #include "common.hpp"
+#include "csr_device.hpp"
 #include "kernels.hpp"
 
 namespace mfhip {
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kPer = 8;
-constexpr int kTile = kThreads * kPer;  // entries per workgroup of the tiled walks
-constexpr int kWaves = kThreads / 64;   // gfx950 runs wave64
-
-// the merge-sort path off, as in kernels_als_append.hip
-using SortCfg = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config, rocprim::default_config, 0>;
-
-int bits_for(uint64_t v) {  // radix bits that hold every value < v
-  int b = 1;
-  while (b < 32 && (uint64_t{1} << b) < v) ++b;
-  return b;
-}
-
-unsigned grid_for(int64_t n) {
-  return static_cast<unsigned>(std::max<int64_t>(1, std::min<int64_t>((n + kThreads - 1) / kThreads, 1 << 16)));
-}
+using dev::lower;
+using dev::upper;
+constexpr int kThreads = dev::kCsrThreads;
+constexpr int kTile = dev::kCsrTile;   // entries per workgroup of the tiled walks
+constexpr int kPer = kTile / kThreads;
+constexpr int kWaves = kThreads / 64;  // gfx950 runs wave64
 
 // What marks an entry: its key in the sorted batch keys bkey[0, nb), or a mark on its row or its column.
 struct Sel {
@@ -64,43 +49,6 @@ struct Sel {
   const uint8_t* rowmark;
   const uint8_t* colmark;
 };
-
-__global__ void k_remove_iota(int64_t n, int32_t* __restrict__ out) {
-  for (int64_t p = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; p < n;
-       p += static_cast<int64_t>(gridDim.x) * blockDim.x)
-    out[p] = static_cast<int32_t>(p);
-}
-
-// The row of entry e: the largest x in [lo, hi] with off[x] <= e, given off[lo] <= e < off[hi + 1].
-__device__ inline int64_t row_of(const int64_t* __restrict__ off, int64_t lo, int64_t hi, int64_t e) {
-  while (lo < hi) {
-    const int64_t mid = lo + (hi - lo + 1) / 2;
-    if (off[mid] <= e) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
-
-// The first position of [b, e) that holds a value >= x (e when there is none); the values ascend.
-template <typename K>
-__device__ inline int64_t lower(const K* __restrict__ a, int64_t b, int64_t e, K x) {
-  while (b < e) {
-    const int64_t m = b + (e - b) / 2;
-    if (a[m] < x) b = m + 1;
-    else e = m;
-  }
-  return b;
-}
-
-// ... a value > x
-__device__ inline int64_t upper(const uint64_t* __restrict__ a, int64_t b, int64_t e, uint64_t x) {
-  while (b < e) {
-    const int64_t m = b + (e - b) / 2;
-    if (a[m] <= x) b = m + 1;
-    else e = m;
-  }
-  return b;
-}
 
 __device__ inline uint64_t key_of(int64_t row, int32_t col) {
   return (static_cast<uint64_t>(row) << 32) | static_cast<uint32_t>(col);
@@ -132,18 +80,16 @@ __global__ __launch_bounds__(kThreads) void k_remove_scan(const int64_t* __restr
                                                           int64_t* __restrict__ cand_e, uint64_t* __restrict__ cand_key) {
   __shared__ int64_t span[4];
   __shared__ int wsum[kWaves];
-  const int64_t t0 = blockIdx.x * static_cast<int64_t>(kTile);
-  const int64_t t1 = t0 + kTile < nnz ? t0 + kTile : nnz;
-  if (t0 >= t1) return;  // (the grid has no such workgroup)
-  if (threadIdx.x < 2) span[threadIdx.x] = row_of(off, 0, rows - 1, threadIdx.x == 0 ? t0 : t1 - 1);
-  __syncthreads();
+  dev::CsrTile T;
+  if (!dev::csr_tile(off, rows, nnz, span, T)) return;
+  const int64_t t0 = T.t0, t1 = T.t1, hi = T.hi;
   if (threadIdx.x < 2) {  // the batch keys of the tile's rows
     span[2 + threadIdx.x] =
         S.bkey ? lower<uint64_t>(S.bkey, 0, S.nb, static_cast<uint64_t>(span[threadIdx.x] + threadIdx.x) << 32) : 0;
   }
   __syncthreads();
-  int64_t lo = span[0];
-  const int64_t hi = span[1], blo = span[2], bhi = span[3];
+  int64_t lo = T.lo;
+  const int64_t blo = span[2], bhi = span[3];
   if (S.bkey && blo == bhi) {  // no batch key names a row of this tile
     if (!kEmit && threadIdx.x == 0) tile_cnt[blockIdx.x] = 0;
     return;
@@ -154,7 +100,7 @@ __global__ __launch_bounds__(kThreads) void k_remove_scan(const int64_t* __restr
     bool f = false;
     uint64_t key = 0;
     if (e < t1) {
-      lo = row_of(off, lo, hi, e);  // a lane's entries ascend, so its rows do
+      lo = dev::row_of(off, lo, hi, e);  // a lane's entries ascend, so its rows do
       const int32_t col = cols[e];
       key = key_of(lo, col);
       if (S.bkey) {
@@ -245,34 +191,6 @@ __global__ __launch_bounds__(kThreads) void k_remove_move(int64_t nnz, const int
   }
 }
 
-// the scratch of a rocprim call: grown only with the stream drained (an earlier call may still use it)
-void* tmp_for(hipStream_t st, AlsRemoveScratch& sc, size_t bytes) {
-  if (sc.tmp.bytes() < bytes) {
-    MF_HIP(hipStreamSynchronize(st));
-    sc.tmp.alloc(std::max<size_t>(bytes, 256));
-  }
-  return sc.tmp.get();
-}
-
-void sort_keys(hipStream_t st, AlsRemoveScratch& sc, const uint64_t* kin, uint64_t* kout, int32_t* vout, int64_t n,
-               int end_bit) {
-  sc.iota.alloc(static_cast<size_t>(n) * 4);
-  hipLaunchKernelGGL(k_remove_iota, dim3(grid_for(n)), dim3(kThreads), 0, st, n, sc.iota.as<int32_t>());
-  const unsigned int N = static_cast<unsigned int>(n);
-  size_t tb = 0;
-  MF_HIP(rocprim::radix_sort_pairs<SortCfg>(nullptr, tb, kin, kout, sc.iota.as<int32_t>(), vout, N, 0, end_bit, st));
-  void* tmp = tmp_for(st, sc, tb);
-  MF_HIP(rocprim::radix_sort_pairs<SortCfg>(tmp, tb, kin, kout, sc.iota.as<int32_t>(), vout, N, 0, end_bit, st));
-}
-
-template <typename T>
-void scan(hipStream_t st, AlsRemoveScratch& sc, const T* in, T* out, int64_t n) {
-  size_t tb = 0;
-  MF_HIP(rocprim::exclusive_scan(nullptr, tb, in, out, T(0), static_cast<size_t>(n), rocprim::plus<T>(), st));
-  void* tmp = tmp_for(st, sc, tb);
-  MF_HIP(rocprim::exclusive_scan(tmp, tb, in, out, T(0), static_cast<size_t>(n), rocprim::plus<T>(), st));
-}
-
 }  // namespace
 
 int64_t launch_als_remove_select(const AlsRemoveLaunch& L, AlsRemoveScratch& sc, uint8_t* found, int32_t* rempos) {
@@ -288,11 +206,11 @@ int64_t launch_als_remove_select(const AlsRemoveLaunch& L, AlsRemoveScratch& sc,
   if (found && L.nb > 0) MF_HIP(hipMemsetAsync(found, 0, static_cast<size_t>(L.nb), L.st));
   if (rempos && L.rows > 0) MF_HIP(hipMemsetAsync(rempos, 0, static_cast<size_t>(L.rows) * 4, L.st));
   if (L.nnz == 0 || L.rows == 0 || (batch && L.nb == 0)) return 0;
-  const int key_bits = 32 + bits_for(static_cast<uint64_t>(L.rows));
+  const int key_bits = 32 + radix_bits_for(static_cast<uint64_t>(L.rows));
   if (batch) {
     sc.key.alloc(static_cast<size_t>(L.nb) * 8);
     sc.idx.alloc(static_cast<size_t>(L.nb) * 4);
-    sort_keys(L.st, sc, L.bkey, sc.key.as<uint64_t>(), sc.idx.as<int32_t>(), L.nb, key_bits);
+    sort_positions(L.st, sc.tmp, sc.iota, L.bkey, sc.key.as<uint64_t>(), sc.idx.as<int32_t>(), L.nb, key_bits);
   }
   const Sel S{batch ? sc.key.as<uint64_t>() : nullptr, batch ? L.nb : 0, L.rowmark, L.colmark};
   sc.tile_cnt.alloc(static_cast<size_t>(tiles + 1) * 8);
@@ -300,7 +218,7 @@ int64_t launch_als_remove_select(const AlsRemoveLaunch& L, AlsRemoveScratch& sc,
   MF_HIP(hipMemsetAsync(sc.tile_cnt.as<int64_t>() + tiles, 0, 8, L.st));
   hipLaunchKernelGGL(k_remove_scan<false>, dim3(static_cast<unsigned>(tiles)), dim3(kThreads), 0, L.st, L.off, L.rows,
                      L.nnz, L.cols, S, sc.tile_cnt.as<int64_t>(), nullptr, nullptr, nullptr);
-  scan<int64_t>(L.st, sc, sc.tile_cnt.as<int64_t>(), sc.tile_base.as<int64_t>(), tiles + 1);
+  scan_exclusive(L.st, sc.tmp, sc.tile_cnt.as<int64_t>(), sc.tile_base.as<int64_t>(), tiles + 1);
   int64_t C = 0;
   MF_HIP(hipMemcpyAsync(&C, sc.tile_base.as<int64_t>() + tiles, 8, hipMemcpyDeviceToHost, L.st));
   MF_HIP(hipStreamSynchronize(L.st));
@@ -316,7 +234,8 @@ int64_t launch_als_remove_select(const AlsRemoveLaunch& L, AlsRemoveScratch& sc,
   if (batch) {
     sc.skey.alloc(static_cast<size_t>(C) * 8);
     sc.sidx.alloc(static_cast<size_t>(C) * 4);
-    sort_keys(L.st, sc, sc.cand_key.as<uint64_t>(), sc.skey.as<uint64_t>(), sc.sidx.as<int32_t>(), C, key_bits);
+    sort_positions(L.st, sc.tmp, sc.iota, sc.cand_key.as<uint64_t>(), sc.skey.as<uint64_t>(), sc.sidx.as<int32_t>(), C,
+                   key_bits);
     sc.kill.alloc(static_cast<size_t>(C + 1) * 4);
     sc.before.alloc(static_cast<size_t>(C + 1) * 4);
     MF_HIP(hipMemsetAsync(sc.kill.get(), 0, static_cast<size_t>(C + 1) * 4, L.st));
@@ -325,7 +244,7 @@ int64_t launch_als_remove_select(const AlsRemoveLaunch& L, AlsRemoveScratch& sc,
     if (found)
       hipLaunchKernelGGL(k_remove_found, dim3(grid_for(L.nb)), dim3(kThreads), 0, L.st, sc.key.as<uint64_t>(),
                          sc.idx.as<int32_t>(), L.nb, sc.skey.as<uint64_t>(), C, found);
-    scan<int32_t>(L.st, sc, sc.kill.as<int32_t>(), sc.before.as<int32_t>(), C + 1);
+    scan_exclusive(L.st, sc.tmp, sc.kill.as<int32_t>(), sc.before.as<int32_t>(), C + 1);
     int32_t g = 0;
     MF_HIP(hipMemcpyAsync(&g, sc.before.as<int32_t>() + C, 4, hipMemcpyDeviceToHost, L.st));
     MF_HIP(hipStreamSynchronize(L.st));

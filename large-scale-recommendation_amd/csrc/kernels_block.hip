@@ -29,14 +29,8 @@
 namespace mfhip {
 namespace {
 
-constexpr int kThreads = 256;
-unsigned grid_for(int64_t n) { return static_cast<unsigned>(std::max<int64_t>(1, std::min<int64_t>((n + kThreads - 1) / kThreads, 1 << 20))); }
-
-__global__ void k_iota(int32_t* __restrict__ out, int64_t n) {
-  for (int64_t x = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; x < n;
-       x += static_cast<int64_t>(gridDim.x) * blockDim.x)
-    out[x] = static_cast<int32_t>(x);
-}
+constexpr int kThreads = kGridThreads;
+dim3 grid(int64_t n) { return dim3(grid_for(n, 1 << 20)); }  // this file runs its loops on up to 2^20 workgroups
 
 // head[x] = 1 where a run of equal sorted ids starts
 __global__ void k_heads(const int32_t* __restrict__ sorted, int64_t n, int32_t* __restrict__ head) {
@@ -142,23 +136,14 @@ __global__ void k_block_starts(const uint32_t* __restrict__ keys, int64_t n, int
   start[b] = lo;
 }
 
-int bits_for(uint64_t maxval) {
+int bits_of(uint64_t maxval) {  // the bits of maxval (1 .. 64); not radix_bits_for, which bounds keys < v
   int b = 1;
   while (b < 64 && (maxval >> b) != 0) ++b;
   return b;
 }
 
-// hipcub temp storage, grown on demand
-struct Temp {
-  DevBuf buf;
-  void* get(size_t bytes) {
-    buf.alloc(std::max<size_t>(bytes, 256));
-    return buf.get();
-  }
-};
-
 // One side: rows of every rating (device) and the host SideLayout.
-void block_side(hipStream_t st, Temp& tmp, const int32_t* d_ids, int64_t n, int32_t nb, int64_t seed, SideLayout& S,
+void block_side(hipStream_t st, DevBuf& tmp, const int32_t* d_ids, int64_t n, int32_t nb, int64_t seed, SideLayout& S,
                 DevBuf& d_rows, DevBuf& d_blk_of_row) {
   S = SideLayout();
   S.n_blocks = nb;
@@ -174,22 +159,23 @@ void block_side(hipStream_t st, Temp& tmp, const int32_t* d_ids, int64_t n, int3
   perm.alloc(n * 4);
   head.alloc(n * 4);
   seg.alloc(n * 4);
-  hipLaunchKernelGGL(k_iota, dim3(grid_for(n)), dim3(kThreads), 0, st, idx_in.as<int32_t>(), n);
+  launch_iota(st, idx_in.as<int32_t>(), n);
   size_t tb = 0;
   MF_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, d_ids, keys_out.as<int32_t>(), idx_in.as<int32_t>(),
                                             perm.as<int32_t>(), static_cast<int>(n), 0, 32, st));
-  MF_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.get(tb), tb, d_ids, keys_out.as<int32_t>(), idx_in.as<int32_t>(),
-                                            perm.as<int32_t>(), static_cast<int>(n), 0, 32, st));
-  hipLaunchKernelGGL(k_heads, dim3(grid_for(n)), dim3(kThreads), 0, st, keys_out.as<int32_t>(), n, head.as<int32_t>());
+  MF_HIP(hipcub::DeviceRadixSort::SortPairs(temp_storage(st, tmp, tb), tb, d_ids, keys_out.as<int32_t>(),
+                                            idx_in.as<int32_t>(), perm.as<int32_t>(), static_cast<int>(n), 0, 32, st));
+  hipLaunchKernelGGL(k_heads, grid(n), dim3(kThreads), 0, st, keys_out.as<int32_t>(), n, head.as<int32_t>());
   MF_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, tb, head.as<int32_t>(), seg.as<int32_t>(), static_cast<int>(n), st));
-  MF_HIP(hipcub::DeviceScan::InclusiveSum(tmp.get(tb), tb, head.as<int32_t>(), seg.as<int32_t>(), static_cast<int>(n), st));
+  MF_HIP(hipcub::DeviceScan::InclusiveSum(temp_storage(st, tmp, tb), tb, head.as<int32_t>(), seg.as<int32_t>(),
+                                          static_cast<int>(n), st));
   int32_t dcount = 0;
   MF_HIP(hipMemcpyAsync(&dcount, seg.as<int32_t>() + n - 1, 4, hipMemcpyDeviceToHost, st));
   MF_HIP(hipStreamSynchronize(st));
   const int64_t d = dcount;
   distinct.alloc(d * 4);
   start.alloc((d + 1) * 8);
-  hipLaunchKernelGGL(k_runs, dim3(grid_for(n)), dim3(kThreads), 0, st, keys_out.as<int32_t>(), head.as<int32_t>(),
+  hipLaunchKernelGGL(k_runs, grid(n), dim3(kThreads), 0, st, keys_out.as<int32_t>(), head.as<int32_t>(),
                      seg.as<int32_t>(), n, distinct.as<int32_t>(), start.as<int64_t>());
   DevBuf blk, blk_sorted, iota, order, row_of;
   blk.alloc(d * 4);
@@ -197,15 +183,15 @@ void block_side(hipStream_t st, Temp& tmp, const int32_t* d_ids, int64_t n, int3
   iota.alloc(d * 4);
   order.alloc(d * 4);
   row_of.alloc(d * 4);
-  hipLaunchKernelGGL(k_jvm_block, dim3(grid_for(d)), dim3(kThreads), 0, st, distinct.as<int32_t>(), d, seed, nb,
+  hipLaunchKernelGGL(k_jvm_block, grid(d), dim3(kThreads), 0, st, distinct.as<int32_t>(), d, seed, nb,
                      blk.as<int32_t>(), iota.as<int32_t>());
-  const int bb = bits_for(static_cast<uint64_t>(nb));
+  const int bb = bits_of(static_cast<uint64_t>(nb));
   MF_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, blk.as<int32_t>(), blk_sorted.as<int32_t>(), iota.as<int32_t>(),
                                             order.as<int32_t>(), static_cast<int>(d), 0, bb, st));
-  MF_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.get(tb), tb, blk.as<int32_t>(), blk_sorted.as<int32_t>(),
+  MF_HIP(hipcub::DeviceRadixSort::SortPairs(temp_storage(st, tmp, tb), tb, blk.as<int32_t>(), blk_sorted.as<int32_t>(),
                                             iota.as<int32_t>(), order.as<int32_t>(), static_cast<int>(d), 0, bb, st));
-  hipLaunchKernelGGL(k_rows, dim3(grid_for(d)), dim3(kThreads), 0, st, order.as<int32_t>(), d, row_of.as<int32_t>());
-  hipLaunchKernelGGL(k_rating_rows, dim3(grid_for(n)), dim3(kThreads), 0, st, perm.as<int32_t>(), seg.as<int32_t>(),
+  hipLaunchKernelGGL(k_rows, grid(d), dim3(kThreads), 0, st, order.as<int32_t>(), d, row_of.as<int32_t>());
+  hipLaunchKernelGGL(k_rating_rows, grid(n), dim3(kThreads), 0, st, perm.as<int32_t>(), seg.as<int32_t>(),
                      row_of.as<int32_t>(), n, d_rows.as<uint32_t>());
   // host side of the layout: row y = distinct order[y]
   std::vector<int32_t> h_distinct(d), h_order(d), h_blk_sorted(d);
@@ -239,7 +225,7 @@ void device_blocking(hipStream_t st, const int32_t* u, const int32_t* i, const d
                      RatingBlocks& rb, DevRatingBlocks* keep, bool host_arrays) {
   MF_REQUIRE(n < (int64_t{1} << 31), "device blocking sorts with 32-bit indices (< 2^31 ratings)");
   const int64_t nb2 = static_cast<int64_t>(nb) * nb;
-  Temp tmp;
+  DevBuf tmp;  // hipcub temp storage (temp_storage)
   DevBuf du, di, dr;
   du.alloc(std::max<int64_t>(n, 1) * 4);
   di.alloc(std::max<int64_t>(n, 1) * 4);
@@ -266,29 +252,29 @@ void device_blocking(hipStream_t st, const int32_t* u, const int32_t* i, const d
     uikey.alloc(n * 8);
     uikey2.alloc(n * 8);
   }
-  hipLaunchKernelGGL(k_block_keys, dim3(grid_for(n)), dim3(kThreads), 0, st, urow.as<uint32_t>(), irow.as<uint32_t>(),
+  hipLaunchKernelGGL(k_block_keys, grid(n), dim3(kThreads), 0, st, urow.as<uint32_t>(), irow.as<uint32_t>(),
                      ublk.as<int32_t>(), iblk.as<int32_t>(), du.as<int32_t>(), di.as<int32_t>(), n, nb, ub_lo, ub_hi,
                      bkey.as<uint32_t>(), sort_ui ? uikey.as<uint64_t>() : nullptr);
-  hipLaunchKernelGGL(k_iota, dim3(grid_for(n)), dim3(kThreads), 0, st, idx.as<int32_t>(), n);
+  launch_iota(st, idx.as<int32_t>(), n);
   size_t tb = 0;
-  const int kb = bits_for(static_cast<uint64_t>(nb2));
+  const int kb = bits_of(static_cast<uint64_t>(nb2));
   if (sort_ui) {
     DevBuf p1;
     p1.alloc(n * 4);
     MF_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, uikey.as<uint64_t>(), uikey2.as<uint64_t>(), idx.as<int32_t>(),
                                               p1.as<int32_t>(), static_cast<int>(n), 0, 64, st));
-    MF_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.get(tb), tb, uikey.as<uint64_t>(), uikey2.as<uint64_t>(),
+    MF_HIP(hipcub::DeviceRadixSort::SortPairs(temp_storage(st, tmp, tb), tb, uikey.as<uint64_t>(), uikey2.as<uint64_t>(),
                                               idx.as<int32_t>(), p1.as<int32_t>(), static_cast<int>(n), 0, 64, st));
-    hipLaunchKernelGGL(k_gather_u32, dim3(grid_for(n)), dim3(kThreads), 0, st, p1.as<int32_t>(), bkey.as<uint32_t>(), n,
+    hipLaunchKernelGGL(k_gather_u32, grid(n), dim3(kThreads), 0, st, p1.as<int32_t>(), bkey.as<uint32_t>(), n,
                        bkey2.as<uint32_t>());
     MF_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, bkey2.as<uint32_t>(), bkey.as<uint32_t>(), p1.as<int32_t>(),
                                               perm.as<int32_t>(), static_cast<int>(n), 0, kb, st));
-    MF_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.get(tb), tb, bkey2.as<uint32_t>(), bkey.as<uint32_t>(),
+    MF_HIP(hipcub::DeviceRadixSort::SortPairs(temp_storage(st, tmp, tb), tb, bkey2.as<uint32_t>(), bkey.as<uint32_t>(),
                                               p1.as<int32_t>(), perm.as<int32_t>(), static_cast<int>(n), 0, kb, st));
   } else {
     MF_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, bkey.as<uint32_t>(), bkey2.as<uint32_t>(), idx.as<int32_t>(),
                                               perm.as<int32_t>(), static_cast<int>(n), 0, kb, st));
-    MF_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.get(tb), tb, bkey.as<uint32_t>(), bkey2.as<uint32_t>(),
+    MF_HIP(hipcub::DeviceRadixSort::SortPairs(temp_storage(st, tmp, tb), tb, bkey.as<uint32_t>(), bkey2.as<uint32_t>(),
                                               idx.as<int32_t>(), perm.as<int32_t>(), static_cast<int>(n), 0, kb, st));
   }
   // the sorted keys are in bkey (sort_ui) or bkey2: block starts from their histogram
@@ -297,11 +283,11 @@ void device_blocking(hipStream_t st, const int32_t* u, const int32_t* i, const d
   gu.alloc(n * 4);
   gi.alloc(n * 4);
   gr.alloc(n * 8);
-  hipLaunchKernelGGL(k_gather_u32, dim3(grid_for(n)), dim3(kThreads), 0, st, perm.as<int32_t>(), urow.as<uint32_t>(), n,
+  hipLaunchKernelGGL(k_gather_u32, grid(n), dim3(kThreads), 0, st, perm.as<int32_t>(), urow.as<uint32_t>(), n,
                      gu.as<uint32_t>());
-  hipLaunchKernelGGL(k_gather_u32, dim3(grid_for(n)), dim3(kThreads), 0, st, perm.as<int32_t>(), irow.as<uint32_t>(), n,
+  hipLaunchKernelGGL(k_gather_u32, grid(n), dim3(kThreads), 0, st, perm.as<int32_t>(), irow.as<uint32_t>(), n,
                      gi.as<uint32_t>());
-  hipLaunchKernelGGL(k_gather_f64, dim3(grid_for(n)), dim3(kThreads), 0, st, perm.as<int32_t>(), dr.as<double>(), n,
+  hipLaunchKernelGGL(k_gather_f64, grid(n), dim3(kThreads), 0, st, perm.as<int32_t>(), dr.as<double>(), n,
                      gr.as<double>());
   MF_HIP(hipGetLastError());
   // keys are sorted: block b spans [lower_bound(b), lower_bound(b+1)); n*n (other ranks) last

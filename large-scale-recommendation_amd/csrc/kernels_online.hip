@@ -23,7 +23,6 @@
 #include <hipcub/device/device_radix_sort.hpp>
 #include <hipcub/device/device_reduce.hpp>
 #include <hipcub/device/device_scan.hpp>
-#include <rocprim/device/device_radix_sort.hpp>
 
 #include <algorithm>
 #include <cmath>
@@ -32,14 +31,12 @@
 
 #include "common.hpp"
 #include "kernels.hpp"
+#include "radix_sort_cfg.hpp"
 
 namespace mfhip {
 namespace {
 
-constexpr int kThreads = 256;
-unsigned grid_for(int64_t n) {
-  return static_cast<unsigned>(std::max<int64_t>(1, std::min<int64_t>((n + kThreads - 1) / kThreads, 1 << 16)));
-}
+constexpr int kThreads = kGridThreads;
 
 // per item row, the updates of every S-th entry of the batch (the heavy items only need to be found,
 // not counted exactly: any item -> wave map gives the same factors; a sample cuts the atomics on
@@ -81,12 +78,6 @@ __global__ __launch_bounds__(kHeavyThreads) void k_heavy_assign(const uint32_t* 
     iwave[i] = heavy && pos < H ? static_cast<int32_t>(pos) : -1;
     pos += heavy;
   }
-}
-
-__global__ void k_iota(int64_t n, int32_t* __restrict__ iota) {
-  for (int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; i < n;
-       i += static_cast<int64_t>(gridDim.x) * blockDim.x)
-    iota[i] = static_cast<int32_t>(i);
 }
 
 __global__ void k_keys(const uint32_t* __restrict__ eu, const uint32_t* __restrict__ ei, int64_t n, uint32_t W,
@@ -159,18 +150,6 @@ __global__ void k_head_flags(const uint32_t* __restrict__ sorted, int64_t n, int
     flag[p] = (p == 0 || sorted[p] != sorted[p - 1]) ? 1 : 0;
 }
 
-// The plan's stable sorts: rocprim's radix sort with the merge-sort path off.  Its default config
-// sorts up to 2^20 keys by block sort + 8 merge passes (17 launches of 5-10 us for a 1M batch,
-// gpurun_out/r6o); onesweep takes a histogram, a scan and one pass per 8 key bits.  Both are stable:
-// the same output.
-using SortCfg = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config, rocprim::default_config, 0>;
-
-int bits_for(uint64_t v) {  // radix bits that hold every key < v
-  int b = 1;
-  while (b < 32 && (uint64_t{1} << b) < v) ++b;
-  return b;
-}
-
 // The deterministic sweep's entry arrays (SoA, padded with kDetPad zero entries: the sweep reads
 // whole chunks past a wave's end) from the plan's wave-ordered entries
 __global__ void k_det_soa(const DetEntry* __restrict__ ent, const uint32_t* __restrict__ useq, int64_t n,
@@ -212,13 +191,13 @@ __device__ __forceinline__ uint64_t id_hash(int32_t id) {
   x ^= x >> 16; x *= 0x7feb352dULL; x ^= x >> 15; x *= 0x846ca68bULL; x ^= x >> 16;
   return x;
 }
-// linear probing over a mirror of the host table: the row, or 0xFFFFFFFF (absent / empty table)
+// linear probing over a mirror of the host table: the row, or kRowMiss (absent / empty table)
 __device__ __forceinline__ uint32_t id_find(const int2* __restrict__ slots, uint64_t mask, int32_t id) {
-  if (!slots) return 0xFFFFFFFFu;
+  if (!slots) return kRowMiss;
   uint64_t h = id_hash(id) & mask;
   for (;;) {
     const int2 sl = slots[h];
-    if (sl.y < 0) return 0xFFFFFFFFu;
+    if (sl.y < 0) return kRowMiss;
     if (sl.x == id) return static_cast<uint32_t>(sl.y);
     h = (h + 1) & mask;
   }
@@ -234,7 +213,7 @@ __global__ __launch_bounds__(kThreads) void k_id_lookup(uint32_t* __restrict__ i
     const uint32_t ir = id_find(is, im, static_cast<int32_t>(in[n + j]));
     in[j] = ur;
     in[n + j] = ir;
-    m = (ur == 0xFFFFFFFFu) + (ir == 0xFFFFFFFFu);
+    m = (ur == kRowMiss) + (ir == kRowMiss);
   }
   // one atomic per wave
   const int tot = __popcll(__ballot(m >= 1)) + __popcll(__ballot(m == 2));
@@ -324,7 +303,7 @@ uint32_t online_sweep_plan(hipStream_t st, OnlineSweepScratch& sc, const uint32_
   hipLaunchKernelGGL(k_keys, dim3(grid_for(n)), dim3(kThreads), 0, st, eu, ei, n, W, H,
                      H > 0 && item_rows > 0 ? sc.iwave.as<int32_t>() : nullptr, item_rows, sc.wkey.as<uint32_t>(),
                      sc.iota.as<int32_t>());
-  const int ub = bits_for(user_rows), wb = bits_for(W);
+  const int ub = radix_bits_for(user_rows), wb = radix_bits_for(W);
   // tickets on s2 (user sort, run starts, ranks) and the touched items on s3 (item-row flags)
   // run beside the wave keys and the wave sort on st; both only read the uploaded batch
   sc.side_streams();
@@ -334,7 +313,7 @@ uint32_t online_sweep_plan(hipStream_t st, OnlineSweepScratch& sc, const uint32_
   MF_HIP(hipStreamWaitEvent(sc.s2, sc.ev_in, 0));
   MF_HIP(hipStreamWaitEvent(sc.s3, sc.ev_in, 0));
   size_t tb2 = 0, tb3 = 0;
-  hipLaunchKernelGGL(k_iota, dim3(grid_for(n)), dim3(kThreads), 0, sc.s2, n, sc.iota2.as<int32_t>());
+  launch_iota(sc.s2, sc.iota2.as<int32_t>(), n);
   MF_HIP(rocprim::radix_sort_pairs<SortCfg>(nullptr, tb2, eu, sc.ukey.as<uint32_t>(), sc.iota2.as<int32_t>(),
                                              sc.ux.as<int32_t>(), N, 0, ub, sc.s2));
   sc.tmp2.alloc(std::max<size_t>(tb2, 256));
@@ -432,15 +411,15 @@ __global__ void k_db_scatter(const int32_t* __restrict__ wx, int64_t n, const De
 void det_device_build_reserve(DetBuildScratch& sc, int64_t n_max, uint32_t wave_bound, uint32_t user_rows) {
   MF_REQUIRE(n_max >= 0 && n_max < (int64_t{1} << 31), "det device build: superstep too large");
   const int64_t n = std::max<int64_t>(n_max, 1);
-  const int N = static_cast<int>(n);
+  const int N = static_cast<int>(n), wb = radix_bits_for(wave_bound), ub = radix_bits_for(user_rows);
   sc.ent.alloc(n * sizeof(DetEntry));
   for (DevBuf* b : {&sc.wkey, &sc.wkey2, &sc.ukey, &sc.ukey2, &sc.iota, &sc.wx, &sc.ux, &sc.head, &sc.start, &sc.ticket})
     b->alloc(n * 4);
   size_t a = 0, b2 = 0, c = 0;
   MF_HIP(rocprim::radix_sort_pairs<SortCfg>(nullptr, a, sc.wkey.as<uint32_t>(), sc.wkey2.as<uint32_t>(),
-                                             sc.iota.as<int32_t>(), sc.wx.as<int32_t>(), N, 0, bits_for(wave_bound)));
+                                             sc.iota.as<int32_t>(), sc.wx.as<int32_t>(), N, 0, wb));
   MF_HIP(rocprim::radix_sort_pairs<SortCfg>(nullptr, b2, sc.ukey.as<uint32_t>(), sc.ukey2.as<uint32_t>(),
-                                             sc.iota.as<int32_t>(), sc.ux.as<int32_t>(), N, 0, bits_for(user_rows)));
+                                             sc.iota.as<int32_t>(), sc.ux.as<int32_t>(), N, 0, ub));
   MF_HIP(hipcub::DeviceScan::InclusiveScan(nullptr, c, sc.head.as<int32_t>(), sc.start.as<int32_t>(), hipcub::Max(), N));
   sc.tmp_bytes = std::max<size_t>(std::max(a, b2), 256);
   sc.tmp2_bytes = std::max<size_t>(c, 256);
@@ -454,23 +433,23 @@ void det_device_build(hipStream_t st, DetBuildScratch& sc, const int32_t* ord, i
                       uint32_t user_rows, uint32_t* ou, uint32_t* oi, uint32_t* oq, double* orr) {
   if (n <= 0) return;
   MF_REQUIRE(n <= sc.n_max, "det device build: more ratings than the scratch was reserved for");
-  const int N = static_cast<int>(n);
+  const int N = static_cast<int>(n), wb = radix_bits_for(wave_bound), ub = radix_bits_for(user_rows);
   hipLaunchKernelGGL(k_db_gather, dim3(grid_for(n)), dim3(kThreads), 0, st, ord, n, blocks, nblk, aos, item_wave,
                      sc.ent.as<DetEntry>(), sc.wkey.as<uint32_t>(), sc.ukey.as<uint32_t>(), sc.iota.as<int32_t>());
   size_t tb = 0;
   // wave-major order, a wave's ratings in shuffle order (stable)
   MF_HIP(rocprim::radix_sort_pairs<SortCfg>(nullptr, tb, sc.wkey.as<uint32_t>(), sc.wkey2.as<uint32_t>(),
-                                             sc.iota.as<int32_t>(), sc.wx.as<int32_t>(), N, 0, bits_for(wave_bound), st));
+                                             sc.iota.as<int32_t>(), sc.wx.as<int32_t>(), N, 0, wb, st));
   MF_REQUIRE(tb <= sc.tmp_bytes, "det device build: sort scratch");
   MF_HIP(rocprim::radix_sort_pairs<SortCfg>(sc.tmp.get(), tb, sc.wkey.as<uint32_t>(), sc.wkey2.as<uint32_t>(),
-                                             sc.iota.as<int32_t>(), sc.wx.as<int32_t>(), N, 0, bits_for(wave_bound), st));
+                                             sc.iota.as<int32_t>(), sc.wx.as<int32_t>(), N, 0, wb, st));
   // useq: the rank of a rating among its user's ratings in shuffle order (users of a superstep's
   // blocks are disjoint: each block has its own user block)
   MF_HIP(rocprim::radix_sort_pairs<SortCfg>(nullptr, tb, sc.ukey.as<uint32_t>(), sc.ukey2.as<uint32_t>(),
-                                             sc.iota.as<int32_t>(), sc.ux.as<int32_t>(), N, 0, bits_for(user_rows), st));
+                                             sc.iota.as<int32_t>(), sc.ux.as<int32_t>(), N, 0, ub, st));
   MF_REQUIRE(tb <= sc.tmp_bytes, "det device build: sort scratch");
   MF_HIP(rocprim::radix_sort_pairs<SortCfg>(sc.tmp.get(), tb, sc.ukey.as<uint32_t>(), sc.ukey2.as<uint32_t>(),
-                                             sc.iota.as<int32_t>(), sc.ux.as<int32_t>(), N, 0, bits_for(user_rows), st));
+                                             sc.iota.as<int32_t>(), sc.ux.as<int32_t>(), N, 0, ub, st));
   hipLaunchKernelGGL(k_run_heads, dim3(grid_for(n)), dim3(kThreads), 0, st, sc.ukey2.as<uint32_t>(), n,
                      sc.head.as<int32_t>());
   tb = 0;

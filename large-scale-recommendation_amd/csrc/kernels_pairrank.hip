@@ -28,13 +28,12 @@
 #include <cstdint>
 
 #include "common.hpp"
+#include "csr_search.hpp"
 #include "kernels.hpp"
 #include "mfhip.h"
 
 namespace mfhip {
 namespace {
-
-constexpr uint32_t kMiss = 0xFFFFFFFFu;
 
 // ---- keys: kernels_recommend.hip's order, restated ------------------------------------------
 // Candidate id part: a smaller id gives a larger value.
@@ -69,14 +68,7 @@ __device__ __forceinline__ bool beats(O a, uint32_t ai, O b, uint32_t bi) { retu
 
 // Is candidate row `crow` in the sorted rows [b, e)?
 __device__ __forceinline__ bool excluded(const int32_t* __restrict__ rows, int64_t b, int64_t e, int32_t crow) {
-  while (b < e) {
-    const int64_t m = (b + e) >> 1;
-    const int32_t v = rows[m];
-    if (v == crow) return true;
-    if (v < crow) b = m + 1;
-    else e = m;
-  }
-  return false;
+  return dev::contains(rows, b, e, crow);
 }
 
 // The pair's score part: the chain over f = 0 .. k-1 from 0.
@@ -109,7 +101,7 @@ template <>
 struct OrdOf<double> { using type = uint64_t; };
 
 // ---- targets ------------------------------------------------------------------------------
-// qrow / crow: the pair's factor rows (kMiss: unknown id); qpos (rows + 1 entries): a known query
+// qrow / crow: the pair's factor rows (kRowMiss: unknown id); qpos (rows + 1 entries): a known query
 // row's position in the exclusion CSR eoff / erows.  tord == 0 marks a pair that is not ranked.
 template <typename T>
 __global__ __launch_bounds__(256) void k_pr_target(const T* __restrict__ Qf, const T* __restrict__ Cf,
@@ -127,7 +119,7 @@ __global__ __launch_bounds__(256) void k_pr_target(const T* __restrict__ Qf, con
   O o = 0;
   uint32_t idp = 0;
   int32_t code = MF_PAIR_RANK_COLD, v = 0;
-  if (qr != kMiss && cr != kMiss) {
+  if (qr != kRowMiss && cr != kRowMiss) {
     const int32_t p = qpos[qr];
     const int64_t b = eoff[p], e = eoff[p + 1];
     if (excluded(erows, b, e, static_cast<int32_t>(cr))) {

@@ -28,22 +28,14 @@
 #include <cstdint>
 
 #include "common.hpp"
+#include "csr_search.hpp"
 #include "kernels.hpp"
 #include "mfhip.h"
 
 namespace mfhip {
 namespace {
 
-constexpr int kThreads = 256;
-constexpr uint32_t kMiss = 0xFFFFFFFFu;
-unsigned grid_for(int64_t n) {
-  return static_cast<unsigned>(std::max<int64_t>(1, std::min<int64_t>((n + kThreads - 1) / kThreads, 1 << 16)));
-}
-int bits_for(uint64_t v) {  // radix bits that hold every value < v
-  int b = 1;
-  while (b < 32 && (uint64_t{1} << b) < v) ++b;
-  return b;
-}
+constexpr int kThreads = kGridThreads;
 
 // flag[row] = 1 for every known query row of the pairs (flag has rows + 1 entries, the last stays 0)
 __global__ void k_rank_flags(const uint32_t* __restrict__ qrow, int64_t n, uint32_t rows, int32_t* __restrict__ flag) {
@@ -64,7 +56,7 @@ __global__ void k_rank_compact(const int32_t* __restrict__ flag, const int32_t* 
 
 // key[x] = (position of the pair's query << 32) | low, or nq << 32 for a pair that is dropped.
 // gt: low = cand[x] (an id) with the sign bit flipped, unknown candidates kept; else low = cand[x] (a
-// candidate row), kMiss dropped.
+// candidate row), kRowMiss dropped.
 __global__ void k_rank_keys(const uint32_t* __restrict__ qrow, const uint32_t* __restrict__ cand, int64_t n,
                             uint32_t rows, const int32_t* __restrict__ flag, const int32_t* __restrict__ pos, int64_t nq,
                             bool gt, uint64_t* __restrict__ key) {
@@ -72,7 +64,7 @@ __global__ void k_rank_keys(const uint32_t* __restrict__ qrow, const uint32_t* _
        x += static_cast<int64_t>(gridDim.x) * blockDim.x) {
     const uint32_t r = qrow[x], c = cand[x];
     uint64_t k = static_cast<uint64_t>(nq) << 32;
-    if (r < rows && flag[r] && (gt || c != kMiss))
+    if (r < rows && flag[r] && (gt || c != kRowMiss))
       k = (static_cast<uint64_t>(static_cast<uint32_t>(pos[r])) << 32) | (gt ? c ^ 0x80000000u : c);
     key[x] = k;
   }
@@ -101,27 +93,14 @@ __global__ void k_rank_offsets(const uint64_t* __restrict__ key, const int32_t* 
                                int64_t* __restrict__ off) {
   for (int64_t q = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; q <= nq;
        q += static_cast<int64_t>(gridDim.x) * blockDim.x) {
-    const uint64_t want = static_cast<uint64_t>(q) << 32;
-    int64_t lo = 0, hi = n;  // first position whose key is >= want
-    while (lo < hi) {
-      const int64_t mid = (lo + hi) >> 1;
-      if (key[mid] < want) lo = mid + 1;
-      else hi = mid;
-    }
-    off[q] = wp[lo];
+    const uint64_t want = static_cast<uint64_t>(q) << 32;  // query q's first key
+    off[q] = wp[dev::lower(key, 0, n, want)];
   }
 }
 
 // Is id in the query's sorted ground-truth ids [b, e)?
 __device__ __forceinline__ bool in_truth(const int32_t* __restrict__ ent, int64_t b, int64_t e, int32_t id) {
-  while (b < e) {
-    const int64_t m = (b + e) >> 1;
-    const int32_t v = ent[m];
-    if (v == id) return true;
-    if (v < id) b = m + 1;
-    else e = m;
-  }
-  return false;
+  return dev::contains(ent, b, e, id);
 }
 
 // Grid: ceil(nb / 4) blocks of 4 waves, wave = query of the batch.  goff (nb + 1) / met / cnt point at the
@@ -226,8 +205,8 @@ int64_t rank_query_set(hipStream_t st, RankScratch& sc, const uint32_t* qrow, in
   hipLaunchKernelGGL(k_rank_flags, dim3(grid_for(n)), dim3(kThreads), 0, st, qrow, n, rows, sc.flag.as<int32_t>());
   size_t tb = 0;
   MF_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, sc.flag.as<int32_t>(), sc.pos.as<int32_t>(), R, st));
-  sc.tmp.alloc(std::max<size_t>(tb, 256));
-  MF_HIP(hipcub::DeviceScan::ExclusiveSum(sc.tmp.get(), tb, sc.flag.as<int32_t>(), sc.pos.as<int32_t>(), R, st));
+  MF_HIP(hipcub::DeviceScan::ExclusiveSum(temp_storage(st, sc.tmp, tb), tb, sc.flag.as<int32_t>(),
+                                          sc.pos.as<int32_t>(), R, st));
   int32_t nq = 0;  // pos[rows]: the flags before the zero that ends the array
   MF_HIP(hipMemcpyAsync(&nq, sc.pos.as<int32_t>() + rows, 4, hipMemcpyDeviceToHost, st));
   MF_HIP(hipStreamSynchronize(st));
@@ -265,12 +244,11 @@ void rank_keys_reserve(RankScratch& sc, int64_t n) {
 
 void rank_keys_sort(hipStream_t st, RankScratch& sc, int64_t n, int64_t nq) {
   const int N = static_cast<int>(n);
-  const int end_bit = 32 + bits_for(static_cast<uint64_t>(nq) + 1);  // positions 0 .. nq (nq: dropped)
+  const int end_bit = 32 + radix_bits_for(static_cast<uint64_t>(nq) + 1);  // positions 0 .. nq (nq: dropped)
   size_t tb = 0;
   MF_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, tb, sc.key.as<uint64_t>(), sc.key2.as<uint64_t>(), N, 0, end_bit, st));
-  sc.tmp.alloc(std::max<size_t>(tb, 256));
-  MF_HIP(hipcub::DeviceRadixSort::SortKeys(sc.tmp.get(), tb, sc.key.as<uint64_t>(), sc.key2.as<uint64_t>(), N, 0, end_bit,
-                                           st));
+  MF_HIP(hipcub::DeviceRadixSort::SortKeys(temp_storage(st, sc.tmp, tb), tb, sc.key.as<uint64_t>(),
+                                           sc.key2.as<uint64_t>(), N, 0, end_bit, st));
   hipLaunchKernelGGL(k_rank_heads, dim3(grid_for(n + 1)), dim3(kThreads), 0, st, sc.key2.as<uint64_t>(), n, nq,
                      sc.head.as<int32_t>());
   MF_HIP(hipGetLastError());
@@ -280,8 +258,8 @@ void rank_keys_csr(hipStream_t st, RankScratch& sc, int64_t n, int64_t nq, bool 
   const int N = static_cast<int>(n);
   size_t tb = 0;
   MF_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, sc.head.as<int32_t>(), sc.wp.as<int32_t>(), N + 1, st));
-  sc.tmp.alloc(std::max<size_t>(tb, 256));
-  MF_HIP(hipcub::DeviceScan::ExclusiveSum(sc.tmp.get(), tb, sc.head.as<int32_t>(), sc.wp.as<int32_t>(), N + 1, st));
+  MF_HIP(hipcub::DeviceScan::ExclusiveSum(temp_storage(st, sc.tmp, tb), tb, sc.head.as<int32_t>(),
+                                          sc.wp.as<int32_t>(), N + 1, st));
   hipLaunchKernelGGL(k_rank_entries, dim3(grid_for(n)), dim3(kThreads), 0, st, sc.key2.as<uint64_t>(),
                      sc.head.as<int32_t>(), sc.wp.as<int32_t>(), n, gt, ent);
   hipLaunchKernelGGL(k_rank_offsets, dim3(grid_for(nq + 1)), dim3(kThreads), 0, st, sc.key2.as<uint64_t>(),

@@ -31,6 +31,7 @@
 #include <string>
 
 #include "common.hpp"
+#include "csr_search.hpp"
 #include "kernels.hpp"
 #include "mfhip.h"
 
@@ -110,14 +111,7 @@ __device__ __forceinline__ void list_insert(K* list, int N, K key) {
 
 // Is candidate row `crow` in the query's sorted exclusion rows [b, e)?
 __device__ __forceinline__ bool excluded(const int32_t* __restrict__ rows, int64_t b, int64_t e, int32_t crow) {
-  while (b < e) {
-    const int64_t m = (b + e) >> 1;
-    const int32_t v = rows[m];
-    if (v == crow) return true;
-    if (v < crow) b = m + 1;
-    else e = m;
-  }
-  return false;
+  return dev::contains(rows, b, e, crow);
 }
 
 // ---- f32: MFMA score + select -----------------------------------------------------------------

@@ -14,58 +14,32 @@
 //          follows from the two sorted sequences:
 //              an old entry e with key K       lands at  e + #(novel keys < K)
 //              the i-th novel key, N           lands at  i + #(old keys < N)
-//          k_seen_move walks the OLD ENTRIES in tiles of 2048 as k_als_move does: two searches of old_off per
-//          workgroup for the rows of its first and last entry, one search each for the novel range of its
-//          first and last key, and a lane narrows its row and its count inside those spans.  Every old entry
-//          is read once and written once; a long row is moved by as many workgroups as it has tiles.
+//          k_seen_move takes the OLD ENTRIES by the tile walk of csr_device.hpp, with one more search per end
+//          of the tile for the novel range of its first and last key; a lane narrows its row and its count
+//          inside those spans.  Every old entry is read once and written once.
 // No atomics, no floating point, and no kernel here waits on another wave: the placement depends on no order
 // of execution.  Offsets and positions are 64-bit; a batch holds fewer than 2^31 - 1 pairs.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cstdint>
 
 #include "common.hpp"
+#include "csr_device.hpp"
 #include "kernels.hpp"
 
 namespace mfhip {
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kTile = kThreads * 8;  // entries per workgroup of the tiled walks
-constexpr uint32_t kMiss = 0xFFFFFFFFu;
-
-unsigned grid_for(int64_t n) {
-  return static_cast<unsigned>(std::max<int64_t>(1, std::min<int64_t>((n + kThreads - 1) / kThreads, 1 << 16)));
-}
-
-// The row of entry e: the largest x in [lo, hi] with off[x] <= e, given off[lo] <= e < off[hi + 1] (rows
-// without entries share their offset with the next row).
-__device__ inline int64_t row_of(const int64_t* __restrict__ off, int64_t lo, int64_t hi, int64_t e) {
-  while (lo < hi) {
-    const int64_t mid = lo + (hi - lo + 1) / 2;
-    if (off[mid] <= e) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
-
-// The first position of [b, e) whose entry is >= c (e when there is none); entries ascend.
-__device__ inline int64_t lower_bound(const int32_t* __restrict__ ent, int64_t b, int64_t e, int32_t c) {
-  while (b < e) {
-    const int64_t m = (b + e) >> 1;
-    if (ent[m] < c) b = m + 1;
-    else e = m;
-  }
-  return b;
-}
+using dev::lower;
+constexpr int kThreads = dev::kCsrThreads;
+constexpr int kTile = dev::kCsrTile;  // entries per workgroup of the tiled walks
 
 __global__ void k_seen_pair_keys(const uint32_t* __restrict__ qrow, const uint32_t* __restrict__ crow, int64_t n,
                                  uint32_t rows, uint64_t* __restrict__ key) {
   for (int64_t x = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; x < n;
        x += static_cast<int64_t>(gridDim.x) * blockDim.x) {
     const uint32_t r = qrow[x], c = crow[x];
-    key[x] = (r < rows && c != kMiss) ? (static_cast<uint64_t>(r) << 32) | c : static_cast<uint64_t>(rows) << 32;
+    key[x] = (r < rows && c != kRowMiss) ? (static_cast<uint64_t>(r) << 32) | c : static_cast<uint64_t>(rows) << 32;
   }
 }
 
@@ -73,15 +47,11 @@ __global__ __launch_bounds__(kThreads) void k_seen_csr_keys(const int64_t* __res
                                                             const int32_t* __restrict__ cols, bool swap,
                                                             uint64_t* __restrict__ key) {
   __shared__ int64_t span[2];
-  const int64_t t0 = blockIdx.x * static_cast<int64_t>(kTile);
-  const int64_t t1 = t0 + kTile < nnz ? t0 + kTile : nnz;
-  if (t0 >= t1) return;  // (the grid has no such workgroup)
-  if (threadIdx.x < 2) span[threadIdx.x] = row_of(off, 0, rows - 1, threadIdx.x == 0 ? t0 : t1 - 1);
-  __syncthreads();
-  int64_t lo = span[0];
-  const int64_t hi = span[1];
-  for (int64_t e = t0 + threadIdx.x; e < t1; e += kThreads) {
-    lo = row_of(off, lo, hi, e);  // a lane's entries ascend, so its rows do
+  dev::CsrTile T;
+  if (!dev::csr_tile(off, rows, nnz, span, T)) return;
+  int64_t lo = T.lo;
+  for (int64_t e = T.t0 + threadIdx.x; e < T.t1; e += kThreads) {
+    lo = dev::row_of(off, lo, T.hi, e);  // a lane's entries ascend, so its rows do
     const uint64_t r = static_cast<uint64_t>(lo), c = static_cast<uint32_t>(cols[e]);
     key[e] = swap ? (c << 32) | r : (r << 32) | c;
   }
@@ -99,7 +69,7 @@ __global__ void k_seen_novel(const uint64_t* __restrict__ key2, int32_t* __restr
     int64_t at = old_off[old_rows];  // a row the table does not cover: every old key lies below
     if (r < old_rows) {
       const int64_t e = old_off[r + 1];
-      at = lower_bound(old_ent, old_off[r], e, c);
+      at = lower<int32_t>(old_ent, old_off[r], e, c);
       if (at < e && old_ent[at] == c) head[p] = 0;
     }
     lb[p] = at;
@@ -119,26 +89,22 @@ __global__ __launch_bounds__(kThreads) void k_seen_move(const int64_t* __restric
                                                         const int32_t* __restrict__ nov_ent,
                                                         int32_t* __restrict__ new_ent) {
   __shared__ int64_t span[2], nspan[2];
-  const int64_t t0 = blockIdx.x * static_cast<int64_t>(kTile);
-  const int64_t t1 = t0 + kTile < old_nnz ? t0 + kTile : old_nnz;
-  if (t0 >= t1) return;  // (the grid has no such workgroup)
-  if (threadIdx.x < 2) {
-    // the row of the tile's first / last entry, and the novel keys below that entry's key
-    const int64_t e = threadIdx.x == 0 ? t0 : t1 - 1;
-    const int64_t r = row_of(old_off, 0, old_rows - 1, e);
-    span[threadIdx.x] = r;
-    nspan[threadIdx.x] = lower_bound(nov_ent, nov_off[r], nov_off[r + 1], old_ent[e]);
+  dev::CsrTile T;
+  if (!dev::csr_tile(old_off, old_rows, old_nnz, span, T)) return;
+  if (threadIdx.x < 2) {  // the novel keys below the key of the tile's first / last entry
+    const int64_t e = threadIdx.x == 0 ? T.t0 : T.t1 - 1, r = span[threadIdx.x];
+    nspan[threadIdx.x] = lower<int32_t>(nov_ent, nov_off[r], nov_off[r + 1], old_ent[e]);
   }
   __syncthreads();
-  int64_t lo = span[0];
-  const int64_t hi = span[1], nlo = nspan[0], nhi = nspan[1];
-  for (int64_t e = t0 + threadIdx.x; e < t1; e += kThreads) {
-    lo = row_of(old_off, lo, hi, e);  // a lane's entries ascend, so its rows do
+  int64_t lo = T.lo;
+  const int64_t hi = T.hi, nlo = nspan[0], nhi = nspan[1];
+  for (int64_t e = T.t0 + threadIdx.x; e < T.t1; e += kThreads) {
+    lo = dev::row_of(old_off, lo, hi, e);  // a lane's entries ascend, so its rows do
     const int32_t c = old_ent[e];
     // the novel keys below (lo, c) end inside the row's novel range and inside the tile's
     const int64_t b = nov_off[lo] > nlo ? nov_off[lo] : nlo;
     const int64_t f = nov_off[lo + 1] < nhi ? nov_off[lo + 1] : nhi;
-    new_ent[e + lower_bound(nov_ent, b, f, c)] = c;
+    new_ent[e + lower<int32_t>(nov_ent, b, f, c)] = c;
   }
 }
 
@@ -164,12 +130,6 @@ __global__ void k_seen_gather(const int64_t* __restrict__ off, const int32_t* __
   const int32_t r = qrows[q];
   beg[q] = off[r];
   end[q] = off[r + 1];
-}
-
-__global__ void k_seen_iota(int32_t* __restrict__ out, int64_t n) {
-  for (int64_t x = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; x < n;
-       x += static_cast<int64_t>(gridDim.x) * blockDim.x)
-    out[x] = static_cast<int32_t>(x);
 }
 
 unsigned tiles_of(int64_t nnz) {
@@ -227,12 +187,6 @@ void launch_seen_gather(hipStream_t st, const int64_t* off, const int32_t* qrows
   if (n <= 0) return;
   hipLaunchKernelGGL(k_seen_gather, dim3(static_cast<unsigned>((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, st,
                      off, qrows, n, beg, end);
-  MF_HIP(hipGetLastError());
-}
-
-void launch_seen_iota(hipStream_t st, int32_t* out, int64_t n) {
-  if (n <= 0) return;
-  hipLaunchKernelGGL(k_seen_iota, dim3(grid_for(n)), dim3(kThreads), 0, st, out, n);
   MF_HIP(hipGetLastError());
 }
 

@@ -130,7 +130,6 @@ enum class OnlinePath {
   kLevels,       // one launch per dependency level
 };
 
-constexpr uint32_t kMiss = 0xFFFFFFFFu;  // a rating's row while its id is not in the index
 
 // One online batch on its way through online_update's stages: the caller's arrays, the kernel
 // chosen for it, the upload's layout, the factor rows of its ratings and what is queued on the
@@ -169,7 +168,7 @@ struct OnlineBatch {
   // sweep rounds each rating to float first in any case (online_f32.hpp), so the bits are the same
   bool rf32 = false;
   size_t in_bytes = 0;
-  uint32_t *ur = nullptr, *ir = nullptr;  // factor rows per rating (kMiss: not known yet)
+  uint32_t *ur = nullptr, *ir = nullptr;  // factor rows per rating (kRowMiss: not known yet)
   int64_t misses = 0;
   std::vector<int32_t> fu, fi;  // ids first seen in this batch, in order of appearance
   int32_t* pin4 = nullptr;      // pinned: {lookup misses, sweep error, touched users, touched items}
@@ -372,7 +371,7 @@ bool stage_and_lookup_device(OnlineBatch& b) {
     finish_sweep(b);
     return true;
   }
-  if (m > 0) {  // the rows as found (kMiss where absent) back into the pinned buffer
+  if (m > 0) {  // the rows as found (kRowMiss where absent) back into the pinned buffer
     b.planned = b.det_queued = false;
     MF_HIP(hipMemcpyAsync(ur, up.get(), static_cast<size_t>(n) * 8, hipMemcpyDeviceToHost, s.stream));
     MF_HIP(hipStreamSynchronize(s.stream));
@@ -381,7 +380,7 @@ bool stage_and_lookup_device(OnlineBatch& b) {
   return false;
 }
 
-// Rows of known ids in parallel (the index is only read; kMiss marks the others).
+// Rows of known ids in parallel (the index is only read; kRowMiss marks the others).
 void lookup_host(OnlineBatch& b) {
   mf_ctx* ctx = b.ctx;
   const int64_t n = b.n_in;
@@ -392,7 +391,7 @@ void lookup_host(OnlineBatch& b) {
     ctx->I.index.find_many(b.i + lo2, hi2 - lo2, ir + lo2);
     if (b.direct && !b.sampled()) b.stage_ratings(ir + n, lo2, hi2);
     int64_t m = 0;
-    for (int64_t j = lo2; j < hi2; ++j) m += (ur[j] == kMiss) + (ir[j] == kMiss);
+    for (int64_t j = lo2; j < hi2; ++j) m += (ur[j] == kRowMiss) + (ir[j] == kRowMiss);
     misses += m;
   });
   b.misses = misses;
@@ -404,8 +403,8 @@ void assign_new_rows(OnlineBatch& b) {
   mf_ctx* ctx = b.ctx;
   if (b.misses > 0)
     for (int64_t j = 0; j < b.n_in; ++j) {
-      if (b.ur[j] == kMiss) b.ur[j] = static_cast<uint32_t>(online_row(ctx, ctx->U, b.u[j], b.fu));
-      if (b.ir[j] == kMiss) b.ir[j] = static_cast<uint32_t>(online_row(ctx, ctx->I, b.i[j], b.fi));
+      if (b.ur[j] == kRowMiss) b.ur[j] = static_cast<uint32_t>(online_row(ctx, ctx->U, b.u[j], b.fu));
+      if (b.ir[j] == kRowMiss) b.ir[j] = static_cast<uint32_t>(online_row(ctx, ctx->I, b.i[j], b.fi));
     }
   b.clk.lap("online: id lookup");
 }

@@ -26,7 +26,6 @@
 
 namespace mfhip {
 namespace {
-constexpr uint32_t kMiss = 0xFFFFFFFFu;
 }
 
 int64_t pair_ranks(mf_ctx* ctx, int qside, const int32_t* q, const int32_t* c, int64_t n, const int32_t* eq,
@@ -51,7 +50,7 @@ int64_t pair_ranks(mf_ctx* ctx, int qside, const int32_t* q, const int32_t* c, i
   std::atomic<int64_t> cold_sum{0};
   parallel_for(n, [&](int64_t b, int64_t e, int) {
     int64_t m = 0;
-    for (int64_t j = b; j < e; ++j) m += (qr[j] == kMiss || cr[j] == kMiss) ? 1 : 0;
+    for (int64_t j = b; j < e; ++j) m += (qr[j] == kRowMiss || cr[j] == kRowMiss) ? 1 : 0;
     cold_sum += m;
   });
   const int64_t cold = cold_sum.load();

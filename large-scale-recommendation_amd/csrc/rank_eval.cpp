@@ -18,7 +18,6 @@
 namespace mfhip {
 namespace {
 
-constexpr uint32_t kMiss = 0xFFFFFFFFu;
 
 // One pair list on the device: the query rows in rk_in[0, n), the candidate column in rk_in[n, 2n).
 // The stream is drained first: an earlier table build may still read the buffer.
@@ -102,7 +101,7 @@ void rank_eval(mf_ctx* ctx, int qside, const int32_t* gq, const int32_t* gc, int
     parallel_for(ng, [&](int64_t b, int64_t e, int) {
       std::vector<int32_t> mine;
       for (int64_t j = b; j < e; ++j)
-        if (qr[j] == kMiss) mine.push_back(gq[j]);
+        if (qr[j] == kRowMiss) mine.push_back(gq[j]);
       if (mine.empty()) return;
       std::lock_guard<std::mutex> lk(mu);
       unknown.insert(unknown.end(), mine.begin(), mine.end());

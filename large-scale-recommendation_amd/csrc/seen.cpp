@@ -23,7 +23,6 @@
 namespace mfhip {
 namespace {
 
-constexpr uint32_t kMiss = 0xFFFFFFFFu;
 constexpr int64_t kMaxKeys = (int64_t{1} << 31) - 1;  // one sort holds fewer keys than this
 
 // Room for rows + 1 offsets and some rows to come: a side that gains rows pads in place (seen_view).
@@ -112,7 +111,7 @@ void seen_put(mf_ctx* ctx, const int32_t* u, const int32_t* i, int64_t n, bool a
   std::atomic<int64_t> dropped{0};
   parallel_for(n, [&](int64_t b, int64_t e, int) {
     int64_t m = 0;
-    for (int64_t j = b; j < e; ++j) m += (ur[j] == kMiss || ir[j] == kMiss) ? 1 : 0;
+    for (int64_t j = b; j < e; ++j) m += (ur[j] == kRowMiss || ir[j] == kRowMiss) ? 1 : 0;
     dropped += m;
   });
   if (ignored) *ignored = dropped.load();
@@ -152,7 +151,7 @@ void seen_remove(mf_ctx* ctx, const int32_t* u, const int32_t* i, int64_t n, int
   int64_t dropped = 0;
   std::vector<uint64_t> key;
   for (int64_t j = 0; j < n; ++j) {
-    if (ur[j] == kMiss || ir[j] == kMiss) {
+    if (ur[j] == kRowMiss || ir[j] == kRowMiss) {
       ++dropped;
     } else if (held && static_cast<int64_t>(ur[j]) < T.rows[kSideU]) {  // (a row gained since holds nothing)
       key.push_back((static_cast<uint64_t>(ur[j]) << 32) | ir[j]);
@@ -244,7 +243,7 @@ SeenView seen_view(mf_ctx* ctx, Shard& s, int qside) {
     MF_HIP(hipStreamSynchronize(s.stream));
     T.iota_n = rows + 1 + std::max<int64_t>(1024, rows / 8);
     T.iota.alloc(static_cast<size_t>(T.iota_n) * 4);
-    launch_seen_iota(s.stream, T.iota.as<int32_t>(), T.iota_n);
+    launch_iota(s.stream, T.iota.as<int32_t>(), T.iota_n);
   }
   v.off = T.off[side].as<int64_t>();
   v.ent = T.ent[side].as<int32_t>();
