@@ -598,7 +598,7 @@ int mf_nnls_solve(int32_t k, const double* A /* k*k symmetric */, const double* 
    row is random until it is solved, and items solved from it first would be pulled towards noise.
    rounds == 0 is an append; rounds < 0 is MF_ERR_INVALID.  *solved_users_out / *solved_items_out (may be
    NULL) are the counts of the last round (0 with rounds == 0).  With the ratings of one new user and
-   rounds = 1 this is fold-in. */
+   rounds = 1 this is fold-in that keeps the user; mf_als_foldin below is the fold-in that keeps nothing. */
 #define MF_ALS_SOLVER_CHOLESKY 0
 #define MF_ALS_SOLVER_CG 1
 #define MF_ALS_SOLVER_NNLS 2
@@ -617,6 +617,51 @@ int mf_als_run_rows(mf_ctx* ctx, int side, const int32_t* ids, int64_t n_ids, co
 int mf_als_update(mf_ctx* ctx, const int32_t* users, const int32_t* items, const double* ratings, int64_t n,
                   const mf_als_solve* how, int32_t rounds, int64_t* solved_users_out /* may be NULL */,
                   int64_t* solved_items_out /* may be NULL */);
+
+/* Stateless fold-in: the vector a row of `side` would get if its ratings were a list the caller hands over --
+   a new visitor's basket, an anonymous session, a cold-start item's first ratings -- solved on the device and
+   given back, while the model takes nothing in.  `side` is the side the queries would belong to: with
+   MF_SIDE_USER the lists name items and the vectors are user vectors, with MF_SIDE_ITEM the lists name users
+   (a new item).  Query j owns entries offsets[j] .. offsets[j + 1] of cand_ids / ratings; offsets has
+   n_queries + 1 entries, starts at 0 and never decreases.  Only the lists are uploaded; the ids are resolved,
+   the kept entries compacted and (mf_recommend_foldin) the exclusions built on the device.
+   Kept entries.  An entry naming an id the counterpart side does not hold is dropped and counts in neither
+   the row's count n_a nor its n+; no row is ever inserted.  used_out[j] (may be NULL) is the kept count.
+   Duplicates are kept, as mf_als_prepare keeps them.
+   The vector.  vecs_out (n_queries x k, row-major, f64; f32 results widened) row j is bit for bit the row
+   mf_als_run_rows(side, ..., how) would produce for a row of `side` whose ratings in the prepared data were
+   exactly the kept entries in list order: the same system, the same order of every sum, the same long-row
+   chunks, the same rules for lambda' (n_a is the kept count), for n+ (counted after rounding to the
+   context's precision), for NaN rows and for the NNLS reason codes.  Conjugate gradients start from x = +0.
+   A query with no kept entry gives the +0 vector and used_out 0.  Results depend neither on the order of the
+   queries nor on how the call batches them.
+   G (implicit).  With ALS data prepared, G is summed over the counterpart's rated-row list as it stands (a
+   prepare with n = 0 is "prepared": its list is empty and G = 0).  With no ALS data prepared -- a serving
+   replica after mf_load_model or mf_set_factors -- G is summed over every counterpart row the model holds, in
+   ascending row order and in the same slices, and the long-row chunk length is the one mf_als_prepare would
+   read now.
+   Nothing changes: factor rows and row numbering, both CSRs and the work lists, the half-sweep counter,
+   mf_als_nonneg_stats (the fold-in launches count into scratch counters of their own), the seen set and a
+   prepared DSGD schedule are untouched.  A context on one device, single-process.
+   mf_recommend_foldin returns what mf_recommend_vectors(cand_side = the other side, the fold-in vectors,
+   MF_METRIC_DOT, ...) returns, bit for bit -- ids, scores, counts, order and tie rules, the output layout --
+   without the vectors leaving the device (unless vecs_out is given).  exclude_rated != 0: each query's
+   distinct kept candidates are its exclusions; 0: there are none.  A query with no kept entry gets count 0,
+   and its slots hold id 0 and score 0.0.
+   Errors, all raised before any device work.  MF_ERR_INVALID: NULL ctx or `how`; NULL offsets; NULL vecs_out
+   (mf_als_foldin), ids_out or counts_out (mf_recommend_foldin) with n_queries > 0; a bad side; n_queries < 0;
+   offsets[0] != 0, decreasing offsets, or 2^31 entries or more in total; NULL cand_ids or ratings with
+   entries; exclude_rated other than 0 or 1; top_n outside 1 .. MF_RECOMMEND_MAX_TOP; and whatever the
+   mf_als_run* call of the same `how` refuses (lambda, reg, alpha, cg_steps, an unknown solver, a rank above
+   256).  MF_ERR_NOT_FITTED before a model exists; MF_ERR_STATE on a rank-mode context or one on several
+   devices.  n_queries == 0 is valid. */
+int mf_als_foldin(mf_ctx* ctx, int side, const int64_t* offsets /* [n_queries + 1] */, const int32_t* cand_ids,
+                  const double* ratings, int64_t n_queries, const mf_als_solve* how,
+                  double* vecs_out /* n_queries x k */, int32_t* used_out /* [n_queries] or NULL */);
+int mf_recommend_foldin(mf_ctx* ctx, int side, const int64_t* offsets, const int32_t* cand_ids,
+                        const double* ratings, int64_t n_queries, const mf_als_solve* how, int32_t top_n,
+                        int32_t exclude_rated, int32_t* ids_out, double* scores_out /* may be NULL */,
+                        int32_t* counts_out, double* vecs_out /* may be NULL */, int32_t* used_out /* may be NULL */);
 
 /* Removal, the mirror image of mf_als_append: ratings leave the CSRs on the device, so that a sliding window,
    a retraction (an un-rated item, a returned purchase, a deleted account, a withdrawn item) needs no

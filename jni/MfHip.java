@@ -109,6 +109,22 @@ public final class MfHip {
   public static native void recommendVectors(long ctx, int candSide, double[] vecs, int numQueries, int topN,
                                              int metric, int[] exclQueryIndex, int[] exclCand,
                                              int[] idsOut, double[] scoresOut, int[] countsOut);
+  // Fold-in (mf_als_foldin / mf_recommend_foldin): vectors for users (side 0; the lists name items) or items
+  // (side 1; the lists name users) the model does not hold and does not take in -- nothing of the context
+  // changes.  Query j owns entries offsets[j] .. offsets[j + 1] of candIds / ratings (offsets: numQueries + 1
+  // entries from 0, not decreasing); ids the model does not hold are dropped; the solve is named as for
+  // alsRunRows.  vecsOut: numQueries * k doubles; usedOut (may be null, one entry per query): the kept entries.
+  // recommendFoldin scores the vectors on the device like recommendVectors with the dot product; with
+  // excludeRated a query's kept ids are never returned to it; a query with no kept entry has count 0;
+  // vecsOut may be null there.
+  public static native void alsFoldin(long ctx, int side, int[] offsets, int[] candIds, double[] ratings,
+                                      double lambda, int reg, int implicit, double alpha, int solver, int cgSteps,
+                                      double[] vecsOut, int[] usedOut);
+  public static native void recommendFoldin(long ctx, int side, int[] offsets, int[] candIds, double[] ratings,
+                                            double lambda, int reg, int implicit, double alpha, int solver,
+                                            int cgSteps, int topN, boolean excludeRated,
+                                            int[] idsOut, double[] scoresOut, int[] countsOut,
+                                            double[] vecsOut, int[] usedOut);
   // RankingMetrics of held-out (query, candidate) pairs against the model's topN lists (mf_rank_eval),
   // taken on the device.  metricsOut (length >= 8) receives queries, hits, precision, recall, MAP, NDCG,
   // MRR, hit rate; exclQuery / exclCand as for recommend

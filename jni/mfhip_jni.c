@@ -850,6 +850,73 @@ JNIEXPORT void JNICALL JFN(recommendVectors)(JNIEnv* env, jclass c, jlong h, jin
   check(env, st);
 }
 
+/* Fold-in: mf_als_foldin (rec == 0) / mf_recommend_foldin.  A Java array index is an int, so the offsets come
+   as ints; the C call takes 64-bit offsets. */
+static void foldin(JNIEnv* env, jlong h, jint side, jintArray off, jintArray cand, jdoubleArray r,
+                   const mf_als_solve* how, int rec, jint top, jboolean excl, jintArray ids, jdoubleArray scores,
+                   jintArray counts, jdoubleArray vecs, jintArray used) {
+  const jlong k = rank_of(env, h);
+  if (k < 0) return;
+  if (require(env, off && len(env, off) >= 1, "offsets must hold numQueries + 1 entries")) return;
+  const jsize n = len(env, off) - 1;
+  if (require(env, (!cand && !r) || (cand && r && len(env, cand) == len(env, r)),
+              "candIds and ratings must both be null or match in length"))
+    return;
+  if (require(env, (vecs || rec) && (!vecs || (jlong)len(env, vecs) >= (jlong)n * k), "vecsOut must hold numQueries * k doubles"))
+    return;
+  if (require(env, !used || len(env, used) >= n, "usedOut must hold one entry per query")) return;
+  if (rec && top_lists_fit(env, n, top, ids, scores, counts)) return;
+  int64_t* off64 = (int64_t*)malloc(sizeof(int64_t) * ((size_t)n + 1));
+  if (require(env, off64 != NULL, "out of memory")) return;
+  Elems eo = {0};
+  if (acquire(env, &eo, off, kInt)) {
+    free(off64);
+    return;
+  }
+  int ok = ((const int32_t*)eo.p)[0] == 0;
+  for (jsize x = 0; x <= n; ++x) {
+    off64[x] = ((const int32_t*)eo.p)[x];
+    if (x > 0 && off64[x] < off64[x - 1]) ok = 0;
+  }
+  release(env, &eo, JNI_ABORT);
+  /* the lists' length against what the C call reads, before any element is touched */
+  if (require(env, ok && off64[n] <= (jlong)len(env, cand), "offsets must start at 0, not decrease and end inside candIds")) {
+    free(off64);
+    return;
+  }
+  Elems e[7];
+  const jarray arr[7] = {cand, r, ids, scores, counts, vecs, used};
+  const int kind[7] = {kInt, kDouble, kInt, kDouble, kInt, kDouble, kInt};
+  if (acquire_all(env, e, arr, kind, 7)) {
+    free(off64);
+    return;
+  }
+  int st = rec ? mf_recommend_foldin(CTX(h), side, off64, (const int32_t*)e[0].p, (const double*)e[1].p, n, how, top,
+                                     excl ? 1 : 0, (int32_t*)e[2].p, (double*)e[3].p, (int32_t*)e[4].p, (double*)e[5].p,
+                                     (int32_t*)e[6].p)
+               : mf_als_foldin(CTX(h), side, off64, (const int32_t*)e[0].p, (const double*)e[1].p, n, how,
+                               (double*)e[5].p, (int32_t*)e[6].p);
+  free(off64);
+  for (int x = 6; x >= 2; --x) release(env, &e[x], st == MF_OK ? 0 : JNI_ABORT);
+  for (int x = 1; x >= 0; --x) release(env, &e[x], JNI_ABORT);
+  check(env, st);
+}
+
+JNIEXPORT void JNICALL JFN(alsFoldin)(JNIEnv* env, jclass c, jlong h, jint side, jintArray off, jintArray cand,
+                                      jdoubleArray r, jdouble lambda, jint reg, jint implicit, jdouble alpha,
+                                      jint solver, jint cgSteps, jdoubleArray vecs, jintArray used) {
+  const mf_als_solve how = als_how(lambda, reg, implicit, alpha, solver, cgSteps);
+  foldin(env, h, side, off, cand, r, &how, 0, 0, 0, NULL, NULL, NULL, vecs, used);
+}
+
+JNIEXPORT void JNICALL JFN(recommendFoldin)(JNIEnv* env, jclass c, jlong h, jint side, jintArray off, jintArray cand,
+                                            jdoubleArray r, jdouble lambda, jint reg, jint implicit, jdouble alpha,
+                                            jint solver, jint cgSteps, jint top, jboolean excl, jintArray ids,
+                                            jdoubleArray scores, jintArray counts, jdoubleArray vecs, jintArray used) {
+  const mf_als_solve how = als_how(lambda, reg, implicit, alpha, solver, cgSteps);
+  foldin(env, h, side, off, cand, r, &how, 1, top, excl, ids, scores, counts, vecs, used);
+}
+
 JNIEXPORT void JNICALL JFN(rankEvalSeen)(JNIEnv* env, jclass c, jlong h, jint side, jintArray gq, jintArray gc, jint top,
                                          jdoubleArray metrics) {
   if (require(env, gq && gc && len(env, gq) == len(env, gc), "gtQuery and gtCand must match in length")) return;

@@ -713,6 +713,53 @@ int mf_als_update(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double*
   });
 }
 
+extern "C++" {
+namespace {
+
+// The checks of the two fold-in calls that read nothing of the context; returns the solve's parameters.
+AlsParams foldin_check(mf_ctx* ctx, int side, const int64_t* off, const int32_t* ids, const double* r, int64_t nq,
+                       const mf_als_solve* how) {
+  MF_REQUIRE(ctx, "null context");
+  MF_REQUIRE(side == MF_SIDE_USER || side == MF_SIDE_ITEM, "bad side");
+  MF_REQUIRE(nq >= 0, "negative n_queries");
+  const AlsParams P = als_params_of(how);
+  if (P.implicit) als_check_alpha(P.alpha);
+  als_check_run(P);
+  MF_REQUIRE(off, "null offsets");
+  MF_REQUIRE(off[0] == 0, "offsets[0] must be 0");
+  for (int64_t j = 0; j < nq; ++j) MF_REQUIRE(off[j + 1] >= off[j], "offsets must not decrease");
+  MF_REQUIRE(off[nq] < (int64_t{1} << 31), "the lists hold 2^31 entries or more: total entries must stay below 2^31");
+  MF_REQUIRE(off[nq] == 0 || (ids && r), "null cand_ids or ratings with entries in the lists");
+  return P;
+}
+
+}  // namespace
+}  // extern "C++"
+
+int mf_als_foldin(mf_ctx* ctx, int side, const int64_t* offsets, const int32_t* cand_ids, const double* ratings,
+                  int64_t n_queries, const mf_als_solve* how, double* vecs_out, int32_t* used_out) {
+  return guarded([&] {
+    const AlsParams P = foldin_check(ctx, side, offsets, cand_ids, ratings, n_queries, how);
+    MF_REQUIRE(n_queries == 0 || vecs_out, "null vecs_out");
+    als_foldin(ctx, side, offsets, cand_ids, ratings, n_queries, P, nullptr, vecs_out, used_out);
+  });
+}
+
+int mf_recommend_foldin(mf_ctx* ctx, int side, const int64_t* offsets, const int32_t* cand_ids, const double* ratings,
+                        int64_t n_queries, const mf_als_solve* how, int32_t top_n, int32_t exclude_rated,
+                        int32_t* ids_out, double* scores_out, int32_t* counts_out, double* vecs_out,
+                        int32_t* used_out) {
+  return guarded([&] {
+    const AlsParams P = foldin_check(ctx, side, offsets, cand_ids, ratings, n_queries, how);
+    MF_REQUIRE(exclude_rated == 0 || exclude_rated == 1, "exclude_rated must be 0 or 1");
+    MF_REQUIRE(top_n >= 1 && top_n <= MF_RECOMMEND_MAX_TOP,
+               "top_n must be in [1, " + std::to_string(MF_RECOMMEND_MAX_TOP) + "]");
+    MF_REQUIRE(n_queries == 0 || (ids_out && counts_out), "null ids_out or counts_out");
+    const FoldinRecommend rec{top_n, exclude_rated != 0, ids_out, scores_out, counts_out};
+    als_foldin(ctx, side, offsets, cand_ids, ratings, n_queries, P, &rec, vecs_out, used_out);
+  });
+}
+
 int mf_als_remove(mf_ctx* ctx, const int32_t* u, const int32_t* i, int64_t n, uint8_t* found_out, int64_t* removed_out) {
   return guarded([&] {
     MF_REQUIRE(ctx, "null context");

@@ -5,6 +5,7 @@
 #include <atomic>
 #include <cmath>
 #include <cstring>
+#include <functional>
 #include <numeric>
 #include <random>
 #include <string>
@@ -52,6 +53,24 @@ void als_check_run(const AlsParams& P) {
 }
 
 namespace {
+
+// The chunk, batch, Gram-slice and slab values mf_als_prepare reads now (the constants above, the MFHIP_TEST
+// knobs, the device's CU count): what a prepare keeps in the context, and what a fold-in on a context without
+// prepared data cuts its work by.
+struct AlsCuts {
+  int64_t chunk, batch, gram_slice, slabs;
+};
+AlsCuts als_cuts_now(const mf_ctx* ctx, const Shard& s) {
+  AlsCuts c{kAlsChunk, kAlsBatch, kAlsGramSlice, 0};
+  if (const std::string v = test_knob("als_chunk"); !v.empty()) c.chunk = std::max<int64_t>(1, std::atoll(v.c_str()));
+  if (const std::string v = test_knob("als_batch"); !v.empty()) c.batch = std::max<int64_t>(1, std::atoll(v.c_str()));
+  if (const std::string v = test_knob("als_gram_slice"); !v.empty())
+    c.gram_slice = std::min<int64_t>(std::max<int64_t>(1, std::atoll(v.c_str())), 1 << 30);
+  c.slabs = als_wide_slabs(ctx->P.num_factors, ctx->f64, static_cast<int>(device_cu_count(s.device)));
+  if (const std::string v = test_knob("als_slabs"); !v.empty())
+    c.slabs = std::min<int64_t>(c.slabs, std::max<int64_t>(1, std::atoll(v.c_str())));
+  return c;
+}
 
 // Cuts rows into work items, long-row splits and launches: what mf_als_prepare and mf_als_append do for
 // every rated row of a side and mf_als_run_rows for the rows of one call.  Rows are added in ascending order.
@@ -213,21 +232,15 @@ void als_prepare(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* 
     ctx->have_model = true;
     ++ctx->layout_gen;
   }
-  const int k = ctx->P.num_factors;
   std::vector<uint32_t> ur, ir;
   lookup_rows(ctx->U, u, n, ur);
   lookup_rows(ctx->I, i, n, ir);
   als_insert_rows(ctx, s, u, i, n, ur, ir);
-  ctx->als_chunk = kAlsChunk;
-  ctx->als_batch = kAlsBatch;
-  if (const std::string v = test_knob("als_chunk"); !v.empty()) ctx->als_chunk = std::max<int64_t>(1, std::atoll(v.c_str()));
-  if (const std::string v = test_knob("als_batch"); !v.empty()) ctx->als_batch = std::max<int64_t>(1, std::atoll(v.c_str()));
-  ctx->als_gram_slice = kAlsGramSlice;
-  if (const std::string v = test_knob("als_gram_slice"); !v.empty())
-    ctx->als_gram_slice = std::min<int64_t>(std::max<int64_t>(1, std::atoll(v.c_str())), 1 << 30);
-  ctx->als_slabs = als_wide_slabs(k, ctx->f64, static_cast<int>(device_cu_count(s.device)));
-  if (const std::string v = test_knob("als_slabs"); !v.empty())
-    ctx->als_slabs = std::min<int64_t>(ctx->als_slabs, std::max<int64_t>(1, std::atoll(v.c_str())));
+  const AlsCuts cuts = als_cuts_now(ctx, s);
+  ctx->als_chunk = cuts.chunk;
+  ctx->als_batch = cuts.batch;
+  ctx->als_gram_slice = cuts.gram_slice;
+  ctx->als_slabs = cuts.slabs;
   if (ctx->f64) {
     als_build_side<double>(ctx, s, kSideU, ur, ir, r, n, ctx->U.rows());
     als_build_side<double>(ctx, s, MF_SIDE_ITEM, ir, ur, r, n, ctx->I.rows());
@@ -279,16 +292,21 @@ void write_from_f64(const mf_ctx* ctx, DevBuf& d, const double* src, size_t n) {
   }
 }
 
-// G of `side`'s rated rows into s.als_gram, on the shard's stream: two launches.
-void als_gram_launch(mf_ctx* ctx, Shard& s, int side) {
+// G of rows rated[0 .. m) of `side` into s.als_gram, in slices of `slice` rows, on the shard's stream: two
+// launches.
+void als_gram_launch(mf_ctx* ctx, Shard& s, int side, const int32_t* rated, int64_t m64, int64_t slice64) {
   const int k = ctx->P.num_factors;
-  const int m = static_cast<int>(ctx->als[side].rated), slice = static_cast<int>(ctx->als_gram_slice);
+  const int m = static_cast<int>(m64), slice = static_cast<int>(slice64);
   const size_t ge = als_gram_elems(k) * ctx->es;
   s.als_gram_part.alloc(std::max<size_t>(static_cast<size_t>(als_gram_slices(m, slice)) * ge, 16));
   s.als_gram.alloc(ge);
-  launch_als_gram({s.stream, s.als_rated[side].as<int32_t>(), m, slice, side == kSideU ? s.uf.get() : s.itf.get(), k,
-                   ctx->f64, s.als_gram_part.get(), s.als_gram.get()});
+  launch_als_gram({s.stream, rated, m, slice, side == kSideU ? s.uf.get() : s.itf.get(), k, ctx->f64,
+                   s.als_gram_part.get(), s.als_gram.get()});
   MF_HIP(hipGetLastError());
+}
+// ... of `side`'s rated rows as the prepared data lists them
+void als_gram_launch(mf_ctx* ctx, Shard& s, int side) {
+  als_gram_launch(ctx, s, side, s.als_rated[side].as<int32_t>(), ctx->als[side].rated, ctx->als_gram_slice);
 }
 
 // The chunk items of `side`'s long rows, per batch, with the index of each one's row among the batch's splits.
@@ -331,6 +349,71 @@ mf_ctx::AlsBatch als_row_span(const mf_ctx::AlsSide& A, int64_t row) {
   return {lo - A.items.begin(), hi - lo, sp - A.splits.begin(), sp != A.splits.end() && sp->row == row ? 1 : 0};
 }
 
+// The device copies of a call's work lists: the side's own, or those of one mf_als_run_rows / fold-in batch.
+struct AlsWork {
+  const AlsItem* items;
+  const AlsSplit* splits;
+  const AlsCgWork* work;
+};
+
+// What the launches of one call share beyond the CSR, the slabs Q and X and the NNLS counters (the caller's):
+// the regularisation and the solver's switches, and the scratch sized by the call's work W -- the long rows'
+// partial slots, the conjugate-gradient state of a launch's long rows or (k > 128) the normal-matrix slabs.
+void als_launch_setup(mf_ctx* ctx, Shard& s, AlsLaunch& L, const AlsParams& P, const mf_ctx::AlsSide& W, int64_t slabs) {
+  const int k = ctx->P.num_factors;
+  s.als_part.alloc(std::max<size_t>(static_cast<size_t>(W.max_slots) * als_partial_elems(k) * ctx->es, 16));
+  L.k = k;
+  L.lambda = P.lambda;
+  L.weighted = P.reg == MF_ALS_REG_WEIGHTED;
+  L.f64 = ctx->f64;
+  L.partial = s.als_part.get();
+  L.alpha = P.alpha;
+  if (P.cg_steps > 0) {
+    s.als_cg_state.alloc(std::max<size_t>(static_cast<size_t>(std::max<int64_t>(W.cg_max_splits, 1)) *
+                                              als_cg_state_elems(k) * ctx->es, 16));
+    L.steps = P.cg_steps;
+    L.stage = test_knob("als_cg_stage") != "0";
+    L.state = s.als_cg_state.get();
+  } else {
+    // k > 128: one normal matrix in global memory per workgroup of the grid, however many rows there are
+    L.slabs = static_cast<int>(std::min<int64_t>(slabs, static_cast<int64_t>(W.items.size())));
+    if (L.slabs > 0) s.als_slab.alloc(static_cast<size_t>(L.slabs) * als_gram_elems(k) * ctx->es);
+    L.slab = s.als_slab.get();
+    L.nnls = P.nnls;
+  }
+}
+
+void als_launch_one(AlsLaunch& L, bool cg, const AlsWork& D, const mf_ctx::AlsBatch& b) {
+  L.items = D.items + b.item0;
+  L.n_items = static_cast<int>(b.items);
+  L.splits = D.splits + b.split0;
+  L.n_splits = static_cast<int>(b.splits);
+  cg ? launch_als_cg(L) : launch_als(L);
+  MF_HIP(hipGetLastError());
+}
+
+// The launch loop of a half-sweep, of mf_als_run_rows and of a fold-in batch: W's batches in order, after G
+// (gram != null: the implicit system, G made by *gram before the first launch; a caller that made G itself
+// sets L.gram and passes null).
+void als_launch_batches(mf_ctx* ctx, Shard& s, AlsLaunch& L, const AlsParams& P, const mf_ctx::AlsSide& W,
+                        const AlsWork& D, const std::function<void()>* gram) {
+  const bool cg = P.cg_steps > 0;
+  LaunchTimer t(s, ctx->profiling);
+  if (gram && !W.batches.empty()) {
+    (*gram)();
+    ctx->stats.kernel_launches += 2;
+  }
+  for (size_t b = 0; b < W.batches.size(); ++b) {
+    const mf_ctx::AlsBatch& B = W.batches[b];
+    if (cg) {
+      L.work = D.work + W.cg_work0[b];
+      L.n_work = static_cast<int>(W.cg_work0[b + 1] - W.cg_work0[b]);
+    }
+    als_launch_one(L, cg, D, B);
+    ctx->stats.kernel_launches += 1 + (B.splits > 0 ? (cg ? 2 * (P.cg_steps + 1) : 1) : 0);
+  }
+}
+
 // One side solved from the other (P.implicit: after the counterpart's Gram matrix), by Cholesky, with
 // P.nnls by the non-negative solve in its place or, with P.cg_steps > 0, by conjugate gradients on the
 // same work lists, batches and partial slots.
@@ -363,47 +446,20 @@ bool als_half(mf_ctx* ctx, int side, const AlsParams& P, int64_t only_row = -1,
     als_cg_lists(ctx, s, side);
   }
   const mf_ctx::AlsSide& W = rows ? sub : A;  // the work of this call
-  const AlsItem* d_items = rows ? s.als_sub_items.as<AlsItem>() : s.als_items[side].as<AlsItem>();
-  const AlsSplit* d_splits = rows ? s.als_sub_splits.as<AlsSplit>() : s.als_splits[side].as<AlsSplit>();
-  const AlsCgWork* d_work = rows ? s.als_sub_work.as<AlsCgWork>() : s.als_cg_work[side].as<AlsCgWork>();
-  s.als_part.alloc(std::max<size_t>(static_cast<size_t>(W.max_slots) * als_partial_elems(k) * ctx->es, 16));
+  const AlsWork D{rows ? s.als_sub_items.as<AlsItem>() : s.als_items[side].as<AlsItem>(),
+                  rows ? s.als_sub_splits.as<AlsSplit>() : s.als_splits[side].as<AlsSplit>(),
+                  rows ? s.als_sub_work.as<AlsCgWork>() : s.als_cg_work[side].as<AlsCgWork>()};
   AlsLaunch L;
   L.st = s.stream;
   L.cols = s.als_cols[side].as<int32_t>();
   L.vals = s.als_vals[side].get();
   L.Q = side == kSideU ? s.itf.get() : s.uf.get();
   L.X = side == kSideU ? s.uf.get() : s.itf.get();
-  L.k = k;
-  L.lambda = P.lambda;
-  L.weighted = P.reg == MF_ALS_REG_WEIGHTED;
-  L.f64 = ctx->f64;
-  L.partial = s.als_part.get();
-  L.alpha = P.alpha;
-  if (cg) {
-    s.als_cg_state.alloc(std::max<size_t>(static_cast<size_t>(std::max<int64_t>(W.cg_max_splits, 1)) *
-                                              als_cg_state_elems(k) * ctx->es, 16));
-    L.steps = P.cg_steps;
-    L.stage = test_knob("als_cg_stage") != "0";
-    L.state = s.als_cg_state.get();
-  } else {
-    // k > 128: one normal matrix in global memory per workgroup of the grid, however many rows there are
-    L.slabs = static_cast<int>(std::min<int64_t>(ctx->als_slabs, static_cast<int64_t>(W.items.size())));
-    if (L.slabs > 0) s.als_slab.alloc(static_cast<size_t>(L.slabs) * als_gram_elems(k) * ctx->es);
-    L.slab = s.als_slab.get();
-    L.nnls = P.nnls;
-    L.nnls_stats = s.als_nnls_stats.get();
-  }
-  auto gram = [&] {
+  L.nnls_stats = s.als_nnls_stats.get();
+  als_launch_setup(ctx, s, L, P, W, ctx->als_slabs);
+  const std::function<void()> gram = [&] {
     als_gram_launch(ctx, s, other);
     L.gram = s.als_gram.get();
-  };
-  auto launch = [&](const mf_ctx::AlsBatch& b) {
-    L.items = d_items + b.item0;
-    L.n_items = static_cast<int>(b.items);
-    L.splits = d_splits + b.split0;
-    L.n_splits = static_cast<int>(b.splits);
-    cg ? launch_als_cg(L) : launch_als(L);
-    MF_HIP(hipGetLastError());
   };
   if (only_row >= 0) {
     const mf_ctx::AlsBatch row = als_row_span(A, only_row);
@@ -420,23 +476,10 @@ bool als_half(mf_ctx* ctx, int side, const AlsParams& P, int64_t only_row = -1,
     L.dump = s.als_dump.get();
     L.hook_v = s.als_cg_v.get();
     if (P.implicit) gram();
-    launch(row);
+    als_launch_one(L, cg, D, row);
     return true;
   }
-  LaunchTimer t(s, ctx->profiling);
-  if (P.implicit && !W.batches.empty()) {
-    gram();
-    ctx->stats.kernel_launches += 2;
-  }
-  for (size_t b = 0; b < W.batches.size(); ++b) {
-    const mf_ctx::AlsBatch& B = W.batches[b];
-    if (cg) {
-      L.work = d_work + W.cg_work0[b];
-      L.n_work = static_cast<int>(W.cg_work0[b + 1] - W.cg_work0[b]);
-    }
-    launch(B);
-    ctx->stats.kernel_launches += 1 + (B.splits > 0 ? (cg ? 2 * (P.cg_steps + 1) : 1) : 0);
-  }
+  als_launch_batches(ctx, s, L, P, W, D, P.implicit ? &gram : nullptr);
   return true;
 }
 
@@ -810,6 +853,167 @@ int64_t als_retract(mf_ctx* ctx, const int32_t* u, const int32_t* i, int64_t n, 
   if (solved_users) *solved_users = su;
   if (solved_items) *solved_items = si;
   return gone;
+}
+
+// ---------------------------------------------------------------------------------------
+// Fold-in (mf_als_foldin / mf_recommend_foldin): rows of `side` solved from lists the callers hand over, as
+// mf_als_run_rows would solve rows that held exactly those ratings, and nothing of the context changes.  Per
+// batch of queries the lists are uploaded as they are; the device resolves the ids over the counterpart's id
+// mirror, compacts the kept entries stably into a transient CSR (kernels_foldin.hip) and hands back two int32
+// per query; the host cuts those with AlsCutter, and the launch loop of the half-sweeps runs with cols / vals
+// = the transient CSR, X = a zeroed scratch slab and item.row = the query's position in the batch.  The fused
+// call turns the kept entries into the exclusion CSR on the device and scores the slab where it lies.
+constexpr int64_t kFoldinBatch = 8192;           // queries per batch (MFHIP_TEST foldin_batch=B)
+constexpr int64_t kFoldinEntries = int64_t{1} << 22;  // ... and entries, unless one list alone is longer
+
+void als_foldin(mf_ctx* ctx, int side, const int64_t* off, const int32_t* ids, const double* r, int64_t nq,
+                const AlsParams& P, const FoldinRecommend* rec, double* vecs_out, int32_t* used_out) {
+  als_check(ctx);
+  if (!ctx->have_model)
+    fail(MF_ERR_NOT_FITTED, "The MatrixFactorization model has not been fitted to data. "
+                            "Prior to folding in, it has to be trained on data or loaded.");
+  require_healthy(ctx);
+  if (nq == 0) return;
+  sync_all(ctx);
+  Shard& s = ctx->shards[0];
+  DeviceGuard g(s.device);
+  FoldinScratch& sc = s.fold;
+  const int other = side == kSideU ? MF_SIDE_ITEM : kSideU;
+  const int k = ctx->P.num_factors;
+  const size_t kk = static_cast<size_t>(k), es = ctx->es;
+  const size_t N = rec ? static_cast<size_t>(rec->top_n) : 0;
+  const AlsCuts cuts = ctx->als_prepared
+                           ? AlsCuts{ctx->als_chunk, ctx->als_batch, ctx->als_gram_slice, ctx->als_slabs}
+                           : als_cuts_now(ctx, s);
+  int64_t B = kFoldinBatch;
+  if (const std::string v = test_knob("foldin_batch"); !v.empty()) B = std::max<int64_t>(1, std::atoll(v.c_str()));
+  B = std::min(B, nq);
+
+  DevIndex& mirror = s.didx[other];
+  sync_dev_index(s, side_of(ctx, other).index, mirror);
+  sc.stats.alloc(sizeof(struct mf_als_nonneg_stats));  // counters of the fold-in launches' own, never read
+  MF_HIP(hipMemsetAsync(sc.stats.get(), 0, sizeof(struct mf_als_nonneg_stats), s.stream));
+  // G once per call: the counterpart's factors do not change under it.  With prepared data over the rated-row
+  // list as it stands (a prepare with n = 0: no row, G = 0), without over every row the counterpart holds.
+  const void* gram = nullptr;
+  if (P.implicit) {
+    if (ctx->als_prepared) {
+      als_gram_launch(ctx, s, other);
+    } else {
+      const int64_t C = side_of(ctx, other).rows();
+      sc.iota.alloc(std::max<size_t>(static_cast<size_t>(C) * 4, 16));
+      launch_iota(s.stream, sc.iota.as<int32_t>(), C);
+      als_gram_launch(ctx, s, other, sc.iota.as<int32_t>(), C, cuts.gram_slice);
+    }
+    ctx->stats.kernel_launches += 2;
+    gram = s.als_gram.get();
+    MF_HIP(hipStreamSynchronize(s.stream));  // the batches below grow scratch only on a drained stream
+  }
+
+  // MFHIP_TIMING=1: the phases of every batch on stderr, the stream drained after each (a diagnostic run)
+  PhaseClock clk;
+  auto lap = [&](const char* what) {
+    if (!clk.on) return;
+    MF_HIP(hipStreamSynchronize(s.stream));
+    clk.lap(what);
+  };
+  for (int64_t q0 = 0, q1 = 0; q0 < nq; q0 = q1) {
+    for (q1 = q0 + 1; q1 < nq && q1 - q0 < B && off[q1 + 1] - off[q0] <= kFoldinEntries;) ++q1;
+    const int64_t nb = q1 - q0, e0 = off[q0], n = off[q1] - e0;
+    const bool keys = rec && rec->exclude_rated && n > 0;
+    // the stream is drained here (sync_all, or the previous batch's read-back): scratch may grow
+    const size_t b_r = static_cast<size_t>(n) * 8, b_off = static_cast<size_t>(nb + 1) * 8, b_id = static_cast<size_t>(n) * 4;
+    sc.pin.alloc(b_r + b_off + b_id);
+    sc.in.alloc(b_r + b_off + 2 * b_id);
+    sc.back.alloc(static_cast<size_t>(nb) * 8);
+    sc.cnt.alloc(static_cast<size_t>(nb) * 8);
+    sc.cols.alloc(std::max<size_t>(b_id, 16));
+    sc.vals.alloc(std::max<size_t>(static_cast<size_t>(n) * es, 16));
+    sc.x.alloc(std::max<size_t>(static_cast<size_t>(nb) * kk * es, 16));
+    if (keys) rank_keys_reserve(s.rank_sc, n);
+    if (rec) {
+      s.rec_eoff.alloc(b_off);
+      s.rec_erows.alloc(std::max<size_t>(b_id, 16));
+    }
+    // 1. the lists through the pinned stage: ratings, batch-local offsets, ids
+    char* const pin = sc.pin.as<char>();
+    if (n) std::memcpy(pin, r + e0, b_r);
+    int64_t* const poff = reinterpret_cast<int64_t*>(pin + b_r);
+    for (int64_t j = 0; j <= nb; ++j) poff[j] = off[q0 + j] - e0;
+    if (n) std::memcpy(pin + b_r + b_off, ids + e0, b_id);
+    char* const din = sc.in.as<char>();
+    MF_HIP(hipMemcpyAsync(din, pin, b_r + b_off + b_id, hipMemcpyHostToDevice, s.stream));
+    lap("foldin upload");
+    // 2. + 3. resolve and compact on the device; 4. two int32 per query come back
+    launch_foldin_compact({s.stream, reinterpret_cast<const int64_t*>(din + b_r), nb, n,
+                           reinterpret_cast<uint32_t*>(din + b_r + b_off), reinterpret_cast<const double*>(din),
+                           mirror.cap ? mirror.slots.get() : nullptr, mirror.cap - 1, ctx->f64, sc.cols.as<int32_t>(),
+                           sc.vals.get(), sc.cnt.as<int32_t>(), keys ? s.rank_sc.key.as<uint64_t>() : nullptr},
+                          sc);
+    const int32_t* const cnt = sc.back.as<int32_t>();
+    MF_HIP(hipMemcpyAsync(sc.back.as<char>(), sc.cnt.get(), static_cast<size_t>(nb) * 8, hipMemcpyDeviceToHost, s.stream));
+    MF_HIP(hipStreamSynchronize(s.stream));
+    mf_ctx::AlsSide W;
+    AlsCutter cut{W.items, W.splits, W.batches, W.max_slots, cuts.chunk, cuts.batch};
+    int64_t nk = 0;
+    for (int64_t j = 0; j < nb; ++j) {
+      const int64_t c = cnt[2 * j];
+      if (c > 0) cut.add(j, nk, c, cnt[2 * j + 1]);
+      nk += c;
+    }
+    cut.close();
+    lap("foldin table");
+    // 5. the half-sweeps' launches over the transient CSR into the zeroed slab
+    MF_HIP(hipMemsetAsync(sc.x.get(), 0, std::max<size_t>(static_cast<size_t>(nb) * kk * es, 16), s.stream));
+    if (!W.batches.empty()) {
+      als_upload(s.als_sub_items, W.items.data(), W.items.size() * sizeof(AlsItem));
+      als_upload(s.als_sub_splits, W.splits.data(), W.splits.size() * sizeof(AlsSplit));
+      if (P.cg_steps > 0) {
+        als_cg_work(W.items, W.splits, W.batches, W.cg_work, W.cg_work0, W.cg_max_splits);
+        als_upload(s.als_sub_work, W.cg_work.data(), W.cg_work.size() * sizeof(AlsCgWork));
+      }
+      AlsLaunch L;
+      L.st = s.stream;
+      L.cols = sc.cols.as<int32_t>();
+      L.vals = sc.vals.get();
+      L.Q = side == kSideU ? s.itf.get() : s.uf.get();
+      L.X = sc.x.get();
+      L.nnls_stats = sc.stats.get();
+      L.gram = gram;
+      als_launch_setup(ctx, s, L, P, W, cuts.slabs);
+      als_launch_batches(ctx, s, L, P, W,
+                         {s.als_sub_items.as<AlsItem>(), s.als_sub_splits.as<AlsSplit>(), s.als_sub_work.as<AlsCgWork>()},
+                         nullptr);
+    }
+    lap("foldin solve");
+    // 6. the fused call: the kept entries' keys -> the exclusion CSR, the slab scored where it lies
+    if (rec) {
+      if (keys && nk > 0) {
+        rank_keys_sort(s.stream, s.rank_sc, nk, nb);
+        rank_keys_csr(s.stream, s.rank_sc, nk, nb, false, s.rec_eoff.as<int64_t>(), s.rec_erows.as<int32_t>());
+      } else {
+        MF_HIP(hipMemsetAsync(s.rec_eoff.get(), 0, b_off, s.stream));
+      }
+      int32_t* const io = rec->ids_out + static_cast<size_t>(q0) * N;
+      double* const so = rec->scores_out ? rec->scores_out + static_cast<size_t>(q0) * N : nullptr;
+      recommend_resident(ctx, s, sc.x.get(), nb, other, rec->top_n, s.rec_eoff.as<int64_t>(), s.rec_erows.as<int32_t>(),
+                         io, so, rec->counts_out + q0);
+      for (int64_t j = 0; j < nb; ++j) {  // a query with no kept entry has no list
+        if (cnt[2 * j] > 0) continue;
+        rec->counts_out[q0 + j] = 0;
+        std::fill(io + static_cast<size_t>(j) * N, io + static_cast<size_t>(j + 1) * N, 0);
+        if (so) std::fill(so + static_cast<size_t>(j) * N, so + static_cast<size_t>(j + 1) * N, 0.0);
+      }
+    }
+    MF_HIP(hipStreamSynchronize(s.stream));
+    if (rec) lap("foldin select");
+    if (vecs_out) {
+      const std::vector<double> h = read_as_f64(ctx, sc.x, static_cast<size_t>(nb) * kk);
+      std::memcpy(vecs_out + static_cast<size_t>(q0) * kk, h.data(), h.size() * 8);
+    }
+    if (used_out)
+      for (int64_t j = 0; j < nb; ++j) used_out[q0 + j] = cnt[2 * j];
+  }
 }
 
 // The resident CSR of a side copied back (mf_debug_als_csr): the offsets and entries from the device, the

@@ -216,9 +216,19 @@ class PinnedBuf {
   size_t bytes_ = 0;
 };
 
+// Scratch of mf_als_foldin / mf_recommend_foldin (als.cpp, kernels_foldin.hip), all of it transient and
+// bounded by the batch.  pin / in: one batch of lists as staged and uploaded (ratings, batch-local offsets,
+// ids -- rows after the lookup); flag / wp / miss / tmp: the compaction's; cols / vals: the transient CSR;
+// cnt / back: (kept, n+) per query on the device and as read back; x: the batch's solved vectors; iota: every
+// counterpart row (G without prepared data); stats: NNLS counters of the fold-in launches' own.
+struct FoldinScratch {
+  PinnedBuf pin, back;
+  DevBuf in, flag, wp, miss, tmp, cols, vals, cnt, x, iota, stats;
+};
+
 // Runtime switches.  The library reads five environment variables:
 //   MFHIP_THREADS / OMP_NUM_THREADS  host workers (below);
-//   MFHIP_TIMING                     prepare's and mf_rank_eval's phase timings on stderr;
+//   MFHIP_TIMING                     prepare's, mf_rank_eval's and the fold-in calls' phase timings on stderr;
 //   MFHIP_DEBUG_PLAN                 planner diagnostics and the sweeps' error words on stderr;
 //   MFHIP_DEVICE_SHARERS             rank mode: ranks sharing one device (the one-GPU ring rehearsal);
 //   MFHIP_TEST                       "key=value,..." overrides the test suite uses to force the

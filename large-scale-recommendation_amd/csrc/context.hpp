@@ -163,6 +163,8 @@ struct Shard {
   AlsRemoveScratch als_rem;
   // ... mf_als_run_rows: the item, split and chunk lists of one call
   DevBuf als_sub_items, als_sub_splits, als_sub_work;
+  // ... mf_als_foldin / mf_recommend_foldin (which also use als_sub_*, the rec_* buffers and rank_sc)
+  FoldinScratch fold;
   // profiling
   std::vector<hipEvent_t> ev;
   size_t ev_used = 0;
@@ -368,6 +370,9 @@ void reset_item_loc(mf_ctx* ctx);
 void consolidate(mf_ctx* ctx, Shard& dst);
 
 // online.cpp
+// Brings the device mirror d up to the host table ix (the whole table after a rehash, else the slots written
+// since the last sync); under the caller's DeviceGuard.
+void sync_dev_index(Shard& s, const IdIndex& ix, DevIndex& d);
 void online_update(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n, int flavour,
                    int num_partitions, int64_t* tu, int64_t* ti, double* uout = nullptr, double* iout = nullptr);
 // mf_online_update_sampled: the batch with `negatives` drawn updates (neg_sample.hpp) behind every event
@@ -398,6 +403,13 @@ void similar(mf_ctx* ctx, int side, const int32_t* queries, int64_t nq, int32_t 
 void recommend_vectors(mf_ctx* ctx, int cside, const double* vecs, int64_t nq, int32_t top_n, int metric,
                        const int64_t* eqi, const int32_t* ec, int64_t ne, int32_t* ids_out, double* scores_out,
                        int32_t* counts_out);
+// The score-and-select core for queries that are rows 0 .. nu-1 of a resident slab Q (nu x k, the context's
+// precision) against every row of side cside by MF_METRIC_DOT, with the exclusion CSR on the device (d_eoff
+// [nu + 1], d_erows: sorted distinct candidate rows per query); outputs on the host as mf_recommend's.  Queued
+// behind whatever s.stream holds (the kernels that write Q); under the caller's DeviceGuard.
+void recommend_resident(mf_ctx* ctx, Shard& s, const void* Q, int64_t nu, int cside, int32_t top_n,
+                        const int64_t* d_eoff, const int32_t* d_erows, int32_t* ids_out, double* scores_out,
+                        int32_t* counts_out);
 void get_factors(mf_ctx* ctx, int side, int32_t* ids, double* vecs, int64_t cap, int64_t* written);
 void lookup_factors(mf_ctx* ctx, int side, const int32_t* ids, int64_t n, double* vecs_out, uint8_t* found);
 
@@ -485,6 +497,17 @@ void als_append(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r
 int64_t als_run_rows(mf_ctx* ctx, int side, const int32_t* ids, int64_t n_ids, const AlsParams& P);
 void als_update(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n, const AlsParams& P,
                 int32_t rounds, int64_t* solved_users, int64_t* solved_items);
+// mf_als_foldin / mf_recommend_foldin (rec != null: the fused call; vecs_out may then be null).  The argument
+// checks that read nothing of the context are abi.cpp's.
+struct FoldinRecommend {
+  int32_t top_n;
+  bool exclude_rated;
+  int32_t* ids_out;
+  double* scores_out;  // may be null
+  int32_t* counts_out;
+};
+void als_foldin(mf_ctx* ctx, int side, const int64_t* off, const int32_t* ids, const double* r, int64_t nq,
+                const AlsParams& P, const FoldinRecommend* rec, double* vecs_out, int32_t* used_out);
 // mf_als_remove / mf_als_remove_rows / mf_als_retract (which checks everything mf_als_run_rows would refuse
 // before it removes); each returns the ratings removed.  found: n bytes or null.
 int64_t als_remove(mf_ctx* ctx, const int32_t* u, const int32_t* i, int64_t n, uint8_t* found);

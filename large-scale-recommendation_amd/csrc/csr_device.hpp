@@ -1,5 +1,5 @@
 // csr_device.hpp -- the tile walk of the table kernels (k_als_move, k_seen_csr_keys, k_seen_move,
-// k_remove_scan): a kernel that must touch every entry of a packed CSR and know each entry's row.
+// k_remove_scan, k_fold_compact): a kernel that must touch every entry of a packed CSR and know each entry's row.
 //
 // Such a kernel walks the ENTRIES, not the rows.  A workgroup of kCsrThreads threads takes kCsrTile
 // consecutive entries [t0, t1), whatever rows they belong to.  Threads 0 and 1 find the rows of the tile's

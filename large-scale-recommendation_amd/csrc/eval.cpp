@@ -148,18 +148,18 @@ void exclusion_csr(std::vector<uint64_t>& pairs, int64_t nu, std::vector<int64_t
   for (int64_t u = 0; u < nu; ++u) eoff[u + 1] += eoff[u];
 }
 
-// The core.  nu queries against every row of side cside, minus each query's exclusions (eoff / erows, or
-// with seen_qside >= 0 the resident seen set of that query side): ids [nu][top_n], scores (may be null),
-// counts [nu] on the host.  The queries are either rows qrows[0 .. nu) of a resident factor slab Q of q_rows
-// rows (which may be the candidate slab itself: mf_similar), or, with Q null, the caller's nu x k f64 vectors
-// hvecs (qrows = 0 .. nu-1): those are converted as upload_rows converts factor rows and staged one batch
-// ahead, so the conversion of batch b + 1 runs on the host while the device scores batch b.
-void recommend_core(mf_ctx* ctx, Shard& s, const void* Q, int64_t q_rows, const double* hvecs,
-                    const std::vector<int32_t>& qrows, int cside, int32_t top_n, int metric,
-                    const std::vector<int64_t>& eoff, const std::vector<int32_t>& erows, int seen_qside, int32_t* uid,
-                    double* usc, int32_t* ucnt) {
+// The core.  nu queries against every row of side cside, minus each query's exclusions (the CSR d_eoff [nu + 1]
+// / d_erows on the device, or with seen_qside >= 0 the resident seen set of that query side): ids [nu][top_n],
+// scores (may be null), counts [nu] on the host.  The queries are either the rows s.rec_q[0 .. nu) of a
+// resident factor slab Q of q_rows rows (which may be the candidate slab itself: mf_similar), or, with Q null,
+// the caller's nu x k f64 vectors hvecs (s.rec_q = 0 .. nu-1): those are converted as upload_rows converts
+// factor rows and staged one batch ahead, so the conversion of batch b + 1 runs on the host while the device
+// scores batch b.
+void recommend_scored(mf_ctx* ctx, Shard& s, const void* Q, int64_t q_rows, const double* hvecs, int64_t nu, int cside,
+                      int32_t top_n, int metric, const int64_t* d_eoff, const int32_t* d_erows, int seen_qside,
+                      int32_t* uid, double* usc, int32_t* ucnt) {
   const SideLayout& CS = side_of(ctx, cside);
-  const int64_t C = CS.rows(), nu = static_cast<int64_t>(qrows.size());
+  const int64_t C = CS.rows();
   const int k = ctx->P.num_factors;
   const size_t N = static_cast<size_t>(top_n);
   if (nu == 0) return;
@@ -169,18 +169,11 @@ void recommend_core(mf_ctx* ctx, Shard& s, const void* Q, int64_t q_rows, const 
     std::fill(ucnt, ucnt + nu, 0);
     return;
   }
-  DeviceGuard g(s.device);
   if (s.rec_id_gen[cside] != ctx->layout_gen || s.rec_id[cside].bytes() < static_cast<size_t>(C) * 4) {
     s.rec_id[cside].alloc(static_cast<size_t>(C) * 4);
     MF_HIP(hipMemcpy(s.rec_id[cside].get(), CS.row_id.data(), static_cast<size_t>(C) * 4, hipMemcpyHostToDevice));
     s.rec_id_gen[cside] = ctx->layout_gen;
   }
-  s.rec_q.alloc(static_cast<size_t>(nu) * 4);
-  s.rec_eoff.alloc(eoff.size() * 8);
-  s.rec_erows.alloc(std::max<size_t>(erows.size(), 1) * 4);
-  MF_HIP(hipMemcpy(s.rec_q.get(), qrows.data(), static_cast<size_t>(nu) * 4, hipMemcpyHostToDevice));
-  MF_HIP(hipMemcpy(s.rec_eoff.get(), eoff.data(), eoff.size() * 8, hipMemcpyHostToDevice));
-  if (!erows.empty()) MF_HIP(hipMemcpy(s.rec_erows.get(), erows.data(), erows.size() * 4, hipMemcpyHostToDevice));
 
   int64_t batch = 8192;
   if (const std::string v = test_knob("rec_batch"); !v.empty()) batch = std::max<int64_t>(1, std::atoll(v.c_str()));
@@ -242,8 +235,8 @@ void recommend_core(mf_ctx* ctx, Shard& s, const void* Q, int64_t q_rows, const 
   }
   for (int64_t b0 = 0; b0 < nu; b0 += batch) {
     const int64_t nb = std::min(batch, nu - b0);
-    const int64_t *ebeg = s.rec_eoff.as<int64_t>() + b0, *eend = ebeg + 1;
-    const int32_t* erows_d = s.rec_erows.as<int32_t>();
+    const int64_t *ebeg = d_eoff + b0, *eend = ebeg + 1;
+    const int32_t* erows_d = d_erows;
     if (sv.any) {
       launch_seen_gather(s.stream, sv.off, s.rec_q.as<int32_t>() + b0, static_cast<int>(nb), s.seen.qbeg.as<int64_t>(),
                          s.seen.qend.as<int64_t>());
@@ -271,6 +264,27 @@ void recommend_core(mf_ctx* ctx, Shard& s, const void* Q, int64_t q_rows, const 
                        hipMemcpyDeviceToHost));
     MF_HIP(hipMemcpy(ucnt + b0, s.rec_counts.get(), static_cast<size_t>(nb) * 4, hipMemcpyDeviceToHost));
   }
+}
+
+// The same for queries and exclusions the host holds: the rows qrows[0 .. nu) and the CSR eoff / erows are
+// uploaded, the rest is recommend_scored's.
+void recommend_core(mf_ctx* ctx, Shard& s, const void* Q, int64_t q_rows, const double* hvecs,
+                    const std::vector<int32_t>& qrows, int cside, int32_t top_n, int metric,
+                    const std::vector<int64_t>& eoff, const std::vector<int32_t>& erows, int seen_qside, int32_t* uid,
+                    double* usc, int32_t* ucnt) {
+  const int64_t nu = static_cast<int64_t>(qrows.size());
+  if (nu == 0) return;
+  DeviceGuard g(s.device);
+  if (side_of(ctx, cside).rows() > 0) {
+    s.rec_q.alloc(static_cast<size_t>(nu) * 4);
+    s.rec_eoff.alloc(eoff.size() * 8);
+    s.rec_erows.alloc(std::max<size_t>(erows.size(), 1) * 4);
+    MF_HIP(hipMemcpy(s.rec_q.get(), qrows.data(), static_cast<size_t>(nu) * 4, hipMemcpyHostToDevice));
+    MF_HIP(hipMemcpy(s.rec_eoff.get(), eoff.data(), eoff.size() * 8, hipMemcpyHostToDevice));
+    if (!erows.empty()) MF_HIP(hipMemcpy(s.rec_erows.get(), erows.data(), erows.size() * 4, hipMemcpyHostToDevice));
+  }
+  recommend_scored(ctx, s, Q, q_rows, hvecs, nu, cside, top_n, metric, s.rec_eoff.as<int64_t>(),
+                   s.rec_erows.as<int32_t>(), seen_qside, uid, usc, ucnt);
 }
 
 // The front of the calls whose queries are ids of side qside, candidates the rows of side cside (the other
@@ -390,6 +404,19 @@ void recommend_vectors(mf_ctx* ctx, int cside, const double* vecs, int64_t nq, i
   }
   recommend_core(ctx, s, nullptr, 0, vecs, rows, cside, top_n, metric, eoff, erows, -1, ids_out, scores_out,
                  counts_out);
+}
+
+// mf_recommend_foldin's entry: the queries are the identity rows of a slab that kernels queued on the stream
+// are still writing; the identity list is made on the device.
+void recommend_resident(mf_ctx* ctx, Shard& s, const void* Q, int64_t nu, int cside, int32_t top_n,
+                        const int64_t* d_eoff, const int32_t* d_erows, int32_t* ids_out, double* scores_out,
+                        int32_t* counts_out) {
+  if (nu > 0 && side_of(ctx, cside).rows() > 0) {
+    s.rec_q.alloc(static_cast<size_t>(nu) * 4);
+    launch_iota(s.stream, s.rec_q.as<int32_t>(), nu);
+  }
+  recommend_scored(ctx, s, Q, nu, nullptr, nu, cside, top_n, MF_METRIC_DOT, d_eoff, d_erows, -1, ids_out, scores_out,
+                   counts_out);
 }
 
 // Every row of a side (rank mode: the rank's own users), ascending by id (mf_get_factors).

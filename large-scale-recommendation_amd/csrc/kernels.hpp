@@ -268,11 +268,11 @@ void launch_row_inv_norm(hipStream_t st, const void* X, int64_t rows, int k, boo
 
 // ---- table kernels: what they share (kernels_table.hip, csr_search.hpp, csr_device.hpp) --------
 // The table kernels build, merge, search or compact a packed CSR on the device: kernels_rank.hip,
-// kernels_seen.hip, kernels_als_append.hip, kernels_als_remove.hip, with readers in kernels_recommend.hip
-// and kernels_pairrank.hip.  A new one includes csr_search.hpp for its searches (row_of, lower, upper,
-// contains), csr_device.hpp when it walks a CSR's entries in tiles (csr_tile, kCsrThreads, kCsrTile), takes
-// kRowMiss (id_index.hpp) for "no row", and sizes, fills, sorts and scans with the functions below -- it
-// defines none of these again.
+// kernels_seen.hip, kernels_als_append.hip, kernels_als_remove.hip, kernels_foldin.hip, with readers in
+// kernels_recommend.hip and kernels_pairrank.hip.  A new one includes csr_search.hpp for its searches (row_of,
+// lower, upper, contains), csr_device.hpp when it walks a CSR's entries in tiles (csr_tile, kCsrThreads,
+// kCsrTile), takes kRowMiss (id_index.hpp) for "no row", and sizes, fills, sorts and scans with the functions
+// below -- it defines none of these again.
 //
 // grid_for: workgroups of kGridThreads threads for a grid-stride loop over n elements, at least 1, at most cap.
 constexpr int kGridThreads = 256;
@@ -587,5 +587,32 @@ struct AlsRemoveLaunch {
 int64_t launch_als_remove_select(const AlsRemoveLaunch& L, AlsRemoveScratch& sc, uint8_t* found, int32_t* rempos);
 void launch_als_remove_move(const AlsRemoveLaunch& L, const AlsRemoveScratch& sc, int64_t* new_off, int32_t* new_cols,
                             void* new_vals);
+
+// ---- kernels_foldin.hip: mf_als_foldin, mf_recommend_foldin ---------------------------------------
+// One batch of fold-in lists as uploaded -> the transient CSR the ALS launches read.  off[nq + 1] (device, off[0]
+// = 0, off[nq] = n) cuts the n entries into the batch's nq lists; ids holds 2n words, the lists' ids in the
+// first n (replaced by their rows of the counterpart side, kRowMiss for an id it does not hold -- slots / mask:
+// that side's id mirror as launch_id_lookup takes it) and scratch behind them; ratings are the callers' f64.
+// The kept entries (known ids) are compacted stably: cols / vals (room for n; vals in the context's
+// precision, converted by one rounding) hold query 0's kept entries in list order, then query 1's, ...;
+// cnt[q] = (kept entries, of them rating > 0 after the conversion), two int32 per query -- all the host reads
+// back.  keys (may be null; room for n): per kept entry, beside it, (query position << 32) | row, the keys
+// rank_keys_sort takes.  Entry-tiled (csr_device.hpp): the cost follows the entries, not the longest list.
+struct FoldinScratch;
+struct FoldinLaunch {
+  hipStream_t st;
+  const int64_t* off;
+  int64_t nq, n;
+  uint32_t* ids;
+  const double* ratings;
+  const void* slots;
+  uint64_t mask;
+  bool f64;
+  int32_t* cols;
+  void* vals;
+  int32_t* cnt;
+  uint64_t* keys;
+};
+void launch_foldin_compact(const FoldinLaunch& L, FoldinScratch& sc);
 
 }  // namespace mfhip

@@ -20,8 +20,6 @@ namespace mfhip {
 
 // ---------------------------------------------------------------------------------------
 // Online micro-batches (single shard).
-namespace {
-
 // Brings the device mirror d up to the host table ix: the whole table after a rehash / clear / a
 // table of its own (generation changed), else only the slots written since the last sync.
 void sync_dev_index(Shard& s, const IdIndex& ix, DevIndex& d) {
@@ -55,6 +53,8 @@ void sync_dev_index(Shard& s, const IdIndex& ix, DevIndex& d) {
   MF_HIP(hipStreamSynchronize(s.stream));  // pos / val are released on return
   d.applied = log.size();
 }
+
+namespace {
 
 // The sweep's device plan leaves the batch's entries and, behind them, each entry's ticket value in
 // det_dev.

@@ -178,7 +178,7 @@ EXPORTS = [
     "mf_als_nonneg_stats", "mf_nnls_solve", "mf_als_append", "mf_als_run_rows", "mf_als_update",
     "mf_seen_set", "mf_seen_add", "mf_seen_from_als", "mf_seen_clear", "mf_seen_count", "mf_recommend_seen",
     "mf_rank_eval_seen", "mf_pair_ranks_seen", "mf_online_prequential_seen", "mf_similar", "mf_recommend_vectors",
-    "mf_als_remove", "mf_als_remove_rows", "mf_als_retract", "mf_seen_remove",
+    "mf_als_remove", "mf_als_remove_rows", "mf_als_retract", "mf_seen_remove", "mf_als_foldin", "mf_recommend_foldin",
 ]
 # The test hooks include/mfhip_testing.h declares (not product surface; same library).
 TESTING_EXPORTS = [
@@ -306,6 +306,10 @@ def lib() -> C.CDLL:
                                             _i32p, _i32p]),
         "mf_als_append": (C.c_int, [_ctxp, _i32p, _i32p, _f64p, C.c_int64]),
         "mf_als_run_rows": (C.c_int, [_ctxp, C.c_int, _i32p, C.c_int64, C.POINTER(mf_als_solve), _i64p]),
+        "mf_als_foldin": (C.c_int, [_ctxp, C.c_int, _i64p, _i32p, _f64p, C.c_int64, C.POINTER(mf_als_solve), _f64p,
+                                    _i32p]),
+        "mf_recommend_foldin": (C.c_int, [_ctxp, C.c_int, _i64p, _i32p, _f64p, C.c_int64, C.POINTER(mf_als_solve),
+                                          C.c_int32, C.c_int32, _i32p, _f64p, _i32p, _f64p, _i32p]),
         "mf_als_update": (C.c_int, [_ctxp, _i32p, _i32p, _f64p, C.c_int64, C.POINTER(mf_als_solve), C.c_int32, _i64p,
                                     _i64p]),
         "mf_debug_als_csr": (C.c_int, [_ctxp, C.c_int, _i64p, _i32p, _f64p, _i32p, C.c_int64, C.c_int64, _i64p,

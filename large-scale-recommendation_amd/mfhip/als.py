@@ -95,6 +95,27 @@ class MatrixFactorizationModel:
         return {int(u): [(int(u), int(ids[j, x]), float(sc[j, x])) for x in range(int(cnt[j]))]
                 for j, u in enumerate(users)}
 
+    def recommendProductsForSessions(self, sessions, num: int, lambda_: float = 0.01, implicit: bool = False,
+                                     alpha: float = 0.01, solver: str = "cholesky", cg_steps: int = 3,
+                                     exclude_rated: bool = True) -> List[List[Tuple[int, float]]]:
+        """Fold-in (mf_recommend_foldin): top-num products for users the model does not hold and does not
+        take in -- a new visitor's basket, an anonymous session.  sessions: a list of (product ids, ratings);
+        each is solved as a user with exactly those ratings would be (lambda_, implicit / alpha, solver as
+        als_solve takes them), products the model does not know are dropped, and with exclude_rated a
+        session's own products are never returned to it.  One list of (product, score) per session; a session
+        with no known product gets an empty list.  The model is left exactly as it was."""
+        off = np.zeros(len(sessions) + 1, np.int64)
+        for j, (p, r) in enumerate(sessions):
+            if len(p) != len(r):
+                raise ValueError(f"session {j}: {len(p)} products but {len(r)} ratings")
+            off[j + 1] = off[j] + len(p)
+        ids = np.concatenate([L.as_i32(p) for p, _ in sessions]) if len(sessions) else np.zeros(0, np.int32)
+        r = (np.concatenate([np.asarray(r, np.float64) for _, r in sessions]) if len(sessions)
+             else np.zeros(0, np.float64))
+        how = als_solve(lambda_, L.ALS_REG_WEIGHTED, implicit, alpha, solver, cg_steps)
+        out, sc, cnt, _, _ = self._ctx.recommend_foldin(L.SIDE_USER, off, ids, r, how, num, exclude_rated=exclude_rated)
+        return [[(int(out[j, x]), float(sc[j, x])) for x in range(int(cnt[j]))] for j in range(len(sessions))]
+
     def rankingMetrics(self, heldout_pairs, exclude=None) -> RankingMetrics:
         """RankingMetrics of the model's top-k product lists against held-out (user, product) pairs (tuples
         or two arrays); exclude: (user ids, item ids) pairs never recommended, e.g. the training pairs."""

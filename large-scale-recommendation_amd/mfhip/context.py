@@ -317,6 +317,53 @@ class Context:
                                       C.byref(solved)))
         return int(solved.value)
 
+    def _foldin_lists(self, offsets, ids, ratings):
+        off = np.ascontiguousarray(offsets, np.int64)
+        if off.ndim != 1 or off.size < 1:
+            raise ValueError("offsets must be a 1-d array of n_queries + 1 entries")
+        ci, cr = as_i32(ids), np.ascontiguousarray(ratings, np.float64)
+        ne = same_length(ci, cr)
+        if int(off[-1]) != ne:
+            raise ValueError(f"offsets end at {int(off[-1])} but the lists hold {ne} entries")
+        return off, ci, cr, ne
+
+    def als_foldin(self, side: int, offsets, ids, ratings, how: L.mf_als_solve) -> Tuple[np.ndarray, np.ndarray]:
+        """mf_als_foldin: the vectors rows of `side` would get from mf_als_run_rows with `how` (als_solve) if
+        their ratings were the lists -- query j owns entries offsets[j] .. offsets[j + 1] of ids / ratings, the
+        ids naming the other side -- and nothing of the context changes.  Entries naming an id the model does
+        not hold are dropped.  Returns (vecs [n, k] f64, used [n]: the kept entries per query)."""
+        off, ci, cr, ne = self._foldin_lists(offsets, ids, ratings)
+        n = off.size - 1
+        vecs = np.zeros((max(n, 1), self.k), np.float64)
+        used = np.zeros(max(n, 1), np.int32)
+        check(L.lib().mf_als_foldin(self._h, int(side), ptr(off, C.c_int64), ptr(ci, C.c_int32) if ne else None,
+                                    ptr(cr, C.c_double) if ne else None, n, C.byref(how), ptr(vecs, C.c_double),
+                                    ptr(used, C.c_int32)))
+        return vecs[:n], used[:n]
+
+    def recommend_foldin(self, side: int, offsets, ids, ratings, how: L.mf_als_solve, top_n: int,
+                         exclude_rated: bool = True, scores: bool = True, vectors: bool = False):
+        """mf_recommend_foldin: als_foldin's vectors scored against every row of the other side on the device,
+        as recommend_vectors(vecs, top_n, side=the other side) would; exclude_rated: a query's kept ids are
+        never returned to it.  Returns (ids, scores or None, counts, vecs or None, used); a query with no kept
+        entry has count 0."""
+        off, ci, cr, ne = self._foldin_lists(offsets, ids, ratings)
+        n, top_n = off.size - 1, int(top_n)
+        rows = max(n, 1) * max(top_n, 1)
+        out = np.zeros(rows, np.int32)
+        sc = np.zeros(rows, np.float64) if scores else None
+        counts = np.zeros(max(n, 1), np.int32)
+        vecs = np.zeros((max(n, 1), self.k), np.float64) if vectors else None
+        used = np.zeros(max(n, 1), np.int32)
+        check(L.lib().mf_recommend_foldin(self._h, int(side), ptr(off, C.c_int64), ptr(ci, C.c_int32) if ne else None,
+                                          ptr(cr, C.c_double) if ne else None, n, C.byref(how), top_n,
+                                          1 if exclude_rated else 0, ptr(out, C.c_int32),
+                                          ptr(sc, C.c_double) if scores else None, ptr(counts, C.c_int32),
+                                          ptr(vecs, C.c_double) if vectors else None, ptr(used, C.c_int32)))
+        shape = (n, max(top_n, 1))
+        return (out[:n * shape[1]].reshape(shape), sc[:n * shape[1]].reshape(shape) if scores else None, counts[:n],
+                vecs[:n] if vectors else None, used[:n])
+
     def als_update(self, u, i, r, how: L.mf_als_solve, rounds: int = 1) -> Tuple[int, int]:
         """mf_als_update: als_append, then `rounds` times the batch's users and then its items solved
         (users first: a new user's row is random until solved); returns the last round's (users, items)."""
