@@ -253,6 +253,43 @@ int mf_recommend_vectors(mf_ctx* ctx, int cand_side, const double* vecs, int64_t
                          const int64_t* excl_query_index, const int32_t* excl_cand, int64_t n_excl,
                          int32_t* ids_out, double* scores_out /* may be NULL */, int32_t* counts_out);
 
+/* The top_n WITHIN caller-given candidate lists: "the best 10 among the items in stock", or the second
+   stage "rank these 500 retrieved candidates for this user".  mf_recommend restricted, never the complement
+   spelled out as exclusion pairs.
+   Definition.  Position j of the outputs holds, bit for bit, what
+     mf_recommend(ctx, query_side, &queries[j], 1, top_n, E_j, ...)
+   returns, where E_j is this call's exclusions plus every pair (queries[j], c) of a candidate row c the model
+   holds whose id is NOT in list j.  Ids, scores, counts, the order (score descending, ties by candidate id
+   ascending (signed), NaN below every number, -0 as +0) and the output layout (ids_out / scores_out (may be
+   NULL): n_queries x top_n, row-major; counts_out the only validity signal, slots past it id 0 and score 0.0)
+   are mf_recommend's.
+   Lists.  offsets == NULL: every query uses cand_ids[0 .. n_cand) -- the allow-list.  Otherwise query j owns
+   cand_ids[offsets[j] .. offsets[j + 1]): offsets holds n_queries + 1 entries, offsets[0] == 0, never
+   decreasing, offsets[n_queries] == n_cand.  An id the candidate side does not hold is dropped; an id named
+   several times counts once; an empty list gives count 0; an unknown query id gives count 0; duplicate query
+   ids each take their own position's list.  So
+     counts_out[j] = min(top_n, distinct held ids of list j - those of them excluded for queries[j]).
+   Exclusions.  exclude_seen == 0: the excl_* arrays under mf_recommend's rules (pairs naming an unknown id or
+   a query not asked are ignored, duplicates allowed, n_excl == 0 takes NULL pointers; a pair may name a
+   candidate outside the list).  exclude_seen == 1: the resident seen set of query_side exactly as
+   mf_recommend_seen reads it -- no set, or an empty one, means no exclusions -- and n_excl must be 0.
+   Scores.  mf_recommend's arithmetic: MF_MODE_DETERMINISTIC_F64 the chain pq = pq + a*b over f = 0..k-1 (not
+   fused), MF_MODE_FAST_F32 the f32 fmaf chain over f = 0..k-1 from 0, widened.  Results depend neither on how
+   the queries are batched nor on how the lists are cut into parts, and a shared list gives what the same list
+   repeated for every query gives.  Nothing in the context changes.
+   Errors, all raised before the context is read.  MF_ERR_INVALID: a NULL ctx, a bad side, top_n outside
+   1 .. MF_RECOMMEND_MAX_TOP, a negative count, n_queries or n_cand >= 2^31, a NULL array with a positive count
+   (offsets may be NULL: that is the shared list), offsets[0] != 0, decreasing offsets, offsets[n_queries] !=
+   n_cand, an exclude_seen other than 0 or 1, exclude_seen == 1 with n_excl > 0.  Then MF_ERR_NOT_FITTED before
+   a model exists and MF_ERR_STATE on a rank-mode context, as mf_recommend.  n_queries == 0 is valid; a context
+   on several devices uses its first. */
+int mf_recommend_among(mf_ctx* ctx, int query_side, const int32_t* queries, int64_t n_queries, int32_t top_n,
+                       const int64_t* offsets /* [n_queries + 1], or NULL: one shared list */,
+                       const int32_t* cand_ids, int64_t n_cand,
+                       int32_t exclude_seen,
+                       const int32_t* excl_query, const int32_t* excl_cand, int64_t n_excl,
+                       int32_t* ids_out, double* scores_out /* may be NULL */, int32_t* counts_out);
+
 /* RankingMetrics (precisionAt, meanAveragePrecision, ndcgAt) of MLlib, for the models ALS.train builds
    (sp/OnlineSpark.scala:125-131), plus recall, reciprocal rank and hit rate: held-out (query,
    candidate) pairs against the model's top-N lists, on the device.  The pair tables are built, the

@@ -109,6 +109,14 @@ public final class MfHip {
   public static native void recommendVectors(long ctx, int candSide, double[] vecs, int numQueries, int topN,
                                              int metric, int[] exclQueryIndex, int[] exclCand,
                                              int[] idsOut, double[] scoresOut, int[] countsOut);
+  // the topN among caller-given candidate ids only (mf_recommend_among); outputs as for recommend.  offsets
+  // null: every query ranks the one list candIds (an allow-list); otherwise query j ranks entries offsets[j] ..
+  // offsets[j + 1] of candIds (queries.length + 1 entries from 0 to candIds.length, not decreasing).  Ids the
+  // model does not hold are dropped, repeated ids count once.  excludeSeen: the resident seen set is the
+  // exclusion list and exclQuery / exclCand must be null
+  public static native void recommendAmong(long ctx, int querySide, int[] queries, int topN, int[] offsets,
+                                           int[] candIds, boolean excludeSeen, int[] exclQuery, int[] exclCand,
+                                           int[] idsOut, double[] scoresOut, int[] countsOut);
   // Fold-in (mf_als_foldin / mf_recommend_foldin): vectors for users (side 0; the lists name items) or items
   // (side 1; the lists name users) the model does not hold and does not take in -- nothing of the context
   // changes.  Query j owns entries offsets[j] .. offsets[j + 1] of candIds / ratings (offsets: numQueries + 1

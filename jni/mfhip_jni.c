@@ -850,6 +850,36 @@ JNIEXPORT void JNICALL JFN(recommendVectors)(JNIEnv* env, jclass c, jlong h, jin
   check(env, st);
 }
 
+/* A Java array index is an int, so the offsets come as ints; the C call takes 64-bit offsets. */
+JNIEXPORT void JNICALL JFN(recommendAmong)(JNIEnv* env, jclass c, jlong h, jint side, jintArray q, jint top,
+                                           jintArray off, jintArray cand, jboolean seen, jintArray xq, jintArray xc,
+                                           jintArray ids, jdoubleArray scores, jintArray counts) {
+  if (require(env, q != NULL && cand != NULL, "queries and candIds must not be null")) return;
+  const jsize n = len(env, q), nc = len(env, cand), ne = xq ? len(env, xq) : 0;
+  if (top_lists_fit(env, n, top, ids, scores, counts)) return;
+  if (require(env, !off || len(env, off) == n + 1, "offsets must be null or hold queries.length + 1 entries")) return;
+  if (require(env, (!xq && !xc) || (xq && xc && len(env, xq) == len(env, xc)),
+              "exclQuery and exclCand must both be null or match in length"))
+    return;
+  int64_t* off64 = off ? (int64_t*)malloc(sizeof(int64_t) * ((size_t)n + 1)) : NULL;
+  if (require(env, !off || off64 != NULL, "out of memory")) return;
+  Elems e[8];
+  const jarray arr[8] = {q, off, cand, xq, xc, ids, scores, counts};
+  const int kind[8] = {kInt, kInt, kInt, kInt, kInt, kInt, kDouble, kInt};
+  if (acquire_all(env, e, arr, kind, 8)) {
+    free(off64);
+    return;
+  }
+  for (jsize x = 0; off && x <= n; ++x) off64[x] = ((const int32_t*)e[1].p)[x];
+  int st = mf_recommend_among(CTX(h), side, (const int32_t*)e[0].p, n, top, off64, (const int32_t*)e[2].p, nc,
+                              seen ? 1 : 0, ne ? (const int32_t*)e[3].p : NULL, ne ? (const int32_t*)e[4].p : NULL, ne,
+                              (int32_t*)e[5].p, (double*)e[6].p, (int32_t*)e[7].p);
+  free(off64);
+  for (int x = 7; x >= 5; --x) release(env, &e[x], st == MF_OK ? 0 : JNI_ABORT);
+  for (int x = 4; x >= 0; --x) release(env, &e[x], JNI_ABORT);
+  check(env, st);
+}
+
 /* Fold-in: mf_als_foldin (rec == 0) / mf_recommend_foldin.  A Java array index is an int, so the offsets come
    as ints; the C call takes 64-bit offsets. */
 static void foldin(JNIEnv* env, jlong h, jint side, jintArray off, jintArray cand, jdoubleArray r,

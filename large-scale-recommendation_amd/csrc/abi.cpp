@@ -306,6 +306,36 @@ void rank_check(mf_ctx* ctx, int query_side, const char* who) {
 }
 }  // namespace
 
+int mf_recommend_among(mf_ctx* ctx, int query_side, const int32_t* queries, int64_t n_queries, int32_t top_n,
+                       const int64_t* offsets, const int32_t* cand_ids, int64_t n_cand, int32_t exclude_seen,
+                       const int32_t* excl_query, const int32_t* excl_cand, int64_t n_excl, int32_t* ids_out,
+                       double* scores_out, int32_t* counts_out) {
+  return guarded([&] {
+    MF_REQUIRE(ctx, "null context");
+    MF_REQUIRE(query_side == MF_SIDE_USER || query_side == MF_SIDE_ITEM, "bad side");
+    MF_REQUIRE(top_n >= 1 && top_n <= MF_RECOMMEND_MAX_TOP,
+               "top_n must be in [1, " + std::to_string(MF_RECOMMEND_MAX_TOP) + "]");
+    MF_REQUIRE(n_queries >= 0 && n_cand >= 0 && n_excl >= 0, "negative count");
+    MF_REQUIRE(n_queries < (int64_t{1} << 31), "n_queries must be below 2^31");
+    MF_REQUIRE(n_cand < (int64_t{1} << 31), "n_cand must be below 2^31");
+    MF_REQUIRE(exclude_seen == 0 || exclude_seen == 1, "exclude_seen must be 0 or 1");
+    MF_REQUIRE(exclude_seen == 0 || n_excl == 0, "n_excl must be 0 with exclude_seen = 1: the seen set is the exclusion list");
+    MF_REQUIRE(n_excl == 0 || (excl_query && excl_cand), "null exclusion list");
+    MF_REQUIRE(n_queries == 0 || (queries && ids_out && counts_out), "null argument: queries, ids_out and counts_out");
+    MF_REQUIRE(n_cand == 0 || cand_ids, "null argument: cand_ids");
+    if (offsets) {
+      MF_REQUIRE(offsets[0] == 0, "offsets[0] must be 0");
+      for (int64_t j = 0; j < n_queries; ++j)
+        MF_REQUIRE(offsets[j + 1] >= offsets[j], "offsets must not decrease (at query " + std::to_string(j) + ")");
+      MF_REQUIRE(offsets[n_queries] == n_cand, "offsets[n_queries] must equal n_cand");
+    }
+    rank_check(ctx, query_side, "mf_recommend_among");
+    if (n_queries == 0) return;
+    recommend_among(ctx, query_side, queries, n_queries, top_n, offsets, cand_ids, n_cand, exclude_seen != 0, excl_query,
+                    excl_cand, n_excl, ids_out, scores_out, counts_out);
+  });
+}
+
 int mf_rank_eval(mf_ctx* ctx, int query_side, const int32_t* gt_query, const int32_t* gt_cand, int64_t n_gt,
                  int32_t top_n, const int32_t* excl_query, const int32_t* excl_cand, int64_t n_excl,
                  mf_rank_metrics* out, int32_t* q_ids_out, int32_t* q_counts_out, double* q_metrics_out, int64_t cap) {

@@ -133,6 +133,10 @@ struct Shard {
   // pinned host stage (mf_recommend_vectors)
   DevBuf rec_cinv, rec_qinv, rec_qvec;
   PinnedBuf rec_pin;
+  // ... mf_recommend_among (which also uses the rec_* buffers and rank_sc).  Shared list: its distinct rows (the
+  // position -> row map), the gathered slab and its ids.  Per-query lists, one batch: the lists as uploaded and resolved, the tasks,
+  // and per position its first task, query row and exclusion range
+  DevBuf am_rows, am_slab, am_id, am_in, am_tasks, am_pbeg, am_qrow, am_ebeg, am_eend;
   // ranking metrics (mf_rank_eval, which also uses the rec_* buffers): the table build's scratch, a pair
   // list as uploaded (query rows, then candidate rows or ids), the ground-truth CSR, the per-query
   // metrics and (hits, g), the slice sums, the gain table and the call's totals
@@ -397,6 +401,10 @@ EvalOut evaluate(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* 
 void recommend(mf_ctx* ctx, int qside, const int32_t* queries, int64_t nq, int32_t top_n, const int32_t* eq,
                const int32_t* ec, int64_t ne, int32_t* ids_out, double* scores_out, int32_t* counts_out,
                bool seen = false);
+// mf_recommend_among: off null = one shared list cand[0 .. n_cand), else position j owns cand[off[j] .. off[j + 1]).
+void recommend_among(mf_ctx* ctx, int qside, const int32_t* queries, int64_t nq, int32_t top_n, const int64_t* off,
+                     const int32_t* cand, int64_t n_cand, bool seen, const int32_t* eq, const int32_t* ec, int64_t ne,
+                     int32_t* ids_out, double* scores_out, int32_t* counts_out);
 void similar(mf_ctx* ctx, int side, const int32_t* queries, int64_t nq, int32_t top_n, int metric, bool include_self,
              const int32_t* eq, const int32_t* ec, int64_t ne, int32_t* ids_out, double* scores_out,
              int32_t* counts_out);

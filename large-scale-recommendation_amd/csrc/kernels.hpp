@@ -116,6 +116,9 @@ uint32_t online_sweep_plan(hipStream_t st, OnlineSweepScratch& sc, const uint32_
 // those (the host then gives the unseen ids rows in first-touch order).  A null table: all misses.
 void launch_id_lookup(hipStream_t st, uint32_t* in, int64_t n, const void* uslots, uint64_t umask, const void* islots,
                       uint64_t imask, int32_t* misses);
+// The same lookup for one array of ids against one table, n of any size (launch_id_lookup's grid reaches 2^24
+// entries: an online batch; mf_recommend_among sends whole candidate lists): in[0, n) replaced by rows or kRowMiss.
+void launch_id_lookup_one(hipStream_t st, uint32_t* in, int64_t n, const void* slots, uint64_t mask);
 // slots[pos[j]] = vals[j] (8-B slots): the mirror takes the host table's writes since its last sync
 void launch_id_scatter(hipStream_t st, void* slots, const uint32_t* pos, const void* vals, int64_t m);
 
@@ -257,14 +260,48 @@ void device_fast_schedule(hipStream_t st, const DevRatingBlocks& dr, const Ratin
 // Cosine (mf_similar, mf_recommend_vectors): c_inv given -- one inverse norm per candidate row, q_inv one per
 // row of Q (indexed through qrows like Q), both in the context's precision, as launch_row_inv_norm writes
 // them; a score is then dot * (q_inv * c_inv), scaled before it is selected.  Null: the dot kernels.
+// pos_row (mf_recommend_among's shared list; dot metric only): Cf is a slab gathered from the factor rows,
+// cand_id its ids by slab position, and excl_rows still name factor rows -- position p is row pos_row[p].
 // launch_row_inv_norm: inv[r] = 1 / sqrt(sum over ascending f of X[r][f]^2) for rows [0, rows) of X.
 size_t recommend_key_bytes(bool f64);
 int recommend_query_tile(int top_n, bool f64);
 void launch_recommend(hipStream_t st, const void* Q, const void* Cf, const int32_t* qrows, int nq, int32_t C, int S,
                       int k, int top_n, bool f64, const int32_t* cand_id, const int64_t* excl_beg,
                       const int64_t* excl_end, const int32_t* excl_rows, void* part, int32_t* ids, double* scores,
-                      int32_t* counts, const void* q_inv = nullptr, const void* c_inv = nullptr);
+                      int32_t* counts, const void* q_inv = nullptr, const void* c_inv = nullptr,
+                      const int32_t* pos_row = nullptr);
 void launch_row_inv_norm(hipStream_t st, const void* X, int64_t rows, int k, bool f64, void* inv);
+
+// ---- kernels_among.hip: top N within caller-given candidate lists (mf_recommend_among) ------------
+// The shared list as launch_id_lookup_one resolved it (rows[0, n): candidate rows, kRowMiss for an id the side does
+// not hold; 0 < n < 2^31) -> its distinct held rows, ascending, into out (room for n); returns their count (one
+// small read-back, the stream is drained).  A radix sort, a flag per first occurrence, a scan and a compaction;
+// the scratch is sc's, grown by temp_storage's rule.
+struct RankScratch;
+int64_t among_distinct_rows(hipStream_t st, RankScratch& sc, const uint32_t* rows, int64_t n, int32_t* out);
+// dst row p = row rows[p] of slab src (n rows of k elements in the context's precision),
+// ids[p] = row_id[rows[p]] -- the compact slab, its ids and (rows itself) the position -> row map that
+// launch_recommend takes.
+void launch_among_gather(hipStream_t st, const void* src, const int32_t* rows, int64_t n, int k, bool f64,
+                         const int32_t* row_id, void* dst, int32_t* ids);
+// Per-query lists, one batch of nq positions.  crows: the batch's lists one after the other as launch_id_lookup
+// leaves them (candidate rows, kRowMiss for an id the side does not hold).  A task is one part of one position's
+// list: entries [beg, beg + len) of crows; the tasks of a position are consecutive, pbeg[q] .. pbeg[q + 1]
+// (nq + 1 offsets into tasks, at most 64 per position; none: count 0).  Per position: its query row qrow (a
+// valid row of Q for every position that has tasks) and the range excl_beg / excl_end of excl_rows (sorted
+// candidate rows) never returned.  Scores, keys, order and the outputs ids / scores (may be null) / counts are
+// launch_recommend's; an id named several times in a list counts once.  part: ntasks * top_n keys of
+// recommend_key_bytes(f64) scratch.
+struct AmongTask {
+  int64_t beg;
+  int32_t len;
+  int32_t pos;  // the position of the batch the part belongs to
+};
+static_assert(sizeof(AmongTask) == 16, "AmongTask is one 16-B word");
+void launch_among(hipStream_t st, const void* Q, const void* Cf, const AmongTask* tasks, int64_t ntasks,
+                  const int64_t* pbeg, int nq, const uint32_t* crows, const int32_t* qrow, const int32_t* cand_id,
+                  const int64_t* excl_beg, const int64_t* excl_end, const int32_t* excl_rows, int k, int top_n, bool f64,
+                  void* part, int32_t* ids, double* scores, int32_t* counts);
 
 // ---- table kernels: what they share (kernels_table.hip, csr_search.hpp, csr_device.hpp) --------
 // The table kernels build, merge, search or compact a packed CSR on the device: kernels_rank.hip,

@@ -219,6 +219,13 @@ __global__ __launch_bounds__(kThreads) void k_id_lookup(uint32_t* __restrict__ i
   const int tot = __popcll(__ballot(m >= 1)) + __popcll(__ballot(m == 2));
   if ((threadIdx.x & 63) == 0 && tot) atomicAdd(misses, tot);
 }
+// One array against one table, any length: a grid-stride loop (k_id_lookup's grid covers 2^24 entries).
+__global__ __launch_bounds__(kThreads) void k_id_lookup_one(uint32_t* __restrict__ in, int64_t n,
+                                                           const int2* __restrict__ slots, uint64_t mask) {
+  for (int64_t j = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x; j < n;
+       j += static_cast<int64_t>(gridDim.x) * kThreads)
+    in[j] = id_find(slots, mask, static_cast<int32_t>(in[j]));
+}
 __global__ __launch_bounds__(kThreads) void k_id_scatter(int2* __restrict__ slots, const uint32_t* __restrict__ pos,
                                                         const int2* __restrict__ vals, int64_t m) {
   const int64_t j = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
@@ -231,6 +238,13 @@ void launch_id_lookup(hipStream_t st, uint32_t* in, int64_t n, const void* uslot
   if (n <= 0) return;
   hipLaunchKernelGGL(k_id_lookup, dim3(grid_for(n)), dim3(kThreads), 0, st, in, n, static_cast<const int2*>(uslots),
                      umask, static_cast<const int2*>(islots), imask, misses);
+  MF_HIP(hipGetLastError());
+}
+
+void launch_id_lookup_one(hipStream_t st, uint32_t* in, int64_t n, const void* slots, uint64_t mask) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_id_lookup_one, dim3(grid_for(n)), dim3(kThreads), 0, st, in, n, static_cast<const int2*>(slots),
+                     mask);
   MF_HIP(hipGetLastError());
 }
 

@@ -34,80 +34,12 @@
 #include "csr_search.hpp"
 #include "kernels.hpp"
 #include "mfhip.h"
+#include "rec_keys.hpp"
 
 namespace mfhip {
 namespace {
 
-// ---- keys ---------------------------------------------------------------------------------
-// Candidate id part: a smaller id gives a larger value.
-__device__ __forceinline__ uint32_t id_bits(int32_t id) { return ~(static_cast<uint32_t>(id) ^ 0x80000000u); }
-__device__ __forceinline__ int32_t id_from_bits(uint32_t b) { return static_cast<int32_t>((~b) ^ 0x80000000u); }
-
-// f32: (order-preserving u32 of the score) << 32 | id part.  The score part is >= 1 for every real
-// key (1 = NaN, which no number maps to), so 0 is the empty slot.  -0 orders as +0.
-struct Key32 {
-  uint64_t v;
-};
-__device__ __forceinline__ bool key_gt(Key32 a, Key32 b) { return a.v > b.v; }
-__device__ __forceinline__ bool key_empty(Key32 a) { return a.v == 0; }
-__device__ __forceinline__ uint32_t ord32(float s) {
-  if (s != s) return 1u;
-  if (s == 0.0f) return 0x80000000u;
-  const uint32_t b = __float_as_uint(s);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ Key32 make_key(float s, int32_t id) {
-  return Key32{(static_cast<uint64_t>(ord32(s)) << 32) | id_bits(id)};
-}
-__device__ __forceinline__ double key_score(Key32 k) {
-  const uint32_t o = static_cast<uint32_t>(k.v >> 32);
-  if (o == 1u) return __longlong_as_double(0x7ff8000000000000LL);
-  const uint32_t b = (o & 0x80000000u) ? (o ^ 0x80000000u) : ~o;
-  return static_cast<double>(__uint_as_float(b));
-}
-__device__ __forceinline__ int32_t key_id(Key32 k) { return id_from_bits(static_cast<uint32_t>(k.v)); }
-__device__ __forceinline__ Key32 key_shfl_xor(Key32 k, int m) {
-  const uint32_t lo = __shfl_xor(static_cast<uint32_t>(k.v), m), hi = __shfl_xor(static_cast<uint32_t>(k.v >> 32), m);
-  return Key32{(static_cast<uint64_t>(hi) << 32) | lo};
-}
-
-// f64: the same with a 64-bit score part (hi) and the id part in lo.
-struct Key64 {
-  uint64_t hi, lo;
-};
-__device__ __forceinline__ bool key_gt(Key64 a, Key64 b) { return a.hi > b.hi || (a.hi == b.hi && a.lo > b.lo); }
-__device__ __forceinline__ bool key_empty(Key64 a) { return a.hi == 0; }
-__device__ __forceinline__ Key64 make_key(double s, int32_t id) {
-  uint64_t o;
-  if (s != s) o = 1u;
-  else if (s == 0.0) o = 0x8000000000000000ULL;
-  else {
-    const uint64_t b = static_cast<uint64_t>(__double_as_longlong(s));
-    o = (b >> 63) ? ~b : (b | 0x8000000000000000ULL);
-  }
-  return Key64{o, id_bits(id)};
-}
-__device__ __forceinline__ double key_score(Key64 k) {
-  if (k.hi == 1u) return __longlong_as_double(0x7ff8000000000000LL);
-  const uint64_t b = (k.hi >> 63) ? (k.hi ^ 0x8000000000000000ULL) : ~k.hi;
-  return __longlong_as_double(static_cast<long long>(b));
-}
-__device__ __forceinline__ int32_t key_id(Key64 k) { return id_from_bits(static_cast<uint32_t>(k.lo)); }
-__device__ __forceinline__ Key64 key_shfl_xor(Key64 k, int m) {
-  const Key32 a = key_shfl_xor(Key32{k.hi}, m), b = key_shfl_xor(Key32{k.lo}, m);
-  return Key64{a.v, b.v};
-}
-
-// list[0..N) sorted descending, key beats list[N-1]: insert it, dropping the last.
-template <typename K>
-__device__ __forceinline__ void list_insert(K* list, int N, K key) {
-  int p = N - 1;
-  while (p > 0 && key_gt(key, list[p - 1])) {
-    list[p] = list[p - 1];
-    --p;
-  }
-  list[p] = key;
-}
+using namespace dev;  // the keys and list_insert: rec_keys.hpp
 
 // Is candidate row `crow` in the query's sorted exclusion rows [b, e)?
 __device__ __forceinline__ bool excluded(const int32_t* __restrict__ rows, int64_t b, int64_t e, int32_t crow) {
@@ -129,8 +61,10 @@ __host__ __device__ constexpr int rec_stage_floats(int nw) { return kKC * (kAStr
 // rows [0, C) of slab Cf, split s takes [s * per, min(C, (s + 1) * per)).  part: [nq][S][N] keys.
 // VEC: k % 4 == 0, rows are loaded as float4.  COS: scores are scaled by qinv[query row] * cinv[candidate
 // row]; a tile's 128 candidate inverses ride through LDS with it, one buffer per tile parity (a wave may
-// stage tile T + 1 while another still selects from tile T).
-template <int NW, bool VEC, bool COS>
+// stage tile T + 1 while another still selects from tile T).  MAP (mf_recommend_among's shared list): the
+// candidates are a gathered slab, and the exclusion rows name factor rows: position p of the slab is factor row
+// pos_row[p], read only for a score that has beaten the N-th key and is about to be tested.
+template <int NW, bool VEC, bool COS, bool MAP>
 __global__ __launch_bounds__(NW * 64) void k_rec_f32(const float* __restrict__ Qf, const float* __restrict__ Cf,
                                                      const int32_t* __restrict__ qrows, int nq, int32_t C, int32_t per,
                                                      int k, int N, const int32_t* __restrict__ cand_id,
@@ -138,7 +72,8 @@ __global__ __launch_bounds__(NW * 64) void k_rec_f32(const float* __restrict__ Q
                                                      const int64_t* __restrict__ excl_end,
                                                      const int32_t* __restrict__ excl_rows, Key32* __restrict__ part,
                                                      const float* __restrict__ qinv,
-                                                     const float* __restrict__ cinv) {
+                                                     const float* __restrict__ cinv,
+                                                     const int32_t* __restrict__ pos_row) {
   constexpr int NT = NW * 64, QT = NW * 32, BSTR = rec_bstr(NW);
   constexpr int CI_PER = (kCT + NT - 1) / NT;  // candidate inverses of a tile per thread (COS)
   constexpr int A_PER = kCT * 4 / NT;  // float4 slots of the candidate stage per thread
@@ -284,7 +219,10 @@ __global__ __launch_bounds__(NW * 64) void k_rec_f32(const float* __restrict__ Q
             const uint64_t pv = pend[i * NT + tid];
             const int32_t crow = c0 + static_cast<int32_t>(pv & 0xFFFFFFFFu);
             key = Key32{(pv & 0xFFFFFFFF00000000ULL) | id_bits(cand_id[crow])};
-            have = key_gt(key, mylist[N - 1]) && !excluded(excl_rows, eb, ee, crow);
+            if constexpr (MAP)
+              have = key_gt(key, mylist[N - 1]) && !excluded(excl_rows, eb, ee, pos_row[crow]);
+            else
+              have = key_gt(key, mylist[N - 1]) && !excluded(excl_rows, eb, ee, crow);
           }
           // the two halves of the wave share a query's list: one half at a time
 #pragma unroll
@@ -336,7 +274,8 @@ constexpr int kQW = 4;  // queries per wave
 
 // Grid: (ceil(nq / (4 * kQW)), S), 4 waves per block.  Lane = candidate; the wave's kQW query rows
 // are wave-uniform reads.  COS: as k_rec_f32, one inverse per candidate lane, the queries' wave-uniform.
-template <bool COS>
+// MAP: as k_rec_f32.
+template <bool COS, bool MAP>
 __global__ __launch_bounds__(256) void k_rec_f64(const double* __restrict__ Qf, const double* __restrict__ Cf,
                                                  const int32_t* __restrict__ qrows, int nq, int32_t C, int32_t per,
                                                  int k, int N, const int32_t* __restrict__ cand_id,
@@ -344,7 +283,8 @@ __global__ __launch_bounds__(256) void k_rec_f64(const double* __restrict__ Qf, 
                                                  const int64_t* __restrict__ excl_end,
                                                  const int32_t* __restrict__ excl_rows, Key64* __restrict__ part,
                                                  const double* __restrict__ qinv,
-                                                 const double* __restrict__ cinv) {
+                                                 const double* __restrict__ cinv,
+                                                 const int32_t* __restrict__ pos_row) {
   __shared__ Key64 lists[4][kQW * MF_RECOMMEND_MAX_TOP];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int S = gridDim.y, s = blockIdx.y;
@@ -386,7 +326,11 @@ __global__ __launch_bounds__(256) void k_rec_f64(const double* __restrict__ Qf, 
       Key64* list = wl + i * N;
       const Key64 key = make_key(pq[i], cid);
       bool want = cok && key_gt(key, list[N - 1]);
-      if (want) want = !excluded(excl_rows, excl_beg[q], excl_end[q], crow);
+      if constexpr (MAP) {
+        if (want) want = !excluded(excl_rows, excl_beg[q], excl_end[q], pos_row[crow]);
+      } else {
+        if (want) want = !excluded(excl_rows, excl_beg[q], excl_end[q], crow);
+      }
       // one lane at a time inserts into the query's list
       for (;;) {
         want = want && key_gt(key, list[N - 1]);
@@ -481,25 +425,27 @@ __global__ __launch_bounds__(256) void k_rec_merge(const K* __restrict__ part, i
   if (lane == 0) counts[q] = cnt;
 }
 
-template <int NW, bool VEC, bool COS>
+template <int NW, bool VEC, bool COS, bool MAP>
 void rec_f32_launch(hipStream_t st, const float* Q, const float* Cf, const int32_t* qrows, int nq, int32_t C, int S,
                     int32_t per, int k, int N, const int32_t* cand_id, const int64_t* eb, const int64_t* ee,
-                    const int32_t* er, void* part, const float* qinv, const float* cinv) {
+                    const int32_t* er, void* part, const float* qinv, const float* cinv, const int32_t* pos_row) {
   const dim3 grid(static_cast<unsigned>((nq + NW * 32 - 1) / (NW * 32)), static_cast<unsigned>(S)), block(NW * 64);
   const size_t smem = sizeof(Key32) * NW * 32 * N + 8 * kPend * NW * 64 + sizeof(float) * 2 * rec_stage_floats(NW) +
                       (COS ? sizeof(float) * 2 * kCT : 0);
   // up to 72 KB (NW = 4, top 16; 1 KB more with COS): above the 64 KB a kernel gets without asking
-  const void* fn = reinterpret_cast<const void*>(&k_rec_f32<NW, VEC, COS>);
+  const void* fn = reinterpret_cast<const void*>(&k_rec_f32<NW, VEC, COS, MAP>);
   if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(smem)) != hipSuccess)
     fail(MF_ERR_HIP, "k_rec_f32: " + std::to_string(smem) + " bytes of LDS refused");
-  hipLaunchKernelGGL((k_rec_f32<NW, VEC, COS>), grid, block, smem, st, Q, Cf, qrows, nq, C, per, k, N, cand_id, eb, ee,
-                     er, static_cast<Key32*>(part), qinv, cinv);
+  hipLaunchKernelGGL((k_rec_f32<NW, VEC, COS, MAP>), grid, block, smem, st, Q, Cf, qrows, nq, C, per, k, N, cand_id, eb,
+                     ee, er, static_cast<Key32*>(part), qinv, cinv, pos_row);
 }
 
+// (the map is never combined with the cosine metric: no caller asks for it)
 template <int NW, typename... A>
-void rec_f32_dispatch(bool vec, bool cos, A... a) {
-  if (cos) vec ? rec_f32_launch<NW, true, true>(a...) : rec_f32_launch<NW, false, true>(a...);
-  else vec ? rec_f32_launch<NW, true, false>(a...) : rec_f32_launch<NW, false, false>(a...);
+void rec_f32_dispatch(bool vec, bool cos, bool map, A... a) {
+  if (cos) vec ? rec_f32_launch<NW, true, true, false>(a...) : rec_f32_launch<NW, false, true, false>(a...);
+  else if (map) vec ? rec_f32_launch<NW, true, false, true>(a...) : rec_f32_launch<NW, false, false, true>(a...);
+  else vec ? rec_f32_launch<NW, true, false, false>(a...) : rec_f32_launch<NW, false, false, false>(a...);
 }
 
 }  // namespace
@@ -525,21 +471,26 @@ void launch_row_inv_norm(hipStream_t st, const void* X, int64_t rows, int k, boo
 void launch_recommend(hipStream_t st, const void* Q, const void* Cf, const int32_t* qrows, int nq, int32_t C, int S,
                       int k, int top_n, bool f64, const int32_t* cand_id, const int64_t* excl_beg,
                       const int64_t* excl_end, const int32_t* excl_rows, void* part, int32_t* ids, double* scores,
-                      int32_t* counts, const void* q_inv, const void* c_inv) {
+                      int32_t* counts, const void* q_inv, const void* c_inv, const int32_t* pos_row) {
   if (nq <= 0) return;
   const int32_t per = (C + S - 1) / S;
-  const bool cos = c_inv != nullptr;
+  const bool cos = c_inv != nullptr, map = pos_row != nullptr;
+  if (cos && map) fail(MF_ERR_INVALID, "launch_recommend: a position map with the cosine metric");
   if (f64) {
     const dim3 grid(static_cast<unsigned>((nq + 4 * kQW - 1) / (4 * kQW)), static_cast<unsigned>(S)), block(256);
     const double *qi = static_cast<const double*>(q_inv), *ci = static_cast<const double*>(c_inv);
     if (cos)
-      hipLaunchKernelGGL((k_rec_f64<true>), grid, block, 0, st, static_cast<const double*>(Q),
+      hipLaunchKernelGGL((k_rec_f64<true, false>), grid, block, 0, st, static_cast<const double*>(Q),
                          static_cast<const double*>(Cf), qrows, nq, C, per, k, top_n, cand_id, excl_beg, excl_end,
-                         excl_rows, static_cast<Key64*>(part), qi, ci);
+                         excl_rows, static_cast<Key64*>(part), qi, ci, pos_row);
+    else if (map)
+      hipLaunchKernelGGL((k_rec_f64<false, true>), grid, block, 0, st, static_cast<const double*>(Q),
+                         static_cast<const double*>(Cf), qrows, nq, C, per, k, top_n, cand_id, excl_beg, excl_end,
+                         excl_rows, static_cast<Key64*>(part), qi, ci, pos_row);
     else
-      hipLaunchKernelGGL((k_rec_f64<false>), grid, block, 0, st, static_cast<const double*>(Q),
+      hipLaunchKernelGGL((k_rec_f64<false, false>), grid, block, 0, st, static_cast<const double*>(Q),
                          static_cast<const double*>(Cf), qrows, nq, C, per, k, top_n, cand_id, excl_beg, excl_end,
-                         excl_rows, static_cast<Key64*>(part), qi, ci);
+                         excl_rows, static_cast<Key64*>(part), qi, ci, pos_row);
   } else {
     const float* q = static_cast<const float*>(Q);
     const float* c = static_cast<const float*>(Cf);
@@ -548,11 +499,14 @@ void launch_recommend(hipStream_t st, const void* Q, const void* Cf, const int32
     const int64_t *eb = excl_beg, *ee = excl_end;
     const bool vec = k % 4 == 0;
     if (top_n <= 16)
-      rec_f32_dispatch<4>(vec, cos, st, q, c, qrows, nq, C, S, per, k, top_n, cand_id, eb, ee, excl_rows, part, qi, ci);
+      rec_f32_dispatch<4>(vec, cos, map, st, q, c, qrows, nq, C, S, per, k, top_n, cand_id, eb, ee, excl_rows, part, qi,
+                          ci, pos_row);
     else if (top_n <= 48)
-      rec_f32_dispatch<2>(vec, cos, st, q, c, qrows, nq, C, S, per, k, top_n, cand_id, eb, ee, excl_rows, part, qi, ci);
+      rec_f32_dispatch<2>(vec, cos, map, st, q, c, qrows, nq, C, S, per, k, top_n, cand_id, eb, ee, excl_rows, part, qi,
+                          ci, pos_row);
     else
-      rec_f32_dispatch<1>(vec, cos, st, q, c, qrows, nq, C, S, per, k, top_n, cand_id, eb, ee, excl_rows, part, qi, ci);
+      rec_f32_dispatch<1>(vec, cos, map, st, q, c, qrows, nq, C, S, per, k, top_n, cand_id, eb, ee, excl_rows, part, qi,
+                          ci, pos_row);
   }
   const dim3 mgrid(static_cast<unsigned>((nq + 3) / 4)), mblock(256);
   if (f64)

@@ -179,6 +179,7 @@ EXPORTS = [
     "mf_seen_set", "mf_seen_add", "mf_seen_from_als", "mf_seen_clear", "mf_seen_count", "mf_recommend_seen",
     "mf_rank_eval_seen", "mf_pair_ranks_seen", "mf_online_prequential_seen", "mf_similar", "mf_recommend_vectors",
     "mf_als_remove", "mf_als_remove_rows", "mf_als_retract", "mf_seen_remove", "mf_als_foldin", "mf_recommend_foldin",
+    "mf_recommend_among",
 ]
 # The test hooks include/mfhip_testing.h declares (not product surface; same library).
 TESTING_EXPORTS = [
@@ -327,6 +328,8 @@ def lib() -> C.CDLL:
         "mf_seen_clear": (C.c_int, [_ctxp]),
         "mf_seen_count": (C.c_int, [_ctxp, _i64p]),
         "mf_recommend_seen": (C.c_int, [_ctxp, C.c_int, _i32p, C.c_int64, C.c_int32, _i32p, _f64p, _i32p]),
+        "mf_recommend_among": (C.c_int, [_ctxp, C.c_int, _i32p, C.c_int64, C.c_int32, _i64p, _i32p, C.c_int64, C.c_int32,
+                                         _i32p, _i32p, C.c_int64, _i32p, _f64p, _i32p]),
         "mf_rank_eval_seen": (C.c_int, [_ctxp, C.c_int, _i32p, _i32p, C.c_int64, C.c_int32, C.POINTER(mf_rank_metrics),
                                         _i32p, _i32p, _f64p, C.c_int64]),
         "mf_pair_ranks_seen": (C.c_int, [_ctxp, C.c_int, _i32p, _i32p, C.c_int64, _i32p, _i32p, _f64p]),

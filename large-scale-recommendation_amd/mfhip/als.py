@@ -95,6 +95,16 @@ class MatrixFactorizationModel:
         return {int(u): [(int(u), int(ids[j, x]), float(sc[j, x])) for x in range(int(cnt[j]))]
                 for j, u in enumerate(users)}
 
+    def recommendProductsAmong(self, users, num: int, products, offsets=None) -> dict:
+        """The num best products for each user among the given product ids only (mf_recommend_among).  offsets
+        None: `products` is one list every user ranks (an allow-list); otherwise user j ranks products[offsets[j] :
+        offsets[j + 1]].  Returns {position j: [(user, product, score), ...]} -- keyed by position, since a user
+        may be asked twice with different lists."""
+        users = L.as_i32(users)
+        ids, sc, cnt = self._ctx.recommend_among(users, num, products, offsets=offsets, side=L.SIDE_USER)
+        return {j: [(int(u), int(ids[j, x]), float(sc[j, x])) for x in range(int(cnt[j]))]
+                for j, u in enumerate(users)}
+
     def recommendProductsForSessions(self, sessions, num: int, lambda_: float = 0.01, implicit: bool = False,
                                      alpha: float = 0.01, solver: str = "cholesky", cg_steps: int = 3,
                                      exclude_rated: bool = True) -> List[List[Tuple[int, float]]]:

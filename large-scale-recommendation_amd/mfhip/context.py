@@ -512,6 +512,41 @@ class Context:
         shape = (n, max(top_n, 1))
         return (ids[:n * shape[1]].reshape(shape), sc[:n * shape[1]].reshape(shape) if scores else None, counts[:n])
 
+    def recommend_among(self, queries, top_n: int, candidates, offsets=None, side: int = L.SIDE_USER, exclude=None,
+                        seen: bool = False, scores: bool = True):
+        """mf_recommend_among: recommend() restricted to caller-given candidate ids.  offsets None: every query
+        ranks the one list `candidates` (an allow-list); otherwise query j ranks candidates[offsets[j] :
+        offsets[j + 1]] (len(queries) + 1 offsets from 0 to len(candidates)).  Ids the model does not hold are
+        dropped, repeated ids count once.  exclude: (query ids, candidate ids) pairs never returned; seen=True:
+        the resident seen set instead (exclude must then be None).  Returns (ids, scores or None, counts) laid
+        out as recommend() lays them out."""
+        q, cand = as_i32(queries), as_i32(candidates)
+        n, top_n, nc = len(q), int(top_n), len(cand)
+        off = None
+        if offsets is not None:
+            off = np.ascontiguousarray(offsets, np.int64)
+            if off.ndim != 1 or len(off) != n + 1:
+                raise ValueError(f"offsets must hold len(queries) + 1 = {n + 1} entries, got {off.shape}")
+        rows = max(n, 1) * max(top_n, 1)
+        ids = np.zeros(rows, np.int32)
+        sc = np.zeros(rows, np.float64) if scores else None
+        counts = np.zeros(max(n, 1), np.int32)
+        eq = ec = None
+        ne = 0
+        if exclude is L.SEEN:
+            seen, exclude = True, None
+        if exclude is not None:
+            eq, ec = as_i32(exclude[0]), as_i32(exclude[1])
+            ne = same_length(eq, ec)
+        check(L.lib().mf_recommend_among(self._h, int(side), ptr(q, C.c_int32), n, top_n,
+                                         ptr(off, C.c_int64) if off is not None else None,
+                                         ptr(cand, C.c_int32) if nc else None, nc, int(bool(seen)),
+                                         ptr(eq, C.c_int32) if ne else None, ptr(ec, C.c_int32) if ne else None, ne,
+                                         ptr(ids, C.c_int32), ptr(sc, C.c_double) if scores else None,
+                                         ptr(counts, C.c_int32)))
+        shape = (n, max(top_n, 1))
+        return (ids[:n * shape[1]].reshape(shape), sc[:n * shape[1]].reshape(shape) if scores else None, counts[:n])
+
     def similar(self, queries, top_n: int, side: int = L.SIDE_ITEM, metric: int = L.METRIC_COSINE,
                 include_self: bool = False, exclude=None, scores: bool = True):
         """mf_similar: for every query id of `side` the top_n nearest ids of the same side, by cosine

@@ -226,6 +226,17 @@ class DSGDforMF:
         return {int(u): [(int(u), int(ids[j, x]), float(sc[j, x])) for x in range(int(cnt[j]))]
                 for j, u in enumerate(users)}
 
+    def recommendProductsAmong(self, users, num: int, products, offsets=None) -> dict:
+        """The num best products for each user among the given product ids only (mf_recommend_among).  offsets
+        None: `products` is one list every user ranks (an allow-list); otherwise user j ranks products[offsets[j] :
+        offsets[j + 1]].  Returns {position j: [(user, product, score), ...]} -- keyed by position, since a user
+        may be asked twice with different lists."""
+        self._require_fit()
+        users = L.as_i32(users)
+        ids, sc, cnt = self._ctx.recommend_among(users, num, products, offsets=offsets, side=L.SIDE_USER)
+        return {j: [(int(u), int(ids[j, x]), float(sc[j, x])) for x in range(int(cnt[j]))]
+                for j, u in enumerate(users)}
+
     def rmse(self, labeled) -> Tuple[float, int]:
         self._require_fit()
         u, i, r = _columns(labeled)
