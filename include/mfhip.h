@@ -888,6 +888,85 @@ int mf_online_prequential_seen(mf_ctx* ctx, const int32_t* users, const int32_t*
                                int32_t negatives, double negative_rating, int64_t seed, int64_t first_event,
                                int32_t* sampled_items_out /* [n * negatives] or NULL */,
                                int add_events);
+/* BPR ranking training (Bayesian personalised ranking, Rendle et al. 2009) on the resident seen set, as
+   synchronous minibatches.  A step takes `batch` slots; a slot is a triple (user row u, positive item row i,
+   negative item row j) or void.  Every gradient of a step is taken from the model as the step found it, and
+   every touched row is written once, from a sum taken in a fixed order: no floating-point atomics, and the
+   result is defined operation by operation below, so that it can be replayed bit for bit (mfhip/bpr.py).
+   T is float on a fast context and double on a deterministic one; lr and lambda are rounded to T once.
+
+   The draw (mf_bpr_run).  The table is the seen set's user-major one: per user factor row its distinct item
+   rows, ascending, `pairs` entries in all, entry e belonging to the row with off[row] <= e < off[row + 1];
+   pool = the item rows the model holds.  Draw r of slot s of step t:
+       z = (uint64)seed + 0x9E3779B97F4A7C15 * (t * 2^38 + s * 64 + r + 1)   (mod 2^64),
+   then the SplitMix64 finaliser of mf_online_update_sampled.  r = 0 is the positive: entry e = (z * pairs) >>
+   64 of the table, u = its row, i = the entry.  r = 1 .. 1 + redraws are negatives: c = ((z >> 32) * (pool -
+   1)) >> 32, row = c + (c >= i); the first one that u's table row does not hold is j.  If u holds all of them
+   the slot is void; with pool == 1 or an empty set every slot is void.  A draw depends on (seed, t, s, r) and
+   the table alone, not on the batch size or any other slot.  The library keeps no counter: the caller advances
+   first_step, as first_event of mf_online_update_sampled.  mf_bpr_draws gives, with no GPU, z_out[s * (2 +
+   redraws) + 0] = e and z_out[s * (2 + redraws) + r] = c of draw r >= 1 (pairs == 0: e = 0; pool == 1: c = 0).
+
+   One step.  All reads see the model as the step found it.  No operation is fused: every product is rounded
+   before it is added.
+   1. d[f] = q_i[f] - q_j[f].
+   2. x = p_u . d in 64 partials: partial l is the chain ((0 + p[l] d[l]) + p[l + 64] d[l + 64]) + ... over f = l,
+      l + 64, l + 128, l + 192 below k (0 if there is none); the partials are then added pairwise, v[l] = v[l] +
+      v[l ^ 32] for every l at once, then the same with 16, 8, 4, 2, 1; x = v[0].  (k <= 256.)
+   3. g = T(1 / (1 + E(x))) with x widened to f64 and E(x) evaluated in f64: a NaN stays; x is clamped to [-40,
+      40]; n = rint(x * 1.4426950408889634); r = (x - n * 6.93147180369123816490e-01) - n *
+      1.90821492927058770002e-10; P = the polynomial sum_{i <= 13} r^i / i! by Horner's rule from the coefficient
+      1 / 13! down, each step one multiplication and one addition, the coefficients being the f64 quotients 1.0 /
+      i!; E = ldexp(P, n).  Measured against numpy.exp on [-40, 40]: a largest relative difference of 2.22e-16.
+   4. User row a, over its non-void slots in ascending s (n_a of them): per factor a chain from 0, acc = acc +
+      g_s * d_s[f].  A segment of more than 1,024 slots takes one such chain per 1,024 consecutive slots of it
+      and then adds the chain results to 0 in ascending order.  With c = 1, m = n_a (MF_BPR_SCALE_SUM) or c =
+      T(1) / T(n_a), m = 1 (MF_BPR_SCALE_MEAN): p'[f] = p[f] + lr * (c * acc[f] - (lambda * T(m)) * p[f]), lambda *
+      T(m) rounded once, then the two products, the difference, the product with lr, and the sum.
+   5. Item row b the same, over its entries in ascending (s, positive before negative): + g_s * p_u[f] where b is
+      slot s's positive, - g_s * p_u[f] (the product subtracted) where it is its negative; n_b counts both kinds.
+   6. Both sides are computed from the model as the step found it; neither sees the other's new rows.
+
+   Scale rules.  SUM is the textbook sum of per-triple steps and suits batches in which a row gathers a few
+   slots per step (up to a few thousand slots on 10^2 .. 10^3 rows, any batch on a large catalogue); its step
+   grows with a row's count, and at ~100 slots per row (lr 0.05) the factors overflow.  MEAN divides a row's
+   step by its count, so it holds for any batch, with a learning rate about ten times SUM's.
+
+   mf_bpr_run runs steps first_step .. first_step + steps - 1, queued with no host synchronisation between
+   them; *out (may be NULL) receives the counts summed over the call: slots = steps * batch, the void ones, and
+   the rows written per side (a row counts once per step that writes it).  mf_bpr_step_triples runs one step on
+   n caller-given triples of ids (n <= 2^24), resolved on the device: a triple naming an unknown id or with
+   pos == neg is void, counted and with no other effect; batch, redraws and seed are not read.  mf_bpr_fit
+   gives the unseen ids of the n pairs rows under mf_als_prepare's insertion rules, their initial values
+   multiplied by init_scale in f64 before the rounding to T (rows already held are kept), then is
+   mf_seen_set(users, items, n) and mf_bpr_run(first_step = 0).
+   State.  Single device, single process: MF_ERR_STATE on a rank-mode or multi-device context, and from
+   mf_bpr_run without a seen set.  MF_ERR_NOT_FITTED from mf_bpr_step_triples on a context with no model.
+   MF_ERR_INVALID: a NULL context or params, a NULL array with a positive count, lr not finite or <= 0, lambda
+   not finite or < 0, an unknown scale, batch outside 1 .. 2^24, redraws outside 0 .. 62, a negative count or
+   step, a step at or past 2^26, k > 256, init_scale not finite.  All validation runs before anything changes.
+   The seen set, the ALS data and its half-sweep counter, a prepared DSGD schedule and mf_als_nonneg_stats
+   stay untouched by mf_bpr_run and mf_bpr_step_triples, and rows that no non-void slot names keep their bits. */
+#define MF_BPR_SCALE_SUM  0
+#define MF_BPR_SCALE_MEAN 1
+typedef struct mf_bpr_params {
+  double lr, lambda;
+  int32_t batch;      /* slots per step, 1 .. 2^24 */
+  int32_t scale;      /* MF_BPR_SCALE_* */
+  int32_t redraws;    /* 0 .. 62: further draws of a negative the user has seen */
+  int32_t reserved0;
+  int64_t seed;
+  int32_t reserved[4];
+} mf_bpr_params;
+typedef struct mf_bpr_stats { int64_t slots, void_slots, user_rows_written, item_rows_written; } mf_bpr_stats;
+int mf_bpr_run(mf_ctx* ctx, const mf_bpr_params* params, int64_t first_step, int64_t steps,
+               mf_bpr_stats* out /* or NULL */);
+int mf_bpr_step_triples(mf_ctx* ctx, const mf_bpr_params* params, const int32_t* users, const int32_t* pos_items,
+                        const int32_t* neg_items, int64_t n, mf_bpr_stats* out /* or NULL */);
+int mf_bpr_draws(int64_t seed, int64_t step, int32_t batch, int32_t redraws, int64_t pairs, int64_t pool,
+                 uint64_t* z_out /* batch x (2 + redraws) */);
+int mf_bpr_fit(mf_ctx* ctx, const int32_t* users, const int32_t* items, int64_t n, double init_scale,
+               const mf_bpr_params* params, int64_t steps, mf_bpr_stats* out /* or NULL */);
 /* Vectors for specific ids (found[j] = 0 for unknown ids). */
 int mf_lookup(mf_ctx* ctx, int side, const int32_t* ids, int64_t n, double* vecs_out,
               uint8_t* found);

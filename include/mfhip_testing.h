@@ -158,6 +158,13 @@ int mf_debug_seen_csr(mf_ctx* ctx, int side, int32_t* row_ids_out, int64_t* off_
    = i + #(old keys < novel[i]), the positions in the merged arrays; novel_pos_out has room for n_batch. */
 int mf_debug_seen_merge_placement(const uint64_t* old_keys, int64_t n_old, const uint64_t* batch_keys, int64_t n_batch,
                                   int64_t* old_pos_out, int64_t* novel_pos_out, int64_t* n_novel_out);
+/* mf_debug_bpr_triples: the triples of the last step mf_bpr_run or mf_bpr_step_triples ran on the device, as
+   factor rows, copied back: *n_out = its slots, users_out / pos_out / neg_out [*n_out] = the slot's rows, -1 in
+   all three for a void slot.  A call with steps == 0 changes nothing here: an earlier step's triples stay.  A call
+   on an empty set or with pool == 1 runs no kernel and leaves none.  MF_ERR_STATE when there are none;
+   MF_ERR_CAPACITY when cap < *n_out (only *n_out is written). */
+int mf_debug_bpr_triples(mf_ctx* ctx, int32_t* users_out, int32_t* pos_out, int32_t* neg_out, int64_t cap,
+                         int64_t* n_out);
 
 #ifdef __cplusplus
 }

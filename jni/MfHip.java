@@ -186,6 +186,16 @@ public final class MfHip {
                                                   int flavour, int topN, double[] metricsOut, int[] ranksOut,
                                                   int negatives, double negRating, long seed, long firstEvent,
                                                   int[] sampledOut, boolean addEvents);
+  // BPR ranking training on the seen set (mf_bpr_run / mf_bpr_step_triples / mf_bpr_fit): synchronous minibatch
+  // steps, positives drawn from the set and negatives checked against it on the device.  scale: 0 = sum of the
+  // slots' steps per row, 1 = their mean.  The caller advances firstStep.  statsOut (may be null, length >= 4):
+  // slots, void slots, user rows written, item rows written
+  public static native void bprRun(long ctx, double lr, double lambda, int batch, int scale, int redraws, long seed,
+                                   long firstStep, long steps, double[] statsOut);
+  public static native void bprStepTriples(long ctx, double lr, double lambda, int scale, int[] users,
+                                           int[] posItems, int[] negItems, double[] statsOut);
+  public static native void bprFit(long ctx, int[] users, int[] items, double initScale, double lr, double lambda,
+                                   int batch, int scale, int redraws, long seed, long steps, double[] statsOut);
   public static native void blockUpdate(long ctx, double[] r, int[] uidx, int[] iidx,
                                         double[] users, int[] uomega, double[] items, int[] iomega,
                                         int k, int iteration, int ratingBlockId, long seed,

@@ -768,6 +768,79 @@ JNIEXPORT jlong JNICALL JFN(seenCount)(JNIEnv* env, jclass c, jlong h) {
   return (jlong)pairs;
 }
 
+/* ---- BPR training on the seen set (mf_bpr_run, mf_bpr_step_triples, mf_bpr_fit) ----
+   statsOut (may be null, length >= 4): slots, void slots, user rows written, item rows written (exact in a
+   double below 2^53). */
+static mf_bpr_params bpr_params_of(jdouble lr, jdouble lambda, jint batch, jint scale, jint redraws, jlong seed) {
+  mf_bpr_params p = {0};
+  p.lr = lr;
+  p.lambda = lambda;
+  p.batch = batch;
+  p.scale = scale;
+  p.redraws = redraws;
+  p.seed = seed;
+  return p;
+}
+
+static void bpr_finish(JNIEnv* env, int st, const mf_bpr_stats* s, jdoubleArray statsOut) {
+  if (st == MF_OK && statsOut) {
+    Elems eo;
+    if (acquire(env, &eo, statsOut, kDouble)) return;
+    double* o = (double*)eo.p;
+    o[0] = (double)s->slots;
+    o[1] = (double)s->void_slots;
+    o[2] = (double)s->user_rows_written;
+    o[3] = (double)s->item_rows_written;
+    release(env, &eo, 0);
+  }
+  check(env, st);
+}
+
+JNIEXPORT void JNICALL JFN(bprRun)(JNIEnv* env, jclass c, jlong h, jdouble lr, jdouble lambda, jint batch, jint scale,
+                                   jint redraws, jlong seed, jlong firstStep, jlong steps, jdoubleArray statsOut) {
+  if (require(env, !statsOut || len(env, statsOut) >= 4, "statsOut must hold 4 entries")) return;
+  const mf_bpr_params p = bpr_params_of(lr, lambda, batch, scale, redraws, seed);
+  mf_bpr_stats s = {0, 0, 0, 0};
+  bpr_finish(env, mf_bpr_run(CTX(h), &p, firstStep, steps, &s), &s, statsOut);
+}
+
+JNIEXPORT void JNICALL JFN(bprStepTriples)(JNIEnv* env, jclass c, jlong h, jdouble lr, jdouble lambda, jint scale,
+                                           jintArray u, jintArray pos, jintArray neg, jdoubleArray statsOut) {
+  if (require(env, u && pos && neg && len(env, u) == len(env, pos) && len(env, u) == len(env, neg),
+              "users, posItems and negItems must match in length"))
+    return;
+  if (require(env, !statsOut || len(env, statsOut) >= 4, "statsOut must hold 4 entries")) return;
+  const jsize n = len(env, u);
+  Elems e[3];
+  const jarray arr[3] = {u, pos, neg};
+  const int kind[3] = {kInt, kInt, kInt};
+  if (acquire_all(env, e, arr, kind, 3)) return;
+  const mf_bpr_params p = bpr_params_of(lr, lambda, 1, scale, 0, 0);
+  mf_bpr_stats s = {0, 0, 0, 0};
+  int st = mf_bpr_step_triples(CTX(h), &p, n ? (const int32_t*)e[0].p : NULL, n ? (const int32_t*)e[1].p : NULL,
+                               n ? (const int32_t*)e[2].p : NULL, n, &s);
+  for (int x = 2; x >= 0; --x) release(env, &e[x], JNI_ABORT);
+  bpr_finish(env, st, &s, statsOut);
+}
+
+JNIEXPORT void JNICALL JFN(bprFit)(JNIEnv* env, jclass c, jlong h, jintArray u, jintArray i, jdouble initScale,
+                                   jdouble lr, jdouble lambda, jint batch, jint scale, jint redraws, jlong seed,
+                                   jlong steps, jdoubleArray statsOut) {
+  if (require(env, u && i && len(env, u) == len(env, i), "users and items must match in length")) return;
+  if (require(env, !statsOut || len(env, statsOut) >= 4, "statsOut must hold 4 entries")) return;
+  const jsize n = len(env, u);
+  Elems e[2];
+  const jarray arr[2] = {u, i};
+  const int kind[2] = {kInt, kInt};
+  if (acquire_all(env, e, arr, kind, 2)) return;
+  const mf_bpr_params p = bpr_params_of(lr, lambda, batch, scale, redraws, seed);
+  mf_bpr_stats s = {0, 0, 0, 0};
+  int st = mf_bpr_fit(CTX(h), n ? (const int32_t*)e[0].p : NULL, n ? (const int32_t*)e[1].p : NULL, n, initScale, &p,
+                      steps, &s);
+  for (int x = 1; x >= 0; --x) release(env, &e[x], JNI_ABORT);
+  bpr_finish(env, st, &s, statsOut);
+}
+
 JNIEXPORT void JNICALL JFN(recommendSeen)(JNIEnv* env, jclass c, jlong h, jint side, jintArray q, jint top,
                                           jintArray ids, jdoubleArray scores, jintArray counts) {
   if (require(env, q && ids && counts, "queries, idsOut and countsOut must not be null")) return;

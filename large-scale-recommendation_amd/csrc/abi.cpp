@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 
+#include "bpr_draw.hpp"
 #include "common.hpp"
 #include "context.hpp"
 #include "jvm_random.hpp"
@@ -606,6 +607,73 @@ int mf_debug_seen_merge_placement(const uint64_t* old_keys, int64_t n_old, const
     MF_REQUIRE(n_novel_out && (n_old == 0 || (old_keys && old_pos_out)) && (n_batch == 0 || (batch_keys && novel_pos_out)),
                "null argument");
     seen_merge_placement(old_keys, n_old, batch_keys, n_batch, old_pos_out, novel_pos_out, n_novel_out);
+  });
+}
+
+// ---- BPR training on the seen set ---------------------------------------------------------------------------
+int mf_bpr_run(mf_ctx* ctx, const mf_bpr_params* params, int64_t first_step, int64_t steps, mf_bpr_stats* out) {
+  return guarded([&] {
+    MF_REQUIRE(ctx && params, "null argument");
+    bpr_check_params(*params, true);
+    bpr_check_steps(first_step, steps);
+    bpr_run(ctx, *params, first_step, steps, out);
+  });
+}
+
+int mf_bpr_step_triples(mf_ctx* ctx, const mf_bpr_params* params, const int32_t* users, const int32_t* pos_items,
+                        const int32_t* neg_items, int64_t n, mf_bpr_stats* out) {
+  return guarded([&] {
+    MF_REQUIRE(ctx && params, "null argument");
+    MF_REQUIRE(n >= 0, "negative count");
+    MF_REQUIRE(n <= kBprMaxBatch, "at most 2^24 triples per step");
+    MF_REQUIRE(n == 0 || (users && pos_items && neg_items), "null triple list");
+    bpr_check_params(*params, false);
+    bpr_step_triples(ctx, *params, users, pos_items, neg_items, n, out);
+  });
+}
+
+int mf_bpr_draws(int64_t seed, int64_t step, int32_t batch, int32_t redraws, int64_t pairs, int64_t pool,
+                 uint64_t* z_out) {
+  return guarded([&] {
+    MF_REQUIRE(batch >= 1 && batch <= kBprMaxBatch, "batch must lie in 1 .. 2^24");
+    MF_REQUIRE(redraws >= 0 && redraws <= kBprMaxRedraws, "redraws must lie in 0 .. " + std::to_string(kBprMaxRedraws));
+    MF_REQUIRE(step >= 0 && step < kBprMaxSteps, "step must lie in 0 .. 2^26 - 1");
+    MF_REQUIRE(pairs >= 0, "negative pair count");
+    MF_REQUIRE(pool >= 1 && pool <= (int64_t{1} << 31), "pool must be in [1, 2^31]");
+    MF_REQUIRE(z_out, "null argument");
+    const int per = 2 + redraws;
+    for (int32_t s = 0; s < batch; ++s) {
+      uint64_t* z = z_out + static_cast<size_t>(s) * per;
+      const auto bits = [&](int r) {
+        return bpr_draw_bits(static_cast<uint64_t>(seed), static_cast<uint64_t>(step), static_cast<uint32_t>(s),
+                             static_cast<uint32_t>(r));
+      };
+      z[0] = bpr_entry(bits(0), static_cast<uint64_t>(pairs));
+      for (int r = 1; r < per; ++r) z[r] = pool >= 2 ? bpr_neg_rank(bits(r), static_cast<uint32_t>(pool)) : 0;
+    }
+  });
+}
+
+int mf_bpr_fit(mf_ctx* ctx, const int32_t* users, const int32_t* items, int64_t n, double init_scale,
+               const mf_bpr_params* params, int64_t steps, mf_bpr_stats* out) {
+  return guarded([&] {
+    MF_REQUIRE(ctx && params, "null argument");
+    MF_REQUIRE(n >= 0, "negative count");
+    MF_REQUIRE(n == 0 || (users && items), "null pair list");
+    MF_REQUIRE(n < (int64_t{1} << 31) - 1, "fewer than 2^31 - 1 pairs per call");
+    MF_REQUIRE(std::isfinite(init_scale), "init_scale must be finite");
+    bpr_check_params(*params, true);
+    bpr_check_steps(0, steps);
+    bpr_fit(ctx, users, items, n, init_scale, *params, steps, out);
+  });
+}
+
+int mf_debug_bpr_triples(mf_ctx* ctx, int32_t* users_out, int32_t* pos_out, int32_t* neg_out, int64_t cap,
+                         int64_t* n_out) {
+  return guarded([&] {
+    MF_REQUIRE(ctx && n_out, "null argument");
+    MF_REQUIRE(cap >= 0 && (cap == 0 || (users_out && pos_out && neg_out)), "null argument");
+    bpr_debug_triples(ctx, users_out, pos_out, neg_out, cap, n_out);
   });
 }
 

@@ -184,11 +184,11 @@ void als_build_side(mf_ctx* ctx, Shard& s, int side, const std::vector<uint32_t>
   als_work_lists(ctx, s, side, std::move(off), std::move(npos));
 }
 
-// The factor rows of a rating list for mf_als_prepare and mf_als_append.  ur / ir hold the rows of the ids
-// the model has (lookup_rows); ids it does not have take new rows in order of appearance, the user looked
-// at before the item within one rating, with the initial values a DSGD fit gives them.
+}  // namespace
+
+// (context.hpp)
 void als_insert_rows(mf_ctx* ctx, Shard& s, const int32_t* u, const int32_t* i, int64_t n, std::vector<uint32_t>& ur,
-                     std::vector<uint32_t>& ir) {
+                     std::vector<uint32_t>& ir, double init_scale) {
   const int k = ctx->P.num_factors;
   const int64_t u0 = ctx->U.rows(), i0 = ctx->I.rows();
   std::vector<int32_t> fu, fi;
@@ -211,11 +211,11 @@ void als_insert_rows(mf_ctx* ctx, Shard& s, const int32_t* u, const int32_t* i, 
     if (fresh.empty()) continue;
     std::vector<double> vec;
     init_vectors(fresh.data(), static_cast<int64_t>(fresh.size()), k, true, ctx->init_seed, vec);
+    if (init_scale != 1.0)
+      for (double& v : vec) v *= init_scale;
     upload_rows(ctx, s, side, side == kSideU ? u0 : i0, vec.data(), static_cast<int64_t>(fresh.size()));
   }
 }
-
-}  // namespace
 
 void als_prepare(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n) {
   MF_REQUIRE(n >= 0, "negative rating count");

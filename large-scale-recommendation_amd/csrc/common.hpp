@@ -226,6 +226,19 @@ struct FoldinScratch {
   DevBuf in, flag, wp, miss, tmp, cols, vals, cnt, x, iota, stats;
 };
 
+// Scratch of the BPR trainer (bpr.cpp, kernels_bpr.hip), sized once per call by bpr_reserve.  trip: the step's
+// triples as rows (user rows, positive rows, negative rows; a void slot has kRowMiss for its user); g: the
+// weight per slot; ukey / ikey and their sorted copies; urows: the new user rows until the commit, indexed by
+// row (by_row) or by the segment's first sorted position; csum: the chunk sums of segments longer than a chunk;
+// stats: the four 64-bit counters of mf_bpr_stats; tmp: the sorts' storage.  last_n: the slots of the last step
+// run, whose triples trip still holds (mf_debug_bpr_triples; -1: no step yet, or a call on an empty set or a pool of
+// one row since, which launches nothing; a call with steps == 0 leaves it as it is).
+struct BprScratch {
+  DevBuf trip, g, ukey, ukey2, ikey, ikey2, urows, csum, stats, tmp;
+  bool by_row = true;
+  int64_t last_n = -1;
+};
+
 // Runtime switches.  The library reads five environment variables:
 //   MFHIP_THREADS / OMP_NUM_THREADS  host workers (below);
 //   MFHIP_TIMING                     prepare's, mf_rank_eval's and the fold-in calls' phase timings on stderr;

@@ -169,6 +169,8 @@ struct Shard {
   DevBuf als_sub_items, als_sub_splits, als_sub_work;
   // ... mf_als_foldin / mf_recommend_foldin (which also use als_sub_*, the rec_* buffers and rank_sc)
   FoldinScratch fold;
+  // BPR training (mf_bpr_run, mf_bpr_step_triples)
+  BprScratch bpr;
   // profiling
   std::vector<hipEvent_t> ev;
   size_t ev_used = 0;
@@ -536,6 +538,24 @@ void als_debug_csr(mf_ctx* ctx, int side, int64_t* off_out, int32_t* cols_out, d
 // the sorted keys; batch_pos states the same rule for mf_debug_als_append_placement.
 void als_append_placement(const int64_t* old_off, int64_t old_rows, const uint32_t* batch_row, int64_t n,
                           int64_t new_rows, int64_t* new_off, int64_t* batch_pos);
+// The factor rows of a rating list for mf_als_prepare, mf_als_append and mf_bpr_fit.  ur / ir hold the rows of
+// the ids the model has (lookup_rows); ids it does not have take new rows in order of appearance, the user
+// looked at before the item within one rating, with the initial values a DSGD fit gives them times init_scale
+// (in f64, before the rounding to the context's precision).
+void als_insert_rows(mf_ctx* ctx, Shard& s, const int32_t* u, const int32_t* i, int64_t n, std::vector<uint32_t>& ur,
+                     std::vector<uint32_t>& ir, double init_scale = 1.0);
+
+// bpr.cpp: BPR training on the resident seen set.  The argument checks that read nothing of the context are
+// bpr_check_params'; every entry validates before it changes anything.
+void bpr_check_params(const mf_bpr_params& p, bool sampled);
+void bpr_check_steps(int64_t first_step, int64_t steps);
+void bpr_run(mf_ctx* ctx, const mf_bpr_params& p, int64_t first_step, int64_t steps, mf_bpr_stats* out);
+void bpr_step_triples(mf_ctx* ctx, const mf_bpr_params& p, const int32_t* u, const int32_t* pos, const int32_t* neg,
+                      int64_t n, mf_bpr_stats* out);
+void bpr_fit(mf_ctx* ctx, const int32_t* u, const int32_t* i, int64_t n, double init_scale, const mf_bpr_params& p,
+             int64_t steps, mf_bpr_stats* out);
+void bpr_debug_triples(mf_ctx* ctx, int32_t* u, int32_t* pos, int32_t* neg, int64_t cap, int64_t* n_out);
+
 // nnls.cpp: mf_nnls_solve
 void nnls_solve_host(int32_t k, const double* A, const double* b, bool f64, double* x_out, int32_t* iters_out,
                      int32_t* reason_out);

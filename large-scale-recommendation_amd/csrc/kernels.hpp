@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <functional>
 #include <type_traits>
 
 #include "plan.hpp"
@@ -651,5 +652,33 @@ struct FoldinLaunch {
   uint64_t* keys;
 };
 void launch_foldin_compact(const FoldinLaunch& L, FoldinScratch& sc);
+
+// ---- kernels_bpr.hip: BPR minibatch steps (mf_bpr_run, mf_bpr_step_triples) ------------------------
+// One step over the `batch` triples in sc.trip, as include/mfhip.h defines it: weights from the model as the step
+// found it, every touched row written once.  P / Q: the user / item slabs in the context's precision.  bpr_reserve
+// sizes the scratch for steps of `batch` slots (it drains the stream; the steps after it allocate nothing);
+// launch_bpr_draw fills sc.trip from the seen set's user-major table (off[table_rows + 1], ent, pairs > 0 entries;
+// item_rows >= 2), launch_bpr_resolve from caller-given triples as launch_id_lookup_one left them in sc.trip.
+// launch_bpr_step adds the step's counts to sc.stats (void slots, user rows, item rows at [1], [2], [3]); lap (may
+// be empty) is called with a phase's name after the phase's launches: the caller's phase clock (bpr.cpp).
+struct BprScratch;
+struct BprStep {
+  hipStream_t st;
+  int64_t batch;
+  void* P;
+  void* Q;
+  uint32_t user_rows, item_rows;
+  int k;
+  bool f64;
+  double lr, lambda;
+  bool mean;
+  int64_t chunk;
+};
+void bpr_reserve(hipStream_t st, BprScratch& sc, int64_t batch, int64_t user_rows, int k, size_t es, int64_t chunk);
+void launch_bpr_draw(const BprStep& L, BprScratch& sc, const int64_t* off, const int32_t* ent, int64_t table_rows,
+                     int64_t pairs, int64_t seed, int64_t step, int32_t redraws);
+void launch_bpr_resolve(const BprStep& L, BprScratch& sc);
+using BprLap = std::function<void(const char*)>;
+void launch_bpr_step(const BprStep& L, BprScratch& sc, const BprLap& lap = BprLap());
 
 }  // namespace mfhip

@@ -50,6 +50,10 @@ RANK_NMETRICS = 6  # precision, recall, ap, ndcg, rr, hit: a per-query row of mf
 PAIR_RANK_COLD = -1      # mf_pair_ranks: the model does not hold the query id or the candidate id
 PAIR_RANK_EXCLUDED = -2  # ... the pair itself is in the exclusion list
 NEG_MAX = 64             # mf_online_update_sampled: negatives per event at most
+BPR_SCALE_SUM = 0        # mf_bpr_run: a row's step is the sum of its slots' steps
+BPR_SCALE_MEAN = 1       # ... divided by the row's slot count
+BPR_MAX_REDRAWS = 62
+BPR_MAX_BATCH = 1 << 24
 
 
 class _Seen:
@@ -148,6 +152,23 @@ class mf_als_nonneg_stats(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("rows", "iterations", "max_iterations", "capped", "reason2", "nan_rows")]
 
 
+class mf_bpr_params(C.Structure):
+    _fields_ = [
+        ("lr", C.c_double),
+        ("lambda_", C.c_double),
+        ("batch", C.c_int32),
+        ("scale", C.c_int32),
+        ("redraws", C.c_int32),
+        ("reserved0", C.c_int32),
+        ("seed", C.c_int64),
+        ("reserved", C.c_int32 * 4),
+    ]
+
+
+class mf_bpr_stats(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("slots", "void_slots", "user_rows_written", "item_rows_written")]
+
+
 class mf_als_solve(C.Structure):
     """One of the eight kinds of half-sweep, for mf_als_run_rows / mf_als_update."""
     _fields_ = [
@@ -179,7 +200,7 @@ EXPORTS = [
     "mf_seen_set", "mf_seen_add", "mf_seen_from_als", "mf_seen_clear", "mf_seen_count", "mf_recommend_seen",
     "mf_rank_eval_seen", "mf_pair_ranks_seen", "mf_online_prequential_seen", "mf_similar", "mf_recommend_vectors",
     "mf_als_remove", "mf_als_remove_rows", "mf_als_retract", "mf_seen_remove", "mf_als_foldin", "mf_recommend_foldin",
-    "mf_recommend_among",
+    "mf_recommend_among", "mf_bpr_run", "mf_bpr_step_triples", "mf_bpr_draws", "mf_bpr_fit",
 ]
 # The test hooks include/mfhip_testing.h declares (not product surface; same library).
 TESTING_EXPORTS = [
@@ -189,6 +210,7 @@ TESTING_EXPORTS = [
     "mf_debug_det_slot_table", "mf_debug_sys_placement", "mf_debug_rank_csr", "mf_debug_als_cg_matvec",
     "mf_debug_als_cg_capacity", "mf_debug_als_nnls_row", "mf_debug_als_csr", "mf_debug_als_append_placement",
     "mf_debug_seen_csr", "mf_debug_seen_merge_placement", "mf_debug_als_remove_select",
+    "mf_debug_bpr_triples",
 ]
 
 _i32p = C.POINTER(C.c_int32)
@@ -340,6 +362,14 @@ def lib() -> C.CDLL:
                                         _i64p]),
         "mf_debug_seen_merge_placement": (C.c_int, [C.POINTER(C.c_uint64), C.c_int64, C.POINTER(C.c_uint64), C.c_int64,
                                                     _i64p, _i64p, _i64p]),
+        "mf_bpr_run": (C.c_int, [_ctxp, C.POINTER(mf_bpr_params), C.c_int64, C.c_int64, C.POINTER(mf_bpr_stats)]),
+        "mf_bpr_step_triples": (C.c_int, [_ctxp, C.POINTER(mf_bpr_params), _i32p, _i32p, _i32p, C.c_int64,
+                                          C.POINTER(mf_bpr_stats)]),
+        "mf_bpr_draws": (C.c_int, [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
+                                   C.POINTER(C.c_uint64)]),
+        "mf_bpr_fit": (C.c_int, [_ctxp, _i32p, _i32p, C.c_int64, C.c_double, C.POINTER(mf_bpr_params), C.c_int64,
+                                 C.POINTER(mf_bpr_stats)]),
+        "mf_debug_bpr_triples": (C.c_int, [_ctxp, _i32p, _i32p, _i32p, C.c_int64, _i64p]),
         "mf_debug_ring_schedule": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, _i32p, _i32p, _i32p, _i32p]),
         "mf_debug_det_slot_table": (C.c_int, [_i64p, _i32p, _i32p, C.c_int64, C.c_int64, C.c_int32, C.c_int64, _i64p,
                                               _i32p, _i32p, _i64p]),

@@ -727,6 +727,60 @@ class Context:
                                         ptr(ent, C.c_int32), ptr(eid, C.c_int32), rows, nnz, C.byref(r), C.byref(m)))
         return rid[:r.value], off[:r.value + 1], ent[:m.value], eid[:m.value]
 
+    # -- BPR training on the seen set ---------------------------------------------
+    @staticmethod
+    def bpr_params(lr: float, lam: float, batch: int = 1, scale: int = L.BPR_SCALE_SUM, redraws: int = 0,
+                   seed: int = 0) -> L.mf_bpr_params:
+        p = L.mf_bpr_params()
+        p.lr, p.lambda_, p.batch, p.scale, p.redraws, p.seed = float(lr), float(lam), int(batch), int(scale), \
+            int(redraws), int(seed)
+        return p
+
+    @staticmethod
+    def _bpr_stats(st: L.mf_bpr_stats) -> dict:
+        return {n: int(getattr(st, n)) for n, _ in L.mf_bpr_stats._fields_}
+
+    def bpr_run(self, params: L.mf_bpr_params, first_step: int, steps: int) -> dict:
+        """mf_bpr_run: minibatch steps first_step .. first_step + steps - 1 of BPR on the resident seen set, all
+        queued at once.  The caller advances first_step.  Returns the call's mf_bpr_stats as a dict."""
+        st = L.mf_bpr_stats()
+        check(L.lib().mf_bpr_run(self._h, C.byref(params), int(first_step), int(steps), C.byref(st)))
+        return self._bpr_stats(st)
+
+    def bpr_step_triples(self, params: L.mf_bpr_params, users, pos_items, neg_items) -> dict:
+        """mf_bpr_step_triples: one step on the caller's (user, positive, negative) ids; a triple with an unknown
+        id or pos == neg is void.  params.batch / redraws / seed are not read."""
+        u, a, b = as_i32(users), as_i32(pos_items), as_i32(neg_items)
+        n = same_length(u, a, b)
+        st = L.mf_bpr_stats()
+        check(L.lib().mf_bpr_step_triples(self._h, C.byref(params), ptr(u, C.c_int32) if n else None,
+                                          ptr(a, C.c_int32) if n else None, ptr(b, C.c_int32) if n else None, n,
+                                          C.byref(st)))
+        return self._bpr_stats(st)
+
+    def bpr_fit(self, u, i, params: L.mf_bpr_params, steps: int, init_scale: float = 0.1) -> dict:
+        """mf_bpr_fit: rows for the unseen ids (initial values times init_scale), the pairs as the seen set, then
+        `steps` steps from step 0."""
+        u, i = as_i32(u), as_i32(i)
+        n = same_length(u, i)
+        st = L.mf_bpr_stats()
+        check(L.lib().mf_bpr_fit(self._h, ptr(u, C.c_int32) if n else None, ptr(i, C.c_int32) if n else None, n,
+                                 float(init_scale), C.byref(params), int(steps), C.byref(st)))
+        return self._bpr_stats(st)
+
+    def debug_bpr_triples(self):
+        """mf_debug_bpr_triples: the last step's triples as factor rows (users, positives, negatives), -1 in all
+        three for a void slot."""
+        n = C.c_int64(0)
+        st = L.lib().mf_debug_bpr_triples(self._h, None, None, None, 0, C.byref(n))
+        if st not in (L.MF_OK, L.MF_ERR_CAPACITY):
+            check(st)
+        m = max(int(n.value), 1)
+        u, a, b = (np.zeros(m, np.int32) for _ in range(3))
+        check(L.lib().mf_debug_bpr_triples(self._h, ptr(u, C.c_int32), ptr(a, C.c_int32), ptr(b, C.c_int32), m,
+                                           C.byref(n)))
+        return u[:n.value], a[:n.value], b[:n.value]
+
     # -- online ----------------------------------------------------------------
     def online_update(self, u, i, r, flavour: int = L.ONLINE_NEXT_FACTORS, num_partitions: int = 0):
         u, i, r = as_i32(u), as_i32(i), as_f64(r)
