@@ -753,6 +753,63 @@ int mf_als_retract(mf_ctx* ctx, const int32_t* users, const int32_t* items, int6
                    int32_t rounds, uint8_t* found_out /* [n] or NULL */, int64_t* removed_out /* may be NULL */,
                    int64_t* solved_users_out /* may be NULL */, int64_t* solved_items_out /* may be NULL */);
 
+/* The value of the objective the ALS half-sweeps minimise, on the device, from what mf_als_prepare left there:
+   both CSRs, the work lists, the rated-row lists and the factors.  `how` gives lambda, reg, implicit and alpha;
+   solver and cg_steps are not read.  The value is that of the prepared data as it stands (after any
+   mf_als_append or mf_als_remove) at the factors as they stand.  Nothing is uploaded but the arguments, nothing
+   of the context changes (factors, half-sweep counter, seen set, mf_als_nonneg_stats and a prepared DSGD
+   schedule keep their state), and the call makes one host synchronisation.  A prepare with n = 0 gives all zeros.
+
+   The arithmetic, defined operation by operation so that it can be replayed bit for bit (mfhip/als.py
+   replay_objective).  T is float on a fast context and double on a deterministic one; alpha and lambda are
+   rounded to T once.  No operation is fused: every product is rounded before it is added.  Every sum of terms is
+   taken in f64.
+   dot64(a, b) is step 2 of the mf_bpr_* comment below, unchanged: 64 partials, partial l the chain from 0 over f =
+       l, l + 64, ... below k in ascending order, each product rounded before it is added; then v[l] = v[l] +
+       v[l ^ 32] for every l at once, then the same with 16, 8, 4, 2, 1; the result is v[0].  (k <= 256.)
+   sum64(v[0 .. n)), in f64: lane l chains v[l], v[l + 64], ... from 0.0 in ascending order; then the same
+       butterfly; the result is lane 0.
+   fit walks the USER side's CSR and work list.  For rating j of user row a (CSR order, duplicates included), with
+       q_j the item row: d = dot64(x_a, q_j).  Explicit: e = r - d, t = e * e.  Implicit: w = alpha * |r|; if r >
+       0: c = 1 + w, e = 1 - d, t = (c * e) * e - d * d; else t = (w * d) * d -- so a rating of 0 adds exactly 0,
+       MLlib's rule as in mf_als_run_implicit.  t is widened to f64.  A work item is a whole row of at most
+       als_chunk ratings (mf_als_prepare's chunk length, 16,384) or one chunk of a longer row; it yields sum64 of
+       its terms in CSR order.  fit = sum64 of the work items' sums in work-list order (rows ascending, a row's
+       chunks ascending).  The chunk length is therefore part of the arithmetic, as it is for mf_bpr_run; the
+       launch batch length is not.
+   unobserved (implicit only; 0 otherwise).  GU and GI are the two sides' Gram matrices exactly as the implicit
+       half-sweeps form them over each side's rated rows.  unobserved = sum64 over e = f * k + g (f, g < k) of
+       GU[f][g] * GI[f][g], the product taken in T and then widened.  This is tr(GU GI) = the sum over rated users
+       a and rated items b of (x_a . y_b)^2.  A pair rated m times counts once here and m times in fit.
+   reg.  Per rated row a of a side, in ascending row order: dot64(x_a, x_a), widened; for MF_ALS_REG_WEIGHTED
+       multiplied in f64 by the row's rating count n_a, or when implicit by its count of ratings > 0.  R_side =
+       sum64 of these; reg_side = (double)lambda_T * R_side.  Rows with no rating take no part anywhere: the
+       half-sweeps never touch them.
+   total = ((fit + unobserved) + reg_user) + reg_item.  NaN and infinity propagate; nothing is masked.
+
+   Errors.  MF_ERR_INVALID: NULL ctx, how or out; lambda not finite or below 0 (0 is valid here and gives the
+   unregularised loss); an unknown reg; alpha below 0 or not finite when implicit; k above 256.  MF_ERR_STATE: as
+   mf_als_run_rows.
+
+   mf_als_run_until is, by definition: every argument checked; J_0 = mf_als_objective(how).total; then for t = 1 ..
+   max_iterations: two half-sweeps of the kind `how` names (the run call's own path and counter), J_t = the
+   objective, and stop after iteration t if J_t is not finite or J_{t-1} - J_t <= rel_tol * |J_{t-1}|.
+   *iterations_out (may be NULL) = the t reached, history_out[0 .. t] (may be NULL) the J values.
+   max_iterations == 0 evaluates J_0 and changes nothing.  Errors: mf_als_objective's and the run call's (lambda >
+   0 here, cg_steps, an unknown solver), and MF_ERR_INVALID for a negative max_iterations or a rel_tol that is
+   negative or not finite; all raised before anything changes. */
+typedef struct mf_als_loss {
+  double total;       /* ((fit + unobserved) + reg_user) + reg_item */
+  double fit;         /* the sum over the prepared ratings */
+  double unobserved;  /* implicit: sum over rated users x rated items of (x.y)^2; explicit: 0 */
+  double reg_user, reg_item;
+  int64_t ratings, user_rows, item_rows;   /* entries summed; rated rows per side */
+  double reserved[4];
+} mf_als_loss;
+int mf_als_objective(mf_ctx* ctx, const mf_als_solve* how, mf_als_loss* out);
+int mf_als_run_until(mf_ctx* ctx, const mf_als_solve* how, int32_t max_iterations, double rel_tol,
+                     int32_t* iterations_out /* may be NULL */, double* history_out /* [max_iterations + 1] or NULL */);
+
 /* Exact updateLocalFactors replacement (DSGDforMF.scala:378-418) on caller buffers:
    users[nu x k], items[ni x k] are updated in place; omegas are per row.  Reentrant
    on disjoint buffers with distinct contexts, as Flink calls it per task slot. */

@@ -73,6 +73,16 @@ public final class MfHip {
   public static native void alsUpdate(long ctx, int[] users, int[] items, double[] ratings, double lambda,
                                       int reg, int implicit, double alpha, int solver, int cgSteps, int rounds,
                                       int[] solvedOut);
+  // The objective the half-sweeps minimise (mf_als_objective), on the resident data at the factors as they
+  // stand; nothing is uploaded and nothing changes.  Returns total; lossOut (may be null, length >= 8) receives
+  // total, fit, unobserved, reg_user, reg_item, ratings, user_rows, item_rows.  alsRunUntil (mf_als_run_until)
+  // runs iterations of two half-sweeps until one lowers the objective by no more than relTol times its size, at
+  // most maxIterations; returns the iterations taken; historyOut (may be null, length >= maxIterations + 1)
+  // receives the objective on entry and after every iteration.
+  public static native double alsObjective(long ctx, double lambda, int reg, int implicit, double alpha,
+                                           double[] lossOut);
+  public static native int alsRunUntil(long ctx, double lambda, int reg, int implicit, double alpha, int solver,
+                                       int cgSteps, int maxIterations, double relTol, double[] historyOut);
   // Removal (mf_als_remove / mf_als_remove_rows / mf_als_retract): entry j removes the oldest rating of the
   // pair (users[j], items[j]) still held; alsRemoveRows removes every rating of the named users or items (the
   // factor rows stay); alsRetract removes, then `rounds` times solves the batch's users and then its items.

@@ -357,6 +357,49 @@ JNIEXPORT void JNICALL JFN(alsUpdate)(JNIEnv* env, jclass c, jlong h, jintArray 
   release(env, &eo, 0);
 }
 
+/* mf_als_objective: lossOut (length >= 8) receives total, fit, unobserved, reg_user, reg_item, ratings,
+   user_rows, item_rows; the return value is total.  mf_als_run_until: historyOut (may be null, length >=
+   maxIterations + 1) receives the objective on entry and after every iteration; returns the iterations taken. */
+JNIEXPORT jdouble JNICALL JFN(alsObjective)(JNIEnv* env, jclass c, jlong h, jdouble lambda, jint reg, jint implicit,
+                                            jdouble alpha, jdoubleArray lossOut) {
+  if (require(env, !lossOut || len(env, lossOut) >= 8, "lossOut must hold 8 entries")) return 0.0;
+  const mf_als_solve how = als_how(lambda, reg, implicit, alpha, MF_ALS_SOLVER_CHOLESKY, 0);
+  mf_als_loss loss;
+  if (check(env, mf_als_objective(CTX(h), &how, &loss)) != MF_OK) return 0.0;
+  if (lossOut) {
+    Elems eo = {0};
+    if (acquire(env, &eo, lossOut, kDouble)) return 0.0;
+    double* o = (double*)eo.p;
+    o[0] = loss.total;
+    o[1] = loss.fit;
+    o[2] = loss.unobserved;
+    o[3] = loss.reg_user;
+    o[4] = loss.reg_item;
+    o[5] = (double)loss.ratings;
+    o[6] = (double)loss.user_rows;
+    o[7] = (double)loss.item_rows;
+    release(env, &eo, 0);
+  }
+  return loss.total;
+}
+
+JNIEXPORT jint JNICALL JFN(alsRunUntil)(JNIEnv* env, jclass c, jlong h, jdouble lambda, jint reg, jint implicit,
+                                        jdouble alpha, jint solver, jint cgSteps, jint maxIterations, jdouble relTol,
+                                        jdoubleArray historyOut) {
+  if (require(env, maxIterations >= 0, "maxIterations must be >= 0")) return 0;
+  if (require(env, !historyOut || (jlong)len(env, historyOut) >= (jlong)maxIterations + 1,
+              "historyOut must hold maxIterations + 1 entries"))
+    return 0;
+  const mf_als_solve how = als_how(lambda, reg, implicit, alpha, solver, cgSteps);
+  Elems eh = {0};
+  if (historyOut && acquire(env, &eh, historyOut, kDouble)) return 0;
+  int32_t t = 0;
+  int st = mf_als_run_until(CTX(h), &how, maxIterations, relTol, &t, historyOut ? (double*)eh.p : NULL);
+  if (historyOut) release(env, &eh, 0);
+  check(env, st);
+  return (jint)t;
+}
+
 /* Removal: mf_als_remove, mf_als_remove_rows, mf_als_retract.  foundOut (may be null, length >= n) receives
    0 / 1 per entry; the return value is the number of ratings removed. */
 static int acquire_all(JNIEnv* env, Elems* e, const jarray* a, const int* kind, int n);

@@ -811,6 +811,23 @@ int mf_als_update(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double*
   });
 }
 
+int mf_als_objective(mf_ctx* ctx, const mf_als_solve* how, mf_als_loss* out) {
+  return guarded([&] {
+    MF_REQUIRE(ctx && how && out, "null argument");
+    // solver and cg_steps are not read
+    als_objective(ctx, {how->lambda, how->reg, how->implicit != 0, how->implicit != 0 ? how->alpha : 0.0}, out);
+  });
+}
+
+int mf_als_run_until(mf_ctx* ctx, const mf_als_solve* how, int32_t max_iterations, double rel_tol,
+                     int32_t* iterations_out, double* history_out) {
+  return guarded([&] {
+    MF_REQUIRE(ctx, "null context");
+    const int32_t t = als_run_until(ctx, als_params_of(how), max_iterations, rel_tol, history_out);
+    if (iterations_out) *iterations_out = t;
+  });
+}
+
 extern "C++" {
 namespace {
 

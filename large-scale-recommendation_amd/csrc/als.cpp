@@ -1,6 +1,7 @@
 // als.cpp -- ALS training (mf_als_prepare / mf_als_run / mf_als_fit, their _implicit, _cg, _implicit_cg,
 // _nonneg and _implicit_nonneg variants), incremental ALS (mf_als_append / mf_als_run_rows / mf_als_update),
-// removal (mf_als_remove / mf_als_remove_rows / mf_als_retract) and their testing hooks.
+// removal (mf_als_remove / mf_als_remove_rows / mf_als_retract), the objective (mf_als_objective /
+// mf_als_run_until) and their testing hooks.
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -507,6 +508,114 @@ void als_run(mf_ctx* ctx, int64_t half_sweeps, const AlsParams& P) {
   }
   DeviceGuard g(ctx->shards[0].device);
   MF_HIP(hipStreamSynchronize(ctx->shards[0].stream));
+}
+
+// ---------------------------------------------------------------------------------------
+// The objective (mf_als_objective, kernels_als_objective.hip): a gather-and-reduce pass over the user side's
+// CSR and work list, a row-norm pass per side, and with P.implicit the two Gram matrices and their trace.
+// Everything is queued on the shard's stream and four doubles come back behind one synchronisation; nothing
+// of the context changes but scratch.
+void als_check_objective(const AlsParams& P) {
+  MF_REQUIRE(P.lambda >= 0.0 && std::isfinite(P.lambda), "the ALS objective needs a finite lambda >= 0");
+  MF_REQUIRE(P.reg == MF_ALS_REG_WEIGHTED || P.reg == MF_ALS_REG_PLAIN, "unknown ALS regularisation (reg)");
+  if (P.implicit) als_check_alpha(P.alpha);
+}
+
+namespace {
+
+// The call on an entered context (als_enter): mf_als_objective, and every J of mf_als_run_until.
+void als_objective_entered(mf_ctx* ctx, Shard& s, const AlsParams& P, struct mf_als_loss* out) {
+  std::memset(out, 0, sizeof(*out));
+  const mf_ctx::AlsSide& AU = ctx->als[kSideU];
+  const mf_ctx::AlsSide& AI = ctx->als[MF_SIDE_ITEM];
+  const int64_t n = AU.off.empty() ? 0 : AU.off.back();
+  out->ratings = n;
+  out->user_rows = AU.rated;
+  out->item_rows = AI.rated;
+  if (n == 0) return;
+  DeviceGuard g(s.device);
+  const int k = ctx->P.num_factors;
+  const int64_t n_items = static_cast<int64_t>(AU.items.size());
+  // (the stream is drained here: scratch may grow)
+  s.als_obj_part.alloc(static_cast<size_t>(std::max({n_items, AU.rated, AI.rated})) * 8);
+  s.als_obj_out.alloc(4 * 8);
+  double* const part = s.als_obj_part.as<double>();
+  double* const res = s.als_obj_out.as<double>();  // fit, unobserved, R_user, R_item
+  // MFHIP_TIMING=1: the parts on stderr, the stream drained after each (a diagnostic run)
+  PhaseClock clk;
+  auto lap = [&](const char* what) {
+    if (!clk.on) return;
+    MF_HIP(hipStreamSynchronize(s.stream));
+    clk.lap(what);
+  };
+  MF_HIP(hipMemsetAsync(res, 0, 4 * 8, s.stream));
+  launch_als_objective_fit({s.stream, s.als_items[kSideU].as<AlsItem>(), n_items, s.als_cols[kSideU].as<int32_t>(),
+                            s.als_vals[kSideU].get(), s.uf.get(), s.itf.get(), k, ctx->f64, P.implicit, P.alpha, part});
+  launch_sum64(s.stream, part, n_items, res + 0);
+  MF_HIP(hipGetLastError());
+  lap("objective fit");
+  const int weight = P.reg == MF_ALS_REG_WEIGHTED ? (P.implicit ? 2 : 1) : 0;
+  for (int side = 0; side < 2; ++side) {
+    const int64_t m = ctx->als[side].rated;
+    launch_als_objective_norms(s.stream, s.als_rated[side].as<int32_t>(), m, s.als_off[side].as<int64_t>(),
+                               s.als_vals[side].get(), side == kSideU ? s.uf.get() : s.itf.get(), k, ctx->f64, weight,
+                               part);
+    launch_sum64(s.stream, part, m, res + 2 + side);
+  }
+  MF_HIP(hipGetLastError());
+  lap("objective norms");
+  ctx->stats.kernel_launches += 6;
+  if (P.implicit) {
+    const size_t ge = als_gram_elems(k) * ctx->es;
+    s.als_obj_gram.alloc(ge);
+    als_gram_launch(ctx, s, kSideU);
+    MF_HIP(hipMemcpyAsync(s.als_obj_gram.get(), s.als_gram.get(), ge, hipMemcpyDeviceToDevice, s.stream));
+    als_gram_launch(ctx, s, MF_SIDE_ITEM);
+    launch_als_objective_trace(s.stream, s.als_obj_gram.get(), s.als_gram.get(), k, ctx->f64, res + 1);
+    MF_HIP(hipGetLastError());
+    ctx->stats.kernel_launches += 5;
+    lap("objective gram + trace");
+  }
+  double h[4];
+  MF_HIP(hipMemcpyAsync(h, res, sizeof(h), hipMemcpyDeviceToHost, s.stream));
+  MF_HIP(hipStreamSynchronize(s.stream));
+  const double lam = ctx->f64 ? P.lambda : static_cast<double>(static_cast<float>(P.lambda));
+  out->fit = h[0];
+  out->unobserved = h[1];
+  out->reg_user = lam * h[2];
+  out->reg_item = lam * h[3];
+  out->total = ((out->fit + out->unobserved) + out->reg_user) + out->reg_item;
+}
+
+}  // namespace
+
+void als_objective(mf_ctx* ctx, const AlsParams& P, struct mf_als_loss* out) {
+  als_check_objective(P);
+  Shard& s = als_enter(ctx, "mf_als_objective");
+  als_objective_entered(ctx, s, P, out);
+}
+
+int32_t als_run_until(mf_ctx* ctx, const AlsParams& P, int32_t max_iterations, double rel_tol, double* history) {
+  als_check_objective(P);
+  als_check_run(P);
+  MF_REQUIRE(max_iterations >= 0, "negative iteration count");
+  MF_REQUIRE(rel_tol >= 0.0 && std::isfinite(rel_tol), "rel_tol must be finite and >= 0");
+  Shard& s = als_enter(ctx, "mf_als_run_until");
+  struct mf_als_loss loss;
+  als_objective_entered(ctx, s, P, &loss);
+  double prev = loss.total;
+  if (history) history[0] = prev;
+  int32_t t = 0;
+  while (t < max_iterations) {
+    als_run(ctx, 2, P);
+    als_objective_entered(ctx, s, P, &loss);
+    ++t;
+    const double now = loss.total;
+    if (history) history[t] = now;
+    if (!std::isfinite(now) || prev - now <= rel_tol * std::fabs(prev)) break;
+    prev = now;
+  }
+  return t;
 }
 
 // The normal equations of one row as the kernel accumulates them (mf_debug_als_normal_eq, and with

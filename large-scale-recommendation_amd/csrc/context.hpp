@@ -167,6 +167,9 @@ struct Shard {
   AlsRemoveScratch als_rem;
   // ... mf_als_run_rows: the item, split and chunk lists of one call
   DevBuf als_sub_items, als_sub_splits, als_sub_work;
+  // ... mf_als_objective: the per-item / per-row f64 partials of one pass, the user side's G beside als_gram,
+  // and the four sums that come back
+  DevBuf als_obj_part, als_obj_gram, als_obj_out;
   // ... mf_als_foldin / mf_recommend_foldin (which also use als_sub_*, the rec_* buffers and rank_sc)
   FoldinScratch fold;
   // BPR training (mf_bpr_run, mf_bpr_step_triples)
@@ -507,6 +510,12 @@ void als_append(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r
 int64_t als_run_rows(mf_ctx* ctx, int side, const int32_t* ids, int64_t n_ids, const AlsParams& P);
 void als_update(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n, const AlsParams& P,
                 int32_t rounds, int64_t* solved_users, int64_t* solved_items);
+// mf_als_objective / mf_als_run_until.  als_check_objective: lambda (0 is valid here), reg and, when implicit,
+// alpha; solver and cg_steps are not read.  als_run_until checks als_check_run's too before anything runs;
+// history may be null.  Returns the iterations taken.
+void als_check_objective(const AlsParams& P);
+void als_objective(mf_ctx* ctx, const AlsParams& P, struct mf_als_loss* out);
+int32_t als_run_until(mf_ctx* ctx, const AlsParams& P, int32_t max_iterations, double rel_tol, double* history);
 // mf_als_foldin / mf_recommend_foldin (rec != null: the fused call; vecs_out may then be null).  The argument
 // checks that read nothing of the context are abi.cpp's.
 struct FoldinRecommend {

@@ -566,6 +566,35 @@ size_t als_cg_state_elems(int k);
 int als_cg_capacity(int k, bool f64);
 void launch_als_cg(const AlsLaunch& L);
 
+// ---- kernels_als_objective.hip: mf_als_objective --------------------------------------------------
+// The fit pass over one side's work list (the user side's: its gathers hit the smaller table): item_sums[x] =
+// sum64 of the terms of work item x in CSR order, one wave per item, X the side's own slab and Q the
+// counterpart's.  kAlsObjFlight: the counterpart rows a wave gathers before it uses the first.
+constexpr int kAlsObjFlight = 4;
+struct AlsObjectiveLaunch {
+  hipStream_t st;
+  const AlsItem* items;
+  int64_t n_items;
+  const int32_t* cols;
+  const void* vals;
+  const void* X;
+  const void* Q;
+  int k;
+  bool f64, implicit;
+  double alpha;
+  double* item_sums;
+};
+void launch_als_objective_fit(const AlsObjectiveLaunch& L);
+// out[a] = dot64(x, x) of row rated[a] of X, widened, times the row's weight in f64: weight 0 = 1, 1 = its
+// ratings off[row + 1] - off[row], 2 = those of them whose stored value is > 0.
+void launch_als_objective_norms(hipStream_t st, const int32_t* rated, int64_t m, const int64_t* off, const void* vals,
+                                const void* X, int k, bool f64, int weight, double* out);
+// *out = sum64 over e = f * k + g of GU[f][g] * GI[f][g] (launch_als_gram's layout), the product in T.
+void launch_als_objective_trace(hipStream_t st, const void* GU, const void* GI, int k, bool f64, double* out);
+// *out = sum64(v[0 .. n)): lane l of one wave chains v[l], v[l + 64], ... from 0.0, then v[l] += v[l ^ 32], 16,
+// 8, 4, 2, 1.  n == 0 gives 0.0.
+void launch_sum64(hipStream_t st, const double* v, int64_t n, double* out);
+
 // ---- kernels_als_append.hip: mf_als_append ------------------------------------------------------
 // One side's packed CSR (counterpart rows, rating bits of 4 or 8 bytes) with a batch appended, into fresh
 // arrays: row x keeps its old entries in their order, then takes the batch's in batch order.  Integer

@@ -182,6 +182,21 @@ class mf_als_solve(C.Structure):
     ]
 
 
+class mf_als_loss(C.Structure):
+    """mf_als_objective's result: the objective's value and its parts."""
+    _fields_ = [
+        ("total", C.c_double),
+        ("fit", C.c_double),
+        ("unobserved", C.c_double),
+        ("reg_user", C.c_double),
+        ("reg_item", C.c_double),
+        ("ratings", C.c_int64),
+        ("user_rows", C.c_int64),
+        ("item_rows", C.c_int64),
+        ("reserved", C.c_double * 4),
+    ]
+
+
 # Every symbol include/mfhip.h declares (tests check the library exports all of them).
 EXPORTS = [
     "mf_params_init", "mf_last_error", "mf_version", "mf_device_count", "mf_create",
@@ -201,6 +216,7 @@ EXPORTS = [
     "mf_rank_eval_seen", "mf_pair_ranks_seen", "mf_online_prequential_seen", "mf_similar", "mf_recommend_vectors",
     "mf_als_remove", "mf_als_remove_rows", "mf_als_retract", "mf_seen_remove", "mf_als_foldin", "mf_recommend_foldin",
     "mf_recommend_among", "mf_bpr_run", "mf_bpr_step_triples", "mf_bpr_draws", "mf_bpr_fit",
+    "mf_als_objective", "mf_als_run_until",
 ]
 # The test hooks include/mfhip_testing.h declares (not product surface; same library).
 TESTING_EXPORTS = [
@@ -329,6 +345,8 @@ def lib() -> C.CDLL:
                                             _i32p, _i32p]),
         "mf_als_append": (C.c_int, [_ctxp, _i32p, _i32p, _f64p, C.c_int64]),
         "mf_als_run_rows": (C.c_int, [_ctxp, C.c_int, _i32p, C.c_int64, C.POINTER(mf_als_solve), _i64p]),
+        "mf_als_objective": (C.c_int, [_ctxp, C.POINTER(mf_als_solve), C.POINTER(mf_als_loss)]),
+        "mf_als_run_until": (C.c_int, [_ctxp, C.POINTER(mf_als_solve), C.c_int32, C.c_double, _i32p, _f64p]),
         "mf_als_foldin": (C.c_int, [_ctxp, C.c_int, _i64p, _i32p, _f64p, C.c_int64, C.POINTER(mf_als_solve), _f64p,
                                     _i32p]),
         "mf_recommend_foldin": (C.c_int, [_ctxp, C.c_int, _i64p, _i32p, _f64p, C.c_int64, C.POINTER(mf_als_solve),

@@ -24,11 +24,12 @@ Weighted-lambda regularisation (ALS-WR), as ALS.train uses.  The initial factors
 """
 from __future__ import annotations
 
-from typing import List, Tuple
+from typing import List, Optional, Tuple
 
 import numpy as np
 
 from . import _lib as L
+from .bpr import _dot64
 from .context import Context, als_solve
 from .dsgd import _columns, _pairs
 from .ranking import RankingMetrics
@@ -133,6 +134,74 @@ class MatrixFactorizationModel:
         return RankingMetrics(self._ctx, u, i, exclude=exclude, side=L.SIDE_USER)
 
 
+def _sum64(v: np.ndarray) -> float:
+    """sum64 of include/mfhip.h in f64: lane l chains v[l], v[l + 64], ... from 0.0, then the butterfly."""
+    v = np.asarray(v, np.float64)
+    pad = np.zeros((len(v) + 63) // 64 * 64, np.float64)   # x + 0.0 == x for every x a chain from +0.0 reaches
+    pad[:len(v)] = v
+    acc = np.zeros(64, np.float64)
+    for tile in pad.reshape(-1, 64):
+        acc = acc + tile
+    lanes = np.arange(64)
+    for b in (32, 16, 8, 4, 2, 1):
+        acc = acc + acc[lanes ^ b]
+    return float(acc[0])
+
+
+def replay_objective(P, Q, off, cols, vals, GU, GI, how: L.mf_als_solve, chunk: int, dtype) -> dict:
+    """mf_als_objective's arithmetic in numpy, operation by operation (include/mfhip.h): the five doubles it
+    must return bit for bit, and the three counts.  P / Q: the user / item factors by factor row; off / cols /
+    vals: the USER side's resident CSR (Context.als_csr); GU / GI: the two Gram matrices [k, k] as the device
+    forms them (Context.als_gram; read only when how.implicit); chunk: the prepare's als_chunk; dtype: the
+    context's precision T."""
+    T = np.dtype(dtype).type
+    with np.errstate(all="ignore"):
+        P, Q = np.ascontiguousarray(P, T), np.ascontiguousarray(Q, T)
+        off, cols = np.asarray(off, np.int64), np.asarray(cols, np.int64)
+        r = np.ascontiguousarray(vals, T)
+        k, n, chunk = P.shape[1], int(off[-1]), int(chunk)
+        implicit = bool(how.implicit)
+        lam = float(T(how.lambda_))
+        out = dict(total=0.0, fit=0.0, unobserved=0.0, reg_user=0.0, reg_item=0.0, ratings=n, user_rows=0, item_rows=0)
+        if n == 0:
+            return out
+        counts = np.diff(off)
+        urow = np.repeat(np.arange(len(counts)), counts)
+        # fit: the terms in CSR order, a sum64 per work item, a sum64 over the work items
+        d = _dot64(P[urow], Q[cols[:n]])
+        if implicit:
+            w = T(how.alpha) * np.abs(r[:n])
+            c, e = T(1) + w, T(1) - d
+            t = np.where(r[:n] > 0, (c * e) * e - d * d, (w * d) * d)
+        else:
+            e = r[:n] - d
+            t = e * e
+        t = t.astype(np.float64)
+        sums = []
+        for a in np.flatnonzero(counts):
+            b0, b1 = int(off[a]), int(off[a + 1])
+            step = b1 - b0 if b1 - b0 <= chunk else chunk
+            sums += [_sum64(t[b:min(b + step, b1)]) for b in range(b0, b1, step)]
+        out["fit"] = _sum64(np.array(sums))
+        if implicit:
+            g = (np.ascontiguousarray(GU, T) * np.ascontiguousarray(GI, T)).astype(np.float64)
+            out["unobserved"] = _sum64(g.reshape(-1))
+        # reg: the rated rows of each side ascending, weighted by the row's count (its ratings > 0 when implicit)
+        weighted = how.reg == L.ALS_REG_WEIGHTED
+        pos = (r[:n] > 0).astype(np.int64)
+        for name, F, cnt, npos in (("user", P, counts, np.bincount(urow, pos, len(counts))),
+                                   ("item", Q, np.bincount(cols[:n], minlength=len(Q)),
+                                    np.bincount(cols[:n], pos, len(Q)))):
+            rated = np.flatnonzero(cnt)
+            out[name + "_rows"] = len(rated)
+            nrm = _dot64(F[rated], F[rated]).astype(np.float64)
+            if weighted:
+                nrm = nrm * (npos if implicit else cnt)[rated].astype(np.float64)
+            out["reg_" + name] = lam * _sum64(nrm)
+        out["total"] = ((out["fit"] + out["unobserved"]) + out["reg_user"]) + out["reg_item"]
+    return out
+
+
 class ALS:
     @staticmethod
     def train(ratings, rank: int, iterations: int = 10, lambda_: float = 0.01, mode: str = "deterministic",
@@ -163,10 +232,11 @@ class ALS:
         return MatrixFactorizationModel(ctx)
 
     @staticmethod
-    def withSolver(solver: str = "cholesky", cg_steps: int = 3) -> "_SolverALS":
+    def withSolver(solver: str = "cholesky", cg_steps: int = 3, tol: Optional[float] = None) -> "_SolverALS":
         """train / trainImplicit on the named solver: "cholesky" (ALS.train's own), "cg" or "nnls"
-        (non-negative factors; cg_steps is ignored for it)."""
-        return _SolverALS(solver, cg_steps)
+        (non-negative factors; cg_steps is ignored for it).  tol: training stops before `iterations` once an
+        iteration lowers the objective by no more than tol times its size (mf_als_run_until)."""
+        return _SolverALS(solver, cg_steps, tol)
 
     @staticmethod
     def _context(rank: int, mode: str, seed: int) -> Context:
@@ -271,6 +341,11 @@ class StreamingALS:
         self._run(int(half_sweeps))
         return self
 
+    def objective(self) -> dict:
+        """mf_als_objective of this model's own half-sweeps on everything held so far (after every update and
+        forget), at the factors as they stand: total, fit, unobserved, reg_user, reg_item and the counts."""
+        return self._fitted().als_objective(self.how)
+
     @property
     def model(self) -> MatrixFactorizationModel:
         return MatrixFactorizationModel(self._fitted())
@@ -282,18 +357,41 @@ class StreamingALS:
 
 
 class _SolverALS:
-    """ALS.train / ALS.trainImplicit with the solver of the half-sweeps chosen (ALS.withSolver)."""
+    """ALS.train / ALS.trainImplicit with the solver of the half-sweeps chosen (ALS.withSolver), and with tol set
+    training that stops by the objective (mf_als_run_until) instead of after a fixed count."""
 
-    def __init__(self, solver: str = "cholesky", cg_steps: int = 3):
+    def __init__(self, solver: str = "cholesky", cg_steps: int = 3, tol: Optional[float] = None):
         if solver not in SOLVERS:
             raise ValueError(f"unknown ALS solver {solver!r}: one of {SOLVERS}")
         if not 1 <= int(cg_steps) <= L.ALS_CG_MAX_STEPS:
             raise ValueError(f"cg_steps must lie in 1 .. {L.ALS_CG_MAX_STEPS}")
+        if tol is not None and not (float(tol) >= 0 and np.isfinite(tol)):
+            raise ValueError("tol must be finite and >= 0")
         self.solver = solver
         self.cg_steps = int(cg_steps)
+        self.tol = None if tol is None else float(tol)
+
+    def _until(self, ratings, rank, iterations, mode, seed, how: L.mf_als_solve) -> MatrixFactorizationModel:
+        """prepare, then at most `iterations` iterations, stopping once one lowers the objective by no more than
+        tol times its size."""
+        if int(iterations) < 0:
+            raise ValueError("iterations must be >= 0")
+        u, i, r = _columns(ratings)
+        ctx = ALS._context(rank, mode, seed)
+        try:
+            if len(u):
+                ctx.als_prepare(u, i, r)
+                ctx.als_run_until(how, int(iterations), self.tol)
+        except Exception:
+            ctx.close()
+            raise
+        return MatrixFactorizationModel(ctx)
 
     def train(self, ratings, rank: int, iterations: int = 10, lambda_: float = 0.01, mode: str = "deterministic",
               seed: int = 0) -> MatrixFactorizationModel:
+        if self.tol is not None:
+            return self._until(ratings, rank, iterations, mode, seed,
+                               als_solve(lambda_, solver=self.solver, cg_steps=self.cg_steps))
         if self.solver == "cholesky":
             return ALS.train(ratings, rank, iterations, lambda_, mode, seed)
         u, i, r = _columns(ratings)
@@ -310,6 +408,10 @@ class _SolverALS:
 
     def trainImplicit(self, ratings, rank: int, iterations: int = 10, lambda_: float = 0.01, alpha: float = 0.01,
                       mode: str = "deterministic", seed: int = 0) -> MatrixFactorizationModel:
+        if self.tol is not None:
+            return self._until(ratings, rank, iterations, mode, seed,
+                               als_solve(lambda_, implicit=True, alpha=alpha, solver=self.solver,
+                                         cg_steps=self.cg_steps))
         if self.solver == "cholesky":
             return ALS.trainImplicit(ratings, rank, iterations, lambda_, alpha, mode, seed)
         u, i, r = _columns(ratings)

@@ -317,6 +317,25 @@ class Context:
                                       C.byref(solved)))
         return int(solved.value)
 
+    def als_objective(self, how: L.mf_als_solve) -> dict:
+        """mf_als_objective: the value the half-sweeps of `how` (als_solve; lambda, reg, implicit and alpha are
+        read) minimise, on the resident data at the factors as they stand: total, fit, unobserved, reg_user,
+        reg_item and the counts ratings, user_rows, item_rows.  Nothing of the context changes."""
+        out = L.mf_als_loss()
+        check(L.lib().mf_als_objective(self._h, C.byref(how), C.byref(out)))
+        return {n: (int if t is C.c_int64 else float)(getattr(out, n)) for n, t in out._fields_ if n != "reserved"}
+
+    def als_run_until(self, how: L.mf_als_solve, max_iterations: int, rel_tol: float) -> Tuple[int, np.ndarray]:
+        """mf_als_run_until: iterations (two half-sweeps each) of `how` until the objective falls by no more than
+        rel_tol times its size, or max_iterations; returns (iterations, history [iterations + 1]) with
+        history[0] the objective on entry."""
+        max_iterations = int(max_iterations)
+        hist = np.zeros(max(max_iterations, 0) + 1, np.float64)
+        it = C.c_int32(0)
+        check(L.lib().mf_als_run_until(self._h, C.byref(how), max_iterations, float(rel_tol), C.byref(it),
+                                       ptr(hist, C.c_double)))
+        return int(it.value), hist[:it.value + 1]
+
     def _foldin_lists(self, offsets, ids, ratings):
         off = np.ascontiguousarray(offsets, np.int64)
         if off.ndim != 1 or off.size < 1:
