@@ -1105,8 +1105,9 @@ void als_foldin(mf_ctx* ctx, int side, const int64_t* off, const int32_t* ids, c
       }
       int32_t* const io = rec->ids_out + static_cast<size_t>(q0) * N;
       double* const so = rec->scores_out ? rec->scores_out + static_cast<size_t>(q0) * N : nullptr;
-      recommend_resident(ctx, s, sc.x.get(), nb, other, rec->top_n, s.rec_eoff.as<int64_t>(), s.rec_erows.as<int32_t>(),
-                         io, so, rec->counts_out + q0);
+      recommend_scored(ctx, s, TopNQueries::of_slab(s, sc.x.get(), nb), TopNCandidates::of_side(ctx, other), rec->top_n,
+                       MF_METRIC_DOT, ExclSource::csr(s.rec_eoff.as<int64_t>(), s.rec_erows.as<int32_t>()),
+                       TopNSink{io, so, rec->counts_out + q0, nullptr});
       for (int64_t j = 0; j < nb; ++j) {  // a query with no kept entry has no list
         if (cnt[2 * j] > 0) continue;
         rec->counts_out[q0 + j] = 0;

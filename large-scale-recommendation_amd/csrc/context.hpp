@@ -1,6 +1,7 @@
 // context.hpp -- the context (mf_ctx), its shards, and the helpers more than one host translation
 // unit uses.  Private to the host side: included by the .cpp files only (mfhip.cpp, dsgd_det.cpp,
-// dsgd_fast.cpp, ring.cpp, abi.cpp, online.cpp, eval.cpp, rank_eval.cpp, pair_rank.cpp, als.cpp, seen.cpp),
+// dsgd_fast.cpp, ring.cpp, abi.cpp, online.cpp, eval.cpp, recommend.cpp, rank_eval.cpp, pair_rank.cpp, als.cpp,
+// seen.cpp),
 // never by a .hip file or by kernels.hpp / plan.hpp; placement.cpp, which knows no context, does without it.
 #pragma once
 
@@ -11,6 +12,7 @@
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <functional>
 #include <future>
 #include <string>
 #include <vector>
@@ -403,6 +405,18 @@ void set_factors(mf_ctx* ctx, int side, const int32_t* ids, const double* vecs, 
 void allgather_items(mf_ctx* ctx);
 EvalOut evaluate(mf_ctx* ctx, const int32_t* u, const int32_t* i, const double* r, int64_t n,
                  const int32_t* mult, double lambda, double* pred_out, uint8_t* found_out);
+void get_factors(mf_ctx* ctx, int side, int32_t* ids, double* vecs, int64_t cap, int64_t* written);
+void lookup_factors(mf_ctx* ctx, int side, const int32_t* ids, int64_t n, double* vecs_out, uint8_t* found);
+
+// seen.cpp: what a reader of the resident seen set takes (below)
+struct SeenView {
+  const int64_t* off = nullptr;
+  const int32_t* ent = nullptr;
+  const int32_t* iota = nullptr;
+  bool any = false;
+};
+
+// recommend.cpp: the top-N lists
 void recommend(mf_ctx* ctx, int qside, const int32_t* queries, int64_t nq, int32_t top_n, const int32_t* eq,
                const int32_t* ec, int64_t ne, int32_t* ids_out, double* scores_out, int32_t* counts_out,
                bool seen = false);
@@ -416,15 +430,74 @@ void similar(mf_ctx* ctx, int side, const int32_t* queries, int64_t nq, int32_t 
 void recommend_vectors(mf_ctx* ctx, int cside, const double* vecs, int64_t nq, int32_t top_n, int metric,
                        const int64_t* eqi, const int32_t* ec, int64_t ne, int32_t* ids_out, double* scores_out,
                        int32_t* counts_out);
-// The score-and-select core for queries that are rows 0 .. nu-1 of a resident slab Q (nu x k, the context's
-// precision) against every row of side cside by MF_METRIC_DOT, with the exclusion CSR on the device (d_eoff
-// [nu + 1], d_erows: sorted distinct candidate rows per query); outputs on the host as mf_recommend's.  Queued
-// behind whatever s.stream holds (the kernels that write Q); under the caller's DeviceGuard.
-void recommend_resident(mf_ctx* ctx, Shard& s, const void* Q, int64_t nu, int cside, int32_t top_n,
-                        const int64_t* d_eoff, const int32_t* d_erows, int32_t* ids_out, double* scores_out,
-                        int32_t* counts_out);
-void get_factors(mf_ctx* ctx, int side, int32_t* ids, double* vecs, int64_t cap, int64_t* written);
-void lookup_factors(mf_ctx* ctx, int side, const int32_t* ids, int64_t n, double* vecs_out, uint8_t* found);
+// The row -> id table of a side on the device (s.rec_id[side]), current with the layout.
+void sync_row_ids(mf_ctx* ctx, Shard& s, int side);
+// How n queries (or pairs) are walked against C candidate rows: `batch` of them a launch, the candidate rows in
+// S splits -- enough workgroups for two per CU (qtile: the queries one workgroup owns), each split at least one
+// candidate tile of 128 rows, at most 64 splits, and 1 where there is no candidate.  MFHIP_TEST <batch_knob>=B /
+// <split_knob>=S override both.
+struct TopNShape { int64_t batch, S; };
+TopNShape topn_shape(int64_t n, int64_t C, int qtile, int64_t default_batch, const char* batch_knob,
+                     const char* split_knob);
+// The exclusions of a call, per batch as launch_recommend's (beg, end, rows).  Either the call's CSR on the device
+// (query j of the call: rows[off[j] .. off[j + 1]), sorted distinct candidate rows), or the resident seen set,
+// whose ranges are gathered through the batch's query rows into two buffers that batch() sizes.
+struct ExclSource {
+  struct Range { const int64_t *beg, *end; const int32_t* rows; };
+  static ExclSource csr(const int64_t* off, const int32_t* rows) { return {off, rows, SeenView{}, nullptr, nullptr}; }
+  static ExclSource seen(const SeenView& v, DevBuf& qbeg, DevBuf& qend) { return {nullptr, nullptr, v, &qbeg, &qend}; }
+  // the batch of nb queries from the call's b0-th on, whose rows are qrows[0 .. nb) on the device
+  Range batch(hipStream_t st, int64_t b0, int64_t nb, const int32_t* qrows) const;
+
+  const int64_t* off;
+  const int32_t* rows;
+  SeenView sv;
+  DevBuf *qbeg, *qend;  // (the gather buffers)
+};
+// The queries of a call.  rows (device): query j is row rows[j] of the resident slab Q (q_rows rows of k
+// elements in the context's precision; side: the model side it is, -1 a slab of the caller's that kernels queued
+// on the stream may still be writing).  staged: the queries are the host's n x k f64 vectors instead; they are
+// converted as upload_rows converts factor rows and staged one batch ahead, so the conversion of batch b + 1 runs
+// on the host while the device scores batch b, and rows is the identity 0 .. n-1.
+struct TopNQueries {
+  int64_t n = 0;
+  const int32_t* rows = nullptr;
+  const void* Q = nullptr;
+  int64_t q_rows = 0;
+  int side = -1;
+  bool staged = false;
+  const double* vecs = nullptr;
+  // the rows s.rec_q[0 .. n) of a side; every row of the caller's slab Q (the identity list is made on the
+  // device); host vectors (s.rec_q holds the identity)
+  static TopNQueries of_side(mf_ctx* ctx, Shard& s, int side, int64_t n) {
+    return {n, s.rec_q.as<int32_t>(), side == kSideU ? s.uf.get() : s.itf.get(), side_of(ctx, side).rows(), side};
+  }
+  static TopNQueries of_slab(Shard& s, const void* Q, int64_t n);
+  static TopNQueries of_vectors(Shard& s, const double* vecs, int64_t n) {
+    return {n, s.rec_q.as<int32_t>(), nullptr, 0, -1, true, vecs};
+  }
+};
+// The candidates: every row of a side, or (gathered; mf_recommend_among's shared list, MF_METRIC_DOT) only the
+// rows s.am_rows[0 .. n) of it, distinct and ascending on the device.  Those are gathered into a compact slab
+// with their ids, the kernels walk that slab, and the row list itself maps a slab position back to the factor
+// row the exclusion tables name.
+struct TopNCandidates {
+  int side; bool gathered; int64_t n;
+  static TopNCandidates of_side(mf_ctx* ctx, int side) { return {side, false, side_of(ctx, side).rows()}; }
+  static TopNCandidates of_rows(int side, int64_t n) { return {side, true, n}; }
+};
+// Where a finished batch goes: to the host after a wait for it (ids [n][top_n], scores or null, counts [n]), or to
+// on_batch(b0, nb) -- the lists stay in s.rec_ids / s.rec_counts (no scores), no copy and no wait in the driver.
+struct TopNSink {
+  int32_t* ids = nullptr;
+  double* scores = nullptr;
+  int32_t* counts = nullptr;
+  std::function<void(int64_t, int64_t)> on_batch;
+};
+// The one driver, on the shard's stream under the caller's DeviceGuard: the queries against the candidates minus
+// each query's exclusions, in batches that bound the scratch at batch x S x top_n keys (topn_shape; rec_batch, rec_split).
+void recommend_scored(mf_ctx* ctx, Shard& s, const TopNQueries& q, const TopNCandidates& c, int32_t top_n, int metric,
+                      const ExclSource& ex, const TopNSink& sink);
 
 // rank_eval.cpp
 const std::vector<double>& gain_table();  // 128 gains 1 / log(i + 2), then their 129 prefix sums
@@ -467,12 +540,6 @@ int64_t seen_count(const mf_ctx* ctx);
 // What a reader takes: the table of query side qside, its offsets padded to the side's present rows (a row
 // gained since holds nothing), and the identity as qpos.  any = false: no pair is held (n_excl == 0).  Made
 // on the shard's stream, under the caller's DeviceGuard; the item-major table is built here on first use.
-struct SeenView {
-  const int64_t* off = nullptr;
-  const int32_t* ent = nullptr;
-  const int32_t* iota = nullptr;
-  bool any = false;
-};
 SeenView seen_view(mf_ctx* ctx, Shard& s, int qside);
 void seen_debug_csr(mf_ctx* ctx, int side, int32_t* row_ids_out, int64_t* off_out, int32_t* ent_out, int32_t* ent_ids_out,
                     int64_t cap_rows, int64_t cap_nnz, int64_t* rows_out, int64_t* nnz_out);

@@ -250,27 +250,42 @@ void device_fast_schedule(hipStream_t st, const DevRatingBlocks& dr, const Ratin
 // ---- kernels_recommend.hip: top-N recommendation ------------------------------------------------
 // Top-N recommendation (kernels_recommend.hip): for each of the nq query rows qrows[] of slab Q (all
 // valid rows) the top_n best of candidate rows [0, C) of slab Cf by p.q, as ids / scores / counts
-// ([nq][top_n], [nq]; device).  f64: the sequential pq = pq + a*b chain (k_predict's value); f32:
-// the fmaf chain over f = 0..k-1 on the f32-input MFMA.  cand_id: row -> id of the candidate side.
-// excl_beg / excl_end (nq each) / excl_rows: per query the sorted candidate rows never returned,
-// excl_rows[excl_beg[q], excl_end[q]).  A call's own CSR passes (off, off + 1); the resident seen set passes
-// two arrays gathered from its offsets through qrows (launch_seen_gather).  The candidate
-// rows are walked in S <= 64 splits; part: nq * S * top_n keys of recommend_key_bytes(f64) scratch.
-// recommend_query_tile: the queries one workgroup owns (the host sizes S by it).  scores may be null
-// (mf_rank_eval reads only ids and counts).
-// Cosine (mf_similar, mf_recommend_vectors): c_inv given -- one inverse norm per candidate row, q_inv one per
-// row of Q (indexed through qrows like Q), both in the context's precision, as launch_row_inv_norm writes
-// them; a score is then dot * (q_inv * c_inv), scaled before it is selected.  Null: the dot kernels.
-// pos_row (mf_recommend_among's shared list; dot metric only): Cf is a slab gathered from the factor rows,
-// cand_id its ids by slab position, and excl_rows still name factor rows -- position p is row pos_row[p].
-// launch_row_inv_norm: inv[r] = 1 / sqrt(sum over ascending f of X[r][f]^2) for rows [0, rows) of X.
+// ([nq][top_n], [nq]; device).  What one launch takes; a caller sets per batch only what varies per batch.
+struct RecLaunch {
+  hipStream_t st = nullptr;
+  // the query slab and the candidate slab, in the context's precision.  f64: the sequential pq = pq + a*b
+  // chain (k_predict's value); f32: the fmaf chain over f = 0..k-1 on the f32-input MFMA.
+  const void *Q = nullptr, *Cf = nullptr;
+  int k = 0, top_n = 0;
+  bool f64 = false;
+  const int32_t* cand_id = nullptr;  // row -> id of the candidate side
+  // the candidate rows [0, C) are walked in S <= 64 splits; part: nq * S * top_n keys of
+  // recommend_key_bytes(f64) scratch.  recommend_query_tile: the queries one workgroup owns (the host sizes S
+  // by it).
+  int32_t C = 0;
+  int S = 1;
+  void* part = nullptr;
+  // excl_beg / excl_end (nq each) / excl_rows: per query the sorted candidate rows never returned,
+  // excl_rows[excl_beg[q], excl_end[q]).  A call's own CSR passes (off, off + 1); the resident seen set passes
+  // two arrays gathered from its offsets through qrows (launch_seen_gather).
+  const int64_t *excl_beg = nullptr, *excl_end = nullptr;
+  const int32_t* excl_rows = nullptr;
+  int32_t* ids = nullptr;
+  double* scores = nullptr;  // may be null (mf_rank_eval reads only ids and counts)
+  int32_t* counts = nullptr;
+  // Cosine (mf_similar, mf_recommend_vectors): c_inv given -- one inverse norm per candidate row, q_inv one per
+  // row of Q (indexed through qrows like Q), both in the context's precision, as launch_row_inv_norm writes
+  // them; a score is then dot * (q_inv * c_inv), scaled before it is selected.  Null: the dot kernels.
+  const void *q_inv = nullptr, *c_inv = nullptr;
+  // pos_row (mf_recommend_among's shared list; dot metric only): Cf is a slab gathered from the factor rows,
+  // cand_id its ids by slab position, and excl_rows still name factor rows -- position p is row pos_row[p].
+  // Null: the candidates are factor rows.
+  const int32_t* pos_row = nullptr;
+};
 size_t recommend_key_bytes(bool f64);
 int recommend_query_tile(int top_n, bool f64);
-void launch_recommend(hipStream_t st, const void* Q, const void* Cf, const int32_t* qrows, int nq, int32_t C, int S,
-                      int k, int top_n, bool f64, const int32_t* cand_id, const int64_t* excl_beg,
-                      const int64_t* excl_end, const int32_t* excl_rows, void* part, int32_t* ids, double* scores,
-                      int32_t* counts, const void* q_inv = nullptr, const void* c_inv = nullptr,
-                      const int32_t* pos_row = nullptr);
+void launch_recommend(const RecLaunch& L, const int32_t* qrows, int nq);
+// launch_row_inv_norm: inv[r] = 1 / sqrt(sum over ascending f of X[r][f]^2) for rows [0, rows) of X.
 void launch_row_inv_norm(hipStream_t st, const void* X, int64_t rows, int k, bool f64, void* inv);
 
 // ---- kernels_among.hip: top N within caller-given candidate lists (mf_recommend_among) ------------

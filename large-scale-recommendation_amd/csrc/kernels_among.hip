@@ -18,9 +18,8 @@
 //                  Selection is k_rec_f64's: the keys of rec_keys.hpp, tested against the query's exclusion
 //                  rows only when they beat the list's N-th key; a key the list already holds is the same
 //                  candidate named twice and is skipped (list_insert_distinct).
-//  k_among_merge   the partial lists of a position's parts -> its final top N, k_rec_merge with a part count
-//                  per position; every lane whose head equals the round's maximum advances, so an id that two
-//                  parts both kept counts once.
+//  k_rec_merge     (rec_keys.hpp) the partial lists of a position's parts -> its final top N, with the part
+//                  offsets pbeg: an id that two parts both kept counts once.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -80,13 +79,6 @@ __global__ __launch_bounds__(kGridThreads) void k_among_compact(const uint32_t* 
   for (int64_t p = static_cast<int64_t>(blockIdx.x) * kGridThreads + threadIdx.x; p < n;
        p += static_cast<int64_t>(gridDim.x) * kGridThreads)
     if (head[p]) out[wp[p]] = static_cast<int32_t>(sorted[p]);
-}
-
-// The lanes of a wave exchange data through LDS without a workgroup barrier: order the wave's own LDS accesses.
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // V consecutive elements of a row, moved as one 16-byte access when V > 1.
@@ -159,54 +151,9 @@ __global__ __launch_bounds__(kAmongWaves * 64) void k_among_score(
     const K key = make_key(pq, cok ? cand_id[myrow] : 0);
     bool want = cok && key_gt(key, list[N - 1]);
     if (want) want = !contains(excl_rows, eb, ee, static_cast<int32_t>(myrow));
-    // one lane at a time inserts into the list
-    for (;;) {
-      want = want && key_gt(key, list[N - 1]);
-      const uint64_t m = __ballot(want);
-      if (m == 0) break;
-      if (lane == __ffsll(static_cast<long long>(m)) - 1) {
-        list_insert_distinct(list, N, key);
-        want = false;
-      }
-      wave_lds_sync();
-    }
+    wave_list_insert<true>(list, N, key, want, lane);
   }
   for (int x = lane; x < N; x += 64) part[t * N + x] = list[x];
-}
-
-// One wave per position: lane l < S = pbeg[q + 1] - pbeg[q] holds the head of the position's l-th partial list
-// (each sorted descending, keys distinct inside it); N rounds of a wave-wide maximum.  Slots past the count
-// hold id 0 / score 0.0.  scores may be null.
-template <typename K>
-__global__ __launch_bounds__(256) void k_among_merge(const K* __restrict__ part, const int64_t* __restrict__ pbeg,
-                                                     int nq, int N, int32_t* __restrict__ ids,
-                                                     double* __restrict__ scores, int32_t* __restrict__ counts) {
-  const int lane = threadIdx.x & 63;
-  const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (q >= nq) return;
-  const int64_t p0 = pbeg[q];
-  const int S = static_cast<int>(pbeg[q + 1] - p0);
-  const K* mine = part + (p0 + lane) * N;
-  int pos = 0;
-  int cnt = 0;
-  for (int o = 0; o < N; ++o) {
-    K head{};
-    if (lane < S && pos < N) head = mine[pos];
-    K best = head;
-    for (int m = 1; m < 64; m <<= 1) {
-      const K other = key_shfl_xor(best, m);
-      if (key_gt(other, best)) best = other;
-    }
-    const bool live = !key_empty(best);
-    // the same candidate may head several parts: all of them move on
-    if (live && lane < S && pos < N && !key_gt(best, head) && !key_gt(head, best)) ++pos;
-    if (lane == 0) {
-      ids[static_cast<int64_t>(q) * N + o] = live ? key_id(best) : 0;
-      if (scores) scores[static_cast<int64_t>(q) * N + o] = live ? key_score(best) : 0.0;
-    }
-    cnt += live ? 1 : 0;
-  }
-  if (lane == 0) counts[q] = cnt;
 }
 
 }  // namespace
@@ -254,7 +201,7 @@ void launch_among(hipStream_t st, const void* Q, const void* Cf, const AmongTask
       hipLaunchKernelGGL((k_among_score<T, decltype(vec)::value>), grid, block, 0, st, static_cast<const T*>(Q),
                          static_cast<const T*>(Cf), tasks, ntasks, crows, qrow, cand_id, excl_beg, excl_end, excl_rows,
                          k, top_n, static_cast<K*>(part));
-    hipLaunchKernelGGL((k_among_merge<K>), mgrid, mblock, 0, st, static_cast<const K*>(part), pbeg, nq, top_n, ids,
+    hipLaunchKernelGGL((k_rec_merge<K>), mgrid, mblock, 0, st, static_cast<const K*>(part), pbeg, nq, 0, top_n, ids,
                        scores, counts);
   };
   // whole 16-byte vectors per row?

@@ -14,7 +14,7 @@
 //  k_rec_f64    deterministic contexts.  Plain VALU: a lane owns one candidate's chain
 //               pq = pq + a * b over f = 0..k-1 (this file is compiled with -ffp-contract=off), the
 //               value k_predict gives for the pair, against QW query rows of its wave.
-//  k_rec_merge  the S partial lists of a query (one per candidate split) -> its final top N.
+//  k_rec_merge  (rec_keys.hpp) the S partial lists of a query (one per candidate split) -> its final top N.
 //  k_row_inv_norm  one inverse norm per row, 1 / sqrt(sum x_f^2), for the cosine metric (mf_similar,
 //               mf_recommend_vectors).  Both score kernels take the metric as a template parameter COS:
 //               with it, a score is dot * (inv(query) * inv(candidate)) before it meets the selection,
@@ -40,11 +40,6 @@ namespace mfhip {
 namespace {
 
 using namespace dev;  // the keys and list_insert: rec_keys.hpp
-
-// Is candidate row `crow` in the query's sorted exclusion rows [b, e)?
-__device__ __forceinline__ bool excluded(const int32_t* __restrict__ rows, int64_t b, int64_t e, int32_t crow) {
-  return dev::contains(rows, b, e, crow);
-}
 
 // ---- f32: MFMA score + select -----------------------------------------------------------------
 using f32x16 = __attribute__((ext_vector_type(16))) float;
@@ -220,9 +215,9 @@ __global__ __launch_bounds__(NW * 64) void k_rec_f32(const float* __restrict__ Q
             const int32_t crow = c0 + static_cast<int32_t>(pv & 0xFFFFFFFFu);
             key = Key32{(pv & 0xFFFFFFFF00000000ULL) | id_bits(cand_id[crow])};
             if constexpr (MAP)
-              have = key_gt(key, mylist[N - 1]) && !excluded(excl_rows, eb, ee, pos_row[crow]);
+              have = key_gt(key, mylist[N - 1]) && !contains(excl_rows, eb, ee, pos_row[crow]);
             else
-              have = key_gt(key, mylist[N - 1]) && !excluded(excl_rows, eb, ee, crow);
+              have = key_gt(key, mylist[N - 1]) && !contains(excl_rows, eb, ee, crow);
           }
           // the two halves of the wave share a query's list: one half at a time
 #pragma unroll
@@ -327,21 +322,11 @@ __global__ __launch_bounds__(256) void k_rec_f64(const double* __restrict__ Qf, 
       const Key64 key = make_key(pq[i], cid);
       bool want = cok && key_gt(key, list[N - 1]);
       if constexpr (MAP) {
-        if (want) want = !excluded(excl_rows, excl_beg[q], excl_end[q], pos_row[crow]);
+        if (want) want = !contains(excl_rows, excl_beg[q], excl_end[q], pos_row[crow]);
       } else {
-        if (want) want = !excluded(excl_rows, excl_beg[q], excl_end[q], crow);
+        if (want) want = !contains(excl_rows, excl_beg[q], excl_end[q], crow);
       }
-      // one lane at a time inserts into the query's list
-      for (;;) {
-        want = want && key_gt(key, list[N - 1]);
-        const uint64_t m = __ballot(want);
-        if (m == 0) break;
-        if (lane == __ffsll(static_cast<long long>(m)) - 1) {
-          list_insert(list, N, key);
-          want = false;
-        }
-        __builtin_amdgcn_wave_barrier();
-      }
+      wave_list_insert<false>(list, N, key, want, lane);
     }
   }
   for (int x = lane; x < kQW * N; x += 64) {
@@ -392,57 +377,34 @@ __global__ __launch_bounds__(kNormRows) void k_row_inv_norm(const T* __restrict_
   if (r0 + lane < rows) inv[r0 + lane] = static_cast<T>(1.0 / sqrt(static_cast<double>(nn)));
 }
 
-// ---- merge ------------------------------------------------------------------------------------
-// One wave per query: lane l < S holds the head of partial list l (each sorted descending); N
-// rounds of a wave-wide maximum.  Slots past the count hold id 0 / score 0.0.  scores may be null.
-template <typename K>
-__global__ __launch_bounds__(256) void k_rec_merge(const K* __restrict__ part, int nq, int S, int N,
-                                                   int32_t* __restrict__ ids, double* __restrict__ scores,
-                                                   int32_t* __restrict__ counts) {
-  const int lane = threadIdx.x & 63;
-  const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (q >= nq) return;
-  const K* mine = part + (static_cast<int64_t>(q) * S + lane) * N;
-  int pos = 0;
-  int cnt = 0;
-  for (int o = 0; o < N; ++o) {
-    K head{};
-    if (lane < S && pos < N) head = mine[pos];
-    K best = head;
-    for (int m = 1; m < 64; m <<= 1) {
-      const K other = key_shfl_xor(best, m);
-      if (key_gt(other, best)) best = other;
-    }
-    const bool live = !key_empty(best);
-    // keys are unique (one per candidate), so exactly one lane holds the maximum
-    if (live && lane < S && pos < N && !key_gt(best, head) && !key_gt(head, best)) ++pos;
-    if (lane == 0) {
-      ids[static_cast<int64_t>(q) * N + o] = live ? key_id(best) : 0;
-      if (scores) scores[static_cast<int64_t>(q) * N + o] = live ? key_score(best) : 0.0;
-    }
-    cnt += live ? 1 : 0;
-  }
-  if (lane == 0) counts[q] = cnt;
-}
-
 template <int NW, bool VEC, bool COS, bool MAP>
-void rec_f32_launch(hipStream_t st, const float* Q, const float* Cf, const int32_t* qrows, int nq, int32_t C, int S,
-                    int32_t per, int k, int N, const int32_t* cand_id, const int64_t* eb, const int64_t* ee,
-                    const int32_t* er, void* part, const float* qinv, const float* cinv, const int32_t* pos_row) {
-  const dim3 grid(static_cast<unsigned>((nq + NW * 32 - 1) / (NW * 32)), static_cast<unsigned>(S)), block(NW * 64);
+void rec_f32_launch(const RecLaunch& L, const int32_t* qrows, int nq, int32_t per) {
+  const int N = L.top_n;
+  const dim3 grid(static_cast<unsigned>((nq + NW * 32 - 1) / (NW * 32)), static_cast<unsigned>(L.S)), block(NW * 64);
   const size_t smem = sizeof(Key32) * NW * 32 * N + 8 * kPend * NW * 64 + sizeof(float) * 2 * rec_stage_floats(NW) +
                       (COS ? sizeof(float) * 2 * kCT : 0);
   // up to 72 KB (NW = 4, top 16; 1 KB more with COS): above the 64 KB a kernel gets without asking
   const void* fn = reinterpret_cast<const void*>(&k_rec_f32<NW, VEC, COS, MAP>);
   if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(smem)) != hipSuccess)
     fail(MF_ERR_HIP, "k_rec_f32: " + std::to_string(smem) + " bytes of LDS refused");
-  hipLaunchKernelGGL((k_rec_f32<NW, VEC, COS, MAP>), grid, block, smem, st, Q, Cf, qrows, nq, C, per, k, N, cand_id, eb,
-                     ee, er, static_cast<Key32*>(part), qinv, cinv, pos_row);
+  hipLaunchKernelGGL((k_rec_f32<NW, VEC, COS, MAP>), grid, block, smem, L.st, static_cast<const float*>(L.Q),
+                     static_cast<const float*>(L.Cf), qrows, nq, L.C, per, L.k, N, L.cand_id, L.excl_beg, L.excl_end,
+                     L.excl_rows, static_cast<Key32*>(L.part), static_cast<const float*>(L.q_inv),
+                     static_cast<const float*>(L.c_inv), L.pos_row);
+}
+
+template <bool COS, bool MAP>
+void rec_f64_launch(const RecLaunch& L, const int32_t* qrows, int nq, int32_t per) {
+  const dim3 grid(static_cast<unsigned>((nq + 4 * kQW - 1) / (4 * kQW)), static_cast<unsigned>(L.S)), block(256);
+  hipLaunchKernelGGL((k_rec_f64<COS, MAP>), grid, block, 0, L.st, static_cast<const double*>(L.Q),
+                     static_cast<const double*>(L.Cf), qrows, nq, L.C, per, L.k, L.top_n, L.cand_id, L.excl_beg,
+                     L.excl_end, L.excl_rows, static_cast<Key64*>(L.part), static_cast<const double*>(L.q_inv),
+                     static_cast<const double*>(L.c_inv), L.pos_row);
 }
 
 // (the map is never combined with the cosine metric: no caller asks for it)
 template <int NW, typename... A>
-void rec_f32_dispatch(bool vec, bool cos, bool map, A... a) {
+void rec_f32_dispatch(bool vec, bool cos, bool map, const A&... a) {
   if (cos) vec ? rec_f32_launch<NW, true, true, false>(a...) : rec_f32_launch<NW, false, true, false>(a...);
   else if (map) vec ? rec_f32_launch<NW, true, false, true>(a...) : rec_f32_launch<NW, false, false, true>(a...);
   else vec ? rec_f32_launch<NW, true, false, false>(a...) : rec_f32_launch<NW, false, false, false>(a...);
@@ -468,53 +430,29 @@ void launch_row_inv_norm(hipStream_t st, const void* X, int64_t rows, int k, boo
                        static_cast<float*>(inv));
 }
 
-void launch_recommend(hipStream_t st, const void* Q, const void* Cf, const int32_t* qrows, int nq, int32_t C, int S,
-                      int k, int top_n, bool f64, const int32_t* cand_id, const int64_t* excl_beg,
-                      const int64_t* excl_end, const int32_t* excl_rows, void* part, int32_t* ids, double* scores,
-                      int32_t* counts, const void* q_inv, const void* c_inv, const int32_t* pos_row) {
+void launch_recommend(const RecLaunch& L, const int32_t* qrows, int nq) {
   if (nq <= 0) return;
-  const int32_t per = (C + S - 1) / S;
-  const bool cos = c_inv != nullptr, map = pos_row != nullptr;
+  const int32_t per = (L.C + L.S - 1) / L.S;
+  const bool cos = L.c_inv != nullptr, map = L.pos_row != nullptr;
   if (cos && map) fail(MF_ERR_INVALID, "launch_recommend: a position map with the cosine metric");
-  if (f64) {
-    const dim3 grid(static_cast<unsigned>((nq + 4 * kQW - 1) / (4 * kQW)), static_cast<unsigned>(S)), block(256);
-    const double *qi = static_cast<const double*>(q_inv), *ci = static_cast<const double*>(c_inv);
-    if (cos)
-      hipLaunchKernelGGL((k_rec_f64<true, false>), grid, block, 0, st, static_cast<const double*>(Q),
-                         static_cast<const double*>(Cf), qrows, nq, C, per, k, top_n, cand_id, excl_beg, excl_end,
-                         excl_rows, static_cast<Key64*>(part), qi, ci, pos_row);
-    else if (map)
-      hipLaunchKernelGGL((k_rec_f64<false, true>), grid, block, 0, st, static_cast<const double*>(Q),
-                         static_cast<const double*>(Cf), qrows, nq, C, per, k, top_n, cand_id, excl_beg, excl_end,
-                         excl_rows, static_cast<Key64*>(part), qi, ci, pos_row);
-    else
-      hipLaunchKernelGGL((k_rec_f64<false, false>), grid, block, 0, st, static_cast<const double*>(Q),
-                         static_cast<const double*>(Cf), qrows, nq, C, per, k, top_n, cand_id, excl_beg, excl_end,
-                         excl_rows, static_cast<Key64*>(part), qi, ci, pos_row);
+  if (L.f64) {
+    if (cos) rec_f64_launch<true, false>(L, qrows, nq, per);
+    else if (map) rec_f64_launch<false, true>(L, qrows, nq, per);
+    else rec_f64_launch<false, false>(L, qrows, nq, per);
   } else {
-    const float* q = static_cast<const float*>(Q);
-    const float* c = static_cast<const float*>(Cf);
-    const float *qi = static_cast<const float*>(q_inv), *ci = static_cast<const float*>(c_inv);
     // the lists of a block stay within 32 KB of LDS: 128 queries per block up to top 16, 64 up to 48, else 32
-    const int64_t *eb = excl_beg, *ee = excl_end;
-    const bool vec = k % 4 == 0;
-    if (top_n <= 16)
-      rec_f32_dispatch<4>(vec, cos, map, st, q, c, qrows, nq, C, S, per, k, top_n, cand_id, eb, ee, excl_rows, part, qi,
-                          ci, pos_row);
-    else if (top_n <= 48)
-      rec_f32_dispatch<2>(vec, cos, map, st, q, c, qrows, nq, C, S, per, k, top_n, cand_id, eb, ee, excl_rows, part, qi,
-                          ci, pos_row);
-    else
-      rec_f32_dispatch<1>(vec, cos, map, st, q, c, qrows, nq, C, S, per, k, top_n, cand_id, eb, ee, excl_rows, part, qi,
-                          ci, pos_row);
+    const bool vec = L.k % 4 == 0;
+    if (L.top_n <= 16) rec_f32_dispatch<4>(vec, cos, map, L, qrows, nq, per);
+    else if (L.top_n <= 48) rec_f32_dispatch<2>(vec, cos, map, L, qrows, nq, per);
+    else rec_f32_dispatch<1>(vec, cos, map, L, qrows, nq, per);
   }
   const dim3 mgrid(static_cast<unsigned>((nq + 3) / 4)), mblock(256);
-  if (f64)
-    hipLaunchKernelGGL((k_rec_merge<Key64>), mgrid, mblock, 0, st, static_cast<const Key64*>(part), nq, S, top_n, ids,
-                       scores, counts);
+  if (L.f64)
+    hipLaunchKernelGGL((k_rec_merge<Key64>), mgrid, mblock, 0, L.st, static_cast<const Key64*>(L.part), nullptr, nq, L.S,
+                       L.top_n, L.ids, L.scores, L.counts);
   else
-    hipLaunchKernelGGL((k_rec_merge<Key32>), mgrid, mblock, 0, st, static_cast<const Key32*>(part), nq, S, top_n, ids,
-                       scores, counts);
+    hipLaunchKernelGGL((k_rec_merge<Key32>), mgrid, mblock, 0, L.st, static_cast<const Key32*>(L.part), nullptr, nq, L.S,
+                       L.top_n, L.ids, L.scores, L.counts);
 }
 
 }  // namespace mfhip

@@ -3,7 +3,7 @@
 // preparation, and run_supersteps.  The deterministic supersteps are dsgd_det.cpp, the fast ones
 // dsgd_fast.cpp, the item-block ring between GPUs ring.cpp, the persistent sweeps' launch tables
 // placement.cpp.  The C ABI is abi.cpp; online micro-batches and mf_block_update are online.cpp,
-// evaluation and recommendation eval.cpp, ALS als.cpp; context.hpp declares what they share.
+// evaluation eval.cpp, top-N lists recommend.cpp, ALS als.cpp; context.hpp declares what they share.
 //
 // Execution model:
 //  * A context owns G shards.  Shard g owns user blocks [g*c, (g+1)*c), c = numBlocks / G, and

@@ -25,8 +25,6 @@
 #include "plan.hpp"
 
 namespace mfhip {
-namespace {
-}
 
 int64_t pair_ranks(mf_ctx* ctx, int qside, const int32_t* q, const int32_t* c, int64_t n, const int32_t* eq,
                    const int32_t* ec, int64_t ne, int32_t* rank_out, int32_t* valid_out, double* score_out,
@@ -92,11 +90,7 @@ int64_t pair_ranks(mf_ctx* ctx, int qside, const int32_t* q, const int32_t* c, i
   if (clk.on) MF_HIP(hipStreamSynchronize(s.stream));
   clk.lap("pair_ranks: tables");
 
-  if (s.rec_id_gen[cside] != ctx->layout_gen || s.rec_id[cside].bytes() < static_cast<size_t>(C) * 4) {
-    s.rec_id[cside].alloc(static_cast<size_t>(C) * 4);
-    MF_HIP(hipMemcpy(s.rec_id[cside].get(), CS.row_id.data(), static_cast<size_t>(C) * 4, hipMemcpyHostToDevice));
-    s.rec_id_gen[cside] = ctx->layout_gen;
-  }
+  sync_row_ids(ctx, s, cside);
   const size_t ob = pair_rank_ord_bytes(ctx->f64);
   s.pr_ord.alloc(static_cast<size_t>(n) * ob);
   s.pr_tid.alloc(static_cast<size_t>(n) * 4);
@@ -113,19 +107,12 @@ int64_t pair_ranks(mf_ctx* ctx, int qside, const int32_t* q, const int32_t* c, i
                       s.pr_ord.get(), s.pr_tid.as<uint32_t>(), s.pr_rank.as<int32_t>(), s.pr_valid.as<int32_t>(),
                       s.pr_score.as<double>());
 
-  // batches, and candidate splits as recommend() chooses them: enough workgroups for two per CU, each
-  // split at least one candidate tile of 128 rows
-  int64_t batch = 32768;
-  if (const std::string v = test_knob("pr_batch"); !v.empty()) batch = std::max<int64_t>(1, std::atoll(v.c_str()));
-  batch = std::min(batch, n);
+  // batches and candidate splits, sized as recommend()'s (topn_shape)
   int nw = 4;
   if (const std::string v = test_knob("pr_nw"); !v.empty()) nw = std::atoi(v.c_str());
   nw = nw >= 4 ? 4 : nw >= 2 ? 2 : 1;
-  const int qt = pair_rank_tile(ctx->f64, nw);
-  const int64_t qtiles = (batch + qt - 1) / qt;
-  int64_t S = std::min<int64_t>((512 + qtiles - 1) / qtiles, (C + 127) / 128);
-  if (const std::string v = test_knob("pr_split"); !v.empty()) S = std::atoll(v.c_str());
-  S = std::max<int64_t>(1, std::min<int64_t>({S, 64, C}));
+  const TopNShape sh = topn_shape(n, C, pair_rank_tile(ctx->f64, nw), 32768, "pr_batch", "pr_split");
+  const int64_t batch = sh.batch, S = sh.S;
   // no copy and no wait inside the loop
   for (int64_t b0 = 0; b0 < n; b0 += batch) {
     const int64_t nb = std::min(batch, n - b0);

@@ -83,9 +83,6 @@ void rank_eval(mf_ctx* ctx, int qside, const int32_t* gq, const int32_t* gc, int
   const int cside = 1 - qside;
   const SideLayout& QS = side_of(ctx, qside);
   const SideLayout& CS = side_of(ctx, cside);
-  const int64_t C = CS.rows();
-  const int k = ctx->P.num_factors;
-  const size_t N = static_cast<size_t>(top_n);
   DeviceGuard g(s.device);
 
   // the seen set stands in for the exclusion table of the call (taken first: it may build its item-major
@@ -120,28 +117,10 @@ void rank_eval(mf_ctx* ctx, int qside, const int32_t* gq, const int32_t* gc, int
   if (clk.on) MF_HIP(hipStreamSynchronize(s.stream));
   clk.lap("rank_eval: pair tables");
 
-  if (C > 0 && (s.rec_id_gen[cside] != ctx->layout_gen || s.rec_id[cside].bytes() < static_cast<size_t>(C) * 4)) {
-    s.rec_id[cside].alloc(static_cast<size_t>(C) * 4);
-    MF_HIP(hipMemcpy(s.rec_id[cside].get(), CS.row_id.data(), static_cast<size_t>(C) * 4, hipMemcpyHostToDevice));
-    s.rec_id_gen[cside] = ctx->layout_gen;
-  }
   const std::vector<double>& tab = gain_table();
   s.rk_tab.alloc(tab.size() * 8);
   MF_HIP(hipMemcpyAsync(s.rk_tab.get(), tab.data(), tab.size() * 8, hipMemcpyHostToDevice, s.stream));
 
-  // batches and candidate splits as recommend() chooses them
-  int64_t batch = 8192;
-  if (const std::string v = test_knob("rec_batch"); !v.empty()) batch = std::max<int64_t>(1, std::atoll(v.c_str()));
-  batch = std::min(batch, nq);
-  const int qt = recommend_query_tile(top_n, ctx->f64);
-  const int64_t qtiles = (batch + qt - 1) / qt;
-  int64_t S = std::min<int64_t>((512 + qtiles - 1) / qtiles, (C + 127) / 128);
-  if (const std::string v = test_knob("rec_split"); !v.empty()) S = std::atoll(v.c_str());
-  S = std::max<int64_t>(1, std::min<int64_t>({S, 64, std::max<int64_t>(C, 1)}));
-
-  s.rec_part.alloc(static_cast<size_t>(batch) * S * N * recommend_key_bytes(ctx->f64));
-  s.rec_ids.alloc(static_cast<size_t>(batch) * N * 4);
-  s.rec_counts.alloc(static_cast<size_t>(batch) * 4);
   const int64_t slices = rank_reduce_slices(nq);
   s.rk_met.alloc(static_cast<size_t>(nq) * MF_RANK_NMETRICS * 8);
   s.rk_cnt.alloc(static_cast<size_t>(nq) * 2 * 8);
@@ -151,34 +130,19 @@ void rank_eval(mf_ctx* ctx, int qside, const int32_t* gq, const int32_t* gc, int
   int64_t* ipart = reinterpret_cast<int64_t*>(part + slices * MF_RANK_NMETRICS);
   double* sums = s.rk_res.as<double>();
   int64_t* isums = reinterpret_cast<int64_t*>(sums + MF_RANK_NMETRICS);
-  if (C == 0) MF_HIP(hipMemsetAsync(s.rec_counts.get(), 0, static_cast<size_t>(batch) * 4, s.stream));  // empty lists
-  const void* Q = qside == kSideU ? s.uf.get() : s.itf.get();
-  const void* Cf = cside == kSideU ? s.uf.get() : s.itf.get();
-  if (sv.any) {
-    s.seen.qbeg.alloc(static_cast<size_t>(batch) * 8);
-    s.seen.qend.alloc(static_cast<size_t>(batch) * 8);
-  }
-  // no copy and no wait inside the loop: stream order makes the reuse of a batch's scratch safe
-  for (int64_t b0 = 0; b0 < nq; b0 += batch) {
-    const int64_t nb = std::min(batch, nq - b0);
-    if (C > 0) {
-      const int64_t *ebeg = s.rec_eoff.as<int64_t>() + b0, *eend = ebeg + 1;
-      const int32_t* erows_d = s.rec_erows.as<int32_t>();
-      if (sv.any) {  // the batch's ranges, gathered from the resident offsets through its rows
-        launch_seen_gather(s.stream, sv.off, s.rec_q.as<int32_t>() + b0, static_cast<int>(nb), s.seen.qbeg.as<int64_t>(),
-                           s.seen.qend.as<int64_t>());
-        ebeg = s.seen.qbeg.as<int64_t>();
-        eend = s.seen.qend.as<int64_t>();
-        erows_d = sv.ent;
-      }
-      launch_recommend(s.stream, Q, Cf, s.rec_q.as<int32_t>() + b0, static_cast<int>(nb), static_cast<int32_t>(C),
-                       static_cast<int>(S), k, top_n, ctx->f64, s.rec_id[cside].as<int32_t>(), ebeg, eend, erows_d,
-                       s.rec_part.get(), s.rec_ids.as<int32_t>(), nullptr, s.rec_counts.as<int32_t>());
-    }
+  // the driver's batches (lists of no candidate side: empty), each followed by its metrics.  No copy and no wait
+  // inside the loop: stream order makes the reuse of a batch's scratch safe
+  TopNSink sink;
+  sink.on_batch = [&](int64_t b0, int64_t nb) {
     launch_rank_metrics(s.stream, s.rec_ids.as<int32_t>(), s.rec_counts.as<int32_t>(), static_cast<int>(nb), top_n,
                         s.rk_goff.as<int64_t>() + b0, s.rk_gent.as<int32_t>(), s.rk_tab.as<double>(),
                         s.rk_met.as<double>() + b0 * MF_RANK_NMETRICS, s.rk_cnt.as<int64_t>() + b0 * 2);
-  }
+  };
+  recommend_scored(ctx, s, TopNQueries::of_side(ctx, s, qside, nq), TopNCandidates::of_side(ctx, cside), top_n,
+                   MF_METRIC_DOT,
+                   sv.any ? ExclSource::seen(sv, s.seen.qbeg, s.seen.qend)
+                          : ExclSource::csr(s.rec_eoff.as<int64_t>(), s.rec_erows.as<int32_t>()),
+                   sink);
   launch_rank_reduce(s.stream, s.rk_met.as<double>(), s.rk_cnt.as<int64_t>(), nq, part, ipart, sums, isums);
   MF_HIP(hipGetLastError());
   MF_HIP(hipStreamSynchronize(s.stream));

@@ -1,7 +1,8 @@
 // rec_keys.hpp -- the selection keys of the top-N kernels (kernels_recommend.hip, kernels_among.hip): what
 // defines mf_recommend's order bit for bit.  A key orders by score descending, then candidate id ascending
 // (signed), NaN below every number, -0 as +0 -- one unsigned compare; the all-zero key is the empty slot.
-// A list is N keys sorted descending.
+// A list is N keys sorted descending.  With the keys: the insertions into a list, one lane's and a wave's, and
+// the merge of partial lists (k_rec_merge), one definition each.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -90,6 +91,71 @@ __device__ __forceinline__ void list_insert_distinct(K* list, int N, K key) {
   if (!key_gt(key, list[p])) return;  // equal (list[p] does not beat key, key does not beat list[p])
   for (int x = N - 1; x > p; --x) list[x] = list[x - 1];
   list[p] = key;
+}
+
+// The lanes of a wave exchange data through LDS without a workgroup barrier: order the wave's own LDS accesses.
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// One lane at a time inserts into the list its wave shares (k_rec_f64, k_among_score): per round the first lane
+// that still wants to and whose key still beats the N-th.  DISTINCT: candidates may repeat (list_insert_distinct).
+template <bool DISTINCT, typename K>
+__device__ __forceinline__ void wave_list_insert(K* list, int N, K key, bool want, int lane) {
+  for (;;) {
+    want = want && key_gt(key, list[N - 1]);
+    const uint64_t m = __ballot(want);
+    if (m == 0) break;
+    if (lane == __ffsll(static_cast<long long>(m)) - 1) {
+      if constexpr (DISTINCT) list_insert_distinct(list, N, key);
+      else list_insert(list, N, key);
+      want = false;
+    }
+    wave_lds_sync();
+  }
+}
+
+// The partial lists of a query -> its final top N.  One wave per query: lane l < S holds the head of the
+// query's l-th partial list (each sorted descending, keys distinct inside it); N rounds of a wave-wide
+// maximum.  The lists are parts [q * S, (q + 1) * S) of `part`, or with pbeg (nq + 1 offsets, at most 64
+// parts a query) parts [pbeg[q], pbeg[q + 1]).  Every lane whose head equals the round's maximum advances, so
+// an id that two parts both kept (mf_recommend_among: a list may name a candidate twice) counts once; where
+// the parts are disjoint candidate splits exactly one lane holds the maximum.  Slots past the count hold
+// id 0 / score 0.0.  scores may be null.  No floating-point arithmetic: the same code in every file.
+template <typename K>
+__global__ __launch_bounds__(256) void k_rec_merge(const K* __restrict__ part, const int64_t* __restrict__ pbeg,
+                                                   int nq, int S, int N, int32_t* __restrict__ ids,
+                                                   double* __restrict__ scores, int32_t* __restrict__ counts) {
+  const int lane = threadIdx.x & 63;
+  const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (q >= nq) return;
+  int64_t p0 = static_cast<int64_t>(q) * S;
+  if (pbeg != nullptr) {
+    p0 = pbeg[q];
+    S = static_cast<int>(pbeg[q + 1] - p0);
+  }
+  const K* mine = part + (p0 + lane) * N;
+  int pos = 0;
+  int cnt = 0;
+  for (int o = 0; o < N; ++o) {
+    K head{};
+    if (lane < S && pos < N) head = mine[pos];
+    K best = head;
+    for (int m = 1; m < 64; m <<= 1) {
+      const K other = key_shfl_xor(best, m);
+      if (key_gt(other, best)) best = other;
+    }
+    const bool live = !key_empty(best);
+    if (live && lane < S && pos < N && !key_gt(best, head) && !key_gt(head, best)) ++pos;
+    if (lane == 0) {
+      ids[static_cast<int64_t>(q) * N + o] = live ? key_id(best) : 0;
+      if (scores) scores[static_cast<int64_t>(q) * N + o] = live ? key_score(best) : 0.0;
+    }
+    cnt += live ? 1 : 0;
+  }
+  if (lane == 0) counts[q] = cnt;
 }
 
 }  // namespace mfhip::dev

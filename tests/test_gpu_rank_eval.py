@@ -222,7 +222,7 @@ def raw_eval(ctx, gq, gc, ng, top_n, out, side=L.SIDE_USER, eq=None, ec=None, ne
 
 
 @pytest.mark.parametrize("mode", MODES)
-def test_errors_and_edges(mode):
+def test_errors_and_edges(monkeypatch, mode):
     rng = np.random.default_rng(3)
     one = np.array([1], np.int32)
     out = L.mf_rank_metrics()
@@ -257,6 +257,20 @@ def test_errors_and_edges(mode):
             assert (m.queries, m.gt_pairs, m.hits) == (0, 0, 0) and len(m.ids) == 0
             assert [getattr(m, f) for f in FIELDS] == [0.0] * 6
         assert m.unknown_queries == 2
+    # the candidate side holds no row: every list is empty, so counts and metrics are 0 while the queries and
+    # their ground truth are still counted -- in one batch and in batches of two (SHAPES holds the catalogue
+    # smaller than top_n)
+    with make_ctx(3, mode) as ctx:
+        qids = shuffled_ids(rng, 5)
+        ctx.set_factors(L.SIDE_USER, qids, rng.standard_normal((5, 3)))
+        gq, gc = np.repeat(qids, 2)[:9], np.arange(9, dtype=np.int32)
+        for batch in (8192, 2):
+            set_knob(monkeypatch, "rec_batch", batch)
+            for excl in (None, (gq, gc)):
+                m, cnt = check_against_definition(ctx, qids, gq, gc, 10, excl)
+                assert (m.queries, m.gt_pairs, m.hits) == (5, 9, 0) and not cnt.any()
+                assert not m.counts[:, 0].any() and m.counts[:, 1].sum() == 9 and not m.values.any()
+                assert [getattr(m, f) for f in FIELDS] == [0.0] * 6
     p = L.default_params()
     p.num_factors, p.mode = 6, mode
     with Context(p, rank=(0, 1, 0, b"")) as ctx:  # a rank-mode context (one rank: no communicator)
